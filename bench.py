@@ -20,13 +20,18 @@ Workloads:
         --steps / --warmup are.
   env: one step = one transition of all envs: the fused ssd_step_observe launch with pre-generated synthetic actions
         (resets at the episode boundaries are inside the timed region).
-Rank 0 prints ONE JSON line with the driver's fields plus
+Rank 0 prints ONE JSON line with the driver's fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...) and
+  `config.per_rank` : (N > 1) every rank's own ms_per_step and the time of its gradient all-reduce.
+A plain run does only what that line needs: set-up, warm-up, the timed steps, the outputs (--dump-outputs) and the line.  With
+--full the line also carries what takes measurements of its own after the timed region:
   `roofline`     : the kernel with the largest share of the timestep (measured live with HIP events on the launch stream),
   `kernels`      : the same object for every kernel of the rollout timestep (e2e),
-  `cpu_baseline` : the C oracle on the host cores (rank 0, N = 1 only),
+  `config.breakdown_ms` : (e2e) one more iteration, synchronised between its phases,
+  `cpu_baseline` : the C oracle on the host cores (rank 0, N = 1 only; --no-cpu-baseline leaves it out),
   `env_workload` : (e2e, N = 1) the SURVEY 8(d) kernel-only workload -- fused step + observe with f32 observations -- run for 300
-                   transitions in the same process AFTER the timed region: the HBM fraction of the path's byte-moving kernel,
-  `config.per_rank` : (N > 1) every rank's own ms_per_step and the time of its gradient all-reduce.
+                   transitions in the same process AFTER the timed region: the HBM fraction of the path's byte-moving kernel
+                   (--no-env-workload leaves it out).
+--dump-outputs DIR (rank 0): right after the timed steps, what the last timed step computed goes to DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import json
@@ -52,6 +57,58 @@ def algorithmic_bytes_per_env_step(H, W, n, V, obs_bytes_per_elem=4, planes=3):
     """grid r+w, actions, agent state r+w, obs, 7 f32 scalars per agent.  Format R (default): obs f32
     [n, 3, V, V]; format C: planes = 1, obs_bytes_per_elem = 1 (u8 class codes [n, V, V])."""
     return 2 * H * W + 4 * n + 16 * n + planes * obs_bytes_per_elem * n * V * V + 28 * n
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6      # all .npy files of --dump-outputs together
+DUMP_SAMPLE_SEED = 0x5D5D
+
+
+def _dump_wide(t):
+    """float64 where float32 would not hold every value exactly (f64, 32- and 64-bit integers), else float32"""
+    return (t.dtype.is_floating_point and t.element_size() == 8) or (not t.dtype.is_floating_point and t.element_size() >= 4)
+
+
+def dump_outputs(out_dir, per_env, whole, n_env):
+    """--dump-outputs: write the outputs of the timed path's last step as out_dir/<name>.npy (float32, float64 where float32 would
+    round), at most DUMP_BUDGET_BYTES on disk in all.  per_env: {name: tensor with the env as dim 0}; when they do not fit whole,
+    the same fixed, seeded sample of envs (sorted, written as env_index.npy) is taken from every one of them.  whole: {name:
+    tensor}, written as they are.  Returns (number of files, bytes)."""
+    import numpy as np
+    import torch
+
+    def nbytes(t, rows=None):
+        return (8 if _dump_wide(t) else 4) * (t.numel() if rows is None else t.numel() // max(1, t.shape[0]) * rows)
+
+    fixed = sum(nbytes(t) for t in whole.values()) + 8 * n_env + 4096 * (len(per_env) + len(whole) + 1)     # + env_index, headers
+    per_row = sum(nbytes(t, 1) for t in per_env.values())
+    keep = n_env
+    if fixed + per_row * n_env > DUMP_BUDGET_BYTES:
+        keep = (DUMP_BUDGET_BYTES - fixed) // max(1, per_row)
+        if keep < 1:
+            raise SystemExit("bench.py: the outputs do not fit into %d bytes" % DUMP_BUDGET_BYTES)
+    arrays = {}
+    idx = None
+    if keep < n_env:
+        sample = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_env, keep, replace=False))
+        arrays["env_index"] = sample.astype(np.float64)
+    for name, t in per_env.items():
+        t = t.detach()
+        if keep < n_env:
+            if idx is None or idx.device != t.device:
+                idx = torch.as_tensor(sample, dtype=torch.long, device=t.device)
+            t = t.index_select(0, idx)
+        arrays[name] = t
+    arrays.update((name, t.detach()) for name, t in whole.items())
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        if isinstance(t, torch.Tensor):
+            t = (t.double() if _dump_wide(t) else t.float()).cpu().numpy()
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, t)
+        total += os.path.getsize(path)
+    assert total <= DUMP_BUDGET_BYTES, total
+    return len(arrays), total
 
 
 def host_threads():
@@ -131,10 +188,11 @@ def roofline_entry(k):
     return e
 
 
-def run_env_workload(args, c, rank, local_rank, steps, warmup, in_group=False):
+def run_env_workload(args, c, rank, local_rank, steps, warmup, in_group=False, dump_dir=None):
     """SURVEY.md section 8(d)'s kernel-only workload: the fused ssd_step_observe launch on pre-generated synthetic actions, format R
     (f32 observation [n_env, n, 3, V, V]); resets at the episode boundaries are inside the wall-clock bracket, the kernel time comes
-    from HIP events around every run of back-to-back launches between two resets."""
+    from HIP events around every run of back-to-back launches between two resets.  dump_dir: the last launch's outputs (step
+    outputs and observation buffers) go there after the timed region."""
     import torch
     import torch.distributed as dist
     from homophily_marl_amd import abi
@@ -186,6 +244,9 @@ def run_env_workload(args, c, rank, local_rank, steps, warmup, in_group=False):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     assert env.poll_error() == 0
+    if dump_dir:
+        files, nb = dump_outputs(dump_dir, dict(env.out, **bufs), {}, N)
+        print("[bench] %d outputs of the last timed step (%d bytes) -> %s" % (files, nb, dump_dir), file=sys.stderr, flush=True)
     per_launch = sorted(1e3 * a.elapsed_time(b) / k for (a, b), k in zip(ev, run_len))
     kern = dict(name="ssd::k_env<MODE_STEP_OBS>", bound="hbm", avg_us=sum(1e3 * a.elapsed_time(b) for a, b in ev) / sum(run_len),
                 median_us=per_launch[len(per_launch) // 2], bytes_per_launch=algorithmic_bytes_per_env_step(env.H, env.W, n, env.V) * N)
@@ -293,8 +354,13 @@ def main():
     ap.add_argument("--warm", type=float, default=0.0,
                     help="env workload: fraction of the waste cells turned into clean river after every reset (SURVEY.md 8d 'warm' variant: "
                          "exercises apple spawning; 0 = start from the map's reset state)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-env-workload", action="store_true", help="e2e, 1 GPU: skip the format-R env workload measured after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need, after the timed region: roofline / per-kernel timing, the e2e "
+                         "phase breakdown, the format-R env workload (e2e, 1 GPU) and the CPU baseline (1 GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB; rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
+    ap.add_argument("--no-env-workload", action="store_true", help="--full, e2e, 1 GPU: skip the format-R env workload measured after the timed region")
     ap.add_argument("--env-workload-steps", type=int, default=300)
     ap.add_argument("--cpu-sample-steps", type=int, default=None)
     ap.add_argument("--launch-dry-run", action="store_true", help="form the process group (gloo), count the ranks, print the launch fields; no GPU")
@@ -317,11 +383,13 @@ def main():
     if args.warmup is None:
         args.warmup = 5 if args.workload == "e2e" else 100
 
+    import numpy as np
     import torch
     import torch.distributed as dist
     from homophily_marl_amd import abi
     from homophily_marl_amd.envs.native import NativeEnv
 
+    np.random.seed(0)       # numpy's global generator seeds the replay buffer's sample draws: the same inputs in every run
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -353,7 +421,8 @@ def main():
         result = run_e2e(args, c, rank, world, local_rank)
         units = N * n * T * args.steps * world
     else:
-        result = run_env_workload(args, c, rank, local_rank, args.steps, args.warmup, in_group)
+        result = run_env_workload(args, c, rank, local_rank, args.steps, args.warmup, in_group,
+                                  dump_dir=args.dump_outputs if rank == 0 else None)
         units = N * n * args.steps * world
 
     elapsed = result["elapsed"]
@@ -380,7 +449,7 @@ def main():
                                            "host_ms_avg_per_rank": [round(float(x), 4) for x in rows[:, 3]],
                                            "how": "HIP events on the launch stream around dist.all_reduce of the flat gradient (between the two train graphs)"}
     env_wl = None
-    if rank == 0 and world == 1 and args.workload == "e2e" and not args.no_env_workload:
+    if args.full and rank == 0 and world == 1 and args.workload == "e2e" and not args.no_env_workload:
         # the HBM claim of the path (step + observe in format R) measured in the SAME process right after the e2e
         # timed region -- outside `elapsed`, the headline value is untouched
         ew = run_env_workload(args, c, rank, local_rank, args.env_workload_steps, 100)
@@ -392,10 +461,6 @@ def main():
                   "peak": e["peak"], "frac": e["frac"], "traffic": e["traffic"], "traffic_source": e["traffic_source"],
                   "agent_steps_per_sec": N * n * args.env_workload_steps / ew["elapsed"]}
     if rank == 0:
-        kernels = result["kernels"]
-        attach_traffic(kernels, args.config, "@env_workload" if args.workload == "env" else ("@f32storage" if args.obs_storage == "f32" else ""), N)
-        entries = [roofline_entry(k) for k in kernels]
-        dominant = max(entries, key=lambda e: e["kernel_avg_us"])
         line = {
             "metric": "agent_steps_per_sec", "value": units / elapsed, "unit": "agent-steps/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
@@ -407,15 +472,19 @@ def main():
                             "parallelism": ("dp%d: env shards, no collective in the rollout" % world) +
                                            ("; 1 flat-gradient all-reduce + 2 scalars per train step" if args.workload == "e2e" else "")},
                            **result["extra"]),
-            "roofline": dominant,
         }
-        if len(entries) > 1:
-            line["kernels"] = entries
+        if args.full:
+            kernels = result["kernels"]
+            attach_traffic(kernels, args.config, "@env_workload" if args.workload == "env" else ("@f32storage" if args.obs_storage == "f32" else ""), N)
+            entries = [roofline_entry(k) for k in kernels]
+            line["roofline"] = max(entries, key=lambda e: e["kernel_avg_us"])
+            if len(entries) > 1:
+                line["kernels"] = entries
         if env_wl is not None:
             line["env_workload"] = env_wl
         if per_rank is not None:
             line["config"]["per_rank"] = per_rank
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             per_step = {"cleanup5": 2000, "harvest5": 600, "cleanup10": 500}[args.config]
             line["cpu_baseline"] = cpu_baseline(c, N, args.cpu_sample_steps or per_step)
         sys.stdout.flush()

@@ -129,6 +129,42 @@ def run_e2e(args, c, rank, world, local_rank):
     timed = dict(state)
     assert runner.env.native.poll_error() == 0
     assert timed["trains"] == args.steps * tspr and timed["timesteps"] == args.steps * T
+    code = getattr(args, "obs_storage", "f32") == "code"
+    V = 2 * c["view_size"] + 1
+
+    def result(kernels, bd):
+        extra = dict(obs_format=("u8 class codes [n_env,n,%d,%d] (format C)" % (V, V)) if code else "f32[n_env,n,3,%d,%d]" % (V, V),
+                     qnet_dtype=("fp32 (rollout: two-term f16 split MFMA products, f32-equivalent)" if qnet == "fp32"
+                                 else "bf16 rollout inference (single bf16 MFMA products)"),
+                     learner_dtype=("fp32 (exact-f32 MFMAs in the affine layers, f32-equivalent split products in the recurrence and the encoder)" if ldt == "fp32"
+                                    else "bf16 (LABELLED VARIANT: single bf16 MFMA products in the affine layers, the recurrence and the encoder; f32 master weights, Adam and loss)"),
+                     step="1 bench step = 1 iteration: reset + %d timesteps + slot-T pass + replay insert + sample + %d learner.train" % (T, tspr),
+                     timesteps_timed=timed["timesteps"], train_steps_timed=timed["trains"], rollouts_timed=args.steps,
+                     train="learner.train(batch_size 16 x T 101), double-Q + sim loss, 2x Adam; %d per rollout" % tspr,
+                     buffer="device-resident ReplayBuffer, %d episodes, %s" % (buf.buffer_size, "written in place by the runner" if getattr(runner, "_replay", None) is not None else "copy insertion"),
+                     runner=args.runner, train_graph=bool(args.train_graph), steps_per_rollout_graph=int(getattr(runner, "_graph_steps", 1)))
+        if bd is not None:
+            extra["breakdown_ms"] = bd
+        return dict(elapsed=elapsed, rank_elapsed=rank_elapsed, collectives=coll, grad_bytes=4 * sum(p.numel() for p in learner.params), kernels=kernels,
+                    dtype="fp32" if (qnet == "fp32" and ldt == "fp32") else ("bf16" if (qnet != "fp32" and ldt != "fp32") else "mixed: rollout %s, learner %s" % (qnet, ldt)),
+                    workload="%s_rollout_plus_homophily_train" % args.config, extra=extra)
+
+    dump_dir = getattr(args, "dump_outputs", None)
+    if dump_dir and rank == 0:
+        # what the last timed iteration computed: its rollout (the episode batch the runner returned, a view of its replay slots, not
+        # written again until the ring comes round), the network the train step left and that step's logged losses / statistics
+        batch = runner.batch
+        per_env = dict(batch.data.transition_data)
+        per_env.update(("episode." + k, v) for k, v in batch.data.episode_data.items())
+        whole = {"param." + k: v for k, v in ctx.mac.agent.named_parameters()}
+        logs = getattr(learner, "_static_logs", None)          # (the captured train step's; an eager train step keeps none)
+        if hasattr(logs, "host_items"):
+            whole["train_logs"] = th.tensor([v for _, v in logs.host_items()], dtype=th.float64)      # _FusedLogs.KEYS order
+        from bench import dump_outputs
+        files, nb = dump_outputs(dump_dir, per_env, whole, N)
+        print("[bench] %d outputs of the last timed iteration (%d bytes) -> %s" % (files, nb, dump_dir), file=__import__("sys").stderr, flush=True)
+    if not getattr(args, "full", False):
+        return result([], None)
 
     # Steady-state breakdown of one more rollout + train iteration (synchronised between phases; NOT part of `elapsed`)
     def timed_ms(fn):
@@ -148,8 +184,6 @@ def run_e2e(args, c, rank, world, local_rank):
     # region with HIP events around runs of back-to-back launches of one kernel (every launch is idempotent in its cost: the data it
     # reads is whatever the rollout left).  The env kernel is timed over three whole episodes (reset, then T launches).
     from bench import MFMA_BF16_PEAK_TF, MFMA_F32_PEAK_TF, algorithmic_bytes_per_env_step
-    code = getattr(args, "obs_storage", "f32") == "code"
-    V = 2 * c["view_size"] + 1
     env_bytes = algorithmic_bytes_per_env_step(c["H"], c["W"], n, V, 1, 1) if code else algorithmic_bytes_per_env_step(c["H"], c["W"], n, V)
     if not code and "code" in getattr(runner, "cur", {}):
         env_bytes += n * V * V                      # f32 storage: plus the u8 channel-mask window the fused encoder reads
@@ -209,17 +243,4 @@ def run_e2e(args, c, rank, world, local_rank):
     tot = sum(k["avg_us"] for k in kernels)
     for k in kernels:
         k["share_of_timestep"] = round(k["avg_us"] / tot, 4)
-    return dict(elapsed=elapsed, rank_elapsed=rank_elapsed, collectives=coll, grad_bytes=4 * sum(p.numel() for p in learner.params), kernels=kernels,
-                dtype="fp32" if (qnet == "fp32" and ldt == "fp32") else ("bf16" if (qnet != "fp32" and ldt != "fp32") else "mixed: rollout %s, learner %s" % (qnet, ldt)),
-                workload="%s_rollout_plus_homophily_train" % args.config,
-                extra=dict(obs_format=("u8 class codes [n_env,n,%d,%d] (format C)" % (V, V)) if code else "f32[n_env,n,3,%d,%d]" % (V, V),
-                           qnet_dtype=("fp32 (rollout: two-term f16 split MFMA products, f32-equivalent)" if qnet == "fp32"
-                                       else "bf16 rollout inference (single bf16 MFMA products)"),
-                           learner_dtype=("fp32 (exact-f32 MFMAs in the affine layers, f32-equivalent split products in the recurrence and the encoder)" if ldt == "fp32"
-                                          else "bf16 (LABELLED VARIANT: single bf16 MFMA products in the affine layers, the recurrence and the encoder; f32 master weights, Adam and loss)"),
-                           step="1 bench step = 1 iteration: reset + %d timesteps + slot-T pass + replay insert + sample + %d learner.train" % (T, tspr),
-                           timesteps_timed=timed["timesteps"], train_steps_timed=timed["trains"], rollouts_timed=args.steps,
-                           train="learner.train(batch_size 16 x T 101), double-Q + sim loss, 2x Adam; %d per rollout" % tspr,
-                           buffer="device-resident ReplayBuffer, %d episodes, %s" % (buf.buffer_size, "written in place by the runner" if getattr(runner, "_replay", None) is not None else "copy insertion"),
-                           runner=args.runner, train_graph=bool(args.train_graph), steps_per_rollout_graph=int(getattr(runner, "_graph_steps", 1)),
-                           breakdown_ms=bd))
+    return result(kernels, bd)

@@ -88,3 +88,82 @@ def test_bench_front_door_propagates_a_failing_rank():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--launch-dry-run"], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert p.returncode != 0 and not p.stdout.decode().strip()
+
+
+def test_dump_outputs_writes_a_fixed_float_sample_within_the_budget(tmp_path):
+    """--dump-outputs: float32 / float64 files only (float64 where float32 would round), at most 64 MB on disk, and when the per-env
+    outputs do not fit, the same seeded sample of envs in every run and in every per-env array."""
+    import sys
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    N = 4096
+    code = torch.arange(N, dtype=torch.uint8).view(N, 1, 1, 1).expand(N, 101, 5, 225)      # 465 MB as f32: must be sampled
+    ids = (torch.arange(N, dtype=torch.int64) * 1000003).view(N, 1)                          # beyond f32's exact integers
+    w = torch.randn(64, 9, dtype=torch.float32)
+    runs = []
+    for k in range(2):
+        d = tmp_path / str(k)
+        files, nbytes = bench.dump_outputs(str(d), {"obs": code, "ids": ids}, {"param.w": w}, N)
+        assert files == 4 and nbytes <= bench.DUMP_BUDGET_BYTES
+        assert sum(f.stat().st_size for f in d.iterdir()) == nbytes
+        out = {f.name[:-4]: np.load(f) for f in d.iterdir()}
+        assert sorted(out) == ["env_index", "ids", "obs", "param.w"]
+        assert out["obs"].dtype == np.float32 and out["param.w"].dtype == np.float32
+        assert out["ids"].dtype == np.float64 and out["env_index"].dtype == np.float64
+        sel = out["env_index"].astype(np.int64)
+        assert 0 < len(sel) < N and (np.diff(sel) > 0).all()
+        assert (out["obs"] == (sel % 256).reshape(-1, 1, 1, 1)).all() and (out["ids"][:, 0] == sel * 1000003).all()
+        assert (out["param.w"] == w.numpy()).all()
+        runs.append(sel)
+    assert (runs[0] == runs[1]).all()
+    # outputs that fit are written whole, without an index
+    d = tmp_path / "whole"
+    assert bench.dump_outputs(str(d), {"reward": torch.ones(N, 5)}, {}, N)[0] == 1
+    assert np.load(d / "reward.npy").shape == (N, 5)
+
+
+def test_bench_has_the_full_and_dump_outputs_options():
+    """the plain run and the --full run share one front door: both options parse without touching the GPU"""
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+    assert p.returncode == 0 and "--full" in p.stdout.decode() and "--dump-outputs" in p.stdout.decode()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("workload", ["e2e", "env"])
+def test_plain_bench_run_times_its_steps_and_dumps_its_outputs(workload, tmp_path):
+    """A plain run: exactly --steps timed steps, the headline fields, none of the --full measurements, and the last timed step's
+    outputs under --dump-outputs (float32 / float64, at most 64 MB)."""
+    import subprocess
+    import sys
+    import numpy as np
+    steps = 3 if workload == "e2e" else 50
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                        "--workload", workload, "--dump-outputs", str(tmp_path)],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["metric"] == "agent_steps_per_sec" and d["unit"] == "agent-steps/s" and d["higher_is_better"] is True
+    assert d["dtype"] in ("fp32", "u8") and d["steps"] == steps and d["ms_per_step"] > 0
+    for k in ("roofline", "kernels", "cpu_baseline", "env_workload"):
+        assert k not in d, k
+    assert "breakdown_ms" not in d["config"]
+    cfg = d["config"]
+    units = cfg["n_env_per_gpu"] * cfg["n_agents"] * steps * (cfg["episode_limit"] if workload == "e2e" else 1)
+    assert abs(d["value"] - units / (d["ms_per_step"] * steps / 1e3)) < 1e-3 * d["value"]
+    if workload == "e2e":
+        assert cfg["timesteps_timed"] == steps * cfg["episode_limit"] and cfg["rollouts_timed"] == steps
+    files = {f.name[:-4]: f for f in tmp_path.iterdir()}
+    assert sum(f.stat().st_size for f in files.values()) <= 64 * 10 ** 6
+    assert "reward" in files and "obs" in files
+    if workload == "e2e":
+        assert "train_logs" in files and any(k.startswith("param.") for k in files)
+    for f in files.values():
+        a = np.load(f)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), f.name

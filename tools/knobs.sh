@@ -5,7 +5,7 @@ OUT=${1:-gpurun_out/knobs}
 mkdir -p $OUT
 run() {
     name=$1; shift
-    env "$@" timeout -k 10 150 python3 bench.py --no-cpu-baseline --steps 10 --warmup 3 > $OUT/$name.json 2> $OUT/$name.err
+    env "$@" timeout -k 10 150 python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 3 > $OUT/$name.json 2> $OUT/$name.err
     rc=$?
     echo "$name rc=$rc $(python3 tools/benchsum.py $OUT/$name.json 2>/dev/null | head -1)"
     if [ $rc -ge 124 ]; then echo "killed: stopping"; exit 1; fi

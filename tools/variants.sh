@@ -1,7 +1,7 @@
 #!/bin/bash
 # Diagnostic: build libssd_hip variants with extra -D flags (CPU side, before the GPU call) and bench each on the GPU box.
 #   local:  bash tools/variants.sh build name1 "-DX=1" name2 "-DX=2" ...
-#   box:    bash tools/variants.sh run outdir name1 name2 ...   (runs `python bench.py --no-cpu-baseline $BENCH_ARGS` per variant)
+#   box:    bash tools/variants.sh run outdir name1 name2 ...   (runs `python bench.py --full --no-cpu-baseline $BENCH_ARGS` per variant)
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 mode=$1; shift
@@ -16,7 +16,7 @@ else
   out=$1; shift
   mkdir -p $R/$out
   for name in "$@"; do
-    SSD_HIP_LIB_PATH=$R/build/variants/libssd_$name.so python3 $R/bench.py --no-cpu-baseline $BENCH_ARGS > $R/$out/bench_$name.json 2> $R/$out/bench_$name.err || echo "$name FAILED"
+    SSD_HIP_LIB_PATH=$R/build/variants/libssd_$name.so python3 $R/bench.py --full --no-cpu-baseline $BENCH_ARGS > $R/$out/bench_$name.json 2> $R/$out/bench_$name.err || echo "$name FAILED"
     python3 $R/tools/benchsum.py $R/$out/bench_$name.json
   done
 fi
