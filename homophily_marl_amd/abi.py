@@ -6,7 +6,7 @@ The native library is REQUIRED: there is no CPU fallback on the product path.  `
 import ctypes as C
 import os
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 MAX_AGENTS = 10
 MAX_CELLS = 1024
 MAX_SITES = 256
@@ -320,6 +320,10 @@ HIP_SIGNATURES["ssd_gru_gates_bwd"] = (C.c_int, [C.c_void_p] * 7 + [C.c_int32, C
 HIP_SIGNATURES["ssd_dueling_pick"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32,
                                                C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p])
 HIP_SIGNATURES["ssd_poll_error"] = (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)])
+# render mode (device-only: no CPU counterpart)
+HIP_SIGNATURES["ssd_set_render"] = (C.c_int, [C.c_void_p, C.c_int32])
+HIP_SIGNATURES["ssd_render"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
+ERR_BAD_RENDER = 64
 CPU_SIGNATURES = _sigs("ssd_cpu_", False)
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))

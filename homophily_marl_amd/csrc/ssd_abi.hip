@@ -17,6 +17,9 @@ struct ssd_env {
     DevState st;
     int device;
     int n_spawn;
+    uint32_t* beam_rec;   // render mode (ssd_set_render): [N, n] beam record of the last step; null = render mode off
+    uint8_t* render_lut;  // render mode: full-colour table by render class (17 x 3 bytes)
+    uint8_t host_lut[64];
 };
 
 static thread_local char g_err[512] = "";
@@ -152,6 +155,10 @@ int ssd_create(const ssd_config* cfg, ssd_env** out) {
         lut[C_RIVER][0] = lut[C_STREAM][0] = 113; lut[C_RIVER][1] = lut[C_STREAM][1] = 75; lut[C_RIVER][2] = lut[C_STREAM][2] = 24;
     }
     for (int ch = 1; ch <= 9; ++ch) std::memcpy(lut[5 + ch], agent_rgb[ch], 3);
+    // the render table (ssd_render): the same 15 rows, then 'F' (yellow, DEFAULT_COLOURS) and 'C' (cyan, CLEANUP_COLORS; Cleanup only)
+    std::memcpy(E->host_lut, S.lut, 15 * 3);
+    E->host_lut[15 * 3] = 255; E->host_lut[15 * 3 + 1] = 255; E->host_lut[15 * 3 + 2] = 0;
+    if (S.kind == SSD_ENV_CLEANUP) { E->host_lut[16 * 3] = 100; E->host_lut[16 * 3 + 1] = 255; E->host_lut[16 * 3 + 2] = 255; }
 
     // ---- device side ----
     int prev = 0;
@@ -207,6 +214,7 @@ int ssd_create(const ssd_config* cfg, ssd_env** out) {
 
 int ssd_destroy(ssd_env* E) {
     if (!E) return SSD_OK;
+    (void)hipFree(E->beam_rec); (void)hipFree(E->render_lut);
     (void)hipFree(E->dspec); (void)hipFree(E->st.grid); (void)hipFree(E->st.agents); (void)hipFree(E->st.hdr); (void)hipFree(E->st.err);
     delete E;
     return SSD_OK;
@@ -288,6 +296,7 @@ int ssd_reset(ssd_env* E, const uint8_t* env_mask, const ssd_tape* tape, ssd_ste
     if (E->hs.rng_mode == SSD_RNG_TAPE && E->hs.random_spawn && !t.spawn_order) return fail(SSD_ERR_INVALID, "TAPE mode with random_spawn_point needs tape.spawn_order");
     DevObsOut oo; std::memset(&oo, 0, sizeof oo);
     launch_env(MODE_RESET, E->dspec, E->hs, E->st, nullptr, env_mask, t, make_so(out), oo, (hipStream_t)stream);
+    if (E->beam_rec) launch_beam_clear(E->beam_rec, env_mask, E->hs.N, E->hs.n, (hipStream_t)stream);
     return launched();
 }
 
@@ -295,7 +304,7 @@ int ssd_step(ssd_env* E, const int32_t* actions, const ssd_tape* tape, ssd_step_
     if (!E || !actions) return fail(SSD_ERR_INVALID, "null argument");
     DevTape t; if (int rc = make_tape(E, tape, &t)) return rc;
     DevObsOut oo; std::memset(&oo, 0, sizeof oo);
-    launch_env(MODE_STEP, E->dspec, E->hs, E->st, actions, nullptr, t, make_so(out), oo, (hipStream_t)stream);
+    launch_env(MODE_STEP, E->dspec, E->hs, E->st, actions, nullptr, t, make_so(out), oo, (hipStream_t)stream, E->beam_rec);
     return launched();
 }
 
@@ -311,7 +320,40 @@ int ssd_step_observe(ssd_env* E, const int32_t* actions, const ssd_tape* tape, s
     if (!E || !actions) return fail(SSD_ERR_INVALID, "null argument");
     DevTape t; if (int rc = make_tape(E, tape, &t)) return rc;
     DevObsOut oo; if (int rc = make_oo(E, obs, &oo)) return rc;
-    launch_env(MODE_STEP_OBS, E->dspec, E->hs, E->st, actions, nullptr, t, make_so(out), oo, (hipStream_t)stream);
+    launch_env(MODE_STEP_OBS, E->dspec, E->hs, E->st, actions, nullptr, t, make_so(out), oo, (hipStream_t)stream, E->beam_rec);
+    return launched();
+}
+
+int ssd_set_render(ssd_env* E, int32_t on) {
+    if (!E) return fail(SSD_ERR_INVALID, "null env");
+    if ((on != 0) == (E->beam_rec != nullptr)) return SSD_OK;
+    int prev = 0;
+    HIP_TRY(hipGetDevice(&prev));
+    HIP_TRY(hipSetDevice(E->device));
+    hipError_t e = hipSuccess;
+    if (on) {
+        const size_t bytes = (size_t)E->hs.N * E->hs.n * sizeof(uint32_t);
+        e = hipMalloc((void**)&E->beam_rec, bytes);
+        if (e == hipSuccess) e = hipMalloc((void**)&E->render_lut, sizeof E->host_lut);
+        if (e == hipSuccess) e = hipMemcpy(E->render_lut, E->host_lut, sizeof E->host_lut, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset(E->beam_rec, 0, bytes);      // no beams until the first step
+        if (e != hipSuccess) { (void)hipFree(E->beam_rec); (void)hipFree(E->render_lut); E->beam_rec = nullptr; E->render_lut = nullptr; }
+    } else {
+        e = hipDeviceSynchronize();                                    // launches in flight may still write the record
+        (void)hipFree(E->beam_rec); (void)hipFree(E->render_lut);
+        E->beam_rec = nullptr; E->render_lut = nullptr;
+    }
+    (void)hipSetDevice(prev);
+    if (e != hipSuccess) return fail(SSD_ERR_DEVICE, "ssd_set_render: %s", hipGetErrorString(e));
+    return SSD_OK;
+}
+
+int ssd_render(ssd_env* E, const int32_t* env_ids, int32_t n_sel, uint8_t* frames, const int32_t* slot, int64_t slot_stride, void* stream) {
+    if (!E || !env_ids || !frames) return fail(SSD_ERR_INVALID, "null argument");
+    if (!E->beam_rec) return fail(SSD_ERR_INVALID, "ssd_render needs render mode (ssd_set_render)");
+    if (n_sel < 1) return fail(SSD_ERR_INVALID, "n_sel must be >= 1");
+    if (slot_stride < 0) return fail(SSD_ERR_INVALID, "slot_stride must be >= 0");
+    launch_render(E->dspec, E->hs, E->st, E->beam_rec, E->render_lut, env_ids, n_sel, frames, slot, (long long)slot_stride, (hipStream_t)stream);
     return launched();
 }
 

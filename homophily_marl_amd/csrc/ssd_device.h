@@ -100,7 +100,7 @@ struct DevObsOut {
     unsigned long long* stamps;  // diagnostic builds only
 };
 
-enum : int { ERR_BAD_ACTION = 1, ERR_BAD_TAPE = 2, ERR_KEYERROR = 4, ERR_TAPE_OVERRUN = 8, ERR_SLOT_OVERRUN = 16, ERR_F16_RANGE = 32 };
+enum : int { ERR_BAD_ACTION = 1, ERR_BAD_TAPE = 2, ERR_KEYERROR = 4, ERR_TAPE_OVERRUN = 8, ERR_SLOT_OVERRUN = 16, ERR_F16_RANGE = 32, ERR_BAD_RENDER = 64 };
 // The sticky numeric-status word of the current device (ssd_numeric_status): bit ERR_F16_RANGE is set by the pack kernels, the
 // rollout heads and the learner's recurrence when a SCALED value of a two-term f16 split product leaves f16's range (65 504) -- the
 // product would silently carry inf / NaN.  Allocated on first use (ssd_create and the pack entry points call it outside any capture).
@@ -125,7 +125,11 @@ __host__ __device__ inline int lds_per_wave(const DevHead& s) {
 }
 
 void launch_env(int mode, const DevSpec* spec, const DevSpec& host_spec, DevState st, const int32_t* actions,
-                const uint8_t* env_mask, DevTape tape, DevStepOut so, DevObsOut oo, hipStream_t stream);
+                const uint8_t* env_mask, DevTape tape, DevStepOut so, DevObsOut oo, hipStream_t stream, uint32_t* beam_rec = nullptr);
+// render mode (ssd_env.hip): clear the beam record of the envs a reset resets; draw full-colour frames of selected envs
+void launch_beam_clear(uint32_t* beam_rec, const uint8_t* env_mask, int n_env, int n_agents, hipStream_t stream);
+void launch_render(const DevSpec* spec, const DevSpec& hs, DevState st, const uint32_t* beam_rec, const uint8_t* lut, const int32_t* env_ids,
+                   int n_sel, uint8_t* frames, const int32_t* slot, long long slot_stride, hipStream_t stream);
 
 void launch_export(const DevSpec* spec, const DevSpec& hs, DevState st, ssd_state dst, hipStream_t stream);
 void launch_import(const DevSpec* spec, const DevSpec& hs, DevState st, ssd_state src, hipStream_t stream);

@@ -332,6 +332,43 @@ __device__ __forceinline__ int clean_beams(Env& E, int f) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Render mode only: the cells a beam of agent f covers (update_map_fire's firing_points, map_env.py:722-767), traced on the
+// map as agent f sees it -- before its own CLEAN beam converts anything, after the earlier agents' beams did.  A beam covers
+// every cell up to the first agent, waste cell (CLEAN only) or wall / map edge; the first two are covered, the last is not.
+// Returns the beam record word: covered cells of beam b (0..5) at bits 4b..4b+2, the beam char ('F' / 'C') at bits 16..23.
+// Same lane geometry as clean_beams.
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t beam_record(const Env& E, int f, bool clean) {
+    const int W = E.W, H = E.h->H;
+    const int pf = rl(E.P, f), of = rl(E.O, f);
+    const int pr = (int)udiv((uint32_t)pf, E.h->magic_W), pc = pf - pr * W;
+    const int dr = of == O_LEFT ? -1 : of == O_RIGHT ? 1 : 0;
+    const int dc = of == O_UP ? -1 : of == O_DOWN ? 1 : 0;
+    const int rr = -dc, rc = dr;
+    const int b = E.lane / 5, k = E.lane - 5 * b;
+    const int sr = b == 0 ? pr : b == 1 ? pr + rr - dr : pr - rr - dr;
+    const int sc = b == 0 ? pc : b == 1 ? pc + rc - dc : pc - rc - dc;
+    const int r = sr + (k + 1) * dr, c = sc + (k + 1) * dc;
+    const bool act15 = E.lane < 15;
+    const bool inb = act15 && (unsigned)r < (unsigned)H && (unsigned)c < (unsigned)W;
+    const int cell = inb ? r * W + c : 0;
+    const int gc = inb ? E.g[cell] : C_WALL;
+    const int oc = inb ? E.occ[cell] : 0;
+    const bool open = inb && gc != C_WALL;
+    const bool stop = act15 && (!open || oc != 0 || (clean && gc == C_WASTE));
+    const uint32_t m = (uint32_t)ballot(stop), cov = (uint32_t)ballot(stop && open);
+    uint32_t rec = (uint32_t)(clean ? 'C' : 'F') << 16;
+#pragma unroll
+    for (int bb = 0; bb < 3; ++bb) {
+        const uint32_t field = (m >> (5 * bb)) & 31u;
+        const int k0 = field ? __builtin_ctz(field) : 5;
+        const uint32_t cnt = (uint32_t)k0 + (field ? (cov >> (5 * bb + k0)) & 1u : 0u);
+        rec |= cnt << (4 * bb);
+    }
+    return rec;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // custom_map_update: Cleanup (cleanup.py:146-204) / Harvest (harvest.py:86-122).  Returns the uniforms consumed.
 // ---------------------------------------------------------------------------------------------------------------
 // wave-wide unsigned minimum with DPP (no LDS crossbar): quad swaps, row rotations, then row broadcasts; lane 63 ends with
@@ -871,6 +908,7 @@ __device__ __forceinline__ void observe_phase(Env& E, int env, const DevObsOut& 
 struct EnvArgs {
     DevHead hd; const DevSpec* S; DevState st; const int32_t* actions; const uint8_t* env_mask; DevTape tape; int lds_stride;
     DevStepOut so; DevObsOut oo;
+    uint32_t* beam_rec;     // render mode only (k_env<.., REC = true>): [N, n] beam record
 };
 // k_env's kernarg segment: five pointers and four ints (the preloadable head, see k_env), then the EnvArgs struct
 constexpr int kEnvArgsOffset = (5 * 8 + 4 * 4 + (int)alignof(EnvArgs) - 1) / (int)alignof(EnvArgs) * (int)alignof(EnvArgs);
@@ -902,7 +940,9 @@ __device__ __forceinline__ T cold_kernarg(int offset) {
 #else
 #define SSD_ENV_OCC
 #endif
-template <int MODE, int NT, bool TAPE, int OV = OV_ANY>
+// REC (render mode, ssd_set_render; instantiated for MODE_STEP / MODE_STEP_OBS with OV_ANY only): the step also writes every agent's
+// beam record to EnvArgs::beam_rec [N, n] (beam_record).  The other instantiations never read it.
+template <int MODE, int NT, bool TAPE, int OV = OV_ANY, bool REC = false>
 __global__ __launch_bounds__(kBlock) SSD_ENV_OCC void k_env(EnvHdr* p_hdr, uint2* p_agents, uint8_t* p_grid, const int32_t* p_actions, const DevSpec* p_spec,
                                                 int p_N, int p_GS, int p_PMS, int p_lds_stride, const EnvArgs A) {
     const DevHead& hd = A.hd;
@@ -1126,14 +1166,23 @@ __global__ __launch_bounds__(kBlock) SSD_ENV_OCC void k_env(EnvHdr* p_hdr, uint2
         // update_custom_moves (map_env.py:663-673): sequential over agents, the map is updated after each one
         {
             const uint64_t fire = ballot(E.ag && act >= 7);
+            uint32_t beam_w = 0;                                                  // render mode: this lane's agent's beam record
             for (uint64_t m = fire; m; m &= m - 1) {
                 const int f = first_lane(m);
                 const int af = rl(act, f);
+                if (REC) {                                                        // traced before agent f's own beam cleans anything
+                    const uint32_t w = beam_record(E, f, h->kind == SSD_ENV_CLEANUP && af == 8);
+                    if (lane == f) beam_w = w;
+                }
                 if (h->kind == SSD_ENV_CLEANUP && af == 8) {                      // CLEAN (cleanup.py:135-143)
                     const int c = clean_beams(E, f);
                     if (lane == f) cleaned = c;
                     n_waste_cells -= c;
                 } else if (lane == f) reward -= 1;                                // fire_beam('F') (agent.py:188-190,239-241)
+            }
+            if (REC && E.ag) {
+                uint32_t* rec = cold_kernarg<uint32_t*>((int)(kEnvArgsOffset + offsetof(EnvArgs, beam_rec)));
+                rec[(size_t)env * n + lane] = beam_w;
             }
         }
         STAMP(4);
@@ -1213,14 +1262,27 @@ __global__ __launch_bounds__(kBlock) SSD_ENV_OCC void k_env(EnvHdr* p_hdr, uint2
 }
 
 void launch_env(int mode, const DevSpec* spec, const DevSpec& hs, DevState st, const int32_t* actions,
-                const uint8_t* env_mask, DevTape tape, DevStepOut so, DevObsOut oo, hipStream_t stream) {
+                const uint8_t* env_mask, DevTape tape, DevStepOut so, DevObsOut oo, hipStream_t stream, uint32_t* beam_rec) {
     const int blocks = (hs.N + kWavesPerBlock - 1) / kWavesPerBlock;
     const int stride = lds_per_wave(hs);
     const size_t lds = (size_t)stride * kWavesPerBlock;
     EnvArgs A;
     A.hd = (const DevHead&)hs; A.S = spec; A.st = st; A.actions = actions; A.env_mask = env_mask; A.tape = tape; A.lds_stride = stride;
-    A.so = so; A.oo = oo;
+    A.so = so; A.oo = oo; A.beam_rec = beam_rec;
 #define SSD_ENV_ARGS st.hdr, st.agents, st.grid, actions, spec, (int)hs.N, (int)hs.GS, (int)hs.PMS, stride, A
+    const bool tape_mode = hs.rng_mode == SSD_RNG_TAPE;
+    if (beam_rec && (mode == MODE_STEP || mode == MODE_STEP_OBS)) {
+        // render mode: generic agent count (NT = 0) except the benched 5, any observation format
+#define SSD_LAUNCH_REC(M)                                                                                              \
+        do {                                                                                                           \
+            if (tape_mode) hipLaunchKernelGGL((k_env<M, 0, true, OV_ANY, true>), dim3(blocks), dim3(kBlock), lds, stream, SSD_ENV_ARGS); \
+            else if (hs.n == 5) hipLaunchKernelGGL((k_env<M, 5, false, OV_ANY, true>), dim3(blocks), dim3(kBlock), lds, stream, SSD_ENV_ARGS); \
+            else hipLaunchKernelGGL((k_env<M, 0, false, OV_ANY, true>), dim3(blocks), dim3(kBlock), lds, stream, SSD_ENV_ARGS); \
+        } while (0)
+        if (mode == MODE_STEP) SSD_LAUNCH_REC(MODE_STEP); else SSD_LAUNCH_REC(MODE_STEP_OBS);
+#undef SSD_LAUNCH_REC
+        return;
+    }
 #define SSD_LAUNCH(M, NT_, TP_) hipLaunchKernelGGL((k_env<M, NT_, TP_>), dim3(blocks), dim3(kBlock), lds, stream, SSD_ENV_ARGS)
 #define SSD_LAUNCH_N(M)                                                                                   \
     do {                                                                                                  \
@@ -1228,7 +1290,6 @@ void launch_env(int mode, const DevSpec* spec, const DevSpec& hs, DevState st, c
         else if (hs.n == 5) SSD_LAUNCH(M, 5, false); else if (hs.n == 10) SSD_LAUNCH(M, 10, false);       \
         else if (hs.n == 3) SSD_LAUNCH(M, 3, false); else SSD_LAUNCH(M, 0, false);                        \
     } while (0)
-    const bool tape_mode = hs.rng_mode == SSD_RNG_TAPE;
     switch (mode) {
         case MODE_RESET: if (tape_mode) SSD_LAUNCH(MODE_RESET, 0, true); else SSD_LAUNCH(MODE_RESET, 0, false); break;
         case MODE_STEP: SSD_LAUNCH_N(MODE_STEP); break;
@@ -1315,6 +1376,109 @@ void launch_import(const DevSpec* spec, const DevSpec& hs, DevState st, ssd_stat
     size_t work = (size_t)hs.N * hs.HW;
     int blocks = (int)((work + 255) / 256); if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(k_import, dim3(blocks), dim3(256), 0, stream, spec, st, src);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Render mode: beam record clear (reset) and the full-colour frames of selected envs (MapEnv._render, map_env.py:448-475)
+// ---------------------------------------------------------------------------------------------------------------
+__global__ void k_beam_clear(uint32_t* beam_rec, const uint8_t* env_mask, int n_env, int n) {
+    const int total = n_env * n;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x)
+        if (!env_mask || env_mask[i / n]) beam_rec[i] = 0u;
+}
+
+void launch_beam_clear(uint32_t* beam_rec, const uint8_t* env_mask, int n_env, int n_agents, hipStream_t stream) {
+    int blocks = (n_env * n_agents + 255) / 256; if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(k_beam_clear, dim3(blocks), dim3(256), 0, stream, beam_rec, env_mask, n_env, n_agents);
+}
+
+// Render classes: the cell codes 0..5, then 5 + agent char (6..14), 15 = 'F' (fining beam), 16 = 'C' (cleaning beam).
+// One wave per selected env: the class map is composed in LDS in the reference's overlay order -- world map, agents in id order
+// (the highest id on a cell wins), then every agent's beams in id order (get_map_with_agents_beam, map_env.py:381-404) -- and
+// leaves as RGB bytes in dword stores (the frame of env i starts at any byte: the first and last dwords are written bytewise).
+constexpr int kRenderLut = 64;                            // 17 classes x 3 bytes, padded
+constexpr int kRenderLds = SSD_MAX_CELLS + kRenderLut;
+
+__global__ __launch_bounds__(kBlock) void k_render(DevState st, const uint32_t* __restrict__ beam_rec, const uint8_t* __restrict__ lut_g,
+                                                   const int32_t* __restrict__ env_ids, int n_sel, int N, int n, int H, int W, int GS,
+                                                   uint8_t* __restrict__ frames, const int32_t* __restrict__ slot, long long slot_stride) {
+    __shared__ uint4 smem[kWavesPerBlock * kRenderLds / 16];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int i = blockIdx.x * kWavesPerBlock + wave;
+    if (i >= n_sel) return;
+    uint8_t* cm = (uint8_t*)smem + (size_t)wave * kRenderLds;
+    uint8_t* lut = cm + SSD_MAX_CELLS;
+    const int env = __builtin_amdgcn_readfirstlane(env_ids[i]);
+    const int s = slot ? __builtin_amdgcn_readfirstlane(*slot) : 0;
+    if ((unsigned)env >= (unsigned)N || s < 0) {                  // nothing is read or written for a bad id / slot
+        if (lane == 0) atomicOr(st.err, ERR_BAD_RENDER);
+        return;
+    }
+    uint4 gv = make_uint4(0, 0, 0, 0);
+    if (lane * 16 < GS) gv = *(const uint4*)(st.grid + (size_t)env * GS + lane * 16);
+    uint32_t arec = 0, brec = 0;
+    if (lane < n) { arec = st.agents[(size_t)env * n + lane].x; brec = beam_rec[(size_t)env * n + lane]; }
+    uint32_t lv = 0;
+    if (lane < kRenderLut / 4) lv = ((const uint32_t*)lut_g)[lane];
+    if (lane * 16 < GS) *(uint4*)(cm + lane * 16) = gv;
+    if (lane < kRenderLut / 4) ((uint32_t*)lut)[lane] = lv;
+    const int HW = H * W;
+    const int pr = (int)(arec & 0xFF), pc = (int)((arec >> 8) & 0xFF), po = (int)((arec >> 16) & 3);
+    const int P = lane < n ? pr * W + pc : -1 - lane;
+    wsync();
+    bool higher = false;
+    for (int b = 0; b < n; ++b) higher |= b > lane && rl(P, b) == P;
+    if (lane < n && !higher && (unsigned)P < (unsigned)HW) cm[P] = (uint8_t)(5 + agent_char(lane));
+    wsync();
+    const int b = lane / 5, k = lane - 5 * b;
+    for (int a = 0; a < n; ++a) {
+        const uint32_t w = (uint32_t)rl((int)brec, a);
+        const uint32_t ch = (w >> 16) & 0xFFu;
+        if (ch == 0) continue;                                    // (wave-uniform) agent a did not fire
+        const int ar = rl(pr, a), ac = rl(pc, a), of = rl(po, a);
+        const int dr = of == O_LEFT ? -1 : of == O_RIGHT ? 1 : 0;  // beam_record's geometry
+        const int dc = of == O_UP ? -1 : of == O_DOWN ? 1 : 0;
+        const int rr = -dc, rc = dr;
+        const int sr = b == 0 ? ar : b == 1 ? ar + rr - dr : ar - rr - dr;
+        const int sc = b == 0 ? ac : b == 1 ? ac + rc - dc : ac - rc - dc;
+        const int r = sr + (k + 1) * dr, c = sc + (k + 1) * dc;
+        const int cnt = lane < 15 ? (int)((w >> (4 * b)) & 7u) : 0;
+        if (k < cnt && (unsigned)r < (unsigned)H && (unsigned)c < (unsigned)W) cm[r * W + c] = ch == 'C' ? 16 : 15;
+        wsync();
+    }
+    const int F = HW * 3;
+    uint8_t* base = frames + (long long)s * slot_stride + (long long)i * F;
+    const int head = (int)((uintptr_t)base & 3u);
+    uint32_t* wp = (uint32_t*)(base - head);
+    const int nw = (head + F + 3) >> 2;
+    for (int j = lane; j < nw; j += kWave) {
+        uint32_t v = 0;
+        int in = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int off = 4 * j + q - head;
+            if (off >= 0 && off < F) {
+                const uint32_t p = (uint32_t)off / 3u, chn = (uint32_t)off - 3u * p;
+                const uint32_t cls = cm[p] < 16 ? cm[p] : 16u;
+                v |= (uint32_t)lut[cls * 3 + chn] << (8 * q);
+                in |= 1 << q;
+            }
+        }
+        if (in == 15) wp[j] = v;
+        else {
+            uint8_t* bp = (uint8_t*)(wp + j);
+            for (int q = 0; q < 4; ++q) if ((in >> q) & 1) bp[q] = (uint8_t)(v >> (8 * q));
+        }
+    }
+}
+
+void launch_render(const DevSpec* spec, const DevSpec& hs, DevState st, const uint32_t* beam_rec, const uint8_t* lut, const int32_t* env_ids,
+                   int n_sel, uint8_t* frames, const int32_t* slot, long long slot_stride, hipStream_t stream) {
+    (void)spec;
+    const int blocks = (n_sel + kWavesPerBlock - 1) / kWavesPerBlock;
+    hipLaunchKernelGGL(k_render, dim3(blocks), dim3(kBlock), 0, stream, st, beam_rec, lut, env_ids, n_sel, (int)hs.N, (int)hs.n,
+                       (int)hs.H, (int)hs.W, (int)hs.GS, frames, slot, slot_stride);
 }
 
 }  // namespace ssd

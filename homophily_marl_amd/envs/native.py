@@ -45,6 +45,7 @@ class NativeEnv:
         for k, v in self.out.items():
             setattr(self._so, k, v.data_ptr())
         self._obs_bufs = {}
+        self.render_on = False
 
     # ------------------------------------------------------------------------------------------------------
     def close(self):
@@ -166,6 +167,32 @@ class NativeEnv:
             raise abi.SsdError("actions must have n_env * n_agents elements")
         self._last_actions = a  # keep alive until the launch has consumed it
         return a
+
+    # ---- render mode (ssd_set_render / ssd_render) ------------------------------------------------------------
+    def set_render(self, on=True):
+        """Render mode: steps record every agent's beams (the kernels of the mode), resets clear the record; frames can be drawn."""
+        abi.check(self.lib, self.lib.ssd_set_render(self.h, 1 if on else 0))
+        self.render_on = bool(on)
+
+    def env_id_tensor(self, env_ids=None):
+        ids = range(self.n_env) if env_ids is None else env_ids
+        return torch.as_tensor(list(ids) if not isinstance(ids, torch.Tensor) else ids).to(device=self.device, dtype=torch.int32).contiguous()
+
+    def render_into(self, env_ids, frames, slot=None):
+        """Full-colour frames of the envs `env_ids` (int32 device tensor) into frames[slot] (u8 [..., k, H, W, 3]; slot: int32 device
+        scalar read by the kernel, None = frames itself is [k, H, W, 3])."""
+        k = env_ids.numel()
+        assert frames.dtype == torch.uint8 and frames.device == self.device and tuple(frames.shape[-4:]) == (k, self.H, self.W, 3)
+        assert frames[(0,) * (frames.dim() - 4)].is_contiguous() and env_ids.dtype == torch.int32 and env_ids.device == self.device
+        stride = frames.stride(0) if (slot is not None and frames.dim() == 5) else 0
+        abi.check(self.lib, self.lib.ssd_render(self.h, env_ids.data_ptr(), k, frames.data_ptr(), _ptr(slot), stride, self._stream()))
+
+    def get_frames(self, env_ids=None):
+        """u8 [k, H, W, 3] device tensor: the current frame of each env in env_ids (default: all)."""
+        ids = self.env_id_tensor(env_ids)
+        out = torch.empty(ids.numel(), self.H, self.W, 3, dtype=torch.uint8, device=self.device)
+        self.render_into(ids, out)
+        return out
 
     def poll_error(self):
         bits = C.c_int32(0)

@@ -6,6 +6,8 @@ With the default `n_env=1` every method returns what the reference returns (nump
 the reference's EpisodeRunner.  With `n_env > 1` the same object is a batch of envs and the `*_batch` methods return
 device tensors without any host round trip (used by HipVecRunner).  All dynamics run in libssd_hip.so.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -18,9 +20,7 @@ class SSDHipEnv(MultiAgentEnv):
     ENV = None
 
     def __init__(self, ascii_map=None, num_agents=1, render=False, seed=None, episode_limit=100, is_replay=False, view_size=7,
-                 map="default", extra_args=None, n_env=1, device=0, rng_mode=abi.RNG_COUNTER, env_id_base=0):
-        if render or is_replay:
-            raise NotImplementedError("rendering / replays are out of scope (SURVEY.md section 2, row 21)")
+                 map="default", extra_args=None, n_env=1, device=0, rng_mode=abi.RNG_COUNTER, env_id_base=0, replay_envs=None):
         self.native = NativeEnv(self.ENV, device=device, map=map, num_agents=num_agents, n_env=n_env, view_size=view_size,
                                 episode_limit=episode_limit, extra_args=extra_args, rng_mode=rng_mode,
                                 seed=0 if seed is None else seed, env_id_base=env_id_base)
@@ -42,6 +42,15 @@ class SSDHipEnv(MultiAgentEnv):
         self.avail_actions_batch = torch.tensor(avail, dtype=torch.int32, device=self.device).expand(n_env, n, -1).contiguous()
         self._tape = None
         self._last = None
+        # render / is_replay (map_env.py:448-475, 876-899): render mode -- the step kernels record the beams, frames are drawn on
+        # the device (get_frames).  With n_env = 1 and is_replay, step() writes <k>.png like the reference.
+        self.is_replay = bool(is_replay)
+        self.replay_envs = list(replay_envs or [0])        # the envs a runner records (HipVecRunner / HipGraphRunner)
+        if render or is_replay:
+            self.native.set_render(True)
+        self.replay_path = None
+        self._replay_pngs = []
+        self._rewards = None
 
     @staticmethod
     def native_extra_args(extra_args):
@@ -78,10 +87,14 @@ class SSDHipEnv(MultiAgentEnv):
 
     def reset(self):
         self.native.reset(self._tape)
+        self._episode_steps = 0
+        self._rewards = np.zeros(self.n_agents)
 
     def step(self, actions):
         """Returns reward f64[n], terminated bool, info (map_env.py:874-915)."""
         self._one()
+        if self.is_replay:
+            self._replay_png()
         a = torch.as_tensor(np.asarray([int(x) for x in actions], dtype=np.int32)).reshape(1, self.n_agents)
         o = self.native.step(a, self._tape)
         bits = self.native.poll_error()
@@ -89,6 +102,12 @@ class SSDHipEnv(MultiAgentEnv):
             raise KeyError("action out of range (reference: KeyError in action_map, agent.py:174-176,235-237)")
         reward = o["reward"][0].double().cpu().numpy()
         terminated = bool(o["terminated"][0].item())
+        if self._rewards is None:
+            self._rewards = np.zeros(self.n_agents)
+        self._rewards = self._rewards + reward
+        self._episode_steps = getattr(self, "_episode_steps", 0) + 1
+        if terminated and self.is_replay:
+            self._replay_png()
         info = {}
         if terminated:
             info["collective_return"] = float(o["collective_return"][0].item())
@@ -145,11 +164,39 @@ class SSDHipEnv(MultiAgentEnv):
     def get_stats(self):
         return {}
 
+    # ---- rendering (map_env.py:448-475) -------------------------------------------------------------------------
+    def get_frames(self, env_ids=None):
+        """u8 [k, H, W, 3] device tensor: get_map_with_agents_beam() in full colour for each env of env_ids (default: all)."""
+        if not self.native.render_on:
+            raise RuntimeError("get_frames needs render=True or is_replay=True")
+        return self.native.get_frames(env_ids)
+
     def render(self):
-        raise NotImplementedError("rendering is out of scope")
+        """_render(None): the current frame in a window (plt.show())."""
+        import matplotlib.pyplot as plt
+        self._one()
+        plt.imshow(self.get_frames([0])[0].cpu().numpy(), interpolation="nearest")
+        plt.show()
+
+    def _replay_png(self):
+        """_render(replay_path/<k>.png) with k = steps since the reset (map_env.py:876-877, 897-899)."""
+        from ..utils import replay
+        if self.replay_path is None:
+            self.replay_path = replay.replay_dir("results")
+            os.makedirs(self.replay_path, exist_ok=True)
+        step = getattr(self, "_episode_steps", 0)
+        coll = float(self._rewards.sum()) if self._rewards is not None else 0.0
+        p = os.path.join(self.replay_path, "%d.png" % step)
+        replay.write_frame_png(p, self.get_frames([0])[0].cpu().numpy(), step, coll, self.env_name, self.n_agents)
+        self._replay_pngs.append(p)
 
     def save_replay(self):
-        raise NotImplementedError("replays are out of scope")
+        """The video of the replay PNGs written so far (the reference: make_video_from_image_dir, an mp4 through cv2; here an
+        animated GIF through PIL).  Returns its path, or None when nothing was recorded."""
+        from ..utils import replay
+        if not self._replay_pngs:
+            return None
+        return replay.write_gif(self._replay_pngs, os.path.join(self.replay_path, "replay.gif"))
 
     def seed(self):
         return None

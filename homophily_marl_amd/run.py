@@ -146,9 +146,11 @@ def run_sequential(config, logger=None):
         pick = max(steps) if a.load_step == 0 else min(steps, key=lambda x: abs(x - a.load_step))     # run.py:137-164
         learner.load_models(os.path.join(a.checkpoint_path, str(pick)))
         runner.t_env = pick
-        if a.evaluate:
+        if a.evaluate or getattr(a, "save_replay", False):                  # run.py:166-170
             for _ in range(a.test_nepisode):
                 runner.run(test_mode=True)
+            if getattr(a, "save_replay", False):                            # run.py:76-77 (evaluate_sequential)
+                ctx.replay_dir = runner.save_replay()
             runner.close_env()
             return ctx
     episode, last_test_T, last_log_T, saved_at = 0, -a.test_interval - 1, 0, 0

@@ -380,6 +380,13 @@ class HipGraphRunner(HipVecRunner):
         self.t = 0
         self._episodes += 1
         b = self._bundle
+        if self._begin_recording(test_mode):
+            # a recorded test episode takes the eager launch sequence (no graph is replayed or captured): frame t is one ssd_render
+            # launch after the env step of t
+            self._begin_launches()
+            self.eps.fill_(sel.epsilon)
+            self._recorder.frame()
+            return
         # The episode's opening launches (env reset + first observation, the runner state's fills, the weight packs, the encoder of
         # slot 0) and its closing ones (slot-T pass, statistics) are ~25 small launches the host issues one by one while the GPU waits
         # for them (0.4 of a 7.5 ms iteration); from the third episode of a storage on they are two more hipGraph replays.
@@ -436,12 +443,14 @@ class HipGraphRunner(HipVecRunner):
     def step_once(self):
         if self.t >= self.episode_limit:
             raise RuntimeError("step_once() past episode_limit: the episode storage has no slot left (finish_episode / begin_episode first)")
-        if self._graph is not None:
+        if self._graph is not None and not self._recording:
             if self.t % self._graph_steps == 0:       # one replay advances _graph_steps timesteps
                 self._graph.replay()
         else:
             self._par = self.t & 1
             self._select(True)
+            if self._recording:
+                self._recorder.frame()
         self.t += 1
         return self.t >= self.episode_limit
 
@@ -457,6 +466,7 @@ class HipGraphRunner(HipVecRunner):
             self._stats_on_device_done = stats_on
             return self._finish_stats()
         self._select(False)
+        self._finish_recording()
         if (b.begin_graph is not None and b.finish_graph is None and not self._test_mode and self._par == 0
                 and getattr(self.args, "episode_edge_graphs", True)):
             # the closing launches of a training episode on this storage as a graph (captured after they ran eagerly for this episode)

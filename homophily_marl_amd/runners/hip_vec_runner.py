@@ -7,6 +7,7 @@ incentive-head action selection -> store.  Here the env transition and the obser
 fused kernel launch (ssd_step_observe) and nothing leaves the device.  `runner: "episode"` is the same loop with the
 reference's restriction batch_size_run == 1.
 """
+import os
 from functools import partial
 
 import torch as th
@@ -26,6 +27,8 @@ class HipVecRunner:
         if self.single_env_only:
             assert self.batch_size == 1                                   # episode_runner.py:13
         env_args = dict(args.env_args)
+        # replay_envs: the envs whose test episodes are recorded when the env is in render mode (render / is_replay)
+        self.replay_envs = list(env_args.pop("replay_envs", None) or [0])
         env_args.setdefault("n_env", self.batch_size)
         env_args.setdefault("device", getattr(args, "device_index", 0))
         env_args.setdefault("env_id_base", getattr(args, "env_id_base", 0))
@@ -40,6 +43,7 @@ class HipVecRunner:
         # obs_storage: "code" keeps observations as u8 class codes (simplified palette; 12x fewer bytes in the storage and the
         # replay buffer); the controller expands them where it consumes them
         self.obs_fmt = abi.OBS_CODE if getattr(self.args, "obs_storage", "f32") == "code" else abi.OBS_F32
+        self._recorder, self._recording, self.replays = None, False, []
 
     @property
     def sched_t(self):
@@ -61,8 +65,32 @@ class HipVecRunner:
     def get_env_info(self):
         return self.env.get_env_info()
 
-    def save_replay(self):
-        self.env.save_replay()
+    def save_replay(self, out_dir=None):
+        """Recorded test episodes (render mode) -> <local_results_path>/replays/replay-<timestamp>/episode_<i>/env_<e>/ (<k>.png,
+        frames.npz, replay.gif); without recordings, the env's own replay (n_env = 1, is_replay)."""
+        if not self.replays:
+            return self.env.save_replay()
+        from ..utils import replay
+        out_dir = out_dir or replay.replay_dir(getattr(self.args, "local_results_path", "results"))
+        for i, rec in enumerate(self.replays):
+            replay.write_replay(os.path.join(out_dir, "episode_%d" % i), rec, self.env.env_name, self.replay_envs)
+        self.replays = []
+        return out_dir
+
+    # ---- replay recording (test episodes of a render-mode env) ----------------------------------------------------
+    def _begin_recording(self, test_mode):
+        self._recording = bool(test_mode and getattr(self.env, "native", None) is not None and self.env.native.render_on)
+        if self._recording:
+            if self._recorder is None:
+                from ..utils.replay import ReplayRecorder
+                self._recorder = ReplayRecorder(self.env.native, self.replay_envs, self.episode_limit)
+            self._recorder.begin()
+        return self._recording
+
+    def _finish_recording(self):
+        if self._recording:
+            self.replays.append(self._recorder.finish(self.batch))
+            self._recording = False
 
     def close_env(self):
         self.env.close()
@@ -87,6 +115,8 @@ class HipVecRunner:
         self.mac.init_hidden(batch_size=self.batch_size)
         self._o = self.env.observe_batch(self.obs_fmt)
         self._out = None
+        if self._begin_recording(test_mode):
+            self._recorder.frame()                                      # frame 0: the state after the reset
 
     @th.no_grad()
     def step_once(self):
@@ -101,6 +131,8 @@ class HipVecRunner:
         actions_inc = self.mac.select_actions_inc(actions, self.batch, t_ep=t, t_env=self.sched_t, test_mode=test_mode)
         self.batch.update({"actions_inc": actions_inc}, ts=t)
         self._o = self._out = out
+        if self._recording:
+            self._recorder.frame()
         self.t += 1
         return self.t >= self.episode_limit
 
@@ -113,6 +145,7 @@ class HipVecRunner:
         actions_inc = self.mac.select_actions_inc(actions, self.batch, t_ep=self.t, t_env=self.sched_t, test_mode=test_mode)
         self.batch.update({"actions_inc": actions_inc}, ts=self.t)
         self.batch.update({"actions": actions}, ts=self.t)
+        self._finish_recording()
         return self._finish_stats()
 
     def _finish_stats(self):

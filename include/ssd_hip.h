@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SSD_ABI_VERSION 7
+#define SSD_ABI_VERSION 8
 
 #define SSD_MAX_AGENTS 10   /* maps hold at most 10 spawn points; agent ids >= 10 break the reference (map_env.py:370) */
 #define SSD_MAX_CELLS 1024  /* H*W upper bound (largest reference map is 48x18 = 864) */
@@ -167,9 +167,20 @@ int ssd_step_observe(ssd_env* env, const int32_t* actions, const ssd_tape* tape,
                      ssd_obs_out* obs, void* stream);
 
 /* Sticky device-side error bits (1 action out of range = KeyError in action_map, agent.py:174-176,235-237;
- * 2 malformed tape; 4 agent_by_pos KeyError; 8 tape overrun; 16 observation slot >= obs_t_slots).  Synchronises the device;
- * clears the bits. */
+ * 2 malformed tape; 4 agent_by_pos KeyError; 8 tape overrun; 16 observation slot >= obs_t_slots; 64 bad ssd_render env id / slot).
+ * Synchronises the device; clears the bits. */
 int ssd_poll_error(ssd_env* env, int32_t* bits);
+
+/* Render mode (MapEnv._render with is_replay / render, map_env.py:448-475).  on != 0 allocates the beam record and switches the
+ * handle's step / step_observe to the kernels that write it (every step records the cells each agent's FIRE / CLEAN beams covered;
+ * resets clear the record of the envs they reset); on == 0 frees it.  Call outside any stream capture. */
+int ssd_set_render(ssd_env* env, int32_t on);
+/* Full-colour frames of the envs env_ids[0..n_sel) (int32 device array) as get_map_with_agents_beam() through map_to_colors with
+ * color_map: u8 [n_sel, H, W, 3] written at frames + (*slot) * slot_stride bytes (slot: int32 device pointer read by the kernel,
+ * nullable = 0; the caller sizes the buffer for every slot it passes).  Needs render mode.  An env id outside 0..n_env-1 or a
+ * negative slot writes nothing for that env and raises error bit 64 (ssd_poll_error). */
+int ssd_render(ssd_env* env, const int32_t* env_ids, int32_t n_sel, uint8_t* frames, const int32_t* slot, int64_t slot_stride,
+               void* stream);
 
 int ssd_export_state(ssd_env* env, ssd_state* dst, void* stream);
 int ssd_import_state(ssd_env* env, const ssd_state* src, void* stream);
