@@ -76,6 +76,10 @@ int ssd_create(const ssd_config* cfg, ssd_env** out) {
     S.p_waste = cfg->waste_spawn_prob; S.p_apple = cfg->apple_respawn_prob;
     for (int i = 0; i < 4; ++i) { S.harvest_p[i] = cfg->harvest_spawn_prob[i]; S.harvest_thr[i] = draw_threshold(S.harvest_p[i]); }
     if ((long)S.n * 3 * S.VV >= 65536) { delete E; return fail(SSD_ERR_INVALID, "n_agents * 3 * V * V must stay below 65536"); }
+    // the slice k_env actually reserves per wave (launch_env), and the class-code gather's write range inside its planes (any team
+    // size can take the run-time instantiation: TAPE mode, render mode)
+    if ((long)lds_per_wave(S) * kWavesPerBlock > 160 * 1024) { delete E; return fail(SSD_ERR_INVALID, "k_env's LDS slices exceed the 160 KiB of a workgroup"); }
+    if (code_gather_end(S, kCodeGroupMax) > lds_planes_bytes(S)) { delete E; return fail(SSD_ERR_INVALID, "class-code gather overruns its LDS planes"); }
 
     // Row-major scan of the layout (map_env.py:143-148, cleanup.py:77-90, harvest.py:31-35).
     std::vector<int> spawn;

@@ -110,6 +110,15 @@ constexpr float F16_MAX = 65504.f;
 // LDS bytes one wave needs: grid | agent overlay | padded class map | output planes (+16 alignment slack) | colour lut.
 // The class map + planes region doubles as scratch for the tape-mode waste ranks (2 * 256 bytes) during the step.
 __host__ __device__ inline int lds_planes_bytes(const DevHead& s) { return ((s.n * 3 * s.VV + 16) + 15) & ~15; }
+// The grouped class-code gather (observe_windows, SSD_OBS_CODE without the side output) writes agent a's window to planes bytes
+// [delta + a * VV, delta + (a + 1) * VV), delta < 16.  Its lanes outside the window write to the dump byte behind the last window plus
+// g * VV, g < min(ag, n) the agent's slot in its group of ag; the lanes of absent agents (past n in the last group) write to the dump
+// byte itself.  code_gather_end: one past the last planes byte that gather can touch -- at most lds_planes_bytes (checked by ssd_create).
+__host__ __device__ inline int code_dump_byte(int delta, int n, int VV) { return delta + n * VV; }
+__host__ __device__ inline int code_gather_end(const DevHead& s, int ag) {
+    return code_dump_byte(15, s.n, s.VV) + ((ag < s.n ? ag : s.n) - 1) * s.VV + 1;
+}
+constexpr int kCodeGroupMax = 5;   // the largest group (the run-time team size, NT = 0)
 // (+ one agent's class-code window, V * V rounded up to 16, + 16 for the dump byte of idle lanes: the obs_code side output)
 __host__ __device__ inline bool lds_code_all(const DevHead& s) { return s.n * SSD_CODE_AGENT_STRIDE(s.V) <= 2560; }   // all agents' windows fit
 __host__ __device__ inline int lds_code_bytes(const DevHead& s) { return (lds_code_all(s) ? s.n : 1) * SSD_CODE_AGENT_STRIDE(s.V) + 16; }

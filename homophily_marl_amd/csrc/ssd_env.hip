@@ -686,15 +686,16 @@ __device__ __forceinline__ void observe_windows(Env& E, int env, const DevObsOut
         else if (E.O == O_DOWN) { ci0 = -Wp; cj0 = -1; c00 = (V - 1) * Wp + (V - 1); }
         else { ci0 = 1; cj0 = -Wp; c00 = (V - 1) * Wp; }
         const int base0 = pr0 * Wp + pc0 + c00;
-        const int dumpc = delta + L;                                  // one byte behind the last window (inside the planes' slack)
+        const int dumpc = code_dump_byte(delta, n, VV);               // one byte behind the last window (extent: code_gather_end)
         // Agents in groups of AG: every class read of the group is in flight before the first code is written (one LDS round
         // trip per group and trip, not one per agent -- the reads and writes are byte accesses to buffers the compiler must
         // assume to alias, so it keeps the source order).  The kernel is bound by the NUMBER of vector instructions (4 waves per
         // SIMD keep the vector pipe ~ 3/4 busy), so nothing here is predicated per agent: lanes outside the window (column V of
         // the 2^vshift dealt, rows past V) read whatever byte their affine index lands on -- within a row and a column of the
         // window, inside this wave's LDS -- and write it to a dump zone behind the last window: the destination offsets are
-        // computed once per trip, an agent adds its a * VV.
-        constexpr int AG = (NT > 0 && NT < 5) ? NT : 5;
+        // computed once per trip, an agent adds its a * VV.  Absent agents (past n in the last group) write to the dump byte itself, so
+        // that the zone ends (n + min(AG, n) - 1) * VV bytes past delta, inside the planes even for n = 1 (code_gather_end).
+        constexpr int AG = (NT > 0 && NT < kCodeGroupMax) ? NT : kCodeGroupMax;
         const int dstep = rpi * V;
         for (int a0 = 0; a0 < n; a0 += AG) {
             int sidx[AG], sstep[AG];
@@ -722,7 +723,7 @@ __device__ __forceinline__ void observe_windows(Env& E, int env, const DevObsOut
                     const bool live = (NT > 0 && NT % AG == 0) || a0 + g < n;         // (wave-uniform; a constant for the shipped team sizes)
 #pragma unroll
                     for (int u = 0; u < 4; ++u)   // class bit 1 / 2 / 4 -> code 2 / 1 / 3
-                        E.pl[(live ? wr[u] : dumpc) + g * VV] = PMC ? cls[g][u] : (uint8_t)((0x30120u >> (4 * cls[g][u])) & 0xFu);
+                        E.pl[live ? wr[u] + g * VV : dumpc] = PMC ? cls[g][u] : (uint8_t)((0x30120u >> (4 * cls[g][u])) & 0xFu);
                 }
             }
         }

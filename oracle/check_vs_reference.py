@@ -27,6 +27,14 @@ CONFIGS = [
     dict(env="cleanup", map="default10", num_agents=10, view_size=7),
     dict(env="harvest", map="default10", num_agents=5, view_size=15),
     dict(env="harvest", map="default10", num_agents=10, view_size=7),
+    # the edges of what ssd_create accepts: team sizes 1 / 2 / 8 / 9, windows of 1 x 1 (view 0) and above 32 x 32 (view >= 16)
+    dict(env="cleanup", map="default5", num_agents=1, view_size=7),
+    dict(env="cleanup", map="default5", num_agents=1, view_size=0),
+    dict(env="cleanup", map="default5", num_agents=2, view_size=3),
+    dict(env="harvest", map="default10", num_agents=1, view_size=15),
+    dict(env="harvest", map="default10", num_agents=2, view_size=20),
+    dict(env="cleanup", map="default10", num_agents=8, view_size=16),
+    dict(env="harvest", map="default10", num_agents=9, view_size=16),
 ]
 
 
@@ -132,6 +140,7 @@ def main():
     ap.add_argument("--steps", type=int, default=2000, help="steps per (config, mode, option set)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--obs-every", type=int, default=7)
+    ap.add_argument("--configs", default="", help="comma-separated indices into CONFIGS (default: all)")
     a = ap.parse_args()
     option_sets = [
         None,                                                            # defaults: masked turn/fire, spawn rot 0 (LEFT)
@@ -142,7 +151,7 @@ def main():
     ]
     total = 0
     t0 = time.time()
-    for cfg in CONFIGS:
+    for cfg in [CONFIGS[int(i)] for i in a.configs.split(",")] if a.configs else CONFIGS:
         for mode in ("tape", "counter"):
             for oi, ea in enumerate(option_sets):
                 nsteps = run_config(cfg, a.steps, a.seed + oi, mode, ea, a.obs_every)

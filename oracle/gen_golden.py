@@ -50,6 +50,16 @@ TRAJ = [
      dict(random_spawn_point=True, random_spawn_rotation=None), 51, 0.1),
     ("harvest5_randspawn", dict(env="harvest", map="default10", num_agents=5, view_size=7), 3, 20,
      dict(ALL, random_spawn_point=True), 52, 0.1),
+    # the edges of what ssd_create accepts: 1, 2 and 8 agents (no compile-time team size), windows of 1 x 1 (view 0: the observation
+    # is shorter than one 16-byte vector), 7 x 7, and above 32 x 32 (view >= 16: one window row per pass of the gather)
+    ("cleanup1_default", dict(env="cleanup", map="default5", num_agents=1, view_size=7), 1, 60, None, 61, 0.1),
+    ("cleanup2_allact", dict(env="cleanup", map="default5", num_agents=2, view_size=7), 2, 40, ALL, 62, 0.15),
+    ("cleanup2_v3_full", dict(env="cleanup", map="default5", num_agents=2, view_size=3), 2, 40, dict(ALL, obs_color="full"), 63, 0.15),
+    ("harvest1_v15", dict(env="harvest", map="default10", num_agents=1, view_size=15), 2, 30, ALL, 64, 0.1),
+    ("harvest2_v20_full", dict(env="harvest", map="default10", num_agents=2, view_size=20), 2, 30,
+     dict(ALL, obs_color="full", random_spawn_rotation=None), 65, 0.15),
+    ("cleanup8_v16", dict(env="cleanup", map="default10", num_agents=8, view_size=16), 2, 30, ALL, 66, 0.2),
+    ("cleanup1_v0", dict(env="cleanup", map="default5", num_agents=1, view_size=0), 2, 40, None, 67, 0.1),
 ]
 
 

@@ -68,7 +68,7 @@ def test_frames_match_the_reference(path, n_env):
     env.close()
 
 
-@pytest.mark.parametrize("n", [5, 10])
+@pytest.mark.parametrize("n", [1, 2, 5, 10])
 def test_render_mode_changes_no_dynamics(n):
     """COUNTER mode, 258 envs, every action: the render-mode kernels (step and step+observe) against the shipped ones, same seed."""
     from homophily_marl_amd.envs.native import NativeEnv
