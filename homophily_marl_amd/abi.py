@@ -6,7 +6,7 @@ The native library is REQUIRED: there is no CPU fallback on the product path.  `
 import ctypes as C
 import os
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 MAX_AGENTS = 10
 MAX_CELLS = 1024
 MAX_SITES = 256
@@ -241,8 +241,25 @@ def policy_head_plan(n_env, n_agents, fused_with_encoder=False):
     return a.value, b.value, c.value
 
 
+ENCODE_EDGE_MIN, ENCODE_EDGE_MAX, ENCODE_BANDS_MAX = 3, 63, 6
+
+
+def encode_edge_supported(V):
+    """Whether the class-LUT encoder (ssd_policy_encode, ssd_policy_pack_encoder_lut, ssd_conv_wgrad_codes) takes window edge V:
+    every odd edge 3 .. 63 (view_size 1 .. 31)."""
+    return ENCODE_EDGE_MIN <= V <= ENCODE_EDGE_MAX and V % 2 == 1
+
+
+def encode_band_rows(V):
+    """SSD_ENCODE_BAND_ROWS: output rows per band (O = V - 2 rows; one band up to O = 13, else ceil(O / 10) bands, at most 6)"""
+    O = V - 2
+    nb = 1 if O <= 13 else min(ENCODE_BANDS_MAX, (O + 9) // 10)
+    return (O + nb - 1) // nb
+
+
 def encode_bands(V):
-    return 3 if V == 31 else 1
+    """SSD_ENCODE_BANDS: bands the encoder cuts the output rows into (each writes a partial Linear sum when > 1)"""
+    return (V - 2 + encode_band_rows(V) - 1) // encode_band_rows(V)
 
 
 ENCODE_LAYOUT_TOEPLITZ, ENCODE_LAYOUT_LUT = 0, 1
@@ -251,7 +268,8 @@ ENCODE_LUT_TABLE_BYTES = 3 * 64 * 6 * 4
 
 def encode_lut_ksteps(V):
     """SSD_ENCODE_LUT_KSTEPS: K-steps of the Linear image in the class-LUT layout (4 output positions each, numbered through the bands)"""
-    return 73 + 73 + 66 if V == 31 else 43
+    O, R, nb = V - 2, encode_band_rows(V), encode_bands(V)
+    return (nb - 1) * ((R * O + 3) // 4) + ((O - (nb - 1) * R) * O + 3) // 4
 
 
 def encode_frag_bytes(V, precision, layout=ENCODE_LAYOUT_TOEPLITZ):

@@ -705,21 +705,29 @@ int ssd_set_learner_precision(int32_t precision) {
 }
 int ssd_learner_precision(void) { return learner_precision(); }
 int ssd_conv_wgrad_partial_rows(int32_t rows) { return rows < 1 ? 0 : conv_wgrad_partial_rows(rows); }
+// the class-LUT encoder, its pack and the conv weight gradient: every odd window edge 3 .. 63 (view_size 1 .. 31)
+static bool encode_edge_ok(int V) { return V >= SSD_ENCODE_EDGE_MIN && V <= SSD_ENCODE_EDGE_MAX && (V & 1); }
+#define SSD_EDGE_MSG ": view_edge must be odd, 3 .. 63 (view_size 1 .. 31)"
+
 int ssd_conv_wgrad_codes(const uint8_t* codes, const float* d_conv, float* partial, int32_t rows, int32_t view_edge, void* stream) {
     if (!codes || !d_conv || !partial || rows < 1) return fail(SSD_ERR_INVALID, "bad argument");
-    if (launch_conv_wgrad(codes, d_conv, partial, rows, view_edge, (hipStream_t)stream)) return fail(SSD_ERR_UNSUPPORTED, "ssd_conv_wgrad_codes is instantiated for 15 x 15 and 31 x 31 windows");
+    if (!encode_edge_ok(view_edge)) return fail(SSD_ERR_UNSUPPORTED, "ssd_conv_wgrad_codes" SSD_EDGE_MSG);
+    if (launch_conv_wgrad(codes, d_conv, partial, rows, view_edge, (hipStream_t)stream)) return fail(SSD_ERR_UNSUPPORTED, "ssd_conv_wgrad_codes" SSD_EDGE_MSG);
     return launched();
 }
 
 static int check_encode(const ssd_policy_encode_args* a) {
     if (!a || !a->codes || !a->conv_frags || !a->lin_frags || !a->conv_b || !a->lin_b || a->rows < 1 || a->n_agents < 1 || a->rows % a->n_agents)
         return fail(SSD_ERR_INVALID, "bad argument");
-    if (a->view_edge != 15 && a->view_edge != 31)
-        return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_encode is instantiated for view_size 7 and 15 (15 x 15 / 31 x 31 windows); use ssd_conv_leaky + GEMM");
+    if (!encode_edge_ok(a->view_edge)) return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_encode" SSD_EDGE_MSG "; use ssd_conv_leaky + GEMM");
+    const bool shipped = a->view_edge == 15 || a->view_edge == 31;
+    if (!shipped && a->layout != SSD_ENCODE_LAYOUT_LUT)
+        return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_encode: the Toeplitz layout is instantiated for 15 x 15 / 31 x 31 windows; other edges take SSD_ENCODE_LAYOUT_LUT");
     if (a->precision != 0 && a->precision != 1 && a->precision != 2) return fail(SSD_ERR_INVALID, "precision must be 1 (bf16) or 2 (f32-equivalent)");
     if (a->alphabet != SSD_CODE_CLASS && a->alphabet != SSD_CODE_CHANNEL_MASK) return fail(SSD_ERR_INVALID, "alphabet");
     if (a->layout != SSD_ENCODE_LAYOUT_TOEPLITZ && a->layout != SSD_ENCODE_LAYOUT_LUT) return fail(SSD_ERR_INVALID, "layout");
-    if (a->act && a->layout != SSD_ENCODE_LAYOUT_TOEPLITZ) return fail(SSD_ERR_INVALID, "the activation output (training forward) takes the Toeplitz images");
+    if (a->act && shipped && a->layout != SSD_ENCODE_LAYOUT_TOEPLITZ)
+        return fail(SSD_ERR_INVALID, "the activation output (training forward) takes the Toeplitz images at 15 x 15 / 31 x 31");
     const int bands = SSD_ENCODE_BANDS(a->view_edge);
     if (bands == 1 ? (!a->out || a->part || a->out_stride < 32) : (!a->part || a->out)) return fail(SSD_ERR_INVALID, "one band writes `out`, several bands write `part`");
     if ((reinterpret_cast<uintptr_t>(a->conv_frags) | reinterpret_cast<uintptr_t>(a->lin_frags) | reinterpret_cast<uintptr_t>(a->part)) & 15)
@@ -746,8 +754,9 @@ int ssd_policy_pack_encoder_lut(const float* conv_w, const float* conv_b, const 
     if (!conv_w || !conv_b || !lin_w || !table || !lin_frags) return fail(SSD_ERR_INVALID, "null argument");
     if (precision != 1 && precision != 2) return fail(SSD_ERR_INVALID, "precision must be 1 or 2");
     if ((reinterpret_cast<uintptr_t>(table) | reinterpret_cast<uintptr_t>(lin_frags)) & 15) return fail(SSD_ERR_INVALID, "images must be 16-byte aligned");
+    if (!encode_edge_ok(view_edge)) return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_pack_encoder_lut" SSD_EDGE_MSG);
     if (launch_pack_encoder_lut(conv_w, conv_b, lin_w, view_edge, precision, table, lin_frags, (hipStream_t)stream))
-        return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_pack_encoder_lut: view_edge must be 15 or 31");
+        return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_pack_encoder_lut" SSD_EDGE_MSG);
     return launched();
 }
 
@@ -827,7 +836,7 @@ int ssd_policy_head_inc_encode(const ssd_policy_head* h, const ssd_policy_encode
     if (e->slot_t && (e->slot_t == h->next_t_out)) return fail(SSD_ERR_INVALID, "ssd_policy_head_inc_encode: the encoder must not read the scalar the inc head writes");
     const int rc = launch_policy_inc_encode(h, e, (hipStream_t)stream);
     if (rc == -3) return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_head is instantiated for n_actions 9 (Cleanup) and 8 (Harvest)");
-    if (rc == -2) return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_encode is instantiated for 15 x 15 / 31 x 31 windows");
+    if (rc == -2) return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_head_inc_encode is instantiated for 15 x 15 / 31 x 31 windows (other edges: ssd_policy_encode + ssd_policy_head_inc)");
     if (rc) return fail(SSD_ERR_DEVICE, "ssd_policy_head_inc_encode: launch / hipFuncSetAttribute(max dynamic LDS) failed");
     return launched();
 }

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <stdint.h>
+#include "../../include/ssd_hip.h"
 
 namespace ssd {
 
@@ -598,12 +599,87 @@ __global__ __launch_bounds__(256) void k_conv_wgrad(const uint8_t* __restrict__ 
     }
 }
 
+// k_conv_wgrad for every other odd window edge V = 3 .. 63 (view_size 1 .. 31): the same kernel with V a run-time value (one
+// instantiation; the shipped 15 / 31 kernels stay as they are)
+__global__ __launch_bounds__(256) void k_conv_wgrad_any(const uint8_t* __restrict__ codes, const float* __restrict__ d_conv, float* __restrict__ partial, int R,
+                                                        const int V) {
+    const int O = V - 2, P = O * O, VV = V * V;
+    __shared__ uint8_t win[4][(SSD_ENCODE_EDGE_MAX * SSD_ENCODE_EDGE_MAX + 15) & ~15];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wg = blockIdx.x * 4 + wave;                              // global wave = row of `partial`
+    float acc[6][27], accb[6];
+#pragma unroll
+    for (int oc = 0; oc < 6; ++oc) {
+        accb[oc] = 0.f;
+#pragma unroll
+        for (int k = 0; k < 27; ++k) acc[oc][k] = 0.f;
+    }
+    // items = (window, pass of 64 positions); the six gradient values of the NEXT item are requested before the current one is
+    // accumulated (a wave has nothing else to hide the load latency behind)
+    const int PASSES = (P + 63) / 64;
+    const int row_begin = wg * CW_ROWS, rows_here = row_begin >= R ? 0 : (R - row_begin < CW_ROWS ? R - row_begin : CW_ROWS);
+    const int items = rows_here * PASSES;
+    auto fetch = [&](int it, float (&v)[6]) {
+        const int row = row_begin + it / PASSES, p = (it % PASSES) * 64 + lane;
+        const float* dr = d_conv + (size_t)row * 6 * P;
+#pragma unroll
+        for (int oc = 0; oc < 6; ++oc) v[oc] = p < P ? dr[oc * P + p] : 0.f;
+    };
+    float cur[6], nxt[6];
+    if (items > 0) fetch(0, nxt);
+    for (int it = 0; it < items; ++it) {
+#pragma unroll
+        for (int oc = 0; oc < 6; ++oc) cur[oc] = nxt[oc];
+        if (it + 1 < items) fetch(it + 1, nxt);
+        const int pass = it % PASSES;
+        if (pass == 0) {                                               // a new window: its class codes into the wave's LDS buffer
+            const int row = row_begin + it / PASSES;
+            __builtin_amdgcn_wave_barrier();
+            for (int e = lane; e < VV; e += 64) win[wave][e] = codes[(size_t)row * VV + e];
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+        const int p = pass * 64 + lane;
+        const int pc = p < P ? p : 0, y = pc / O, x = pc - y * O;
+        float mk[27];                                                  // [tap = dy * 3 + dx][plane]: 1 where the patch cell lights the plane
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int c = win[wave][(y + t / 3) * V + x + t % 3];
+            mk[3 * t + 0] = c == 2 ? 1.f : 0.f;                        // waste -> R
+            mk[3 * t + 1] = c == 1 ? 1.f : 0.f;                        // apple -> G
+            mk[3 * t + 2] = c == 3 ? 1.f : 0.f;                        // wall / agent -> B
+        }
+#pragma unroll
+        for (int oc = 0; oc < 6; ++oc) {
+            const float v = cur[oc];                                   // 0 for the lanes past the last position
+            accb[oc] += v;
+#pragma unroll
+            for (int k = 0; k < 27; ++k) acc[oc][k] = fmaf(v, mk[k], acc[oc][k]);
+        }
+    }
+    // sum over the 64 lanes (fixed order), lane 63 writes; layout: [oc][ch][dy][dx] then the 6 bias sums
+    float* out = partial + (size_t)wg * CW_OUT;
+#pragma unroll
+    for (int oc = 0; oc < 6; ++oc) {
+#pragma unroll
+        for (int k = 0; k < 27; ++k) {
+            const float v = wave_sum_to_lane63(acc[oc][k]);
+            const int t = k / 3, ch = k - 3 * t;
+            if (lane == 63) out[(oc * 3 + ch) * 9 + t] = v * (255.f / 256.f);
+        }
+        const float b = wave_sum_to_lane63(accb[oc]);
+        if (lane == 63) out[6 * 27 + oc] = b;
+    }
+}
+
 int conv_wgrad_partial_rows(int R) { return ((R + CW_ROWS - 1) / CW_ROWS + 3) / 4 * 4; }
 
 int launch_conv_wgrad(const uint8_t* codes, const float* d_conv, float* partial, int R, int V, hipStream_t s) {
     const int waves = conv_wgrad_partial_rows(R);
     if (V == 15) hipLaunchKernelGGL(k_conv_wgrad<15>, dim3(waves / 4), dim3(256), 0, s, codes, d_conv, partial, R);
     else if (V == 31) hipLaunchKernelGGL(k_conv_wgrad<31>, dim3(waves / 4), dim3(256), 0, s, codes, d_conv, partial, R);
+    else if (V >= SSD_ENCODE_EDGE_MIN && V <= SSD_ENCODE_EDGE_MAX && (V & 1))
+        hipLaunchKernelGGL(k_conv_wgrad_any, dim3(waves / 4), dim3(256), 0, s, codes, d_conv, partial, R, V);
     else return -2;
     return 0;
 }

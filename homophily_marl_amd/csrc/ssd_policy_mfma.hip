@@ -1182,6 +1182,8 @@ void launch_pack_head(const ssd_policy_head_params* p, int prec, void* image, hi
 template <int V> struct Geo;
 template <> struct Geo<15> { static constexpr int O = 13, CP = 16, NXT = 2, XTP = 1, R = 13, NB = 1; };
 template <> struct Geo<31> { static constexpr int O = 29, CP = 32, NXT = 4, XTP = 2, R = 10, NB = 3; };
+static_assert(Geo<15>::R == SSD_ENCODE_BAND_ROWS(15) && Geo<15>::NB == SSD_ENCODE_BANDS(15) && Geo<31>::R == SSD_ENCODE_BAND_ROWS(31) &&
+              Geo<31>::NB == SSD_ENCODE_BANDS(31), "the shipped bands are the header's geometry");
 // (a template parameter BT of the kernels: 4 for 15 x 15 windows at up to 32 768 rows -- Cleanup-5 x 4096: 320 workgroups balance the
 // chip better behind the inc heads, k_inc_encode 32.4 -> 30.5 us -- else 5, which moves fewer Linear fragments per row)
 constexpr int ENC_BT_MAX = 5;                      // batch tiles (16 rows each) per workgroup: Linear weights are fetched once per 80 rows
@@ -1738,6 +1740,204 @@ static int enc_bt(int V, int rows) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// k_encode_lut_any: encode_body_lut for every other odd window edge V = 3 .. 63 (view_size 1 .. 31), with the geometry a run-time
+// value: ONE instantiation per precision serves all 29 edges (the shipped 15 / 31 kernels stay as they are).  Geometry of V
+// (include/ssd_hip.h): O = V - 2, bands of R = SSD_ENCODE_BAND_ROWS(V) output rows (blockIdx.y), WPR = ceil(V / 16) packed dwords per
+// window row; a position's three cells are bits 2 (x & 15) .. + 5 of the dword pair (x >> 4, + 1) of its row.  The staging walks
+// (batch row, input row, 16-cell chunk) items with one unaligned 16-byte load each (the tail path of encode_body_lut at the buffer's
+// end).  With `act` (the learner's forward) the lane that evaluates a position also writes LeakyReLU(conv) of its six channels.
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int ENC_ANY_BT = 5;
+__host__ __device__ constexpr int lut_any_batch_row_dwords(int V) { return ((SSD_ENCODE_BAND_ROWS(V) + 3) * ((V + 15) >> 4)) | 1; }
+__host__ __device__ constexpr size_t enc_lut_any_lds_bytes(int V) {
+    const size_t work = (size_t)((ENC_ANY_BT * 16 * lut_any_batch_row_dwords(V) * 4 + 15) & ~15) + LUT_TABLE_BYTES;
+    const size_t red = (size_t)ENC_WAVES * ENC_ANY_BT * 2 * 1024;
+    return work > red ? work : red;
+}
+
+template <int PREC>
+__global__ __launch_bounds__(ENC_WAVES * 64) void k_encode_lut_any(EncK a, int V) {
+    constexpr int BT = ENC_ANY_BT;
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+    const int O = V - 2, R = SSD_ENCODE_BAND_ROWS(V), WPR = (V + 15) >> 4, PRW = lut_any_batch_row_dwords(V), P = O * O;
+    const int PACKED = (BT * 16 * PRW * 4 + 15) & ~15;
+    constexpr float CS = PREC == 2 ? ENC_CSCALE : 1.f, INV = PREC == 2 ? 1.f / (ENC_CSCALE * ENC_LSCALE) : 1.f;
+    uint32_t* packed = reinterpret_cast<uint32_t*>(lds_raw);          // [BT * 16 rows][PRW dwords]
+    float* table = reinterpret_cast<float*>(lds_raw + PACKED);         // [3][64][6]
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int m = lane & 15, q = lane >> 4;
+    const int row0 = (int)blockIdx.x * (BT * 16);
+    const int band = (int)blockIdx.y, y0 = band * R;
+    const int Rb = O - y0 < R ? O - y0 : R;
+    const int64_t slot_now = a.slot_t ? *a.slot_t : 0;
+    const long t_off = a.slot_t ? ((long)slot_now + a.slot_add) * a.slot_stride : 0;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
+        if (a.slot_t_copy) *a.slot_t_copy = slot_now;
+        if (a.counter_inc) *a.counter_inc += 1;
+    }
+    // ---- stage: the table, class codes -> packed rows ----------------------------------------------------------------------------
+    {
+        constexpr int NV = LUT_TABLE_BYTES / 16;
+        if (tid < NV) reinterpret_cast<u32x4*>(table)[tid] = reinterpret_cast<const u32x4*>(a.conv_frags)[tid];
+        typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(1)));
+        typedef __attribute__((address_space(1))) u32x4_u gl_u32x4_u;
+        typedef __attribute__((address_space(1))) uint32_t gl_u32;
+        const uintptr_t cbase = reinterpret_cast<uintptr_t>(a.codes), cend = cbase + (uintptr_t)a.code_bytes;
+        const int items = BT * 16 * (R + 2) * WPR;
+        for (int it = tid; it < items; it += ENC_WAVES * 64) {
+            const int h = it % WPR, ry = it / WPR, yy = ry % (R + 2), r = ry / (R + 2);
+            const int row = row0 + r, y = y0 + yy;
+            uint32_t word = 0u;
+            if (row < a.rows && y < V) {
+                const int b = row / a.n, i = row - b * a.n;
+                const uintptr_t ptr = cbase + (uintptr_t)((long)b * a.env_stride + t_off + (long)i * a.agent_stride + y * V + 16 * h);
+                u32x4 c;
+                if (ptr + 16 <= cend) c = *reinterpret_cast<const gl_u32x4_u*>(ptr);
+                else {                                                 // the buffer's last bytes: aligned dwords that hold readable bytes
+                    const uintptr_t al = ptr & ~(uintptr_t)3, lim = (cend + 3) & ~(uintptr_t)3;
+                    uint32_t prev = *reinterpret_cast<const gl_u32*>(al);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const uintptr_t nx = al + 4 * (e + 1);
+                        const uint32_t next = nx + 4 <= lim ? *reinterpret_cast<const gl_u32*>(nx) : 0u;
+                        c[e] = __builtin_amdgcn_alignbyte(next, prev, (uint32_t)(ptr & 3));
+                        prev = next;
+                    }
+                }
+                // (bytes past the row's V cells belong to the next row: no position reads them)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    uint32_t cls = c[e] & 0x03030303u;
+                    if (a.mask_alphabet) {
+                        const uint32_t b0 = c[e] & 0x01010101u, b1 = (c[e] >> 1) & 0x01010101u, b2 = (c[e] >> 2) & 0x01010101u;
+                        cls = (b1 | b2) | ((b0 | b2) << 1);
+                    }
+                    word |= pack4x2(cls) << (8 * e);
+                }
+            }
+            packed[r * PRW + yy * WPR + h] = word;
+        }
+    }
+    __syncthreads();
+    // ---- K-steps of this band, a contiguous range per wave ---------------------------------------------------------------------------
+    f32x4 accl[BT][2];
+#pragma unroll
+    for (int bt = 0; bt < BT; ++bt) { accl[bt][0] = f32x4{0.f, 0.f, 0.f, 0.f}; accl[bt][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    const int KS = (Rb * O + 3) >> 2, ks_base = band * ((R * O + 3) >> 2);      // (every band before the last holds R rows)
+    const int s_begin = (wave * KS) / ENC_WAVES, s_end = ((wave + 1) * KS) / ENC_WAVES;
+    const float inv_o = 1.f / (float)O;                                // p / O for p < 61 * 13: (p + 0.5) / O is >= 1 / 122 from an integer
+    auto load_la = [&](int sl, u32x4 (&la)[2][PREC]) {
+        const size_t gs = (size_t)(ks_base + sl);
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int t = 0; t < PREC; ++t)
+                la[mt][t] = *reinterpret_cast<const u32x4*>(a.lin_frags + (((gs * 2 + mt) * PREC + t) * 64 + lane) * 16);
+    };
+    u32x4 la[2][PREC], la_next[2][PREC];
+    if (s_begin < s_end) load_la(s_begin, la_next);
+    const uint32_t* my_rows = packed + m * PRW;
+    for (int sl = s_begin; sl < s_end; ++sl) {
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int t = 0; t < PREC; ++t) la[mt][t] = la_next[mt][t];
+        if (sl + 1 < s_end) load_la(sl + 1, la_next);
+        const int p = 4 * sl + q;
+        int yl = (int)(((float)p + 0.5f) * inv_o), x = p - yl * O;
+        const bool live = yl < Rb;                                     // positions past the band read row 0 (zero Linear weights)
+        if (!live) { yl = 0; x = 0; }
+        const uint32_t* rp = my_rows + yl * WPR + (x >> 4);
+        const int sh = 2 * (x & 15);
+#pragma unroll
+        for (int bt = 0; bt < BT; ++bt) {
+            const uint32_t* rb = rp + bt * 16 * PRW;
+            int idx[3];
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy) {
+                const uint64_t w = (uint64_t)rb[dy * WPR] | ((uint64_t)rb[dy * WPR + 1] << 32);
+                idx[dy] = (int)((w >> sh) & 63u);
+            }
+            f32x2 sums[3];
+            {
+                const f32x2* t0 = reinterpret_cast<const f32x2*>(table + idx[0] * LUT_ENTRY_F);
+                const f32x2* t1 = reinterpret_cast<const f32x2*>(table + LUT_DY_F + idx[1] * LUT_ENTRY_F);
+                const f32x2* t2 = reinterpret_cast<const f32x2*>(table + 2 * LUT_DY_F + idx[2] * LUT_ENTRY_F);
+#pragma unroll
+                for (int c2 = 0; c2 < 3; ++c2) sums[c2] = (t0[c2] + t1[c2]) + t2[c2];
+            }
+            float v[8];
+#pragma unroll
+            for (int c2 = 0; c2 < 3; ++c2) { v[2 * c2] = leaky(sums[c2].x); v[2 * c2 + 1] = leaky(sums[c2].y); }
+            v[6] = 0.f; v[7] = 0.f;
+            if (a.act && live) {                                       // the training forward keeps the conv activations
+                const int row = row0 + bt * 16 + m;
+                if (row < a.rows) {
+                    float* ar = a.act + (size_t)row * 6 * P + (y0 + yl) * O + x;
+#pragma unroll
+                    for (int c = 0; c < 6; ++c) ar[(size_t)c * P] = v[c] * (1.f / CS);
+                }
+            }
+            u32x4 xh, xl;
+            split8<PREC>(v, xh, xl);
+            if (PREC == 2) {
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) accl[bt][mt] = mma<PREC>(la[mt][PREC - 1], xh, accl[bt][mt]);
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) accl[bt][mt] = mma<PREC>(la[mt][0], xl, accl[bt][mt]);
+            }
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) accl[bt][mt] = mma<PREC>(la[mt][0], xh, accl[bt][mt]);
+        }
+    }
+    // ---- add the waves' partial sums in a fixed order (deterministic), finish ----------------------------------------------------------
+    __syncthreads();
+    f32x4* red = reinterpret_cast<f32x4*>(lds_raw);                    // [wave][bt][mt][lane]
+#pragma unroll
+    for (int bt = 0; bt < BT; ++bt)
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) red[((wave * BT + bt) * 2 + mt) * 64 + lane] = accl[bt][mt];
+    __syncthreads();
+    for (int it = tid; it < BT * 2 * 64; it += ENC_WAVES * 64) {
+        const int l = it & 63, mt = (it >> 6) & 1, bt = it >> 7;
+        f32x4 sum = red[((0 * BT + bt) * 2 + mt) * 64 + l];
+#pragma unroll
+        for (int w = 1; w < ENC_WAVES; ++w) sum += red[((w * BT + bt) * 2 + mt) * 64 + l];
+        const int row = row0 + bt * 16 + (l & 15), f0 = 16 * mt + 4 * (l >> 4);
+        if (row < a.rows) {
+            const int b = row / a.n, i = row - b * a.n;
+            const size_t orow = a.agent_major ? (size_t)i * (a.rows / a.n) + b : (size_t)row;
+            if (a.part) {
+                f32x4 o;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) o[r] = sum[r] * INV;
+                *reinterpret_cast<f32x4*>(a.part + ((size_t)band * a.rows + orow) * 32 + f0) = o;
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) a.out[orow * a.out_stride + f0 + r] = leaky(fmaf(sum[r], INV, a.lin_b[f0 + r]));
+            }
+        }
+    }
+}
+
+template <int PREC>
+static int launch_encode_lut_any(const EncK& k, int V, hipStream_t s) {
+    constexpr size_t lds_max = enc_lut_any_lds_bytes(SSD_ENCODE_EDGE_MAX);
+    static_assert(lds_max >= enc_lut_any_lds_bytes(15) && lds_max <= 160 * 1024, "LDS of the run-time-edge encoder");
+    static bool done[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
+    if (!done[dev]) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_encode_lut_any<PREC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max) != hipSuccess)
+            return -1;
+        done[dev] = true;
+    }
+    const int groups = (k.rows + ENC_ANY_BT * 16 - 1) / (ENC_ANY_BT * 16);
+    hipLaunchKernelGGL(k_encode_lut_any<PREC>, dim3(groups, SSD_ENCODE_BANDS(V)), dim3(ENC_WAVES * 64), enc_lut_any_lds_bytes(V), s, k, V);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // k_inc_encode: the inc head of timestep t and the encoder of timestep t + 1 as ONE launch (pipelined rollout).  Both follow the env
 // step of t and share no data: the inc head reads the input rows of t (one buffer of a pair), the encoder reads the observation the
 // env step just stored in slot t + 1 and writes the other buffer.  Either kernel fills the register file of a CU with one workgroup,
@@ -1898,6 +2098,8 @@ int launch_policy_encode(const ssd_policy_encode_args* p, hipStream_t s) {
     EncK k;
     encode_args(p, k);
     const int prec = p->precision == 1 ? 1 : 2;
+    if (p->act && p->layout == SSD_ENCODE_LAYOUT_LUT)   // the learner's forward at the other window edges (the class-LUT body writes `act`)
+        return prec == 2 ? launch_encode_lut_any<2>(k, p->view_edge, s) : launch_encode_lut_any<1>(k, p->view_edge, s);
     if (p->act) {       // the learner's forward (also emits LeakyReLU(conv)): f32-equivalent, or the labelled bf16 variant
         if (p->view_edge == 15) return prec == 2 ? launch_encode_t<15, 2, true>(k, s) : launch_encode_t<15, 1, true>(k, s);
         if (p->view_edge == 31) return prec == 2 ? launch_encode_t<31, 2, true>(k, s) : launch_encode_t<31, 1, true>(k, s);
@@ -1906,7 +2108,7 @@ int launch_policy_encode(const ssd_policy_encode_args* p, hipStream_t s) {
     if (p->layout == SSD_ENCODE_LAYOUT_LUT) {
         if (p->view_edge == 15) return prec == 2 ? launch_encode_lut_t<15, 2>(k, s) : launch_encode_lut_t<15, 1>(k, s);
         if (p->view_edge == 31) return prec == 2 ? launch_encode_lut_t<31, 2>(k, s) : launch_encode_lut_t<31, 1>(k, s);
-        return -2;
+        return prec == 2 ? launch_encode_lut_any<2>(k, p->view_edge, s) : launch_encode_lut_any<1>(k, p->view_edge, s);
     }
     if (p->view_edge == 15) return prec == 2 ? launch_encode_t<15, 2, false>(k, s) : launch_encode_t<15, 1, false>(k, s);
     if (p->view_edge == 31) return prec == 2 ? launch_encode_t<31, 2, false>(k, s) : launch_encode_t<31, 1, false>(k, s);
@@ -1995,6 +2197,42 @@ __global__ __launch_bounds__(256) void k_pack_encoder_lut(const float* __restric
     }
 }
 
+// the same images for the other window edges (k_encode_lut_any): V a run-time value, one instantiation per precision
+template <int PREC>
+__global__ __launch_bounds__(256) void k_pack_encoder_lut_any(const float* __restrict__ cw, const float* __restrict__ cb, const float* __restrict__ lw, float* table,
+                                                              uint8_t* lin_frags, int32_t* err, int V) {
+    const int O = V - 2, R = SSD_ENCODE_BAND_ROWS(V), NB = SSD_ENCODE_BANDS(V), P = O * O, KSTEPS = SSD_ENCODE_LUT_KSTEPS(V);
+    const int NTAB = 3 * LUT_DY_F, NLIN = KSTEPS * 2 * 512, KF = (R * O + 3) / 4;     // KF: K-steps of a full band
+    constexpr float CS = PREC == 2 ? ENC_CSCALE : 1.f, LS = PREC == 2 ? ENC_LSCALE : 1.f;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (PREC == 2 && e < 6 && err) {      // range of the conv activations at the scale CS: see k_pack_encoder
+        float bound = fabsf(cb[e]);
+        for (int tap = 0; tap < 9; ++tap) {
+            float mx = 0.f;
+            for (int ch = 0; ch < 3; ++ch) mx = fmaxf(mx, fabsf(cw[(e * 3 + ch) * 9 + tap]));
+            bound += mx * (255.f / 256.f);
+        }
+        if (!(bound * CS <= F16_MAX)) atomicOr(err, ERR_F16_RANGE);
+    }
+    if (e < NTAB) {                       // the table: as k_pack_encoder_lut
+        const int dy = e / LUT_DY_F, idx = (e / LUT_ENTRY_F) % 64, c = e % LUT_ENTRY_F;
+        double v = dy == 0 ? (double)cb[c] : 0.0;
+        for (int dx = 0; dx < 3; ++dx) {
+            const int cls = (idx >> (2 * dx)) & 3;
+            const int plane = cls == 2 ? 0 : (cls == 1 ? 1 : (cls == 3 ? 2 : -1));
+            if (plane >= 0) v += (double)cw[((c * 3 + plane) * 3 + dy) * 3 + dx] * (255.0 / 256.0);
+        }
+        table[e] = (float)(v * (double)CS);
+    } else if (e < NTAB + NLIN) {
+        const int i = e - NTAB, mt = (i >> 9) & 1, gs = i >> 10, lane = (i >> 3) & 63, j = i & 7, q = lane >> 4, m = lane & 15;
+        const int band = gs / KF < NB - 1 ? gs / KF : NB - 1, base = band * KF;
+        const int Rb = O - band * R < R ? O - band * R : R;
+        const int p = 4 * (gs - base) + q, yl = p / O, x = p - yl * O;
+        const float w = (j < 6 && yl < Rb) ? lw[(size_t)(16 * mt + m) * (6 * P) + j * P + (band * R + yl) * O + x] * LS : 0.f;
+        store_term<PREC>(lin_frags + (((size_t)(gs * 2 + mt) * PREC) * 64 + lane) * 16 + 2 * j, w, (size_t)64 * 16, err);
+    }
+}
+
 int launch_pack_encoder_lut(const float* cw, const float* cb, const float* lw, int V, int prec, void* table, void* lin_frags, hipStream_t s) {
     float* t = static_cast<float*>(table);
     uint8_t* l = static_cast<uint8_t*>(lin_frags);
@@ -2007,7 +2245,11 @@ int launch_pack_encoder_lut(const float* cw, const float* cb, const float* lw, i
     if (V == 15) { if (prec == 2) SSD_PACKL(15, 2); else SSD_PACKL(15, 1); return 0; }
     if (V == 31) { if (prec == 2) SSD_PACKL(31, 2); else SSD_PACKL(31, 1); return 0; }
 #undef SSD_PACKL
-    return -2;
+    if (V < SSD_ENCODE_EDGE_MIN || V > SSD_ENCODE_EDGE_MAX || !(V & 1)) return -2;
+    const int total = 3 * LUT_DY_F + SSD_ENCODE_LUT_KSTEPS(V) * 2 * 512;
+    if (prec == 2) hipLaunchKernelGGL(k_pack_encoder_lut_any<2>, dim3((total + 255) / 256), dim3(256), 0, s, cw, cb, lw, t, l, err, V);
+    else hipLaunchKernelGGL(k_pack_encoder_lut_any<1>, dim3((total + 255) / 256), dim3(256), 0, s, cw, cb, lw, t, l, err, V);
+    return 0;
 }
 
 int launch_pack_encoder(const float* cw, const float* cb, const float* lw, int V, int prec, void* conv_frags, void* lin_frags, hipStream_t s) {

@@ -42,14 +42,20 @@ class FastPolicy:
         self.fused = bool(fused) and H == 64 and self.inp + self.A <= 64 and self.A + 7 <= 16 and mac.input_flags is not None
         # the per-layer composition assembles the shipped input layout only (ssd_build_inputs)
         assert self.fused or mac.shipped_flags, "FastPolicy: this _build_inputs flag set needs the fused heads (FastPolicy.supports)"
-        # the fused encoder exists for 15 x 15 and 31 x 31 windows (view_size 7 / 15: the shipped configurations)
-        self.fused_enc = self.fused and self.V in (15, 31) and tuple(a.obs_dims) == (self.V, self.V)
-        self.bands = abi.encode_bands(self.V) if self.fused_enc else 1
         # encoder images: the class-LUT layout (conv as a table sum, no conv MFMAs: include/ssd_hip.h SSD_ENCODE_LAYOUT_LUT) unless
         # enc_layout / SSD_ENC_LAYOUT asks for round 3's Toeplitz fragments (kept as the cross-check and for the training forward)
         import os
         lay = getattr(a, "enc_layout", None) or os.environ.get("SSD_ENC_LAYOUT", "lut")
         self.enc_layout = abi.ENCODE_LAYOUT_TOEPLITZ if str(lay).lower() in ("toeplitz", "0") else abi.ENCODE_LAYOUT_LUT
+        # the fused encoder: the class-LUT layout for every odd window edge 3 .. 63 (view_size 1 .. 31), the Toeplitz layout for
+        # 15 x 15 and 31 x 31 windows (view_size 7 / 15: the shipped configurations)
+        shipped = self.V in (15, 31)
+        self.fused_enc = self.fused and abi.encode_edge_supported(self.V) and tuple(a.obs_dims) == (self.V, self.V) \
+            and (shipped or self.enc_layout == abi.ENCODE_LAYOUT_LUT)
+        # act_inc_encode (inc head of t + encoder of t + 1 as one launch: the pipelined rollout) is instantiated for 15 / 31 only;
+        # at the other edges the rollout takes the standalone encoder and inc-head launches
+        self.inc_encode = self.fused_enc and shipped
+        self.bands = abi.encode_bands(self.V) if self.fused_enc else 1
         # bf16 MFMA products an f32-equivalent product costs (bench.py's roofline accounting); conv: the planes are exact, 2
         self.n_products = dict(encode_conv=2, encode_lin=3, head_env=3, head_inc=3) if precision == 2 else \
             dict(encode_conv=1, encode_lin=1, head_env=1, head_inc=1)
@@ -323,7 +329,7 @@ class FastPolicy:
         """act_inc of timestep t on inputs_pair[buf] AND encode of timestep t + 1 into inputs_pair[buf ^ 1] (31 x 31 windows: into
         the band sums) as ONE launch (ssd_policy_head_inc_encode): the pipelined rollout's third launch of a timestep.  `codes` /
         slot_t / slot_add as in encode(): the observation the env step of t just produced (storage slot *slot_t + slot_add)."""
-        assert self.fused and self.fused_enc
+        assert self.fused and self.inc_encode
         ha = self._inc_args(actions, pos, orient, reward, clean_num, apple_den, eps, step, q_out=q_out, file=file, buf=buf)
         ea, codes = self._encode_args(None, codes, slot_t, mask_alphabet, buf=buf ^ 1, slot_add=slot_add)
         abi.check(self.lib, self.lib.ssd_policy_head_inc_encode(C.byref(ha), C.byref(ea), self._stream()))

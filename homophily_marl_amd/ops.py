@@ -636,7 +636,7 @@ def expand_codes(codes):
 
 
 def encode_codes_supported(codes):
-    return codes.is_cuda and codes.dtype == th.uint8 and codes.shape[-1] == codes.shape[-2] and codes.shape[-1] in (15, 31)
+    return codes.is_cuda and codes.dtype == th.uint8 and codes.shape[-1] == codes.shape[-2] and abi.encode_edge_supported(codes.shape[-1])
 
 
 class _EncodeCodes(th.autograd.Function):
@@ -660,11 +660,12 @@ class _EncodeCodes(th.autograd.Function):
         prec = LEARNER_PRECISION
         need = any(ctx.needs_input_grad[1:])
         # the training forward also emits LeakyReLU(conv) and runs on the Toeplitz images; a forward without gradients (the target net)
-        # takes the class-LUT layout: the conv as a table sum, a third of the matrix-core work
-        layout = abi.ENCODE_LAYOUT_TOEPLITZ if need else abi.ENCODE_LAYOUT_LUT
+        # takes the class-LUT layout: the conv as a table sum, a third of the matrix-core work.  Other window edges than 15 / 31 have
+        # the class-LUT kernel only, which then also emits LeakyReLU(conv).
+        layout = abi.ENCODE_LAYOUT_TOEPLITZ if need and V in (15, 31) else abi.ENCODE_LAYOUT_LUT
         cbytes, lbytes = abi.encode_frag_bytes(V, prec, layout)
         cf, lf = th.empty(cbytes, dtype=th.uint8, device=dev), th.empty(lbytes, dtype=th.uint8, device=dev)
-        pack = lib.ssd_policy_pack_encoder if need else lib.ssd_policy_pack_encoder_lut
+        pack = lib.ssd_policy_pack_encoder if layout == abi.ENCODE_LAYOUT_TOEPLITZ else lib.ssd_policy_pack_encoder_lut
         abi.check(lib, pack(cw.data_ptr(), cb.data_ptr(), lw.data_ptr(), V, prec, cf.data_ptr(), lf.data_ptr(), st))
         act = th.empty(R, 6, O, O, dtype=th.float32, device=dev) if need else None
         bands = abi.encode_bands(V)
@@ -680,7 +681,7 @@ class _EncodeCodes(th.autograd.Function):
             feat = th.empty(R, 32, dtype=th.float32, device=dev)
             ea.out, ea.out_stride = feat.data_ptr(), 32
             abi.check(lib, lib.ssd_policy_encode(C.byref(ea), st))
-        else:       # 31 x 31 windows: per-band partial sums of the Linear, finished here (each output adds `bands` values)
+        else:       # 31 x 31 windows and up: per-band partial sums of the Linear, finished here (each output adds `bands` values)
             part = th.empty(bands, R, 32, dtype=th.float32, device=dev)
             ea.part = part.data_ptr()
             abi.check(lib, lib.ssd_policy_encode(C.byref(ea), st))
@@ -715,7 +716,7 @@ class _EncodeCodes(th.autograd.Function):
 
 
 def encode_codes(codes, conv_w, conv_b, lin_w, lin_b):
-    """features [R, 32] of windows given as u8 class codes [R, V, V] (V = 15 or 31, on the device): see _EncodeCodes."""
+    """features [R, 32] of windows given as u8 class codes [R, V, V] (V odd, 3 .. 63, on the device): see _EncodeCodes."""
     return _EncodeCodes.apply(codes, conv_w, conv_b, lin_w, lin_b)
 
 

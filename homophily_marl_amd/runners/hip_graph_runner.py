@@ -56,7 +56,7 @@ class HipGraphRunner(HipVecRunner):
         # the fused encoder reads u8 class codes: the env kernel emits them next to the f32 observation (format R storage) or the
         # storage itself holds them (format C)
         self._want_code = bool(getattr(a, "fast_policy", True) and getattr(a, "fused_policy", True) and simplified
-                               and self.obs_fmt != abi.OBS_CODE and self.env.native.V in (15, 31))
+                               and self.obs_fmt != abi.OBS_CODE and abi.encode_edge_supported(self.env.native.V))
         self._dense_cur = self.env.native.obs_buffers(self.obs_fmt, want_code=self._want_code)   # obs / pos / orient written by the env kernel
         self.cur = self._dense_cur
         self.t_dev = th.zeros(1, dtype=th.long, device=dev)
@@ -112,7 +112,7 @@ class HipGraphRunner(HipVecRunner):
             self.direct_obs = self.fast.fused_enc and self.obs_fmt in (abi.OBS_F32, abi.OBS_CODE)
             self.fold_store = self.direct_obs and G == 1 and bool(getattr(a, "fold_store", True))
             if self.obs_fmt == abi.OBS_CODE and not self.direct_obs:
-                # class-code storage is consumed by the fused encoder only; other window sizes take the generic timestep
+                # class-code storage is consumed by the fused encoder only; windows it does not take (view 0) take the generic timestep
                 # (the torch controller expands the codes itself)
                 self.fast, self.fasts, self.fold_store = None, [], False
         # Pipelined timestep (3 launches): env head -> env step -> [inc head of t + encoder of t + 1] as one launch
@@ -123,7 +123,7 @@ class HipGraphRunner(HipVecRunner):
             K -= 1
         self._graph_steps_planned = K
         use_graph = bool(getattr(a, "rollout_graph", True))
-        self.pipe = bool(self.fast is not None and self.fold_store and self.fast.fused and self.fast.fused_enc and self.groups == 1
+        self.pipe = bool(self.fast is not None and self.fold_store and self.fast.fused and self.fast.inc_encode and self.groups == 1
                          and getattr(a, "pipeline_encode", True) and (K % 2 == 0 or not use_graph)
                          and (self.obs_fmt == abi.OBS_CODE or self._want_code))
         self.rng_copy = th.zeros(1, dtype=th.long, device=dev)          # pipelined: the env head's copy of rng_ctr for the inc head

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SSD_ABI_VERSION 8
+#define SSD_ABI_VERSION 9
 
 #define SSD_MAX_AGENTS 10   /* maps hold at most 10 spawn points; agent ids >= 10 break the reference (map_env.py:370) */
 #define SSD_MAX_CELLS 1024  /* H*W upper bound (largest reference map is 48x18 = 864) */
@@ -487,7 +487,7 @@ int ssd_set_learner_precision(int32_t precision);
 int ssd_learner_precision(void);
 
 /* Weight (and bias) gradient of the encoder's Conv2d(3, 6, 3) on windows given as SSD_OBS_CODE class codes u8 [rows, V, V]
- * (V = 15 / 31): d_conv = dL/d(conv output) f32 [rows, 6, V-2, V-2] -> partial f32 [ssd_conv_wgrad_partial_rows(rows), 168]: per
+ * (V odd, 3 .. 63; ABI 9: every edge, before 15 / 31 only): d_conv = dL/d(conv output) f32 [rows, 6, V-2, V-2] -> partial f32 [ssd_conv_wgrad_partial_rows(rows), 168]: per
  * wave, 162 weight-gradient sums in conv_w order [oc][ch][dy][dx] (the planes' 255/256 included) followed by the 6 bias sums; the
  * caller adds the rows (ssd_column_sums).  Rows past the last wave's windows are written as zeros. */
 #define SSD_CONV_WGRAD_COLS 168
@@ -647,7 +647,9 @@ typedef struct ssd_policy_head_params {
 /* image: [n, SSD_POLICY_IMAGE_BYTES(precision)] */
 int ssd_policy_pack_head(const ssd_policy_head_params* params, int32_t precision, void* image, void* stream);
 
-/* ssd_policy_encode: rgb_preprocess for 15 x 15 (view_size 7) and 31 x 31 (view_size 15) windows of the SIMPLIFIED palette.
+/* ssd_policy_encode: rgb_preprocess for odd window edges V = 3 .. 63 (view_size 1 .. 31) of the SIMPLIFIED palette: the Toeplitz layout
+ * below for 15 x 15 (view_size 7) and 31 x 31 (view_size 15) windows, the class-LUT layout (SSD_ENCODE_LAYOUT_LUT) for every edge
+ * (ABI 9; other edges than 15 / 31 with `act` too: the learner's training forward there).  Even edges, V < 3 and V > 63 are refused.
  * Input: one byte per window cell in either alphabet (`alphabet`: SSD_CODE_CLASS = the SSD_OBS_CODE classes of an episode storage,
  * SSD_CODE_CHANNEL_MASK = the side buffer of ssd_obs_out.obs_code); the three colour planes are rebuilt in LDS as one-hot bytes, so the
  * conv is a banded (Toeplitz) GEMM over 16 batch rows per MFMA and the whole encoder runs on the matrix cores:
@@ -675,7 +677,7 @@ int ssd_policy_pack_head(const ssd_policy_head_params* params, int32_t precision
  *   lin_frags  [unit = ((y * XTP + xtp) * 3 + s)][output tile 2][term][lane][8]: element (q, m, j) = lin_w[16 Mt + m][oc * P + y * O + x],
  *              r = 4 q + (j & 3), oc = 2 s + (r >> 3), x = 8 (2 xtp + (j >> 2)) + (r & 7), 0 where x >= O   (XTP = 1 / 2 pairs of
  *              8-position tiles per output row) */
-/* SSD_ENCODE_LAYOUT_LUT (ssd_policy_encode_args.layout; launches without `act`): the CONVOLUTION AS A TABLE SUM.  A window cell is one
+/* SSD_ENCODE_LAYOUT_LUT (ssd_policy_encode_args.layout; at 15 / 31 launches without `act`): the CONVOLUTION AS A TABLE SUM.  A window cell is one
  * of four classes and lights at most one plane at 255/256, so the three taps of input row dy contribute to all six channels a value
  * that depends only on the three classes under them: conv[c](y, x) = sum_dy T[dy][cls(y+dy, x) + 4 cls(y+dy, x+1) + 16 cls(y+dy, x+2)][c]
  * (T[0] carries the bias) -- exact f32 sums of entries built by ssd_policy_pack_encoder_lut, no matrix-core work for the conv.  Images:
@@ -689,9 +691,20 @@ int ssd_policy_pack_head(const ssd_policy_head_params* params, int32_t precision
 #define SSD_ENCODE_LAYOUT_TOEPLITZ 0
 #define SSD_ENCODE_LAYOUT_LUT 1
 #define SSD_ENCODE_LUT_TABLE_BYTES (3 * 64 * 6 * 4)
-#define SSD_ENCODE_LUT_KSTEPS(V) ((V) == 31 ? 73 + 73 + 66 : 43)
+/* Band geometry of an odd window edge V = 3 .. 63 (O = V - 2 output rows): O <= 13 is one band; else ceil(O / 10) bands, at most 6
+ * (the env head folds at most 6 band sums), of SSD_ENCODE_BAND_ROWS(V) = ceil(O / bands) rows, the last band holding the rest.
+ * 15 -> 1 band of 13 rows, 31 -> 3 bands of 10 rows, 63 -> 6 bands of 11 rows. */
+#define SSD_ENCODE_EDGE_MIN 3
+#define SSD_ENCODE_EDGE_MAX 63
+#define SSD_ENCODE_BANDS_MAX 6
+#define SSD_ENCODE_NB0_(O) ((O) <= 13 ? 1 : ((O) + 9) / 10 < SSD_ENCODE_BANDS_MAX ? ((O) + 9) / 10 : SSD_ENCODE_BANDS_MAX)
+#define SSD_ENCODE_BAND_ROWS(V) (((V) - 2 + SSD_ENCODE_NB0_((V) - 2) - 1) / SSD_ENCODE_NB0_((V) - 2))
+#define SSD_ENCODE_BANDS(V) (((V) - 2 + SSD_ENCODE_BAND_ROWS(V) - 1) / SSD_ENCODE_BAND_ROWS(V))
+/* K-steps of 4 positions: ceil(R * O / 4) per full band, ceil(rows of the last band * O / 4) for the last (15 -> 43, 31 -> 212) */
+#define SSD_ENCODE_LUT_KSTEPS(V)                                                                                                   \
+    ((SSD_ENCODE_BANDS(V) - 1) * ((SSD_ENCODE_BAND_ROWS(V) * ((V) - 2) + 3) / 4) +                                                 \
+     (((V) - 2 - (SSD_ENCODE_BANDS(V) - 1) * SSD_ENCODE_BAND_ROWS(V)) * ((V) - 2) + 3) / 4)
 #define SSD_ENCODE_LUT_LIN_BYTES(V, precision) (SSD_ENCODE_LUT_KSTEPS(V) * 2 * (precision) * 1024)
-#define SSD_ENCODE_BANDS(V) ((V) == 31 ? 3 : 1)
 #define SSD_ENCODE_UNITS(V) ((V) == 31 ? 29 * 2 * 3 : 13 * 1 * 3)
 #define SSD_ENCODE_CONV_FRAG_BYTES(V, precision) ((precision) * 9 * 1024)
 #define SSD_ENCODE_LIN_FRAG_BYTES(V, precision) (SSD_ENCODE_UNITS(V) * 2 * (precision) * 1024)
@@ -711,18 +724,19 @@ typedef struct ssd_policy_encode_args {
                                       activations the learner's backward needs (the training forward of the encoder) */
     int32_t slot_add;              /* the time slot read is *slot_t + slot_add (the pipelined rollout encodes slot t + 1 while the
                                       device time index still says t); the caller keeps it inside the storage */
-    int32_t layout;                /* ABI 7: SSD_ENCODE_LAYOUT_TOEPLITZ (0: images of ssd_policy_pack_encoder) or SSD_ENCODE_LAYOUT_LUT (images
-                                      of ssd_policy_pack_encoder_lut; not with `act`) */
+    int32_t layout;                /* ABI 7: SSD_ENCODE_LAYOUT_TOEPLITZ (0: images of ssd_policy_pack_encoder; V = 15 / 31) or
+                                      SSD_ENCODE_LAYOUT_LUT (images of ssd_policy_pack_encoder_lut; with `act` only for V other than 15 / 31) */
 } ssd_policy_encode_args;
 int ssd_policy_encode(const ssd_policy_encode_args* args, void* stream);
 /* ssd_policy_head_inc(inc_args) and ssd_policy_encode(enc_args) as ONE launch -- the pipelined rollout's third launch of a timestep:
  * both follow the env step of t and share no data (the inc head reads the input rows of t, the encoder reads the observation of slot
  * t + 1 and must write a DIFFERENT `inputs` buffer / `part`), so one launch-to-launch gap of the timestep disappears.  enc_args: no
- * act, no slot_t_copy / counter_inc (the heads hand the counters over, see ssd_policy_head); same precision as inc_args. */
+ * act, no slot_t_copy / counter_inc (the heads hand the counters over, see ssd_policy_head); same precision as inc_args.  Instantiated
+ * for 15 x 15 / 31 x 31 windows; other edges: ssd_policy_encode + ssd_policy_head_inc (SSD_ERR_UNSUPPORTED here). */
 int ssd_policy_head_inc_encode(const ssd_policy_head* inc_args, const ssd_policy_encode_args* enc_args, void* stream);
 /* conv_b (f32 [6]): read only for the range bound of the conv activations (see SSD_ERRBIT_F16_RANGE). */
 /* conv_w f32 [6, 3, 3, 3], conv_b [6], lin_w [32, 6 (V-2)^2] -> the images of SSD_ENCODE_LAYOUT_LUT: table (SSD_ENCODE_LUT_TABLE_BYTES,
- * 16-byte aligned) and lin_frags (SSD_ENCODE_LUT_LIN_BYTES(V, precision)). */
+ * 16-byte aligned) and lin_frags (SSD_ENCODE_LUT_LIN_BYTES(V, precision)); V odd, 3 .. 63. */
 int ssd_policy_pack_encoder_lut(const float* conv_w, const float* conv_b, const float* lin_w, int32_t view_edge, int32_t precision, void* table,
                                 void* lin_frags, void* stream);
 int ssd_policy_pack_encoder(const float* conv_w, const float* conv_b, const float* lin_w, int32_t view_edge, int32_t precision, void* conv_frags,
