@@ -6,7 +6,7 @@ The native library is REQUIRED: there is no CPU fallback on the product path.  `
 import ctypes as C
 import os
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 MAX_AGENTS = 10
 MAX_CELLS = 1024
 MAX_SITES = 256
@@ -199,7 +199,7 @@ class SsdTdLossArgs(C.Structure):
                 ("q_env", C.c_void_p), ("q_inc", C.c_void_p), ("tq_env", C.c_void_p), ("tq_inc", C.c_void_p),
                 ("actions", C.c_void_p), ("actions_inc", C.c_void_p), ("avail", C.c_void_p), ("reward", C.c_void_p), ("clean_num", C.c_void_p),
                 ("terminated", C.c_void_p), ("filled", C.c_void_p), ("dens", C.c_void_p),
-                ("dq_env", C.c_void_p), ("dq_inc", C.c_void_p), ("partials", C.c_void_p)]
+                ("dq_env", C.c_void_p), ("dq_inc", C.c_void_p), ("partials", C.c_void_p), ("consider_others_inc", C.c_int32)]
 
 
 TD_LOSS_PARTIALS = 16

@@ -138,6 +138,10 @@ __global__ void k_incentive_transfer(int32_t B, int32_t T, int32_t n, const int6
 //                                  td = q_env[t, a_t] - (r_env + gamma_env (1 - terminated) tq_env[t+1, a*])
 //   inc head TD                    per receiver j != i: a*_j = argmax_c q_inc[t+1, i, j, c];
 //                                  td = sum_j q_inc[t, i, j, a_inc_ij] - (r_inc + gamma_inc (1 - terminated) sum_j tq_inc[t+1, i, j, a*_j])
+//     consider_others_inc (:122-126,148-171), with recv_c,j(t) = the RECEIVER j's received counts (zero, +, -) at t (receive_*
+//     [bs, t, n].unsqueeze(2) broadcasts over the giver i):
+//                                  chosen_ij = sum_c q_inc[t, i, j, c] recv_c,j(t) / (n - 1);
+//                                  tmax_ij = (tq_inc[t+1, i, j, a*_j] + sum_c tq_inc[t+1, i, j, c] recv_c,j(t+1) - tq_inc[t+1, i, j, a_inc(t+1)_ij]) / (n - 1)
 //   similarity loss (:184-217)     window (sim_horizon) activity flags -> cluster = 2 rw + cn (the exact-value rule standing in for x-means,
 //                                  SURVEY.md 8c), idle = cn + rw; for every ordered triple i != k != j != i with equal clusters:
 //                                  clamp_min(-log softmax(q_inc[t, i, j])[a_inc_kj], threshold) * idle_i * idle_k
@@ -220,19 +224,44 @@ __global__ __launch_bounds__(128) void k_td_sim_loss(ssd_td_loss_args a) {
     for (int k = 0; k < A; ++k) dqe[k] = k == a_t ? g_env : 0.f;
     // ---- inc head: TD over the receivers j != i ---------------------------------------------------------------------------------
     const size_t qi = (size_t)it * n * 3, qi1 = qi + (size_t)n * n * 3;
+    // consider_others_inc: the chosen value and the target weigh receiver j's received counts (zero, +, -) at t and t + 1, over n - 1
+    const bool others = a.consider_others_inc != 0;
+    const int64_t* ainc1 = ainc + (size_t)n * n;                                // (b, t + 1)
+    auto recv_of = [&](const int64_t* acts, int j, float& r0, float& r1, float& r2) {
+        int p = 0, m = 0;
+        for (int g = 0; g < n; ++g) {
+            if (g == j) continue;
+            const int64_t x = acts[(size_t)g * n + j];
+            p += x == 1; m += x == 2;
+        }
+        r0 = (float)(n - 1 - p - m); r1 = (float)p; r2 = (float)m;
+    };
     float sum_chosen = 0.f, sum_tmax = 0.f, q_inc_taken = 0.f;
     for (int j = 0; j < n; ++j) {
         const int c = (int)ainc[(size_t)i * n + j];
         const float qc = a.q_inc[qi + j * 3 + c];
         q_inc_taken += qc;
         if (j == i) continue;
-        sum_chosen += qc;
         const float* sel = (a.double_q ? a.q_inc : a.tq_inc) + qi1 + j * 3;
         const int best = sel[1] > sel[0] ? (sel[2] > sel[1] ? 2 : 1) : (sel[2] > sel[0] ? 2 : 0);   // first maximum
-        sum_tmax += a.tq_inc[qi1 + j * 3 + best];
+        const float* tq = a.tq_inc + qi1 + j * 3;
+        if (others) {
+            const float* q = a.q_inc + qi + j * 3;
+            float r0, r1, r2;
+            recv_of(ainc, j, r0, r1, r2);
+            sum_chosen += (q[0] * r0 + q[1] * r1 + q[2] * r2) / (float)(n - 1);
+            recv_of(ainc1, j, r0, r1, r2);
+            const float other = tq[0] * r0 + tq[1] * r1 + tq[2] * r2;
+            sum_tmax += (tq[best] + other - tq[(int)ainc1[(size_t)i * n + j]]) / (float)(n - 1);
+        } else {
+            sum_chosen += qc;
+            sum_tmax += tq[best];
+        }
     }
     const float td_inc = sum_chosen - (r_inc + a.gamma_inc * live * sum_tmax);
     const float g_inc = 2.f * td_inc * mask * mask / den0;
+    // d chosen_ij / d q_inc[t, i, j, x]: 1 at the taken action, or recv_x,j(t) / (n - 1) with consider_others_inc
+    const float gd = g_inc / (float)(n - 1);
     // ---- similarity loss (:208-217) and the inc gradient rows ------------------------------------------------------------------------
     float sim_num = 0.f;
     const float wsim = a.sim_loss_weight / den1;
@@ -256,7 +285,13 @@ __global__ __launch_bounds__(128) void k_td_sim_loss(ssd_td_loss_args a) {
             }
         }
         const int cij = (int)ainc[(size_t)i * n + j];
-        for (int x = 0; x < 3; ++x) dqi[j * 3 + x] = wsim * g[x] + ((j != i && x == cij) ? g_inc : 0.f);
+        if (others && j != i) {
+            float r0, r1, r2;
+            recv_of(ainc, j, r0, r1, r2);
+            dqi[j * 3] = wsim * g[0] + gd * r0; dqi[j * 3 + 1] = wsim * g[1] + gd * r1; dqi[j * 3 + 2] = wsim * g[2] + gd * r2;
+        } else {
+            for (int x = 0; x < 3; ++x) dqi[j * 3 + x] = wsim * g[x] + ((j != i && x == cij) ? g_inc : 0.f);
+        }
     }
     out[2] = (td_env * mask) * (td_env * mask); out[3] = (td_inc * mask) * (td_inc * mask); out[4] = sim_num;
     out[5] = chosen_env; out[6] = q_inc_taken; out[7] = (float)give; out[8] = rv;

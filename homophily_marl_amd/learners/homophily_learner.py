@@ -214,10 +214,9 @@ class HomophilyLearner:
 
     def _fused(self, batch):
         """The loss and its gradient w.r.t. the Q-values as ONE HIP launch (ssd_td_sim_loss) instead of ~100 tensor ops + autograd:
-        device batches with the shipped loss flags; everything else (CPU tensors of the CPU suite / gloo rehearsal,
-        consider_others_inc) keeps the tensor-op statement below, which is also what the GPU tests check the kernel against."""
-        return (bool(getattr(self.args, "fused_loss", True)) and batch["reward"].is_cuda and not self.args.consider_others_inc
-                and self.n_agents >= 2)
+        device batches under every loss flag (double_q, consider_others_inc); CPU tensors (the CPU suite / gloo rehearsal) keep the
+        tensor-op statement below, which is also what the GPU tests check the kernel against."""
+        return bool(getattr(self.args, "fused_loss", True)) and batch["reward"].is_cuda and self.n_agents >= 2
 
     def denominators(self, batch):
         """[mask.sum(), sim_mask.sum()] of the GLOBAL batch (all-reduced over the data-parallel group)."""
@@ -309,7 +308,9 @@ class HomophilyLearner:
             tmax_env = th.gather(target_q_env, dim=-1, index=best_env)          # [bs, t-1, n, 1]
             tmax_inc_self = th.gather(target_q_inc, dim=-1, index=best_inc).squeeze(-1)
         else:
-            tmax_env = target_q_env.max(dim=-1)[0]
+            # keepdim: [bs, t-1, n, 1] as in the double-Q branch (the reference's :160 drops the action axis, so that .sum(dim=-1)
+            # below would add the agents and the target would not broadcast against the rewards)
+            tmax_env = target_q_env.max(dim=-1, keepdim=True)[0]
             tmax_inc_self = target_q_inc.max(dim=-1)[0]
         tmax_inc = (tmax_inc_self + other - target_next_inc) / (n - 1) if a.consider_others_inc else tmax_inc_self
 

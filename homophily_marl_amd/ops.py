@@ -165,6 +165,7 @@ def _td_loss_args(batch, a, n_actions, partials):
     t.gamma_env, t.gamma_inc, t.reward_scale = float(a.gamma_env), float(a.gamma_inc), float(a.reward_scale)
     t.incentive_ratio, t.incentive_cost, t.incentive = float(a.incentive_ratio), float(a.incentive_cost), float(a.incentive)
     t.seq_len, t.sim_threshold, t.sim_loss_weight = float(T1), float(a.sim_threshold), float(a.sim_loss_weight)
+    t.consider_others_inc = int(bool(a.consider_others_inc))
     for k, v in keep.items():
         setattr(t, k, v.data_ptr())
     t.partials = partials.data_ptr()

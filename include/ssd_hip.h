@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SSD_ABI_VERSION 9
+#define SSD_ABI_VERSION 10
 
 #define SSD_MAX_AGENTS 10   /* maps hold at most 10 spawn points; agent ids >= 10 break the reference (map_env.py:370) */
 #define SSD_MAX_CELLS 1024  /* H*W upper bound (largest reference map is 48x18 = 864) */
@@ -330,7 +330,12 @@ int ssd_clip_adam_step(const ssd_clip_adam_args* args, void* stream);
  *         and partials f32 [B * T * n, SSD_TD_LOSS_PARTIALS] per (b, t, i): 0 mask, 1 sim mask sum, 2 (td_env mask)^2,
  *         3 (td_inc mask)^2, 4 similarity terms, 5 q_env taken, 6 sum_j q_inc taken, 7 give, 8 recv+ - recv-, 9 clean (recv+ - recv-),
  *         10 clean flag, 11 r (recv+ - recv-), 12 r  -- the caller adds the rows in a fixed order (losses and the learner's log values).
- * consider_others_inc (config/algs/homophily.yaml, default False) is not covered: the caller keeps its tensor-op path for it. */
+ * consider_others_inc (config/algs/homophily.yaml, default False; homophily_learner.py:118-164): with rz, rp, rn = the received counts
+ *         (zero, +, -) of the RECEIVER j (receive_*.unsqueeze(2) broadcasts over the giver i) and j != i, the inc head's chosen value is
+ *         (q_inc[t,i,j,0] rz_j(t) + q_inc[t,i,j,1] rp_j(t) + q_inc[t,i,j,2] rn_j(t)) / (n-1) and its target
+ *         (tmax_self + sum_c tq_inc[t+1,i,j,c] recv_c,j(t+1) - tq_inc[t+1,i,j,a_inc[t+1,i,j]]) / (n-1), tmax_self being the double_q /
+ *         plain-max selection; dq_inc[t,i,j,c] = (similarity part) + g_inc recv_c,j(t) / (n-1).  The logged q_inc taken stays the
+ *         gather at a_inc. */
 #define SSD_TD_LOSS_PARTIALS 16
 typedef struct ssd_td_loss_args {
     int32_t batch, t_slots, n_agents, n_actions, sim_horizon, double_q;
@@ -343,6 +348,7 @@ typedef struct ssd_td_loss_args {
     const int64_t* filled;
     const float* dens;
     float *dq_env, *dq_inc, *partials;
+    int32_t consider_others_inc;
 } ssd_td_loss_args;
 int ssd_td_sim_loss(const ssd_td_loss_args* args, int32_t mode, void* stream);
 
