@@ -400,10 +400,18 @@ int ssd_import_state(ssd_env* E, const ssd_state* src, void* stream) {
     return launched();
 }
 
+// ssd_build_inputs / _flags: the kernels take the row count batch * n_agents as an `int` (the element index and the grid are 64-bit):
+// any team size and action count whose row count and widest row (every block of the flag word present) stay below 2^31 is computed,
+// anything larger refused.  ssd_unroll_other / ssd_td_sim_loss form the thread index in `int` as well: SSD_ROWS32_MAX
+static bool build_inputs_fits(int64_t batch, int64_t n, int64_t A, int64_t out_offset) {
+    return batch * n <= INT32_MAX && out_offset >= 0 && out_offset + n * A + A + 2 * n + 4 <= INT32_MAX;
+}
+
 int ssd_build_inputs(int32_t batch, int32_t n_agents, int32_t n_actions, int32_t t0, const int64_t* last_actions,
                      const float* last_reward, const int64_t* last_actions_inc, const float* pos, float pos_scale,
                      float* out, int32_t out_stride, int32_t out_offset, void* stream) {
     if (batch < 1 || n_agents < 1 || n_actions < 1 || !out || !pos) return fail(SSD_ERR_INVALID, "bad argument");
+    if (!build_inputs_fits(batch, n_agents, n_actions, out_offset)) return fail(SSD_ERR_INVALID, "ssd_build_inputs: batch * n_agents and the row width must fit 32 bits, out_offset >= 0");
     if (!(t0 & 1) && (!last_actions || !last_reward || !last_actions_inc)) return fail(SSD_ERR_INVALID, "t > 0 needs the t-1 tensors");
     if (out_stride < out_offset + n_actions + n_agents + 4) return fail(SSD_ERR_INVALID, "out_stride too small");
     launch_build_inputs(batch, n_agents, n_actions, t0, last_actions, last_reward, last_actions_inc, pos, pos_scale, out,
@@ -415,6 +423,7 @@ int ssd_unroll_other(const int64_t* actions, const float* pos, const float* orie
                      float pos_scale, int32_t batch, int32_t T, int32_t n_agents, int32_t n_actions, float* other, float* act_tm, void* stream) {
     if (!actions || !pos || !orient || !reward || !clean_num || !apple_den || !other || !act_tm || batch < 1 || T < 1 || n_agents < 1 || n_actions < 1 ||
         !(pos_scale > 0.f)) return fail(SSD_ERR_INVALID, "bad argument");
+    if ((int64_t)batch * T * n_agents > SSD_ROWS32_MAX || n_actions > INT32_MAX - 7) return fail(SSD_ERR_INVALID, "ssd_unroll_other: batch * T * n_agents over SSD_ROWS32_MAX");
     launch_unroll_other(actions, pos, orient, reward, clean_num, apple_den, pos_scale, batch, T, n_agents, n_actions, other, act_tm, (hipStream_t)stream);
     return launched();
 }
@@ -447,6 +456,7 @@ int ssd_build_inputs_flags(int32_t batch, int32_t n_agents, int32_t n_actions, i
                            const float* last_reward, const int64_t* last_actions_inc, const float* pos, float pos_scale, float* out,
                            int32_t out_stride, int32_t out_offset, void* stream) {
     if (batch < 1 || n_agents < 1 || n_actions < 1 || !out || !pos) return fail(SSD_ERR_INVALID, "bad argument");
+    if (!build_inputs_fits(batch, n_agents, n_actions, out_offset)) return fail(SSD_ERR_INVALID, "ssd_build_inputs_flags: batch * n_agents and the row width must fit 32 bits, out_offset >= 0");
     if ((input_flags & ~SSD_INPUT_EXPLICIT) & ~127u) return fail(SSD_ERR_UNSUPPORTED, "ssd_build_inputs_flags: unknown input_flags bit");
     if (!(t0 & 1) && (!last_actions || !last_reward || !last_actions_inc)) return fail(SSD_ERR_INVALID, "t > 0 needs the t-1 tensors");
     if (out_stride < out_offset + build_inputs_layout(n_agents, n_actions, input_flags).width) return fail(SSD_ERR_INVALID, "out_stride too small");
@@ -495,7 +505,7 @@ int ssd_copy_blocks(const ssd_block_copy* blocks, int32_t count, void* stream) {
     for (int i = 0; i < count; ++i) {
         const ssd_block_copy& b = blocks[i];
         if (!b.src || !b.dst || b.rows < 1 || b.cols < 1 || b.src_stride < b.cols || b.dst_stride < b.cols ||
-            (int64_t)b.rows * b.cols > INT32_MAX)
+            (int64_t)b.rows * b.cols > SSD_COPY_BLOCK_ELEMS_MAX)
             return fail(SSD_ERR_INVALID, "ssd_copy_blocks: bad block");
     }
     launch_copy_blocks(blocks, count, (hipStream_t)stream);
@@ -519,6 +529,7 @@ int ssd_runner_stats(const float* collective_return, const float* equality, cons
 int ssd_td_sim_loss(const ssd_td_loss_args* a, int32_t mode, void* stream) {
     if (!a || a->batch < 1 || a->t_slots < 2 || a->n_agents < 2 || a->n_agents > SSD_MAX_AGENTS || a->n_actions < 1 || a->sim_horizon < 1)
         return fail(SSD_ERR_INVALID, "bad argument");
+    if ((int64_t)a->batch * a->t_slots * a->n_agents > SSD_ROWS32_MAX) return fail(SSD_ERR_INVALID, "ssd_td_sim_loss: batch * t_slots * n_agents over SSD_ROWS32_MAX");
     if (!a->reward || !a->clean_num || !a->terminated || !a->filled || !a->partials) return fail(SSD_ERR_INVALID, "null argument");
     if (mode && (!a->q_env || !a->q_inc || !a->tq_env || !a->tq_inc || !a->actions || !a->actions_inc || !a->avail || !a->dens || !a->dq_env || !a->dq_inc))
         return fail(SSD_ERR_INVALID, "null argument");

@@ -466,11 +466,13 @@ int launch_bias_bmm_bwd(const float* g, const float* x, const float* w, float* d
                         long w_set) {
     BmmK k = {};
     k.act_y = act_y;
+    // refusals first: nothing is allocated or launched for a shape the kernels have no code for
+    if ((long)R * I >= (1L << 30) || (long)R * O >= (1L << 30) || (long)I * O >= (1L << 30)) return -2;       // 32-bit byte offsets inside a weight / operand set
     if (x2) {                      // two-source rows: dw / db only (dx of the first source is a row-group sum: the caller forms it from the summed g)
         if (dx || (I1 & 15) || x1_div < 1 || R % x1_div) return -3;
         k.x2 = x2; k.I1 = I1; k.x1_div = x1_div; k.x2_set = x2_shared ? 0 : (long)R * (I - I1);
         k.x1_magic = x1_div == 1 ? 0u : (uint32_t)(((1ull << 32) + (uint64_t)x1_div - 1) / (uint64_t)x1_div);
-        if (R >= (1 << 28)) return -2;
+        if (R >= (1 << 28) || (uint64_t)R * (uint64_t)x1_div > (1ull << 32)) return -2;       // r / x1_div by x1_magic is exact for r * x1_div <= 2^32
     }
     k.w_set = w_set;
     k.g = g; k.x = x; k.w = w; k.dx = dx; k.dw = dw; k.db = db; k.slope_of = slope_of; k.n = n; k.R = R; k.I = I; k.O = O;
@@ -487,7 +489,6 @@ int launch_bias_bmm_bwd(const float* g, const float* x, const float* w, float* d
         float* part = bmm_scratch(s);
         if (c > 1 && part && (size_t)n * dwb * c * BMM_PART * sizeof(float) <= BMM_SCRATCH_BYTES) { k.row_chunks = c; k.part = part; dwb *= c; }
     }
-    if ((long)R * I >= (1L << 30) || (long)R * O >= (1L << 30) || (long)I * O >= (1L << 30)) return -2;       // 32-bit byte offsets inside a weight / operand set
     const dim3 grid(dwb + dxb, n), block(BMM_BWD_WAVES * 64);
     const bool ov = (O & 3) == 0, bf = g_learner_precision == 1;
 #define SSD_BWD(OV_, ACT_, BF_) hipLaunchKernelGGL((k_bias_bmm_bwd<OV_, ACT_, BF_>), grid, block, 0, s, k, dwb)

@@ -316,16 +316,16 @@ void launch_store_step(const ssd_store_step* a, hipStream_t s) {
     hipLaunchKernelGGL(k_store_step, dim3(blocks), dim3(256), 0, s, k);
 }
 void launch_gru_gates(const float* gi, const float* gh, float* h, int R, int H, hipStream_t s) {
-    size_t total = (size_t)R * H; int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096;
+    const size_t total = (size_t)R * H, want = (total + 255) / 256; const int blocks = want > 4096 ? 4096 : (int)want;   // (any rows x hidden: the kernels stride)
     hipLaunchKernelGGL(k_gru_gates, dim3(blocks), dim3(256), 0, s, gi, gh, h, R, H);
 }
 void launch_gru_fwd_train(const float* gi, const float* gh, const float* h, float* h_new, float* rzn, int R, int H, hipStream_t s) {
-    size_t total = (size_t)R * H; int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096;
+    const size_t total = (size_t)R * H, want = (total + 255) / 256; const int blocks = want > 4096 ? 4096 : (int)want;   // (any rows x hidden: the kernels stride)
     hipLaunchKernelGGL(k_gru_fwd_train, dim3(blocks), dim3(256), 0, s, gi, gh, h, h_new, rzn, R, H);
 }
 void launch_gru_bwd(const float* dh, const float* rzn, const float* gh, const float* h, float* d_gi, float* d_gh, float* dh_prev, int R,
                     int H, hipStream_t s) {
-    size_t total = (size_t)R * H; int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096;
+    const size_t total = (size_t)R * H, want = (total + 255) / 256; const int blocks = want > 4096 ? 4096 : (int)want;   // (any rows x hidden: the kernels stride)
     hipLaunchKernelGGL(k_gru_bwd, dim3(blocks), dim3(256), 0, s, dh, rzn, gh, h, d_gi, d_gh, dh_prev, R, H);
 }
 void launch_dueling_pick(const float* av, int R, int A, const uint8_t* avail, const float* eps, const int64_t* step, uint32_t seed,

@@ -202,6 +202,8 @@ int ssd_get_info(const ssd_env* env, ssd_info* out);
  * bits 8.. = T > 0: `batch` counts [episodes, T] rows and the three history tensors hold every step's OWN action / reward / incentives
  * -- the kernel reads the row of the previous timestep and takes the t == 0 branch at the first step of each episode (the learner's
  * time-batched assembly without shifted copies of the tensors). */
+/* Any n_agents / n_actions >= 1 is computed (the kernels loop over them; SSD_MAX_AGENTS bounds the env, not these); refused with
+ * SSD_ERR_INVALID: batch * n_agents or the widest row (out_offset + n * n_actions + n_actions + 2 n + 4) past 2^31 - 1, out_offset < 0. */
 int ssd_build_inputs(int32_t batch, int32_t n_agents, int32_t n_actions, int32_t t0,
                      const int64_t* last_actions /*[B,n]*/, const float* last_reward /*[B,n]*/,
                      const int64_t* last_actions_inc /*[B,n,n]*/, const float* pos /*[B,n,2]*/,
@@ -214,6 +216,12 @@ int ssd_build_inputs(int32_t batch, int32_t n_agents, int32_t n_actions, int32_t
  * actions i64 [B, T, n], pos / orient f32 [B, T, n, 2], reward / clean_num / apple_den f32 [B, T, n] (contiguous) ->
  * other f32 [T * B, n, n_actions + 7] = [one-hot(a_j), pos_j / pos_scale, orient_j, r_j, clean_j, apple_den_j] at row t * B + b, and
  * act_tm f32 [n, T * B, n_actions] = the one-hot alone, agent-major (the extra input columns of fc1_inc). */
+/* Row kernels that form `workgroup * 256 + thread` in 32 bits (ssd_unroll_other, ssd_td_sim_loss): the last workgroup's index must still
+ * fit, so the row count stops one workgroup short of 2^31 - 1; more is refused (SSD_ERR_INVALID). */
+#define SSD_ROWS32_MAX (INT32_MAX - 256)
+/* ssd_unroll_other: any n_agents / n_actions >= 1 (an action outside [0, n_actions), e.g. -1, gives an all-zero one-hot); batch * T *
+ * n_agents over SSD_ROWS32_MAX is refused.  ssd_incentive_transfer: any n_agents >= 1,
+ * 64-bit row arithmetic throughout -- nothing to refuse beyond the sizes below 1 (T below 2). */
 int ssd_unroll_other(const int64_t* actions, const float* pos, const float* orient, const float* reward, const float* clean_num, const float* apple_den,
                      float pos_scale, int32_t batch, int32_t T, int32_t n_agents, int32_t n_actions, float* other, float* act_tm, void* stream);
 int ssd_incentive_transfer(int32_t batch, int32_t T, int32_t n_agents, const int64_t* actions_inc,
@@ -243,6 +251,8 @@ int ssd_dueling_q_bwd(const float* dq, float* da, float* dv, int32_t n, int32_t 
  * a dense array of rows of row_bytes bytes (any alignment).  ReplayBuffer.sample (episode_buffer.py:240-244) draws 16 episodes out of
  * thirteen storage fields with it: one launch instead of one indexing kernel per field.  `fields` is a HOST array read during the call,
  * ids a DEVICE array of n_ids int64 (each within the fields' rows: the caller checks). */
+/* Any row_bytes >= 1 is copied: the kernel strides over a row with its whole grid, so rows longer than one grid sweep (32 x 256 x 4
+ * bytes) take several passes (tests/test_learner_kernel_bounds.py: row_bytes = 131072 + 4). */
 typedef struct ssd_row_gather {
     const void* src;
     void* dst;
@@ -259,6 +269,9 @@ int ssd_gather_rows(const ssd_row_gather* fields, int32_t count, const int64_t* 
 int ssd_sample_ids(uint64_t seed, uint32_t call, int32_t population, int32_t count, int64_t* ids, void* stream);
 
 #define SSD_COPY_BLOCKS_MAX 32
+/* rows * cols of one block: the kernel walks a block with a 32-bit index in strides of the whole grid (64 x 256 threads), so the last
+ * stride past the end must still fit; a larger block is refused (SSD_ERR_INVALID). */
+#define SSD_COPY_BLOCK_ELEMS_MAX (INT32_MAX - 64 * 256)
 typedef struct ssd_block_copy {
     const float* src;
     float* dst;
@@ -335,7 +348,9 @@ int ssd_clip_adam_step(const ssd_clip_adam_args* args, void* stream);
  *         (q_inc[t,i,j,0] rz_j(t) + q_inc[t,i,j,1] rp_j(t) + q_inc[t,i,j,2] rn_j(t)) / (n-1) and its target
  *         (tmax_self + sum_c tq_inc[t+1,i,j,c] recv_c,j(t+1) - tq_inc[t+1,i,j,a_inc[t+1,i,j]]) / (n-1), tmax_self being the double_q /
  *         plain-max selection; dq_inc[t,i,j,c] = (similarity part) + g_inc recv_c,j(t) / (n-1).  The logged q_inc taken stays the
- *         gather at a_inc. */
+ *         gather at a_inc.
+ * Refused (SSD_ERR_INVALID): n_agents outside 2 .. SSD_MAX_AGENTS (the agents' window flags are bits of one word), batch * t_slots *
+ * n_agents over SSD_ROWS32_MAX (32-bit thread index).  partials columns 13 .. 15 are never written. */
 #define SSD_TD_LOSS_PARTIALS 16
 typedef struct ssd_td_loss_args {
     int32_t batch, t_slots, n_agents, n_actions, sim_horizon, double_q;
@@ -403,6 +418,8 @@ typedef struct ssd_store_step {
 } ssd_store_step;
 int ssd_store_step_launch(const ssd_store_step* args, void* stream);
 int ssd_gru_gates(const float* gi, const float* gh, float* h, int32_t rows, int32_t hidden, void* stream);
+/* ssd_gru_gates / _fwd / _bwd: any rows >= 1 and any hidden >= 1 (elementwise kernels that stride over rows x hidden with a grid of at
+ * most 4096 workgroups; 64-bit offsets) -- the bounds suite runs hidden 1, 3, 64, 65. */
 /* Training forms of the GRU gate arithmetic: forward also stores (r, z, n) [rows, 3 * hidden]; backward turns dL/dh_new into
  * dL/dgi, dL/dgh [rows, 3 * hidden] and the direct part of dL/dh_prev [rows, hidden]. */
 int ssd_gru_gates_fwd(const float* gi, const float* gh, const float* h, float* h_new, float* rzn, int32_t rows, int32_t hidden, void* stream);
