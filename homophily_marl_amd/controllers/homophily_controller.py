@@ -35,6 +35,11 @@ class HomophilyMAC(nn.Module):
                                  (1 * bool(args.obs_last_action) | 2 * bool(args.obs_agent_id) | 4 * bool(args.obs_reward)
                                   | 8 * bool(args.obs_inc_reward) | 16 * bool(getattr(args, "obs_distance", False)) | 32 * bool(args.obs_agent_pos)))
                                 | 64 * bool(getattr(args, "obs_others_last_action", False)))
+        # opt-in (config key fused_others_last_action, default False): the flag word the ROLLOUT heads take, bit 64 included -- the
+        # heads gather fc1's rows for the others' last-action block instead of widening the image (FastPolicy.supports decides by the
+        # dense width).  Key off: the same as input_flags, and every path is the one it was.
+        self.rollout_input_flags = (self.input_flags_all if (getattr(args, "fused_others_last_action", False)
+                                                             and getattr(args, "obs_others_last_action", False)) else self.input_flags)
         self.input_shape = self._get_input_shape(scheme)
         self.agent = agent_REGISTRY[args.agent](self.input_shape, args)
         self.agent_output_type = args.agent_output_type

@@ -276,6 +276,15 @@ struct HeadCold {
     uint64_t tail_layout;          // env head: first tail column of each _build_inputs block as 6 signed bytes (TAIL_ABSENT = not present):
                                    // last action | agent id | sign(r) | sign(received incentives) | 1 - distances | pos
 };
+// GEN = 2 (obs_others_last_action) needs three more pointers: others_rows f32 [n(owner), n * A, 64] (the block's rows of fc1_w), prev_rec
+// (every agent's previous env action, one byte per agent, 16 bytes per env: the buffer this timestep READS) and, env head, prev_rec_out
+// (the buffer of the next timestep: byte `agent` of the env's record <- the action picked).  HeadCold cannot grow -- k_inc_encode's EncK
+// sits behind it, and every shipped kernel keeps its argument offsets -- so they travel in slots of the OTHER head's filing, which
+// this head's code never reads (gather_slots; launch_policy_head stores them there):
+//   env head: p_inc | d_actions_inc | d_reward (block B is the inc head's)      inc head: pos_copy | orient_copy (the env head's pose copies)
+template <int INC> constexpr int gather_slots() { return INC ? (int)offsetof(HeadCold, pos_copy) : (int)offsetof(HeadCold, p_inc); }
+static_assert(offsetof(HeadCold, orient_copy) == offsetof(HeadCold, pos_copy) + 8 && offsetof(HeadCold, d_actions_inc) == offsetof(HeadCold, p_inc) + 8 &&
+              offsetof(HeadCold, d_reward) == offsetof(HeadCold, p_inc) + 16, "others_rows | prev_rec | prev_rec_out are consecutive slots");
 static_assert(offsetof(HeadCold, p_inc) == 64 && offsetof(HeadCold, d_pos) == 128, "cold argument blocks");
 constexpr int TAIL_ABSENT = -64;
 constexpr int HEAD_COLD_OFFSET = (int)((sizeof(HeadK) + alignof(HeadCold) - 1) / alignof(HeadCold) * alignof(HeadCold));   // second kernel argument
@@ -532,7 +541,10 @@ __device__ __forceinline__ void load_tile(const HeadK& a, int tile, int agent, i
 
 // AT: the env's action count (9 Cleanup, 8 Harvest) at compile time: the one-hot / dueling loops unroll.  GEN (env head): the
 // tail blocks sit where HeadCold::tail_layout says (any _build_inputs flag set that fits); GEN = 0 is the shipped layout with
-// compile-time columns -- the register allocation of the tuned kernel is left as it was.
+// compile-time columns -- the register allocation of the tuned kernel is left as it was.  GEN = 2 (both heads):
+// obs_others_last_action.  The block is n one-hot vectors, so its product with fc1 is the sum of n weight ROWS: the dense blocks sit
+// in compacted columns as if the block were absent (GEN = 1's tail_layout, the same 64-column image and MFMA chain) and the rows
+// W1[off + g A + a_g, :] are gathered as f32 from HeadCold::others_rows and added to fc1's output with the bias (others_gather).
 // WAVES: compute waves per workgroup = 16-row tiles per workgroup (the host sizes the grid: bpa = ceil(tiles per agent / WAVES)); the
 // workgroup has WAVES + 1 waves, the last one is the loader.
 // LOOP: a wave walks tiles tile, tile + bpa * WAVES, ... (grids larger than the chip: Cleanup-10 x 8192 has 512 tiles per agent); with
@@ -619,6 +631,16 @@ __device__ __forceinline__ void head_body(const HeadK& a_entry, uint8_t* lds_raw
         else if (!INC && a.feat_part) { load_tile<INC, false, PRE_SMALL>(a, tile, agent, lane, in); }     // (band partials instead of the input row: Harvest)
         else load_tile<INC, true, PRE_SMALL>(a, tile, agent, lane, in);
     }
+    // GEN 2: the env's previous-action record (16 bytes: byte g = agent g's last action, 0xFF = none) -- the last load of the input phase
+    u32x4 prec = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    if constexpr (GEN == 2) {
+        if (tile < tiles) {
+            auto rec = cold_ptr<const uint8_t>(COLD_BASE, gather_slots<INC>() + 8);
+            const int b0 = tile * 16 + m, bc0 = b0 < N ? b0 : N - 1;
+            prec = *(const u32x4 SSD_GLOBAL*)(rec + (size_t)bc0 * 16);
+        }
+    }
+    f32x4 gsum[4];                                                     // GEN 2: the gathered rows' sum, features 16 ot + 4 q .. + 3 of row m
     if (!INC) PSTAMP(10);
     uint32_t step = 0;                                                 // (both assigned once the loads above are pinned, see below)
     bool file = false;
@@ -714,6 +736,44 @@ __device__ __forceinline__ void head_body(const HeadK& a_entry, uint8_t* lds_raw
         }
         operand<PREC>(x, XS, bh, bl);
         (void)valid; (void)bc;
+        if constexpr (GEN == 2) {
+            // sum over the agents g with a previous action of others_rows[agent][g A + pa_g][16 ot + 4 q ..]: one 16-byte load per (g, ot),
+            // requested three agents at a time (12 loads in flight, then added: 40 results are never live at once); agents past n and
+            // agents without a previous step re-read row 0 and add zeros -- nothing branches on a loaded value.  The loads are this
+            // wave's own (the image is the loader wave's), so they delay no chunk; they land under the wait for fc1's fragments.
+#pragma unroll
+            for (int ot = 0; ot < 4; ++ot) gsum[ot] = f32x4{0.f, 0.f, 0.f, 0.f};
+            const uint32_t row0 = (uint32_t)agent * (uint32_t)n * (uint32_t)A;
+            auto orows = cold_ptr<const float>(COLD_BASE, gather_slots<INC>());      // (fetched here: no pointer is held through the input phase)
+#pragma unroll
+            for (int g0 = 0; g0 < SSD_MAX_AGENTS; g0 += 3) {
+                if (g0 < n) {                                          // (wave-uniform)
+                    f32x4 part[3][4];
+                    uint32_t keep[3];                                 // all ones = the row counts (a lane mask in a vector register, not an SGPR pair)
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        const int g = g0 + k;
+                        if (g >= SSD_MAX_AGENTS) continue;
+                        const int pa = (int)(int8_t)(uint8_t)(prec[g >> 2] >> (8 * (g & 3)));
+                        keep[k] = (g < n && pa >= 0 && pa < A) ? 0xFFFFFFFFu : 0u;
+                        const uint32_t row = row0 + ((uint32_t)(g * A + pa) & keep[k]);
+#pragma unroll
+                        for (int ot = 0; ot < 4; ++ot) part[k][ot] = *(const f32x4 SSD_GLOBAL*)((const uint8_t SSD_GLOBAL*)orows + (size_t)((row * 64u + 16u * ot + 4u * (uint32_t)q) * 4u));
+                    }
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        if (g0 + k >= SSD_MAX_AGENTS) continue;
+#pragma unroll
+                        for (int ot = 0; ot < 4; ++ot)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                const float v = part[k][ot][r];         // (a copy: __builtin_bit_cast of a vector ELEMENT reads element 0)
+                                gsum[ot][r] += __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, v) & keep[k]);
+                            }
+                    }
+                }
+            }
+        }
     };
     // the env head's by-products of the input phase: the finished encoder features (31 x 31 windows) and the tail columns into the
     // agent's input row (the inc head reads the full row), the pose BEFORE the env step (inc head input, storage slot t)
@@ -790,7 +850,10 @@ __device__ __forceinline__ void head_body(const HeadK& a_entry, uint8_t* lds_raw
         for (int ot = 0; ot < 4; ++ot) {
             const f32x4 bias = *reinterpret_cast<const f32x4*>(tail + HT_B1 + 16 * ot + 4 * q);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) x1[ot][r] = leaky(fmaf(x1[ot][r], INV, bias[r]));
+            for (int r = 0; r < 4; ++r) {
+                if constexpr (GEN == 2) x1[ot][r] = leaky(fmaf(x1[ot][r], INV, bias[r]) + gsum[ot][r]);
+                else x1[ot][r] = leaky(fmaf(x1[ot][r], INV, bias[r]));
+            }
         }
         if (first) PSTAMP(3);
         // ---- GRU cell: r, z share one accumulator for the input and the hidden side; n needs both separately -------------------
@@ -882,6 +945,10 @@ __device__ __forceinline__ void head_body(const HeadK& a_entry, uint8_t* lds_raw
                 out_actions[(size_t)bb * n + agent] = act;
                 if (out_i32) out_i32[(size_t)bb * n + agent] = act;
                 if (p_act) p_act[(size_t)bb * n + agent] = act;
+                if constexpr (GEN == 2) {                              // the OTHER buffer of the pair: sibling workgroups still read this timestep's
+                    auto rec_out = cold_ptr<uint8_t>(COLD_BASE, gather_slots<0>() + 16);
+                    if (rec_out) rec_out[(size_t)bb * 16 + agent] = (uint8_t)act;
+                }
                 if (d_actions && file) {
                     const size_t sr = ((size_t)bb * a.slots + slot_t) * n + agent;
                     d_actions[sr] = act;
@@ -993,24 +1060,32 @@ constexpr int HEAD_WAVES = SSD_HEAD_WAVES;
 #define SSD_HEAD_WAVES_LOOP 8
 #endif
 constexpr int HEAD_WAVES_LOOP = SSD_HEAD_WAVES_LOOP;   // (round 3: 6, when the looped instantiations filled the register file; 160-168 registers now)
-constexpr int head_waves(bool loop) { return loop ? HEAD_WAVES_LOOP : HEAD_WAVES; }
+// GEN = 2 holds 16 more registers through fc1 (the gathered sum) and up to 48 while a gather group is in flight: 7 compute waves + the
+// loader = two waves per SIMD and the 256-register budget k_inc_encode's head half has
+#ifndef SSD_HEAD_WAVES_GATHER
+#define SSD_HEAD_WAVES_GATHER 7
+#endif
+constexpr int HEAD_WAVES_GATHER = SSD_HEAD_WAVES_GATHER;
+constexpr int head_waves(bool loop, int gen = 0) { return gen == 2 ? HEAD_WAVES_GATHER : loop ? HEAD_WAVES_LOOP : HEAD_WAVES; }
 // The leading scalar arguments repeat what a compute wave needs for its largest loads (the tile's state and input rows): built
 // with -amdgpu-kernarg-preload-count they arrive in SGPRs with the wave (struct arguments are not preloaded).  The looped
 // instantiations re-read HeadK from the segment at every pass (refetch_head_args) and ignore them.
 constexpr int HEAD_LEAD_BYTES = 2 * 4 + 6 * 8;     // (N | n << 24, bpa, six pointers: 14 dwords, what gfx950 preloads)
 template <int INC, int PREC, int AT, int GEN = 0, bool LOOP = false>
-__global__ __launch_bounds__((head_waves(LOOP) + 1) * 64) void k_head(uint32_t p_Nn, int p_bpa, float* p_h, float* p_inputs, const int64_t* p_prev_actions,
+__global__ __launch_bounds__((head_waves(LOOP, GEN) + 1) * 64) void k_head(uint32_t p_Nn, int p_bpa, float* p_h, float* p_inputs, const int64_t* p_prev_actions,
                                                                       const float* p_prev_reward, const uint8_t* p_recv, const float* p_pos, HeadK a, HeadCold cold_unused) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
-    if constexpr (LOOP) head_body<INC, PREC, AT, GEN, head_waves(LOOP), LOOP, HEAD_LEAD_BYTES>(a, lds_raw, (int)blockIdx.x);
+    if constexpr (LOOP) head_body<INC, PREC, AT, GEN, head_waves(LOOP, GEN), LOOP, HEAD_LEAD_BYTES>(a, lds_raw, (int)blockIdx.x);
     else {
         HeadK al = a;
         al.N = (int)(p_Nn & 0xFFFFFFu); al.n = (int)(p_Nn >> 24); al.bpa = p_bpa; al.h = p_h; al.inputs = p_inputs;
         if constexpr (!INC) { al.prev_actions = p_prev_actions; al.prev_reward = p_prev_reward; al.recv = p_recv; al.pos = p_pos; }
-        head_body<INC, PREC, AT, GEN, head_waves(LOOP), LOOP, HEAD_LEAD_BYTES, !INC>(al, lds_raw, (int)blockIdx.x);
+        head_body<INC, PREC, AT, GEN, head_waves(LOOP, GEN), LOOP, HEAD_LEAD_BYTES, !INC>(al, lds_raw, (int)blockIdx.x);
     }
 }
 
+// obs_others_last_action: the GEN = 2 kernels (both heads)
+static bool head_gathers(const ssd_policy_head* p) { return p->input_flags && (p->input_flags & SSD_INPUT_OTHERS_LAST_ACTION); }
 static int chip_cus() {
     static int cus[64] = {};
     int dev = 0;
@@ -1032,6 +1107,7 @@ static void head_args(const ssd_policy_head* p, HeadK& k, HeadCold& c, int waves
     k.feat_part = p->feat_part; k.feat_bands = p->feat_bands; k.lin_b = p->lin_b;
     k.ep_ret = p->ep_return; k.term = p->terminated;
     k.recv = p->recv_inc; k.avail_bits = p->avail_bits; c.recv_out = p->recv_inc_out;
+    if (head_gathers(p)) k.inp -= k.n * k.A;       // the dense width: the inc head's one-hot action follows the compacted columns
     c.out_actions = p->out_actions; c.q_out = p->q_out; c.out_actions_i32 = p->out_actions_i32; c.pos_copy = p->pos_copy; c.orient_copy = p->orient_copy;
     c.d_pos = p->dst_pos; c.d_orient = p->dst_orient; c.d_onehot = p->dst_actions_onehot; c.d_reward = p->dst_reward;
     c.d_clean = p->dst_clean_num; c.d_den = p->dst_apple_den; c.d_term = p->dst_terminated;
@@ -1075,9 +1151,17 @@ static int head_plan(const ssd_policy_head* p, HeadK& k, HeadCold& c, bool gen, 
 int launch_policy_head(const ssd_policy_head* p, int inc, hipStream_t s) {
     HeadK k;
     HeadCold c;
-    const bool gen = !inc && p->input_flags && (p->input_flags & ~SSD_INPUT_EXPLICIT) != (uint32_t)SSD_INPUT_FLAGS_SHIPPED;
+    const bool gather = head_gathers(p);
+    const bool gen = !gather && !inc && p->input_flags && (p->input_flags & ~SSD_INPUT_EXPLICIT) != (uint32_t)SSD_INPUT_FLAGS_SHIPPED;
     bool looped = false;
-    const int waves = head_plan(p, k, c, gen, looped);
+    int waves;
+    if (gather) {           // one tile per wave while that grid fits the chip, else the looped instantiation: both exist
+        head_args(p, k, c, HEAD_WAVES_GATHER);
+        looped = head_loops(k, HEAD_WAVES_GATHER);
+        waves = HEAD_WAVES_GATHER;
+        const void* g3[3] = {p->others_rows, p->prev_record, p->prev_record_out};      // (see gather_slots)
+        __builtin_memcpy(reinterpret_cast<uint8_t*>(&c) + (inc ? gather_slots<1>() : gather_slots<0>()), g3, inc ? 16 : 24);
+    } else waves = head_plan(p, k, c, gen, looped);
     const int prec = p->precision == 1 ? 1 : 2;
     const int bpa = k.bpa;
     const size_t lds = (size_t)head_lds_bytes(waves, prec);
@@ -1108,21 +1192,42 @@ int launch_policy_head(const ssd_policy_head* p, int inc, hipStream_t s) {
             if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2) != hipSuccess) return -1;
         gen_attr_done_dev[dev] = true;
     }
+#define SSD_G2(I, P, AT_) reinterpret_cast<const void*>(&k_head<I, P, AT_, 2, false>), reinterpret_cast<const void*>(&k_head<I, P, AT_, 2, true>)
+    const void* gather_fns[16] = {SSD_G2(0, 2, 9), SSD_G2(1, 2, 9), SSD_G2(0, 1, 9), SSD_G2(1, 1, 9),      // [A == 8][prec == 1][inc][looped]
+                                  SSD_G2(0, 2, 8), SSD_G2(1, 2, 8), SSD_G2(0, 1, 8), SSD_G2(1, 1, 8)};
+#undef SSD_G2
+    static bool gather_attr_done_dev[64] = {};
+    if (gather && !gather_attr_done_dev[dev]) {
+        const size_t l2 = (size_t)head_lds_bytes(HEAD_WAVES_GATHER, 2);
+        for (const void* f : gather_fns)
+            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2) != hipSuccess) return -1;
+        gather_attr_done_dev[dev] = true;
+    }
     if (k.N >= (1 << 24) || k.n >= 256) return -1;
     uint32_t nn = (uint32_t)k.N | ((uint32_t)k.n << 24);
     void* args[10] = {&nn, &k.bpa, &k.h, &k.inputs, &k.prev_actions, &k.prev_reward, &k.recv, &k.pos, &k, &c};
-    const void* fn = gen ? gen_fns[(k.A == 8 ? 2 : 0) + (prec == 1 ? 1 : 0)]
+    const void* fn = gather ? gather_fns[(k.A == 8 ? 8 : 0) + (prec == 1 ? 4 : 0) + (inc ? 2 : 0) + (looped ? 1 : 0)]
+                   : gen ? gen_fns[(k.A == 8 ? 2 : 0) + (prec == 1 ? 1 : 0)]
                          : fns[(looped ? 8 : 0) + (k.A == 8 ? 4 : 0) + (prec == 1 ? 2 : 0) + (inc ? 1 : 0)];
     if (hipLaunchKernel(fn, dim3(k.n * bpa), dim3((waves + 1) * 64), args, lds, s) != hipSuccess) return -1;
     return 0;
 }
 
 // ---- pack: reference-shaped f32 parameters -> the per-agent head image --------------------------------------------------------
-template <int PREC>
-__global__ __launch_bounds__(256) void k_pack_head(ssd_policy_head_params p, uint8_t* image, int32_t* err) {
+// OTHERS (ssd_policy_head_params.input_flags has SSD_INPUT_OTHERS_LAST_ACTION): fc1_w's rows [off, off + n A) -- the others' last-action
+// block, off = 32 + the widths of the blocks in front of it -- go to p.others_rows as they are (f32 [agent][n A][64]); the rows on both
+// sides of the block are the image's fc1 rows in compacted order (column k of the image = row k, or k + n A behind the block).
+__host__ __device__ inline int others_offset(uint32_t flags, int n, int A) {
+    return 32 + ((flags & SSD_INPUT_LAST_ACTION) ? A : 0) + ((flags & SSD_INPUT_AGENT_ID) ? n : 0) + ((flags & SSD_INPUT_REWARD) ? 1 : 0) +
+           ((flags & SSD_INPUT_INC_REWARD) ? 1 : 0);
+}
+template <int PREC, bool OTHERS>
+__device__ __forceinline__ void pack_head_body(const ssd_policy_head_params& p, uint8_t* image, int32_t* err) {
     constexpr size_t IMAGE_BYTES = SSD_POLICY_IMAGE_BYTES(PREC);
     constexpr float WS = PREC == 2 ? HEAD_WSCALE : 1.f;
     const int agent = blockIdx.y, e = blockIdx.x * 256 + threadIdx.x;
+    const int blk = OTHERS ? p.n_agents * p.n_actions : 0, off = OTHERS ? others_offset(p.input_flags, p.n_agents, p.n_actions) : 0;
+    if (OTHERS && e < blk * 64) p.others_rows[(size_t)agent * blk * 64 + e] = p.fc1_w[((size_t)agent * p.fc1_in + off) * 64 + e];
     uint8_t* img = image + (size_t)agent * IMAGE_BYTES;
     if (e < HF_TOT * 512) {
         const int F = e >> 9, lane = (e >> 3) & 63, j = e & 7, q = lane >> 4, m = lane & 15;
@@ -1130,7 +1235,10 @@ __global__ __launch_bounds__(256) void k_pack_head(ssd_policy_head_params p, uin
         int piece, term_pieces = 4;                                    // hi term's piece; the lo term sits term_pieces further
         if (F < HF_WI) {
             const int ot = F >> 1, s = F & 1, out = 16 * ot + m, k = 32 * s + 16 * (j >> 2) + 4 * q + (j & 3);
-            if (k < p.fc1_in) w = p.fc1_w[((size_t)agent * p.fc1_in + k) * 64 + out];
+            if (OTHERS) {
+                const int row = k < off ? k : k + blk;
+                if (row < p.fc1_in) w = p.fc1_w[((size_t)agent * p.fc1_in + row) * 64 + out];
+            } else if (k < p.fc1_in) w = p.fc1_w[((size_t)agent * p.fc1_in + k) * 64 + out];
             piece = step_piece<PREC>(s, 0, ot);
         } else if (F < HF_FC2) {
             const bool hid = F >= HF_WH;
@@ -1164,11 +1272,18 @@ __global__ __launch_bounds__(256) void k_pack_head(ssd_policy_head_params p, uin
         reinterpret_cast<float*>(img + (size_t)tail_piece<PREC>() * 1024)[e] = v;      // the tail follows fc2 in the resident chunk
     }
 }
+template <int PREC>
+__global__ __launch_bounds__(256) void k_pack_head(ssd_policy_head_params p, uint8_t* image, int32_t* err) { pack_head_body<PREC, false>(p, image, err); }
+template <int PREC>
+__global__ __launch_bounds__(256) void k_pack_head_others(ssd_policy_head_params p, uint8_t* image, int32_t* err) { pack_head_body<PREC, true>(p, image, err); }
 
 void launch_pack_head(const ssd_policy_head_params* p, int prec, void* image, hipStream_t s) {
     const dim3 grid((HF_TOT * 512 + 255) / 256, p->n_agents);
     int32_t* err = numeric_err_word();
-    if (prec == 2) hipLaunchKernelGGL(k_pack_head<2>, grid, dim3(256), 0, s, *p, static_cast<uint8_t*>(image), err);
+    if (p->input_flags & SSD_INPUT_OTHERS_LAST_ACTION) {      // the grid covers the block's n A x 64 floats too (29 696 threads per agent)
+        if (prec == 2) hipLaunchKernelGGL(k_pack_head_others<2>, grid, dim3(256), 0, s, *p, static_cast<uint8_t*>(image), err);
+        else hipLaunchKernelGGL(k_pack_head_others<1>, grid, dim3(256), 0, s, *p, static_cast<uint8_t*>(image), err);
+    } else if (prec == 2) hipLaunchKernelGGL(k_pack_head<2>, grid, dim3(256), 0, s, *p, static_cast<uint8_t*>(image), err);
     else hipLaunchKernelGGL(k_pack_head<1>, grid, dim3(256), 0, s, *p, static_cast<uint8_t*>(image), err);
 }
 

@@ -10,7 +10,11 @@ homophily_agent.py:154-208) with agent-major activations [n, N, 64] and the weig
   * per-layer path (fused=False, or window sizes / palettes without a fused encoder): every per-agent layer as one batched GEMM
     (hipBLASLt) between the small kernels of csrc/ssd_policy.hip; the incentive head's pairwise layer [h_i | other_j] @ W is
     split into h_i @ W_h + other_j @ W_o, so the [n, N * n, H + E] concatenation is never materialised.
-Both implement the shipped _build_inputs flag set (config/default.yaml:45-51).
+Both implement the shipped _build_inputs flag set (config/default.yaml:45-51).  obs_others_last_action (fused heads, opt-in through
+the controller's rollout_input_flags): the block's n * n_actions columns are n one-hot vectors, so the heads add the matching rows of
+fc1 (others_rows, snapshot by the pack launch) instead of multiplying by them; the previous actions of all agents travel in a pair of
+per-env byte records selected by the timestep's parity (prev_rec: the env head of t reads [t & 1] and writes the other, the inc head of
+t reads [t & 1]) -- no launch reads what a sibling workgroup writes.
 Action RNG: the package's counter generator (not torch's Philox) keyed by the GLOBAL env id (env_id_base + local env), so env
 shards draw what the unsharded job draws; exploration draws are not parity-pinned against torch.
 """
@@ -33,13 +37,17 @@ class FastPolicy:
         self.N, self.n, self.H, self.A = n_env, mac.n_agents, a.rnn_hidden_dim, a.n_actions
         self.dev = next(self.agent.parameters()).device
         self.inp = mac.input_shape
+        flags = getattr(mac, "rollout_input_flags", mac.input_flags)
+        self.flags = flags
+        self.others = flags is not None and bool(flags & abi.INPUT_OTHERS_LAST_ACTION)
+        self.inp_dense = self.inp - (self.n * self.A if self.others else 0)     # columns of the 64-column image / of `inputs`
         self.V = int(a.obs_dims[0])
         self.precision, self.env_id_base = int(precision), int(env_id_base) & 0xFFFFFFFF
         n, N, H = self.n, self.N, self.H
         f32 = dict(dtype=th.float32, device=self.dev)
         # fused: one launch per head (csrc/ssd_policy_mfma.hip), inputs padded to 64 columns; otherwise the per-layer
         # composition below (batched hipBLASLt GEMMs + the small kernels of csrc/ssd_policy.hip)
-        self.fused = bool(fused) and H == 64 and self.inp + self.A <= 64 and self.A + 7 <= 16 and mac.input_flags is not None
+        self.fused = bool(fused) and H == 64 and self.inp_dense + self.A <= 64 and self.A + 7 <= 16 and flags is not None
         # the per-layer composition assembles the shipped input layout only (ssd_build_inputs)
         assert self.fused or mac.shipped_flags, "FastPolicy: this _build_inputs flag set needs the fused heads (FastPolicy.supports)"
         # encoder images: the class-LUT layout (conv as a table sum, no conv MFMAs: include/ssd_hip.h SSD_ENCODE_LAYOUT_LUT) unless
@@ -54,7 +62,7 @@ class FastPolicy:
             and (shipped or self.enc_layout == abi.ENCODE_LAYOUT_LUT)
         # act_inc_encode (inc head of t + encoder of t + 1 as one launch: the pipelined rollout) is instantiated for 15 / 31 only;
         # at the other edges the rollout takes the standalone encoder and inc-head launches
-        self.inc_encode = self.fused_enc and shipped
+        self.inc_encode = self.fused_enc and shipped and not self.others     # (obs_others_last_action: the four standalone launches)
         self.bands = abi.encode_bands(self.V) if self.fused_enc else 1
         # bf16 MFMA products an f32-equivalent product costs (bench.py's roofline accounting); conv: the planes are exact, 2
         self.n_products = dict(encode_conv=2, encode_lin=3, head_env=3, head_inc=3) if precision == 2 else \
@@ -77,6 +85,8 @@ class FastPolicy:
         self._avail_bits = 0x80000000 | sum(1 << k for k, v in enumerate(avail_mask_u8.detach().cpu().reshape(-1).tolist()[:31]) if v)   # ssd_policy_head.avail_bits
         self.seed = seed & 0xFFFFFFFF
         self.arange_n = th.arange(n, device=self.dev).unsqueeze(1)
+        # every agent's previous env action, one byte per agent (0xFF = none), 16 bytes per env, as a pair selected by the timestep's parity
+        self.prev_rec = th.full((2, N, abi.PREV_RECORD_BYTES), 0xFF, dtype=th.uint8, device=self.dev) if self.others else None
         if share_packs_from is not None:
             self.p = share_packs_from.p          # same weights: one packed copy serves every group
         else:
@@ -132,6 +142,8 @@ class FastPolicy:
             if self.fused:
                 for head in ("env", "inc"):
                     self.p["img_" + head] = th.zeros(self.n, abi.policy_image_bytes(self.precision), **u8)
+                    if self.others:     # fc1's rows of the others' last-action block, f32 as they are (written by the pack launch)
+                        self.p["rows_" + head] = th.zeros(self.n, self.n * self.A, 64, dtype=th.float32, device=self.dev)
             if self.fused_enc:
                 cbytes, lbytes = abi.encode_frag_bytes(self.V, self.precision, self.enc_layout)
                 self.p["conv_frags"], self.p["lin_frags"] = th.zeros(cbytes, **u8), th.zeros(lbytes, **u8)
@@ -142,6 +154,9 @@ class FastPolicy:
         if self.fused:
             for head in ("env", "inc"):
                 hp = self._head_params(head)
+                if self.others:
+                    hp.input_flags, hp.n_actions = abi.INPUT_EXPLICIT | int(self.flags), self.A
+                    hp.others_rows = self.p["rows_" + head].data_ptr()
                 abi.check(self.lib, self.lib.ssd_policy_pack_head(C.byref(hp), self.precision, self.p["img_" + head].data_ptr(), st))
         if self.fused_enc:
             pack = self.lib.ssd_policy_pack_encoder_lut if self.enc_layout == abi.ENCODE_LAYOUT_LUT else self.lib.ssd_policy_pack_encoder
@@ -151,13 +166,17 @@ class FastPolicy:
     @staticmethod
     def supports(mac, fused=True):
         """Whether the rollout kernels build this controller's input layout: the shipped flag set on either path, any other
-        combination of the _build_inputs flags (homophily_controller.py:137-184) on the fused heads as long as the inputs (+ the inc
-        head's one-hot action) fit the 64-column weight image -- obs_others_last_action never does."""
+        combination of the _build_inputs flags (homophily_controller.py:137-184) on the fused heads as long as the DENSE inputs (+ the
+        inc head's one-hot action) fit the 64-column weight image.  obs_others_last_action is not dense -- the heads gather fc1's rows
+        for it -- and is taken when the controller opts in (rollout_input_flags holds bit 64; else its flag word is None)."""
         a = mac.args
         if mac.shipped_flags:
             return True
-        return bool(fused) and mac.input_flags is not None and a.rnn_hidden_dim == 64 and mac.input_shape + a.n_actions <= 64 \
-            and a.n_actions + 7 <= 16
+        flags = getattr(mac, "rollout_input_flags", mac.input_flags)
+        if flags is None:
+            return False
+        dense = mac.input_shape - (mac.n_agents * a.n_actions if flags & abi.INPUT_OTHERS_LAST_ACTION else 0)
+        return bool(fused) and a.rnn_hidden_dim == 64 and dense + a.n_actions <= 64 and a.n_actions + 7 <= 16
 
     def _head_params(self, head):
         """ssd_policy_head_params of one head: pointers to the reference-shaped parameters (homophily_agent.py:37-125)."""
@@ -176,7 +195,7 @@ class FastPolicy:
         hp.fc2_in, hp.fc2_out = g("fc2_%s_w" % head).shape[2], g("fc2_%s_w" % head).shape[3]
         return hp
 
-    def _head_args(self, inc, eps, step, q_out=None, buf=0):
+    def _head_args(self, inc, eps, step, q_out=None, buf=0, par=0):
         a = abi.SsdPolicyHead()
         a.n_env, a.n_agents, a.n_actions, a.input_shape = self.N, self.n, self.A, self.inp
         a.pos_scale = float(self.mac.pos_scale)
@@ -187,11 +206,23 @@ class FastPolicy:
         a.epsilon, a.step = eps.data_ptr(), step.data_ptr()
         a.q_out = None if q_out is None else q_out.data_ptr()
         a.precision, a.env_id_base = self.precision, self.env_id_base
-        a.input_flags = abi.INPUT_EXPLICIT | int(self.mac.input_flags)
+        a.input_flags = abi.INPUT_EXPLICIT | int(self.flags)
+        if self.others:
+            a.others_rows = self.p["rows_inc" if inc else "rows_env"].data_ptr()
+            a.prev_record = self.prev_rec[par & 1].data_ptr()
+            if not inc:
+                a.prev_record_out = self.prev_rec[(par & 1) ^ 1].data_ptr()
         return a
 
     def reset(self):
         self.h_env.zero_(); self.h_inc.zero_()
+        if self.prev_rec is not None:
+            self.prev_rec.fill_(0xFF)
+
+    def set_prev_actions(self, prev_actions, par=0):
+        """obs_others_last_action: write previous actions i64 [N, n] (-1 = none) into the record buffer of parity `par` -- for callers
+        that hold the actions themselves (tests, a resumed episode); inside a rollout the env head carries the records."""
+        self.prev_rec[par & 1, :, :self.n] = prev_actions.to(th.int8).view(th.uint8)
 
     # ---- env head -----------------------------------------------------------------------------------------------
     @th.no_grad()
@@ -278,12 +309,16 @@ class FastPolicy:
 
     @th.no_grad()
     def head_env(self, prev_actions, prev_reward, prev_inc, pos, eps, step, q_out=None, orient=None, actions_i32=None, pos_copy=None,
-                 orient_copy=None, file=None, buf=0):
-        """input tail + fc1 + GRU + dueling + epsilon-greedy of the env head on the features encode() left in `inputs`."""
+                 orient_copy=None, file=None, buf=0, par=None):
+        """input tail + fc1 + GRU + dueling + epsilon-greedy of the env head on the features encode() left in `inputs`.
+        obs_others_last_action: `par` = the timestep's parity -- the head reads prev_rec[par] and writes its picks to prev_rec[par ^ 1]
+        (the rollout); par = None: a stand-alone call, the record is first set from `prev_actions` (set_prev_actions) and parity 0 used."""
         p, lib, n, N, H = self.p, self.lib, self.n, self.N, self.H
         st = self._stream()
         if self.fused:
-            ha = self._head_args(False, eps, step, q_out, buf)
+            if self.others and par is None:
+                self.set_prev_actions(prev_actions, 0)
+            ha = self._head_args(False, eps, step, q_out, buf, par or 0)
             ha.avail = self.avail.data_ptr()
             ha.avail_bits = self._avail_bits       # the mask itself (a constant of the env class): the kernel issues no loads for it
             ha.prev_actions, ha.prev_reward, ha.prev_actions_inc, ha.pos = (prev_actions.data_ptr(), prev_reward.data_ptr(),
@@ -314,8 +349,8 @@ class FastPolicy:
 
     # ---- incentive head ---------------------------------------------------------------------------------------------
     @th.no_grad()
-    def _inc_args(self, actions, pos, orient, reward, clean_num, apple_den, eps, step, q_out=None, file=None, buf=0):
-        ha = self._head_args(True, eps, step, q_out, buf)
+    def _inc_args(self, actions, pos, orient, reward, clean_num, apple_den, eps, step, q_out=None, file=None, buf=0, par=None):
+        ha = self._head_args(True, eps, step, q_out, buf, par or 0)
         ha.actions, ha.pos_pre, ha.orient_pre = actions.data_ptr(), pos.data_ptr(), orient.data_ptr()
         ha.reward, ha.clean_num, ha.apple_den = reward.data_ptr(), clean_num.data_ptr(), apple_den.data_ptr()
         ha.out_actions = self.actions_inc.data_ptr()
@@ -337,13 +372,14 @@ class FastPolicy:
         return self.actions_inc
 
     @th.no_grad()
-    def act_inc(self, actions, pos, orient, reward, clean_num, apple_den, eps, step, q_out=None, file=None, buf=0):
+    def act_inc(self, actions, pos, orient, reward, clean_num, apple_den, eps, step, q_out=None, file=None, buf=0, par=None):
         """actions i64 [N, n] (the env actions just taken); pos / orient: the PRE-step pose [N, n, 2]; reward, clean_num,
-        apple_den [N, n] of this step.  Returns actions_inc i64 [N, n, n] with a zero diagonal (static buffer)."""
+        apple_den [N, n] of this step.  Returns actions_inc i64 [N, n, n] with a zero diagonal (static buffer).
+        obs_others_last_action: reads prev_rec[par] (the same buffer the env head of this timestep read; None = 0)."""
         p, lib, n, N, H = self.p, self.lib, self.n, self.N, self.H
         st = self._stream()
         if self.fused:
-            ha = self._inc_args(actions, pos, orient, reward, clean_num, apple_den, eps, step, q_out=q_out, file=file, buf=buf)
+            ha = self._inc_args(actions, pos, orient, reward, clean_num, apple_den, eps, step, q_out=q_out, file=file, buf=buf, par=par)
             abi.check(lib, lib.ssd_policy_head_inc(C.byref(ha), st))
             return self.actions_inc
         assert buf == 0

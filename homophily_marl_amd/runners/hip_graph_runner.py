@@ -12,7 +12,9 @@ mechanics that make a timestep capturable and replayable for every t:
     t together with k_encode of slot t + 1 (they share no data; the input rows live in a buffer pair indexed by the parity of t);
     the heads file actions / pose / rewards in slot t, carry the runner state and hand the device-side counters over.  Several env
     groups or an odd number of timesteps per graph take the four standalone launches (k_encode, k_head<env>, env, k_head<inc>).
-    Other configurations (obs_others_last_action, fast_policy=False) take the generic torch timestep, captured the same way;
+    obs_others_last_action with fused_others_last_action takes the same four launches (the heads gather fc1's rows; the previous actions
+    of all agents travel in FastPolicy.prev_rec, a buffer pair indexed by the parity of t like the input rows).
+    Other configurations (obs_others_last_action without that key, fast_policy=False) take the generic torch timestep, captured the same way;
   * epsilon is a device scalar; exploration uses the package's counter generator (no multinomial, no host sync).
 The first episode runs eagerly (warm-up of hipBLASLt plans and the allocator); graphs are captured from the second on.
 The returned EpisodeBatch is the persistent storage: consume it (buffer.insert_episode_batch) before the next run(), as the
@@ -121,6 +123,10 @@ class HipGraphRunner(HipVecRunner):
         K = max(1, int(getattr(a, "steps_per_graph", 10)))
         while self.episode_limit % K:
             K -= 1
+        if self.fast is not None and self.fast.others and K % 2:
+            # the previous-action records alternate with the parity of t, which a captured graph bakes in: an even number of timesteps
+            # per graph, or (odd episode lengths) eager timesteps
+            K = max([k for k in range(2, K, 2) if self.episode_limit % k == 0], default=0)
         self._graph_steps_planned = K
         use_graph = bool(getattr(a, "rollout_graph", True))
         self.pipe = bool(self.fast is not None and self.fold_store and self.fast.fused and self.fast.inc_encode and self.groups == 1
@@ -248,7 +254,7 @@ class HipGraphRunner(HipVecRunner):
             sl = self.gslices[g]
             extra = dict(orient=orient[sl], actions_i32=self.actions_i32[sl], pos_copy=pos_t[sl], orient_copy=orient_t[sl]) if fused else {}
             self.fasts[g].head_env(self.prev_actions[sl], self.prev_reward[sl], self.prev_inc[sl], pos[sl], self.eps, self.rng_ctr,
-                                   file=bundle.file_env, **extra)
+                                   file=bundle.file_env, par=self._par, **extra)
 
         def env_step():
             if not fused:
@@ -265,7 +271,7 @@ class HipGraphRunner(HipVecRunner):
             else:
                 reward = clean = den = self._zeros_nn
             self.fasts[g].act_inc(actions[sl], pos_t[sl], orient_t[sl], reward[sl], clean[sl], den[sl], self.eps, self.rng_ctr,
-                                  file=bundle.file_inc if store_env_step else bundle.file_inc_last)
+                                  file=bundle.file_inc if store_env_step else bundle.file_inc_last, par=self._par)
 
         return [("ssd::k_encode", "encode", lambda: self._fork(encode)),
                 ("ssd::k_head<env>", "head_env", lambda: self._fork(env_head)),
@@ -396,7 +402,7 @@ class HipGraphRunner(HipVecRunner):
             return
         self._begin_launches()
         self.eps.fill_(sel.epsilon)
-        if self._graph is None and self._episodes >= 2 and getattr(self.args, "rollout_graph", True):
+        if self._graph is None and self._episodes >= 2 and getattr(self.args, "rollout_graph", True) and self._graph_steps_planned:
             th.cuda.synchronize()
             g = th.cuda.CUDAGraph()
             # K consecutive timesteps per graph (the device-side time index makes every step of the replay land in its own
@@ -428,7 +434,8 @@ class HipGraphRunner(HipVecRunner):
         # episode returns, the hidden states (the generic timestep's, or FastPolicy's own)
         hidden = [self.h_env, self.h_inc] if self.fast is None else [h for fp in self.fasts for h in (fp.h_env, fp.h_inc)]
         ops.fill_blocks([(self.t_dev, 0), (self.prev_actions, 0xFFFFFFFF), (self.prev_reward, 0), (self.prev_inc, 0), (self.ep_return, 0)]
-                        + ([(self.recv_inc, 0)] if self.recv_inc is not None else []) + [(h, 0) for h in hidden])
+                        + ([(self.recv_inc, 0)] if self.recv_inc is not None else []) + [(h, 0) for h in hidden]
+                        + [(fp.prev_rec, 0xFFFFFFFF) for fp in (self.fasts if self.fast is not None else []) if fp.prev_rec is not None])
         if self.fast is not None:
             if in_capture:
                 self.fast._pack_eager()   # the learner may have stepped the weights since the last episode (packs are shared)

@@ -612,8 +612,9 @@ typedef struct ssd_policy_head {
     /* env head: which blocks _build_inputs appends after the 32 encoder features (homophily_controller.py:137-184, in that order;
      * SSD_INPUT_* bits, or-ed with SSD_INPUT_EXPLICIT so that the empty set can be told from 0).  0 = SSD_INPUT_FLAGS_SHIPPED
      * (config/default.yaml).  input_shape must equal 32 + the blocks' widths and
-     * input_shape + n_actions <= 64; obs_others_last_action (n * n_actions more columns) does not fit the 64-column image and is
-     * rejected with SSD_ERR_UNSUPPORTED. */
+     * input_shape + n_actions <= 64.  SSD_INPUT_OTHERS_LAST_ACTION (both heads): the block's n * n_actions columns are not columns of
+     * the 64-column image -- see others_rows below; input_shape is then the reference's full width (32 + all set blocks) and the limit
+     * is on the DENSE width: input_shape - n * n_actions + n_actions <= 64. */
     uint32_t input_flags;
     /* Counter hand-over of the pipelined rollout (all nullable).  inc head: *next_step_out = *step + 1 (like next_t_out for the time
      * index).  env head: *t_copy_out = *t_index, *step_copy_out = *step.  A launch never writes a scalar that it reads: the env head
@@ -630,6 +631,23 @@ typedef struct ssd_policy_head {
     const uint8_t* recv_inc;
     uint8_t* recv_inc_out;
     uint32_t avail_bits;
+    /* ---- appended in ABI 10 (zero = as before) ---- */
+    /* obs_others_last_action (input_flags has SSD_INPUT_OTHERS_LAST_ACTION; env head and inc head).  The block is n one-hot vectors,
+     * so its product with fc1 is a sum of n weight rows: the heads add others_rows[agent][g * n_actions + a_g][0..63] for every agent g
+     * with a previous action a_g >= 0 to fc1's output (exact f32 rows, both precisions); the six dense blocks occupy compacted
+     * columns of `inputs` and of the image as if the block were absent (the inc head's one-hot action follows them).
+     *   others_rows      f32 [n(owner), n * n_actions, 64] from ssd_policy_pack_head, 16-byte aligned
+     *   prev_record      every agent's previous env action as one byte per agent, 16 bytes per env (u8 [n_env, 16]; 0xFF = no previous
+     *                    step; bytes >= n unused), 16-byte aligned: what this timestep READS (both heads of a timestep read the same)
+     *   prev_record_out  env head, nullable: byte `agent` of every env's record <- the action picked.  It must be the OTHER buffer of a
+     *                    pair selected by the timestep's parity: the workgroups of the other agents read prev_record in the same
+     *                    launch, and the inc head of this timestep still reads it afterwards.
+     * Missing others_rows / prev_record, n_agents > SSD_MAX_AGENTS, prev_record_out on the inc head or equal to prev_record:
+     * SSD_ERR_INVALID.  ssd_policy_head_inc_encode refuses the flag (SSD_ERR_UNSUPPORTED): these configurations take the four
+     * standalone launches per timestep. */
+    const float* others_rows;
+    const uint8_t* prev_record;
+    uint8_t* prev_record_out;
 } ssd_policy_head;
 #define SSD_INPUT_LAST_ACTION 1u   /* obs_last_action: one-hot of the previous env action, n_actions columns */
 #define SSD_INPUT_AGENT_ID    2u   /* obs_agent_id: one-hot of the agent, n columns */
@@ -638,7 +656,8 @@ typedef struct ssd_policy_head {
 #define SSD_INPUT_DISTANCE    16u  /* obs_distance: 1 - |pos - pos_g| / pos_scale for every agent g, n columns */
 #define SSD_INPUT_AGENT_POS   32u  /* obs_agent_pos: pos / pos_scale, 2 columns */
 #define SSD_INPUT_OTHERS_LAST_ACTION 64u   /* obs_others_last_action: every agent's last-action one-hot, n * n_actions columns, between
-                                             the received-incentive sign and the distances -- ssd_build_inputs_flags only */
+                                             the received-incentive sign and the distances -- ssd_build_inputs_flags builds the columns;
+                                             the fused heads gather fc1's rows instead (ssd_policy_head.others_rows) */
 #define SSD_INPUT_EXPLICIT    0x80000000u   /* marks a given flag word (the empty set is SSD_INPUT_EXPLICIT alone) */
 #define SSD_INPUT_FLAGS_SHIPPED (SSD_INPUT_LAST_ACTION | SSD_INPUT_AGENT_ID | SSD_INPUT_REWARD | SSD_INPUT_INC_REWARD | SSD_INPUT_AGENT_POS)
 /* ssd_build_inputs for ANY _build_inputs flag set (homophily_controller.py:137-184; the learner's time-batched input assembly):
@@ -666,6 +685,14 @@ typedef struct ssd_policy_head_params {
     const float *w_i[3], *w_h[3], *b_i[3], *b_h[3];
     const float *fc2_w, *fc2_b, *fc2_v_w, *fc2_v_b;
     int32_t n_agents, fc1_in, fc2_in, fc2_out;
+    /* ---- appended in ABI 10 (zero = as before) ---- */
+    /* input_flags with SSD_INPUT_OTHERS_LAST_ACTION (SSD_INPUT_* of the controller's flag set; n_actions = the env's action count):
+     * fc1_in is the reference's full width (inc: + n_actions).  The rows of fc1_w on both sides of the others' last-action block are
+     * packed into the 64-column image in compacted order (fc1_in - n_agents * n_actions <= 64), the block's n_agents * n_actions rows
+     * are written as they are to others_rows f32 [n, n_agents * n_actions, 64] (16-byte aligned) by the same launch. */
+    uint32_t input_flags;
+    int32_t n_actions;
+    float* others_rows;
 } ssd_policy_head_params;
 /* image: [n, SSD_POLICY_IMAGE_BYTES(precision)] */
 int ssd_policy_pack_head(const ssd_policy_head_params* params, int32_t precision, void* image, void* stream);
