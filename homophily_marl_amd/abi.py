@@ -19,6 +19,7 @@ CODE_CLASS, CODE_CHANNEL_MASK = 0, 1
 # ssd_policy_head.input_flags (include/ssd_hip.h, SSD_INPUT_*): the _build_inputs blocks in the reference's order
 INPUT_LAST_ACTION, INPUT_AGENT_ID, INPUT_REWARD, INPUT_INC_REWARD, INPUT_DISTANCE, INPUT_AGENT_POS = 1, 2, 4, 8, 16, 32
 INPUT_OTHERS_LAST_ACTION = 64     # ssd_build_inputs_flags builds the columns; the fused heads gather fc1's rows (ssd_policy_head.others_rows)
+INPUT_GATHER_ONEHOT = 0x100       # a layout, not a block: the fused heads gather fc1's rows for EVERY one-hot block (ssd_policy_head.onehot_rows)
 PREV_RECORD_BYTES = 16            # ssd_policy_head.prev_record: one byte per agent, 16 bytes per env
 INPUT_EXPLICIT = 0x80000000   # marks a given flag word: the empty set is INPUT_EXPLICIT alone, 0 means the shipped set
 STREAM_UNIFORM, STREAM_MOVE, STREAM_WASTE, STREAM_SPAWN_ROT = 0, 1, 2, 3
@@ -171,7 +172,7 @@ class SsdPolicyHead(C.Structure):
                 ("lin_b", C.c_void_p), ("input_flags", C.c_uint32),
                 ("next_step_out", C.c_void_p), ("t_copy_out", C.c_void_p), ("step_copy_out", C.c_void_p),
                 ("recv_inc", C.c_void_p), ("recv_inc_out", C.c_void_p), ("avail_bits", C.c_uint32),
-                ("others_rows", C.c_void_p), ("prev_record", C.c_void_p), ("prev_record_out", C.c_void_p)]
+                ("others_rows", C.c_void_p), ("prev_record", C.c_void_p), ("prev_record_out", C.c_void_p), ("onehot_rows", C.c_void_p)]
 
 
 class SsdPolicyHeadParams(C.Structure):
@@ -179,7 +180,7 @@ class SsdPolicyHeadParams(C.Structure):
     _fields_ = [("fc1_w", C.c_void_p), ("fc1_b", C.c_void_p), ("w_i", C.c_void_p * 3), ("w_h", C.c_void_p * 3), ("b_i", C.c_void_p * 3),
                 ("b_h", C.c_void_p * 3), ("fc2_w", C.c_void_p), ("fc2_b", C.c_void_p), ("fc2_v_w", C.c_void_p), ("fc2_v_b", C.c_void_p),
                 ("n_agents", C.c_int32), ("fc1_in", C.c_int32), ("fc2_in", C.c_int32), ("fc2_out", C.c_int32),
-                ("input_flags", C.c_uint32), ("n_actions", C.c_int32), ("others_rows", C.c_void_p)]
+                ("input_flags", C.c_uint32), ("n_actions", C.c_int32), ("others_rows", C.c_void_p), ("onehot_rows", C.c_void_p)]
 
 
 class SsdPolicyEncodeArgs(C.Structure):
@@ -210,6 +211,11 @@ POLICY_HEAD_FRAGS, POLICY_HEAD_TAIL_FLOATS = 58, 464 + 64
 
 
 POLICY_TAIL_PIECES = 3
+
+
+def onehot_rows(n_agents, n_actions, flags):
+    """include/ssd_hip.h SSD_ONEHOT_ROWS: rows per owner of the INPUT_GATHER_ONEHOT table (id row | last action | inc action | others)."""
+    return 1 + 2 * n_actions + (n_agents * n_actions if flags & INPUT_OTHERS_LAST_ACTION else 0)
 
 
 def policy_image_bytes(precision):

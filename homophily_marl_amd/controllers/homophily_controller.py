@@ -40,6 +40,11 @@ class HomophilyMAC(nn.Module):
         # dense width).  Key off: the same as input_flags, and every path is the one it was.
         self.rollout_input_flags = (self.input_flags_all if (getattr(args, "fused_others_last_action", False)
                                                              and getattr(args, "obs_others_last_action", False)) else self.input_flags)
+        # opt-in (config key fused_onehot_gather, default False): with a one-hot block in the flag set (last action, agent id, the
+        # others' last actions) the rollout heads take the gathered layout -- bit 0x100 on top of all seven flags -- at any team size;
+        # every dense block then fits the 64-column image.  Without a one-hot block the dense layout fits as it is.
+        if getattr(args, "fused_onehot_gather", False) and self.input_flags_all & (1 | 2 | 64):
+            self.rollout_input_flags = self.input_flags_all | 0x100
         self.input_shape = self._get_input_shape(scheme)
         self.agent = agent_REGISTRY[args.agent](self.input_shape, args)
         self.agent_output_type = args.agent_output_type

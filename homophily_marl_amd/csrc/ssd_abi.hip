@@ -785,6 +785,23 @@ int ssd_policy_pack_head(const ssd_policy_head_params* p, int32_t precision, voi
     if (!p || !image || !p->fc1_w || !p->fc1_b || !p->fc2_w || !p->fc2_b || !p->fc2_v_w || !p->fc2_v_b) return fail(SSD_ERR_INVALID, "null argument");
     for (int g = 0; g < 3; ++g) if (!p->w_i[g] || !p->w_h[g] || !p->b_i[g] || !p->b_h[g]) return fail(SSD_ERR_INVALID, "null GRU parameter");
     if (precision != 1 && precision != 2) return fail(SSD_ERR_INVALID, "precision must be 1 or 2");
+    if (p->input_flags & SSD_INPUT_GATHER_ONEHOT) {       // every one-hot block as gathered rows: the dense blocks always fit the image
+        const uint32_t fl = p->input_flags;
+        if (p->n_actions < 1 || p->n_agents < 1 || p->n_agents > SSD_MAX_AGENTS)
+            return fail(SSD_ERR_INVALID, "ssd_policy_pack_head: SSD_INPUT_GATHER_ONEHOT needs n_actions and 1 .. SSD_MAX_AGENTS agents");
+        if (fl & ~(SSD_INPUT_EXPLICIT | SSD_INPUT_GATHER_ONEHOT | 127u)) return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_pack_head: input_flags holds a block no head builds");
+        const int full = 32 + ((fl & SSD_INPUT_LAST_ACTION) ? p->n_actions : 0) + ((fl & SSD_INPUT_AGENT_ID) ? p->n_agents : 0) +
+                         ((fl & SSD_INPUT_REWARD) ? 1 : 0) + ((fl & SSD_INPUT_INC_REWARD) ? 1 : 0) +
+                         ((fl & SSD_INPUT_OTHERS_LAST_ACTION) ? p->n_agents * p->n_actions : 0) +
+                         ((fl & SSD_INPUT_DISTANCE) ? p->n_agents : 0) + ((fl & SSD_INPUT_AGENT_POS) ? 2 : 0);
+        if ((p->fc1_in != full && p->fc1_in != full + p->n_actions) || p->n_actions > 15 || p->fc2_in < 64 || p->fc2_in > 80 || p->fc2_out < 1 || p->fc2_out > 15)
+            return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_pack_head: SSD_INPUT_GATHER_ONEHOT: fc1_in = 32 + the widths of the input_flags blocks (inc head: + n_actions), 64 <= fc2_in <= 80, fc2_out <= 15");
+        if (!p->onehot_rows || (reinterpret_cast<uintptr_t>(p->onehot_rows) & 15))
+            return fail(SSD_ERR_INVALID, "ssd_policy_pack_head: SSD_INPUT_GATHER_ONEHOT needs onehot_rows, 16-byte aligned");
+        if (reinterpret_cast<uintptr_t>(image) & 15) return fail(SSD_ERR_INVALID, "image must be 16-byte aligned");
+        launch_pack_head(p, precision, image, (hipStream_t)stream);
+        return launched();
+    }
     const bool others = (p->input_flags & SSD_INPUT_OTHERS_LAST_ACTION) != 0;
     if (others && (p->n_actions < 1 || p->n_agents < 1)) return fail(SSD_ERR_INVALID, "ssd_policy_pack_head: obs_others_last_action needs n_actions");
     const int dense_in = p->fc1_in - (others ? p->n_agents * p->n_actions : 0);
@@ -825,13 +842,23 @@ static int check_head(const ssd_policy_head* a, int inc) {
     // layout limits of the fused kernel: 32 encoder features + tail (+ one-hot action for inc) within 64 columns, 16 fc2 rows
     {
         const uint32_t fl = a->input_flags ? (a->input_flags & ~SSD_INPUT_EXPLICIT) : (uint32_t)SSD_INPUT_FLAGS_SHIPPED;
-        if (fl & ~127u) return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_head: input_flags holds a block the fused head does not build");
-        const bool others = (fl & SSD_INPUT_OTHERS_LAST_ACTION) != 0;      // gathered rows of fc1, not columns of the image
-        const int block = others ? a->n_agents * a->n_actions : 0;
+        if (fl & ~(127u | SSD_INPUT_GATHER_ONEHOT)) return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_head: input_flags holds a block the fused head does not build");
+        const bool onehot = (fl & SSD_INPUT_GATHER_ONEHOT) != 0;           // every one-hot block as gathered rows of fc1
+        const bool others = !onehot && (fl & SSD_INPUT_OTHERS_LAST_ACTION) != 0;      // gathered rows of fc1, not columns of the image
+        const int block = (fl & SSD_INPUT_OTHERS_LAST_ACTION) ? a->n_agents * a->n_actions : 0;
         const int tail = ((fl & SSD_INPUT_LAST_ACTION) ? a->n_actions : 0) + ((fl & SSD_INPUT_AGENT_ID) ? a->n_agents : 0) +
                          ((fl & SSD_INPUT_REWARD) ? 1 : 0) + ((fl & SSD_INPUT_INC_REWARD) ? 1 : 0) +
                          ((fl & SSD_INPUT_DISTANCE) ? a->n_agents : 0) + ((fl & SSD_INPUT_AGENT_POS) ? 2 : 0);
-        if (a->input_shape != 32 + tail + block || 32 + tail + a->n_actions > 64 || a->n_actions + 7 > 16)
+        if (onehot) {       // the dense columns (at most 32 + 1 + 1 + n + 2) always fit: only the width has to match the flags
+            if (a->input_shape != 32 + tail + block || a->n_actions + 7 > 16)
+                return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_head: SSD_INPUT_GATHER_ONEHOT: input_shape must be 32 + the width of the input_flags blocks");
+            if (!a->onehot_rows || !a->prev_record) return fail(SSD_ERR_INVALID, "ssd_policy_head: SSD_INPUT_GATHER_ONEHOT needs onehot_rows and prev_record");
+            if (a->n_agents > SSD_MAX_AGENTS) return fail(SSD_ERR_INVALID, "ssd_policy_head: SSD_INPUT_GATHER_ONEHOT takes at most SSD_MAX_AGENTS agents");
+            if ((reinterpret_cast<uintptr_t>(a->onehot_rows) | reinterpret_cast<uintptr_t>(a->prev_record) | reinterpret_cast<uintptr_t>(a->prev_record_out)) & 15)
+                return fail(SSD_ERR_INVALID, "ssd_policy_head: onehot_rows / prev_record / prev_record_out must be 16-byte aligned");
+            if (a->prev_record_out && (inc || a->prev_record_out == a->prev_record))
+                return fail(SSD_ERR_INVALID, "ssd_policy_head: prev_record_out is the env head's output and the other buffer of the pair");
+        } else if (a->input_shape != 32 + tail + block || 32 + tail + a->n_actions > 64 || a->n_actions + 7 > 16)
             return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_head: input_shape must be 32 + the width of the input_flags blocks and fit 64 columns");
         if (others) {
             if (!a->others_rows || !a->prev_record) return fail(SSD_ERR_INVALID, "ssd_policy_head: obs_others_last_action needs others_rows and prev_record");
@@ -860,6 +887,8 @@ static int policy_head(const ssd_policy_head* a, int inc, void* stream) {
     return launched();
 }
 int ssd_policy_head_inc_encode(const ssd_policy_head* h, const ssd_policy_encode_args* e, void* stream) {
+    if (h && h->input_flags && (h->input_flags & SSD_INPUT_GATHER_ONEHOT))
+        return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_head_inc_encode: SSD_INPUT_GATHER_ONEHOT takes ssd_policy_encode + ssd_policy_head_inc");
     if (h && h->input_flags && (h->input_flags & SSD_INPUT_OTHERS_LAST_ACTION))
         return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_head_inc_encode: obs_others_last_action takes ssd_policy_encode + ssd_policy_head_inc");
     if (const int bad = check_head(h, 1)) return bad;

@@ -282,6 +282,8 @@ struct HeadCold {
 // sits behind it, and every shipped kernel keeps its argument offsets -- so they travel in slots of the OTHER head's filing, which
 // this head's code never reads (gather_slots; launch_policy_head stores them there):
 //   env head: p_inc | d_actions_inc | d_reward (block B is the inc head's)      inc head: pos_copy | orient_copy (the env head's pose copies)
+// GEN = 3 (SSD_INPUT_GATHER_ONEHOT) uses the same three slots: its table onehot_rows takes the place of others_rows, and byte 6 of
+// tail_layout (both heads) says whether the table ends with the others' last-action block.
 template <int INC> constexpr int gather_slots() { return INC ? (int)offsetof(HeadCold, pos_copy) : (int)offsetof(HeadCold, p_inc); }
 static_assert(offsetof(HeadCold, orient_copy) == offsetof(HeadCold, pos_copy) + 8 && offsetof(HeadCold, d_actions_inc) == offsetof(HeadCold, p_inc) + 8 &&
               offsetof(HeadCold, d_reward) == offsetof(HeadCold, p_inc) + 16, "others_rows | prev_rec | prev_rec_out are consecutive slots");
@@ -545,6 +547,9 @@ __device__ __forceinline__ void load_tile(const HeadK& a, int tile, int agent, i
 // obs_others_last_action.  The block is n one-hot vectors, so its product with fc1 is the sum of n weight ROWS: the dense blocks sit
 // in compacted columns as if the block were absent (GEN = 1's tail_layout, the same 64-column image and MFMA chain) and the rows
 // W1[off + g A + a_g, :] are gathered as f32 from HeadCold::others_rows and added to fc1's output with the bias (others_gather).
+// GEN = 3 (both heads): SSD_INPUT_GATHER_ONEHOT -- EVERY one-hot block is gathered: the agent's own last action, the agent id (row 0 of
+// the owner's table: constant per agent, a second bias row the pack launch wrote), the inc head's one-hot of the action just chosen and,
+// when tail_layout's byte 6 is set, the others' block as in GEN = 2.  The image holds only 32 + sign r + sign inc + distances + pos.
 // WAVES: compute waves per workgroup = 16-row tiles per workgroup (the host sizes the grid: bpa = ceil(tiles per agent / WAVES)); the
 // workgroup has WAVES + 1 waves, the last one is the loader.
 // LOOP: a wave walks tiles tile, tile + bpa * WAVES, ... (grids larger than the chip: Cleanup-10 x 8192 has 512 tiles per agent); with
@@ -631,16 +636,16 @@ __device__ __forceinline__ void head_body(const HeadK& a_entry, uint8_t* lds_raw
         else if (!INC && a.feat_part) { load_tile<INC, false, PRE_SMALL>(a, tile, agent, lane, in); }     // (band partials instead of the input row: Harvest)
         else load_tile<INC, true, PRE_SMALL>(a, tile, agent, lane, in);
     }
-    // GEN 2: the env's previous-action record (16 bytes: byte g = agent g's last action, 0xFF = none) -- the last load of the input phase
+    // GEN 2 / 3: the env's previous-action record (16 bytes: byte g = agent g's last action, 0xFF = none) -- the last load of the input phase
     u32x4 prec = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-    if constexpr (GEN == 2) {
+    if constexpr (GEN >= 2) {
         if (tile < tiles) {
             auto rec = cold_ptr<const uint8_t>(COLD_BASE, gather_slots<INC>() + 8);
             const int b0 = tile * 16 + m, bc0 = b0 < N ? b0 : N - 1;
             prec = *(const u32x4 SSD_GLOBAL*)(rec + (size_t)bc0 * 16);
         }
     }
-    f32x4 gsum[4];                                                     // GEN 2: the gathered rows' sum, features 16 ot + 4 q .. + 3 of row m
+    f32x4 gsum[4];                                                     // GEN 2 / 3: the gathered rows' sum, features 16 ot + 4 q .. + 3 of row m
     if (!INC) PSTAMP(10);
     uint32_t step = 0;                                                 // (both assigned once the loads above are pinned, see below)
     bool file = false;
@@ -725,7 +730,7 @@ __device__ __forceinline__ void head_body(const HeadK& a_entry, uint8_t* lds_raw
 #pragma unroll
             for (int ct = 0; ct < 4; ++ct) {
                 x[ct] = in.x[ct];
-                if (ct >= 2) {
+                if (ct >= 2 && GEN != 3) {                            // (GEN 3: the action's row of fc1 is gathered below)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int k = 16 * ct + 4 * q + r - a.inp;     // [inputs | one-hot(action)] (homophily_agent.py:181)
@@ -736,18 +741,53 @@ __device__ __forceinline__ void head_body(const HeadK& a_entry, uint8_t* lds_raw
         }
         operand<PREC>(x, XS, bh, bl);
         (void)valid; (void)bc;
-        if constexpr (GEN == 2) {
+        if constexpr (GEN >= 2) {
             // sum over the agents g with a previous action of others_rows[agent][g A + pa_g][16 ot + 4 q ..]: one 16-byte load per (g, ot),
             // requested three agents at a time (12 loads in flight, then added: 40 results are never live at once); agents past n and
             // agents without a previous step re-read row 0 and add zeros -- nothing branches on a loaded value.  The loads are this
             // wave's own (the image is the loader wave's), so they delay no chunk; they land under the wait for fc1's fragments.
+            if constexpr (GEN == 2) {
 #pragma unroll
-            for (int ot = 0; ot < 4; ++ot) gsum[ot] = f32x4{0.f, 0.f, 0.f, 0.f};
-            const uint32_t row0 = (uint32_t)agent * (uint32_t)n * (uint32_t)A;
+                for (int ot = 0; ot < 4; ++ot) gsum[ot] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+            uint32_t row0 = (uint32_t)agent * (uint32_t)n * (uint32_t)A;
+            bool others_on = true;
             auto orows = cold_ptr<const float>(COLD_BASE, gather_slots<INC>());      // (fetched here: no pointer is held through the input phase)
+            if constexpr (GEN == 3) {
+                // the owner's table: row 0 = its agent-id row | A rows of its last action | A rows of the inc head's action | [n A rows of
+                // the others' block].  Three rows per lane quarter, all requested before any is used; the own previous action is byte
+                // `agent` of the record (wave-uniform shift), -1 / 0xFF re-reads row 1 and adds zeros; the inc action is clamped, not tested.
+                others_on = ((COLD_U64(tail_layout) >> 48) & 1u) != 0;                // (wave-uniform)
+                const uint32_t base = (uint32_t)agent * (uint32_t)(1 + 2 * A + (others_on ? n * A : 0));
+                row0 = base + (uint32_t)(1 + 2 * A);
+                const uint32_t w = (agent >> 2) == 0 ? prec[0] : (agent >> 2) == 1 ? prec[1] : (agent >> 2) == 2 ? prec[2] : prec[3];
+                const int pa = (int)(int8_t)(uint8_t)(w >> (8 * (agent & 3)));
+                const uint32_t keep_own = (pa >= 0 && pa < A) ? 0xFFFFFFFFu : 0u;
+                const uint32_t row_own = base + 1u + ((uint32_t)pa & keep_own);
+                int ai = 0;
+                if constexpr (INC) ai = in.act < 0 ? 0 : in.act > A - 1 ? A - 1 : in.act;
+                const uint32_t row_inc = base + (uint32_t)(1 + A + ai);
+                f32x4 r_id[4], r_own[4], r_inc[4];
+#pragma unroll
+                for (int ot = 0; ot < 4; ++ot) {
+                    const uint32_t col = 16u * ot + 4u * (uint32_t)q;
+                    r_id[ot] = *(const f32x4 SSD_GLOBAL*)((const uint8_t SSD_GLOBAL*)orows + (size_t)((base * 64u + col) * 4u));
+                    r_own[ot] = *(const f32x4 SSD_GLOBAL*)((const uint8_t SSD_GLOBAL*)orows + (size_t)((row_own * 64u + col) * 4u));
+                    if constexpr (INC) r_inc[ot] = *(const f32x4 SSD_GLOBAL*)((const uint8_t SSD_GLOBAL*)orows + (size_t)((row_inc * 64u + col) * 4u));
+                }
+#pragma unroll
+                for (int ot = 0; ot < 4; ++ot)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float v = r_own[ot][r];
+                        float sum = r_id[ot][r] + __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, v) & keep_own);
+                        if constexpr (INC) sum += r_inc[ot][r];
+                        gsum[ot][r] = sum;
+                    }
+            }
 #pragma unroll
             for (int g0 = 0; g0 < SSD_MAX_AGENTS; g0 += 3) {
-                if (g0 < n) {                                          // (wave-uniform)
+                if (g0 < n && others_on) {                             // (wave-uniform)
                     f32x4 part[3][4];
                     uint32_t keep[3];                                 // all ones = the row counts (a lane mask in a vector register, not an SGPR pair)
 #pragma unroll
@@ -851,7 +891,7 @@ __device__ __forceinline__ void head_body(const HeadK& a_entry, uint8_t* lds_raw
             const f32x4 bias = *reinterpret_cast<const f32x4*>(tail + HT_B1 + 16 * ot + 4 * q);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                if constexpr (GEN == 2) x1[ot][r] = leaky(fmaf(x1[ot][r], INV, bias[r]) + gsum[ot][r]);
+                if constexpr (GEN >= 2) x1[ot][r] = leaky(fmaf(x1[ot][r], INV, bias[r]) + gsum[ot][r]);
                 else x1[ot][r] = leaky(fmaf(x1[ot][r], INV, bias[r]));
             }
         }
@@ -945,7 +985,7 @@ __device__ __forceinline__ void head_body(const HeadK& a_entry, uint8_t* lds_raw
                 out_actions[(size_t)bb * n + agent] = act;
                 if (out_i32) out_i32[(size_t)bb * n + agent] = act;
                 if (p_act) p_act[(size_t)bb * n + agent] = act;
-                if constexpr (GEN == 2) {                              // the OTHER buffer of the pair: sibling workgroups still read this timestep's
+                if constexpr (GEN >= 2) {                              // the OTHER buffer of the pair: sibling workgroups still read this timestep's
                     auto rec_out = cold_ptr<uint8_t>(COLD_BASE, gather_slots<0>() + 16);
                     if (rec_out) rec_out[(size_t)bb * 16 + agent] = (uint8_t)act;
                 }
@@ -1066,7 +1106,7 @@ constexpr int HEAD_WAVES_LOOP = SSD_HEAD_WAVES_LOOP;   // (round 3: 6, when the 
 #define SSD_HEAD_WAVES_GATHER 7
 #endif
 constexpr int HEAD_WAVES_GATHER = SSD_HEAD_WAVES_GATHER;
-constexpr int head_waves(bool loop, int gen = 0) { return gen == 2 ? HEAD_WAVES_GATHER : loop ? HEAD_WAVES_LOOP : HEAD_WAVES; }
+constexpr int head_waves(bool loop, int gen = 0) { return gen >= 2 ? HEAD_WAVES_GATHER : loop ? HEAD_WAVES_LOOP : HEAD_WAVES; }
 // The leading scalar arguments repeat what a compute wave needs for its largest loads (the tile's state and input rows): built
 // with -amdgpu-kernarg-preload-count they arrive in SGPRs with the wave (struct arguments are not preloaded).  The looped
 // instantiations re-read HeadK from the segment at every pass (refetch_head_args) and ignore them.
@@ -1086,6 +1126,8 @@ __global__ __launch_bounds__((head_waves(LOOP, GEN) + 1) * 64) void k_head(uint3
 
 // obs_others_last_action: the GEN = 2 kernels (both heads)
 static bool head_gathers(const ssd_policy_head* p) { return p->input_flags && (p->input_flags & SSD_INPUT_OTHERS_LAST_ACTION); }
+// SSD_INPUT_GATHER_ONEHOT: the GEN = 3 kernels (both heads; with or without the others' block)
+static bool head_gathers_onehot(const ssd_policy_head* p) { return p->input_flags && (p->input_flags & SSD_INPUT_GATHER_ONEHOT); }
 static int chip_cus() {
     static int cus[64] = {};
     int dev = 0;
@@ -1107,14 +1149,20 @@ static void head_args(const ssd_policy_head* p, HeadK& k, HeadCold& c, int waves
     k.feat_part = p->feat_part; k.feat_bands = p->feat_bands; k.lin_b = p->lin_b;
     k.ep_ret = p->ep_return; k.term = p->terminated;
     k.recv = p->recv_inc; k.avail_bits = p->avail_bits; c.recv_out = p->recv_inc_out;
-    if (head_gathers(p)) k.inp -= k.n * k.A;       // the dense width: the inc head's one-hot action follows the compacted columns
+    const bool onehot = head_gathers_onehot(p);
+    if (onehot) {                                  // the dense width: features | sign r | sign inc | distances | pos
+        const uint32_t fl = p->input_flags;
+        k.inp = 32 + ((fl & SSD_INPUT_REWARD) ? 1 : 0) + ((fl & SSD_INPUT_INC_REWARD) ? 1 : 0) + ((fl & SSD_INPUT_DISTANCE) ? k.n : 0) +
+                ((fl & SSD_INPUT_AGENT_POS) ? 2 : 0);
+    } else if (head_gathers(p)) k.inp -= k.n * k.A;       // the dense width: the inc head's one-hot action follows the compacted columns
     c.out_actions = p->out_actions; c.q_out = p->q_out; c.out_actions_i32 = p->out_actions_i32; c.pos_copy = p->pos_copy; c.orient_copy = p->orient_copy;
     c.d_pos = p->dst_pos; c.d_orient = p->dst_orient; c.d_onehot = p->dst_actions_onehot; c.d_reward = p->dst_reward;
     c.d_clean = p->dst_clean_num; c.d_den = p->dst_apple_den; c.d_term = p->dst_terminated;
     c.d_actions = p->dst_actions; c.d_actions_inc = p->dst_actions_inc; c.p_act = p->prev_actions_out; c.p_inc = p->prev_actions_inc_out;
     c.p_rew = p->prev_reward_out; c.ep_ret = p->ep_return; c.next_t = p->next_t_out;
     {   // first tail column of each block, reference order (homophily_controller.py:137-184); input_flags 0 = the shipped set
-        const uint32_t fl = p->input_flags ? (p->input_flags & ~SSD_INPUT_EXPLICIT) : (uint32_t)SSD_INPUT_FLAGS_SHIPPED;
+        uint32_t fl = p->input_flags ? (p->input_flags & ~SSD_INPUT_EXPLICIT) : (uint32_t)SSD_INPUT_FLAGS_SHIPPED;
+        if (onehot) fl &= ~(uint32_t)(SSD_INPUT_LAST_ACTION | SSD_INPUT_AGENT_ID);      // gathered: no columns
         const int width[6] = {k.A, k.n, 1, 1, k.n, 2};
         const uint32_t bit[6] = {SSD_INPUT_LAST_ACTION, SSD_INPUT_AGENT_ID, SSD_INPUT_REWARD, SSD_INPUT_INC_REWARD, SSD_INPUT_DISTANCE,
                                  SSD_INPUT_AGENT_POS};
@@ -1125,6 +1173,7 @@ static void head_args(const ssd_policy_head* p, HeadK& k, HeadCold& c, int waves
             if (fl & bit[f]) col += width[f];
             lay |= (uint64_t)(uint8_t)(int8_t)o << (8 * f);
         }
+        if (onehot && (fl & SSD_INPUT_OTHERS_LAST_ACTION)) lay |= 1ull << 48;           // byte 6 (GEN 3, both heads): the table ends with the others' block
         c.tail_layout = lay;
     }
     c.next_step = p->next_step_out; c.t_copy = p->t_copy_out; c.step_copy = p->step_copy_out;
@@ -1151,7 +1200,8 @@ static int head_plan(const ssd_policy_head* p, HeadK& k, HeadCold& c, bool gen, 
 int launch_policy_head(const ssd_policy_head* p, int inc, hipStream_t s) {
     HeadK k;
     HeadCold c;
-    const bool gather = head_gathers(p);
+    const bool onehot = head_gathers_onehot(p);
+    const bool gather = onehot || head_gathers(p);
     const bool gen = !gather && !inc && p->input_flags && (p->input_flags & ~SSD_INPUT_EXPLICIT) != (uint32_t)SSD_INPUT_FLAGS_SHIPPED;
     bool looped = false;
     int waves;
@@ -1159,7 +1209,7 @@ int launch_policy_head(const ssd_policy_head* p, int inc, hipStream_t s) {
         head_args(p, k, c, HEAD_WAVES_GATHER);
         looped = head_loops(k, HEAD_WAVES_GATHER);
         waves = HEAD_WAVES_GATHER;
-        const void* g3[3] = {p->others_rows, p->prev_record, p->prev_record_out};      // (see gather_slots)
+        const void* g3[3] = {onehot ? p->onehot_rows : p->others_rows, p->prev_record, p->prev_record_out};      // (see gather_slots)
         __builtin_memcpy(reinterpret_cast<uint8_t*>(&c) + (inc ? gather_slots<1>() : gather_slots<0>()), g3, inc ? 16 : 24);
     } else waves = head_plan(p, k, c, gen, looped);
     const int prec = p->precision == 1 ? 1 : 2;
@@ -1196,8 +1246,19 @@ int launch_policy_head(const ssd_policy_head* p, int inc, hipStream_t s) {
     const void* gather_fns[16] = {SSD_G2(0, 2, 9), SSD_G2(1, 2, 9), SSD_G2(0, 1, 9), SSD_G2(1, 1, 9),      // [A == 8][prec == 1][inc][looped]
                                   SSD_G2(0, 2, 8), SSD_G2(1, 2, 8), SSD_G2(0, 1, 8), SSD_G2(1, 1, 8)};
 #undef SSD_G2
+#define SSD_G3(I, P, AT_) reinterpret_cast<const void*>(&k_head<I, P, AT_, 3, false>), reinterpret_cast<const void*>(&k_head<I, P, AT_, 3, true>)
+    const void* onehot_fns[16] = {SSD_G3(0, 2, 9), SSD_G3(1, 2, 9), SSD_G3(0, 1, 9), SSD_G3(1, 1, 9),      // (the same order)
+                                  SSD_G3(0, 2, 8), SSD_G3(1, 2, 8), SSD_G3(0, 1, 8), SSD_G3(1, 1, 8)};
+#undef SSD_G3
+    static bool onehot_attr_done_dev[64] = {};
+    if (onehot && !onehot_attr_done_dev[dev]) {
+        const size_t l2 = (size_t)head_lds_bytes(HEAD_WAVES_GATHER, 2);
+        for (const void* f : onehot_fns)
+            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2) != hipSuccess) return -1;
+        onehot_attr_done_dev[dev] = true;
+    }
     static bool gather_attr_done_dev[64] = {};
-    if (gather && !gather_attr_done_dev[dev]) {
+    if (gather && !onehot && !gather_attr_done_dev[dev]) {
         const size_t l2 = (size_t)head_lds_bytes(HEAD_WAVES_GATHER, 2);
         for (const void* f : gather_fns)
             if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2) != hipSuccess) return -1;
@@ -1206,7 +1267,7 @@ int launch_policy_head(const ssd_policy_head* p, int inc, hipStream_t s) {
     if (k.N >= (1 << 24) || k.n >= 256) return -1;
     uint32_t nn = (uint32_t)k.N | ((uint32_t)k.n << 24);
     void* args[10] = {&nn, &k.bpa, &k.h, &k.inputs, &k.prev_actions, &k.prev_reward, &k.recv, &k.pos, &k, &c};
-    const void* fn = gather ? gather_fns[(k.A == 8 ? 8 : 0) + (prec == 1 ? 4 : 0) + (inc ? 2 : 0) + (looped ? 1 : 0)]
+    const void* fn = gather ? (onehot ? onehot_fns : gather_fns)[(k.A == 8 ? 8 : 0) + (prec == 1 ? 4 : 0) + (inc ? 2 : 0) + (looped ? 1 : 0)]
                    : gen ? gen_fns[(k.A == 8 ? 2 : 0) + (prec == 1 ? 1 : 0)]
                          : fns[(looped ? 8 : 0) + (k.A == 8 ? 4 : 0) + (prec == 1 ? 2 : 0) + (inc ? 1 : 0)];
     if (hipLaunchKernel(fn, dim3(k.n * bpa), dim3((waves + 1) * 64), args, lds, s) != hipSuccess) return -1;
@@ -1221,13 +1282,47 @@ __host__ __device__ inline int others_offset(uint32_t flags, int n, int A) {
     return 32 + ((flags & SSD_INPUT_LAST_ACTION) ? A : 0) + ((flags & SSD_INPUT_AGENT_ID) ? n : 0) + ((flags & SSD_INPUT_REWARD) ? 1 : 0) +
            ((flags & SSD_INPUT_INC_REWARD) ? 1 : 0);
 }
-template <int PREC, bool OTHERS>
+// SSD_INPUT_GATHER_ONEHOT: fc1's row behind dense column k of the image (k >= 32: sign r | sign inc | distances | pos, each iff flagged,
+// at their places in the reference's full row), -1 = a padding column
+__host__ __device__ inline int onehot_dense_row(uint32_t flags, int n, int A, int k) {
+    if (k < 32) return k;
+    const int start_r = 32 + ((flags & SSD_INPUT_LAST_ACTION) ? A : 0) + ((flags & SSD_INPUT_AGENT_ID) ? n : 0);
+    const int start_i = start_r + ((flags & SSD_INPUT_REWARD) ? 1 : 0);
+    const int start_d = others_offset(flags, n, A) + ((flags & SSD_INPUT_OTHERS_LAST_ACTION) ? n * A : 0);
+    const int start_p = start_d + ((flags & SSD_INPUT_DISTANCE) ? n : 0);
+    int j = k - 32;
+    if (flags & SSD_INPUT_REWARD) { if (j < 1) return start_r + j; j -= 1; }
+    if (flags & SSD_INPUT_INC_REWARD) { if (j < 1) return start_i + j; j -= 1; }
+    if (flags & SSD_INPUT_DISTANCE) { if (j < n) return start_d + j; j -= n; }
+    if (flags & SSD_INPUT_AGENT_POS) { if (j < 2) return start_p + j; j -= 2; }
+    return -1;
+}
+// fc1's row behind row r of the owner's gather table (the layout of ssd_policy_head.onehot_rows), -1 = a row of zeros.  `full` = the
+// reference's width of the env input row; the inc head's fc1 has n_actions more rows (the one-hot of the action just chosen).
+__host__ __device__ inline int onehot_table_row(uint32_t flags, int n, int A, int agent, int fc1_in, int r) {
+    const int full = others_offset(flags, n, A) + ((flags & SSD_INPUT_OTHERS_LAST_ACTION) ? n * A : 0) + ((flags & SSD_INPUT_DISTANCE) ? n : 0) +
+                     ((flags & SSD_INPUT_AGENT_POS) ? 2 : 0);
+    if (r == 0) return (flags & SSD_INPUT_AGENT_ID) ? 32 + ((flags & SSD_INPUT_LAST_ACTION) ? A : 0) + agent : -1;
+    if (r < 1 + A) return (flags & SSD_INPUT_LAST_ACTION) ? 32 + r - 1 : -1;
+    if (r < 1 + 2 * A) return fc1_in == full + A ? full + r - 1 - A : -1;
+    return others_offset(flags, n, A) + r - 1 - 2 * A;
+}
+// MODE: 0 = every column of fc1 is a column of the image, 1 = OTHERS, 2 = SSD_INPUT_GATHER_ONEHOT
+template <int PREC, int MODE>
 __device__ __forceinline__ void pack_head_body(const ssd_policy_head_params& p, uint8_t* image, int32_t* err) {
+    constexpr bool OTHERS = MODE == 1;
     constexpr size_t IMAGE_BYTES = SSD_POLICY_IMAGE_BYTES(PREC);
     constexpr float WS = PREC == 2 ? HEAD_WSCALE : 1.f;
     const int agent = blockIdx.y, e = blockIdx.x * 256 + threadIdx.x;
     const int blk = OTHERS ? p.n_agents * p.n_actions : 0, off = OTHERS ? others_offset(p.input_flags, p.n_agents, p.n_actions) : 0;
     if (OTHERS && e < blk * 64) p.others_rows[(size_t)agent * blk * 64 + e] = p.fc1_w[((size_t)agent * p.fc1_in + off) * 64 + e];
+    if constexpr (MODE == 2) {
+        const int rows = SSD_ONEHOT_ROWS(p.n_agents, p.n_actions, p.input_flags);
+        if (e < rows * 64) {
+            const int src = onehot_table_row(p.input_flags, p.n_agents, p.n_actions, agent, p.fc1_in, e >> 6);
+            p.onehot_rows[(size_t)agent * rows * 64 + e] = src >= 0 ? p.fc1_w[((size_t)agent * p.fc1_in + src) * 64 + (e & 63)] : 0.f;
+        }
+    }
     uint8_t* img = image + (size_t)agent * IMAGE_BYTES;
     if (e < HF_TOT * 512) {
         const int F = e >> 9, lane = (e >> 3) & 63, j = e & 7, q = lane >> 4, m = lane & 15;
@@ -1235,7 +1330,10 @@ __device__ __forceinline__ void pack_head_body(const ssd_policy_head_params& p, 
         int piece, term_pieces = 4;                                    // hi term's piece; the lo term sits term_pieces further
         if (F < HF_WI) {
             const int ot = F >> 1, s = F & 1, out = 16 * ot + m, k = 32 * s + 16 * (j >> 2) + 4 * q + (j & 3);
-            if (OTHERS) {
+            if constexpr (MODE == 2) {
+                const int row = onehot_dense_row(p.input_flags, p.n_agents, p.n_actions, k);
+                if (row >= 0 && row < p.fc1_in) w = p.fc1_w[((size_t)agent * p.fc1_in + row) * 64 + out];
+            } else if (OTHERS) {
                 const int row = k < off ? k : k + blk;
                 if (row < p.fc1_in) w = p.fc1_w[((size_t)agent * p.fc1_in + row) * 64 + out];
             } else if (k < p.fc1_in) w = p.fc1_w[((size_t)agent * p.fc1_in + k) * 64 + out];
@@ -1273,14 +1371,19 @@ __device__ __forceinline__ void pack_head_body(const ssd_policy_head_params& p, 
     }
 }
 template <int PREC>
-__global__ __launch_bounds__(256) void k_pack_head(ssd_policy_head_params p, uint8_t* image, int32_t* err) { pack_head_body<PREC, false>(p, image, err); }
+__global__ __launch_bounds__(256) void k_pack_head(ssd_policy_head_params p, uint8_t* image, int32_t* err) { pack_head_body<PREC, 0>(p, image, err); }
 template <int PREC>
-__global__ __launch_bounds__(256) void k_pack_head_others(ssd_policy_head_params p, uint8_t* image, int32_t* err) { pack_head_body<PREC, true>(p, image, err); }
+__global__ __launch_bounds__(256) void k_pack_head_others(ssd_policy_head_params p, uint8_t* image, int32_t* err) { pack_head_body<PREC, 1>(p, image, err); }
+template <int PREC>
+__global__ __launch_bounds__(256) void k_pack_head_onehot(ssd_policy_head_params p, uint8_t* image, int32_t* err) { pack_head_body<PREC, 2>(p, image, err); }
 
 void launch_pack_head(const ssd_policy_head_params* p, int prec, void* image, hipStream_t s) {
     const dim3 grid((HF_TOT * 512 + 255) / 256, p->n_agents);
     int32_t* err = numeric_err_word();
-    if (p->input_flags & SSD_INPUT_OTHERS_LAST_ACTION) {      // the grid covers the block's n A x 64 floats too (29 696 threads per agent)
+    if (p->input_flags & SSD_INPUT_GATHER_ONEHOT) {           // the grid covers the table too (at most 1 + 2 A + n A rows of 64 floats)
+        if (prec == 2) hipLaunchKernelGGL(k_pack_head_onehot<2>, grid, dim3(256), 0, s, *p, static_cast<uint8_t*>(image), err);
+        else hipLaunchKernelGGL(k_pack_head_onehot<1>, grid, dim3(256), 0, s, *p, static_cast<uint8_t*>(image), err);
+    } else if (p->input_flags & SSD_INPUT_OTHERS_LAST_ACTION) {      // the grid covers the block's n A x 64 floats too (29 696 threads per agent)
         if (prec == 2) hipLaunchKernelGGL(k_pack_head_others<2>, grid, dim3(256), 0, s, *p, static_cast<uint8_t*>(image), err);
         else hipLaunchKernelGGL(k_pack_head_others<1>, grid, dim3(256), 0, s, *p, static_cast<uint8_t*>(image), err);
     } else if (prec == 2) hipLaunchKernelGGL(k_pack_head<2>, grid, dim3(256), 0, s, *p, static_cast<uint8_t*>(image), err);

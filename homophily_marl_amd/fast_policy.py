@@ -14,7 +14,10 @@ Both implement the shipped _build_inputs flag set (config/default.yaml:45-51).  
 the controller's rollout_input_flags): the block's n * n_actions columns are n one-hot vectors, so the heads add the matching rows of
 fc1 (others_rows, snapshot by the pack launch) instead of multiplying by them; the previous actions of all agents travel in a pair of
 per-env byte records selected by the timestep's parity (prev_rec: the env head of t reads [t & 1] and writes the other, the inc head of
-t reads [t & 1]) -- no launch reads what a sibling workgroup writes.
+t reads [t & 1]) -- no launch reads what a sibling workgroup writes.  fused_onehot_gather (rollout_input_flags holds
+abi.INPUT_GATHER_ONEHOT): every one-hot block is gathered that way -- the own last action, the agent id, the inc head's one-hot action,
+the others' block if flagged -- from one table per head (onehot_<head>); the image keeps 32 + sign r + sign inc + distances + pos, which
+fits at any team size.  The own previous action is then read from prev_rec as well.
 Action RNG: the package's counter generator (not torch's Philox) keyed by the GLOBAL env id (env_id_base + local env), so env
 shards draw what the unsharded job draws; exploration draws are not parity-pinned against torch.
 """
@@ -40,14 +43,17 @@ class FastPolicy:
         flags = getattr(mac, "rollout_input_flags", mac.input_flags)
         self.flags = flags
         self.others = flags is not None and bool(flags & abi.INPUT_OTHERS_LAST_ACTION)
+        self.gather = flags is not None and bool(flags & abi.INPUT_GATHER_ONEHOT)
         self.inp_dense = self.inp - (self.n * self.A if self.others else 0)     # columns of the 64-column image / of `inputs`
+        if self.gather:     # every one-hot block is gathered: the inc head's action too (nothing follows the dense columns)
+            self.inp_dense -= (self.A if flags & abi.INPUT_LAST_ACTION else 0) + (self.n if flags & abi.INPUT_AGENT_ID else 0)
         self.V = int(a.obs_dims[0])
         self.precision, self.env_id_base = int(precision), int(env_id_base) & 0xFFFFFFFF
         n, N, H = self.n, self.N, self.H
         f32 = dict(dtype=th.float32, device=self.dev)
         # fused: one launch per head (csrc/ssd_policy_mfma.hip), inputs padded to 64 columns; otherwise the per-layer
         # composition below (batched hipBLASLt GEMMs + the small kernels of csrc/ssd_policy.hip)
-        self.fused = bool(fused) and H == 64 and self.inp_dense + self.A <= 64 and self.A + 7 <= 16 and flags is not None
+        self.fused = bool(fused) and H == 64 and self.inp_dense + (0 if self.gather else self.A) <= 64 and self.A + 7 <= 16 and flags is not None
         # the per-layer composition assembles the shipped input layout only (ssd_build_inputs)
         assert self.fused or mac.shipped_flags, "FastPolicy: this _build_inputs flag set needs the fused heads (FastPolicy.supports)"
         # encoder images: the class-LUT layout (conv as a table sum, no conv MFMAs: include/ssd_hip.h SSD_ENCODE_LAYOUT_LUT) unless
@@ -62,7 +68,7 @@ class FastPolicy:
             and (shipped or self.enc_layout == abi.ENCODE_LAYOUT_LUT)
         # act_inc_encode (inc head of t + encoder of t + 1 as one launch: the pipelined rollout) is instantiated for 15 / 31 only;
         # at the other edges the rollout takes the standalone encoder and inc-head launches
-        self.inc_encode = self.fused_enc and shipped and not self.others     # (obs_others_last_action: the four standalone launches)
+        self.inc_encode = self.fused_enc and shipped and not self.others and not self.gather     # (gathered layouts: the four standalone launches)
         self.bands = abi.encode_bands(self.V) if self.fused_enc else 1
         # bf16 MFMA products an f32-equivalent product costs (bench.py's roofline accounting); conv: the planes are exact, 2
         self.n_products = dict(encode_conv=2, encode_lin=3, head_env=3, head_inc=3) if precision == 2 else \
@@ -86,7 +92,7 @@ class FastPolicy:
         self.seed = seed & 0xFFFFFFFF
         self.arange_n = th.arange(n, device=self.dev).unsqueeze(1)
         # every agent's previous env action, one byte per agent (0xFF = none), 16 bytes per env, as a pair selected by the timestep's parity
-        self.prev_rec = th.full((2, N, abi.PREV_RECORD_BYTES), 0xFF, dtype=th.uint8, device=self.dev) if self.others else None
+        self.prev_rec = th.full((2, N, abi.PREV_RECORD_BYTES), 0xFF, dtype=th.uint8, device=self.dev) if (self.others or self.gather) else None
         if share_packs_from is not None:
             self.p = share_packs_from.p          # same weights: one packed copy serves every group
         else:
@@ -142,7 +148,9 @@ class FastPolicy:
             if self.fused:
                 for head in ("env", "inc"):
                     self.p["img_" + head] = th.zeros(self.n, abi.policy_image_bytes(self.precision), **u8)
-                    if self.others:     # fc1's rows of the others' last-action block, f32 as they are (written by the pack launch)
+                    if self.gather:     # fc1's rows of every one-hot block (ssd_policy_head.onehot_rows; written by the pack launch)
+                        self.p["onehot_" + head] = th.zeros(self.n, abi.onehot_rows(self.n, self.A, self.flags), 64, dtype=th.float32, device=self.dev)
+                    elif self.others:   # fc1's rows of the others' last-action block, f32 as they are (written by the pack launch)
                         self.p["rows_" + head] = th.zeros(self.n, self.n * self.A, 64, dtype=th.float32, device=self.dev)
             if self.fused_enc:
                 cbytes, lbytes = abi.encode_frag_bytes(self.V, self.precision, self.enc_layout)
@@ -154,7 +162,10 @@ class FastPolicy:
         if self.fused:
             for head in ("env", "inc"):
                 hp = self._head_params(head)
-                if self.others:
+                if self.gather:
+                    hp.input_flags, hp.n_actions = abi.INPUT_EXPLICIT | int(self.flags), self.A
+                    hp.onehot_rows = self.p["onehot_" + head].data_ptr()
+                elif self.others:
                     hp.input_flags, hp.n_actions = abi.INPUT_EXPLICIT | int(self.flags), self.A
                     hp.others_rows = self.p["rows_" + head].data_ptr()
                 abi.check(self.lib, self.lib.ssd_policy_pack_head(C.byref(hp), self.precision, self.p["img_" + head].data_ptr(), st))
@@ -168,13 +179,16 @@ class FastPolicy:
         """Whether the rollout kernels build this controller's input layout: the shipped flag set on either path, any other
         combination of the _build_inputs flags (homophily_controller.py:137-184) on the fused heads as long as the DENSE inputs (+ the
         inc head's one-hot action) fit the 64-column weight image.  obs_others_last_action is not dense -- the heads gather fc1's rows
-        for it -- and is taken when the controller opts in (rollout_input_flags holds bit 64; else its flag word is None)."""
+        for it -- and is taken when the controller opts in (rollout_input_flags holds bit 64; else its flag word is None).  Under
+        abi.INPUT_GATHER_ONEHOT (config key fused_onehot_gather) no one-hot block is dense and every flag set fits."""
         a = mac.args
         if mac.shipped_flags:
             return True
         flags = getattr(mac, "rollout_input_flags", mac.input_flags)
         if flags is None:
             return False
+        if flags & abi.INPUT_GATHER_ONEHOT:     # dense: 32 + sign r + sign inc + distances + pos <= 46 at n <= 10
+            return bool(fused) and a.rnn_hidden_dim == 64 and a.n_actions + 7 <= 16 and mac.n_agents <= abi.MAX_AGENTS
         dense = mac.input_shape - (mac.n_agents * a.n_actions if flags & abi.INPUT_OTHERS_LAST_ACTION else 0)
         return bool(fused) and a.rnn_hidden_dim == 64 and dense + a.n_actions <= 64 and a.n_actions + 7 <= 16
 
@@ -207,8 +221,11 @@ class FastPolicy:
         a.q_out = None if q_out is None else q_out.data_ptr()
         a.precision, a.env_id_base = self.precision, self.env_id_base
         a.input_flags = abi.INPUT_EXPLICIT | int(self.flags)
-        if self.others:
+        if self.gather:
+            a.onehot_rows = self.p["onehot_inc" if inc else "onehot_env"].data_ptr()
+        elif self.others:
             a.others_rows = self.p["rows_inc" if inc else "rows_env"].data_ptr()
+        if self.prev_rec is not None:
             a.prev_record = self.prev_rec[par & 1].data_ptr()
             if not inc:
                 a.prev_record_out = self.prev_rec[(par & 1) ^ 1].data_ptr()
@@ -316,7 +333,7 @@ class FastPolicy:
         p, lib, n, N, H = self.p, self.lib, self.n, self.N, self.H
         st = self._stream()
         if self.fused:
-            if self.others and par is None:
+            if self.prev_rec is not None and par is None:
                 self.set_prev_actions(prev_actions, 0)
             ha = self._head_args(False, eps, step, q_out, buf, par or 0)
             ha.avail = self.avail.data_ptr()

@@ -13,7 +13,8 @@ mechanics that make a timestep capturable and replayable for every t:
     the heads file actions / pose / rewards in slot t, carry the runner state and hand the device-side counters over.  Several env
     groups or an odd number of timesteps per graph take the four standalone launches (k_encode, k_head<env>, env, k_head<inc>).
     obs_others_last_action with fused_others_last_action takes the same four launches (the heads gather fc1's rows; the previous actions
-    of all agents travel in FastPolicy.prev_rec, a buffer pair indexed by the parity of t like the input rows).
+    of all agents travel in FastPolicy.prev_rec, a buffer pair indexed by the parity of t like the input rows).  fused_onehot_gather:
+    the same four launches for ANY flag set at any team size (every one-hot block is gathered; the same record pair).
     Other configurations (obs_others_last_action without that key, fast_policy=False) take the generic torch timestep, captured the same way;
   * epsilon is a device scalar; exploration uses the package's counter generator (no multinomial, no host sync).
 The first episode runs eagerly (warm-up of hipBLASLt plans and the allocator); graphs are captured from the second on.
@@ -123,7 +124,7 @@ class HipGraphRunner(HipVecRunner):
         K = max(1, int(getattr(a, "steps_per_graph", 10)))
         while self.episode_limit % K:
             K -= 1
-        if self.fast is not None and self.fast.others and K % 2:
+        if self.fast is not None and self.fast.prev_rec is not None and K % 2:
             # the previous-action records alternate with the parity of t, which a captured graph bakes in: an even number of timesteps
             # per graph, or (odd episode lengths) eager timesteps
             K = max([k for k in range(2, K, 2) if self.episode_limit % k == 0], default=0)

@@ -648,6 +648,23 @@ typedef struct ssd_policy_head {
     const float* others_rows;
     const uint8_t* prev_record;
     uint8_t* prev_record_out;
+    /* ---- appended for SSD_INPUT_GATHER_ONEHOT (zero = as before) ---- */
+    /* input_flags has SSD_INPUT_GATHER_ONEHOT (env head and inc head): EVERY one-hot block leaves the 64-column image -- the agent's
+     * own last action, the agent id, the others' last actions (if SSD_INPUT_OTHERS_LAST_ACTION is set too) and the inc head's one-hot
+     * of the action just chosen.  Each is one row of fc1 per one-hot vector, added as exact f32 where the bias is added.  The dense
+     * blocks (32 features | sign r | sign inc | distances | pos, each iff flagged: at most 46 columns at n = 10) occupy compacted
+     * columns of `inputs` and of the image, zeros behind them; input_shape is the reference's full width.
+     *   onehot_rows   f32 [n(owner), SSD_ONEHOT_ROWS(n, n_actions, flags), 64] from ssd_policy_pack_head, 16-byte aligned; per owner:
+     *                 row 0 = fc1's row of the owner's agent-id column (zeros without SSD_INPUT_AGENT_ID; constant per agent, so it
+     *                 acts as a second bias row), rows 1 .. A = the last-action block (zeros without SSD_INPUT_LAST_ACTION), rows
+     *                 1 + A .. 2A = the inc head's action block (zeros in the env head's table), then the n * A rows of the others'
+     *                 last-action block if flagged.
+     *   prev_record / prev_record_out as above: byte `agent` is the agent's own previous action (prev_actions is not read for the
+     *                 input row), 0xFF / any value outside [0, n_actions) adds zeros.  others_rows is not used.
+     * Missing onehot_rows / prev_record, misalignment, n_agents > SSD_MAX_AGENTS, prev_record_out on the inc head or equal to
+     * prev_record: SSD_ERR_INVALID.  input_shape != 32 + the widths of all flagged blocks: SSD_ERR_UNSUPPORTED.
+     * ssd_policy_head_inc_encode refuses the bit (SSD_ERR_UNSUPPORTED). */
+    const float* onehot_rows;
 } ssd_policy_head;
 #define SSD_INPUT_LAST_ACTION 1u   /* obs_last_action: one-hot of the previous env action, n_actions columns */
 #define SSD_INPUT_AGENT_ID    2u   /* obs_agent_id: one-hot of the agent, n columns */
@@ -658,6 +675,10 @@ typedef struct ssd_policy_head {
 #define SSD_INPUT_OTHERS_LAST_ACTION 64u   /* obs_others_last_action: every agent's last-action one-hot, n * n_actions columns, between
                                              the received-incentive sign and the distances -- ssd_build_inputs_flags builds the columns;
                                              the fused heads gather fc1's rows instead (ssd_policy_head.others_rows) */
+#define SSD_INPUT_GATHER_ONEHOT 0x100u   /* not a block: the LAYOUT in which the fused heads gather fc1's rows for every one-hot block
+                                           (ssd_policy_head.onehot_rows) -- any flag set then fits the 64-column image at n <= 10.
+                                           (0x80 stays unassigned: no head builds it.) */
+#define SSD_ONEHOT_ROWS(n, A, flags) (1 + 2 * (A) + (((flags) & SSD_INPUT_OTHERS_LAST_ACTION) ? (n) * (A) : 0))
 #define SSD_INPUT_EXPLICIT    0x80000000u   /* marks a given flag word (the empty set is SSD_INPUT_EXPLICIT alone) */
 #define SSD_INPUT_FLAGS_SHIPPED (SSD_INPUT_LAST_ACTION | SSD_INPUT_AGENT_ID | SSD_INPUT_REWARD | SSD_INPUT_INC_REWARD | SSD_INPUT_AGENT_POS)
 /* ssd_build_inputs for ANY _build_inputs flag set (homophily_controller.py:137-184; the learner's time-batched input assembly):
@@ -693,6 +714,12 @@ typedef struct ssd_policy_head_params {
     uint32_t input_flags;
     int32_t n_actions;
     float* others_rows;
+    /* ---- appended for SSD_INPUT_GATHER_ONEHOT (zero = as before) ---- */
+    /* input_flags with SSD_INPUT_GATHER_ONEHOT: fc1_in is the reference's full width (env head) or that + n_actions (inc head);
+     * anything else is SSD_ERR_UNSUPPORTED.  The rows of the dense blocks are packed into the image in compacted order and the
+     * one-hot blocks' rows are written to onehot_rows f32 [n, SSD_ONEHOT_ROWS, 64] (layout: ssd_policy_head.onehot_rows; 16-byte
+     * aligned, null: SSD_ERR_INVALID) by the same launch.  others_rows is not used.  Images of every other layout are unchanged. */
+    float* onehot_rows;
 } ssd_policy_head_params;
 /* image: [n, SSD_POLICY_IMAGE_BYTES(precision)] */
 int ssd_policy_pack_head(const ssd_policy_head_params* params, int32_t precision, void* image, void* stream);
