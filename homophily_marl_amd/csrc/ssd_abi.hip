@@ -899,7 +899,7 @@ int ssd_policy_head_inc_encode(const ssd_policy_head* h, const ssd_policy_encode
     if (e->slot_t && (e->slot_t == h->next_t_out)) return fail(SSD_ERR_INVALID, "ssd_policy_head_inc_encode: the encoder must not read the scalar the inc head writes");
     const int rc = launch_policy_inc_encode(h, e, (hipStream_t)stream);
     if (rc == -3) return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_head is instantiated for n_actions 9 (Cleanup) and 8 (Harvest)");
-    if (rc == -2) return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_head_inc_encode is instantiated for 15 x 15 / 31 x 31 windows (other edges: ssd_policy_encode + ssd_policy_head_inc)");
+    if (rc == -2) return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_head_inc_encode takes the Toeplitz layout at 15 x 15 / 31 x 31 windows only; every other odd edge 3 .. 63 takes SSD_ENCODE_LAYOUT_LUT (or ssd_policy_encode + ssd_policy_head_inc)");
     if (rc) return fail(SSD_ERR_DEVICE, "ssd_policy_head_inc_encode: launch / hipFuncSetAttribute(max dynamic LDS) failed");
     return launched();
 }

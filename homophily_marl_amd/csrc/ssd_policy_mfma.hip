@@ -1974,9 +1974,8 @@ __host__ __device__ constexpr size_t enc_lut_any_lds_bytes(int V) {
 }
 
 template <int PREC>
-__global__ __launch_bounds__(ENC_WAVES * 64) void k_encode_lut_any(EncK a, int V) {
+__device__ __forceinline__ void encode_body_lut_any(const EncK& a, const int V, uint8_t* lds_raw, const int block_x, const int block_y) {
     constexpr int BT = ENC_ANY_BT;
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     const int O = V - 2, R = SSD_ENCODE_BAND_ROWS(V), WPR = (V + 15) >> 4, PRW = lut_any_batch_row_dwords(V), P = O * O;
     const int PACKED = (BT * 16 * PRW * 4 + 15) & ~15;
     constexpr float CS = PREC == 2 ? ENC_CSCALE : 1.f, INV = PREC == 2 ? 1.f / (ENC_CSCALE * ENC_LSCALE) : 1.f;
@@ -1984,12 +1983,12 @@ __global__ __launch_bounds__(ENC_WAVES * 64) void k_encode_lut_any(EncK a, int V
     float* table = reinterpret_cast<float*>(lds_raw + PACKED);         // [3][64][6]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m = lane & 15, q = lane >> 4;
-    const int row0 = (int)blockIdx.x * (BT * 16);
-    const int band = (int)blockIdx.y, y0 = band * R;
+    const int row0 = block_x * (BT * 16);
+    const int band = block_y, y0 = band * R;
     const int Rb = O - y0 < R ? O - y0 : R;
     const int64_t slot_now = a.slot_t ? *a.slot_t : 0;
     const long t_off = a.slot_t ? ((long)slot_now + a.slot_add) * a.slot_stride : 0;
-    if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
+    if (block_x == 0 && block_y == 0 && tid == 0) {
         if (a.slot_t_copy) *a.slot_t_copy = slot_now;
         if (a.counter_inc) *a.counter_inc += 1;
     }
@@ -2137,6 +2136,11 @@ __global__ __launch_bounds__(ENC_WAVES * 64) void k_encode_lut_any(EncK a, int V
         }
     }
 }
+template <int PREC>
+__global__ __launch_bounds__(ENC_WAVES * 64) void k_encode_lut_any(EncK a, int V) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+    encode_body_lut_any<PREC>(a, V, lds_raw, (int)blockIdx.x, (int)blockIdx.y);
+}
 
 template <int PREC>
 static int launch_encode_lut_any(const EncK& k, int V, hipStream_t s) {
@@ -2193,6 +2197,32 @@ __global__ __launch_bounds__(FUSED_WAVES * 64) void k_inc_encode(int heads, int 
         el.codes = p_codes; el.slot_t = p_slot_t;
         if constexpr (LUT) encode_body_lut<V, PREC, BT>(el, lds_raw, i - by * enc_groups, by);
         else encode_body<V, PREC, false, BT>(el, lds_raw, i - by * enc_groups, by);
+    }
+}
+
+// k_inc_encode_any: the same launch for every other odd window edge 3 .. 63 under the class-LUT layout -- the head half does not
+// depend on V, the encoder half is encode_body_lut_any with V a run-time value (the LAST argument: everything in front of it sits
+// where k_inc_encode has it, so the heads' cold-argument offsets and refetch_head_args hold).  8 instantiations for all 29 edges.
+template <int PREC, int AT, bool LOOP>
+__global__ __launch_bounds__(FUSED_WAVES * 64) void k_inc_encode_any(int heads, int enc_groups, int p_N, int p_n, int p_bpa, int p_pad, float* p_h, float* p_inputs,
+                                                                     const uint8_t* p_codes, const int64_t* p_slot_t, HeadK a, HeadCold cold_unused, EncK e, int V) {
+    constexpr int LEAD_ANY = 6 * 4 + 4 * 8;                           // (= k_inc_encode's LEAD)
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+    const int total = (int)gridDim.x;
+    const int b = SSD_ENC_FIRST ? ((int)blockIdx.x + heads) % total : (int)blockIdx.x;
+    if (b < heads) {
+        if constexpr (LOOP) head_body<1, PREC, AT, 0, FUSED_WAVES - 1, LOOP, LEAD_ANY>(a, lds_raw, b);
+        else {
+            HeadK al = a;
+            al.N = p_N; al.n = p_n; al.bpa = p_bpa; al.h = p_h; al.inputs = p_inputs;
+            head_body<1, PREC, AT, 0, FUSED_WAVES - 1, LOOP, LEAD_ANY>(al, lds_raw, b);
+        }
+    } else {
+        const int i = b - heads, by = i / enc_groups;
+        if (FUSED_WAVES > ENC_WAVES && (int)threadIdx.x >= ENC_WAVES * 64) return;
+        EncK el = e;
+        el.codes = p_codes; el.slot_t = p_slot_t;
+        encode_body_lut_any<PREC>(el, V, lds_raw, i - by * enc_groups, by);
     }
 }
 
@@ -2276,6 +2306,32 @@ static int launch_inc_encode_t(HeadK& k, HeadCold& c, EncK& e, hipStream_t s) {
     return launch_inc_encode_bt<PREC, AT, V, LOOP, 5, false>(k, c, e, s);
 }
 
+constexpr size_t inc_encode_any_lds_max(int prec) {
+    size_t m = (size_t)head_lds_bytes(FUSED_WAVES - 1, prec);
+    for (int V = SSD_ENCODE_EDGE_MIN; V <= SSD_ENCODE_EDGE_MAX; V += 2) m = enc_lut_any_lds_bytes(V) > m ? enc_lut_any_lds_bytes(V) : m;
+    return m;
+}
+template <int PREC, int AT, bool LOOP>
+static int launch_inc_encode_any(HeadK& k, HeadCold& c, EncK& e, int V, hipStream_t s) {
+    constexpr size_t lds_max = inc_encode_any_lds_max(PREC);
+    static_assert(lds_max <= 160 * 1024, "LDS of the run-time-edge fused launch");
+    const size_t lh = (size_t)head_lds_bytes(FUSED_WAVES - 1, PREC), le = enc_lut_any_lds_bytes(V);
+    const size_t lds = lh > le ? lh : le;
+    static bool done[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
+    const void* fn = reinterpret_cast<const void*>(&k_inc_encode_any<PREC, AT, LOOP>);
+    if (!done[dev]) {
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max) != hipSuccess) return -1;
+        done[dev] = true;
+    }
+    int heads = k.n * k.bpa, groups = (e.rows + ENC_ANY_BT * 16 - 1) / (ENC_ANY_BT * 16);
+    int pad = 0;
+    void* args[14] = {&heads, &groups, &k.N, &k.n, &k.bpa, &pad, &k.h, &k.inputs, &e.codes, &e.slot_t, &k, &c, &e, &V};
+    if (hipLaunchKernel(fn, dim3(heads + groups * SSD_ENCODE_BANDS(V)), dim3(FUSED_WAVES * 64), args, lds, s) != hipSuccess) return -1;
+    return 0;
+}
+
 // How a head launch of (n_env, n_agents) is cut: workgroups per agent, compute waves per workgroup, and the number of 16-row tiles the
 // busiest wave walks (1 = the kernel without a back edge; > 1 = the LOOP instantiation).  fused: the inc head inside k_inc_encode.
 void policy_head_plan(int n_env, int n_agents, int fused, int* wg_per_agent, int* waves_out, int* tiles_per_wave) {
@@ -2294,7 +2350,7 @@ void policy_head_plan(int n_env, int n_agents, int fused, int* wg_per_agent, int
     *tiles_per_wave = (tiles + k.bpa * waves - 1) / (k.bpa * waves);
 }
 
-// inc head (timestep t) + encoder (timestep t + 1) as one launch; -2: no instance for this window size, -3: for this action count
+// inc head (timestep t) + encoder (timestep t + 1) as one launch; -2: no instance for this window size / layout, -3: for this action count
 int launch_policy_inc_encode(const ssd_policy_head* ph, const ssd_policy_encode_args* pe, hipStream_t s) {
     HeadK k;
     HeadCold c;
@@ -2303,8 +2359,14 @@ int launch_policy_inc_encode(const ssd_policy_head* ph, const ssd_policy_encode_
     encode_args(pe, e);
     const int prec = ph->precision == 1 ? 1 : 2, V = pe->view_edge;
     if (k.A != 9 && k.A != 8) return -3;
-    if (V != 15 && V != 31) return -2;
     const bool loops = head_loops(k, FUSED_WAVES - 1);
+    if (V != 15 && V != 31) {       // every other odd edge 3 .. 63: the run-time-geometry encoder half, class-LUT images only
+        if (V < SSD_ENCODE_EDGE_MIN || V > SSD_ENCODE_EDGE_MAX || !(V & 1) || e.layout != SSD_ENCODE_LAYOUT_LUT) return -2;
+#define SSD_IEA(P_, A_) if (prec == P_ && k.A == A_) return loops ? launch_inc_encode_any<P_, A_, true>(k, c, e, V, s) : launch_inc_encode_any<P_, A_, false>(k, c, e, V, s)
+        SSD_IEA(2, 9); SSD_IEA(2, 8); SSD_IEA(1, 9); SSD_IEA(1, 8);
+#undef SSD_IEA
+        return -2;
+    }
 #define SSD_IE(P_, A_, V_) if (prec == P_ && k.A == A_ && V == V_) return loops ? launch_inc_encode_t<P_, A_, V_, true>(k, c, e, s) : launch_inc_encode_t<P_, A_, V_, false>(k, c, e, s)
     SSD_IE(2, 9, 15); SSD_IE(2, 9, 31); SSD_IE(2, 8, 15); SSD_IE(2, 8, 31);
     SSD_IE(1, 9, 15); SSD_IE(1, 9, 31); SSD_IE(1, 8, 15); SSD_IE(1, 8, 31);

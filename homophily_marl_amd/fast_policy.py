@@ -66,9 +66,11 @@ class FastPolicy:
         shipped = self.V in (15, 31)
         self.fused_enc = self.fused and abi.encode_edge_supported(self.V) and tuple(a.obs_dims) == (self.V, self.V) \
             and (shipped or self.enc_layout == abi.ENCODE_LAYOUT_LUT)
-        # act_inc_encode (inc head of t + encoder of t + 1 as one launch: the pipelined rollout) is instantiated for 15 / 31 only;
-        # at the other edges the rollout takes the standalone encoder and inc-head launches
-        self.inc_encode = self.fused_enc and shipped and not self.others and not self.gather     # (gathered layouts: the four standalone launches)
+        # act_inc_encode (inc head of t + encoder of t + 1 as one launch: the pipelined rollout): 15 / 31 always; every other edge
+        # with the opt-in key pipeline_any_view under the class-LUT layout (k_inc_encode_any), else the standalone encoder and
+        # inc-head launches
+        any_view = bool(getattr(a, "pipeline_any_view", False)) and self.enc_layout == abi.ENCODE_LAYOUT_LUT
+        self.inc_encode = self.fused_enc and (shipped or any_view) and not self.others and not self.gather     # (gathered layouts: the four standalone launches)
         self.bands = abi.encode_bands(self.V) if self.fused_enc else 1
         # bf16 MFMA products an f32-equivalent product costs (bench.py's roofline accounting); conv: the planes are exact, 2
         self.n_products = dict(encode_conv=2, encode_lin=3, head_env=3, head_inc=3) if precision == 2 else \
@@ -378,7 +380,7 @@ class FastPolicy:
     @th.no_grad()
     def act_inc_encode(self, actions, pos, orient, reward, clean_num, apple_den, eps, step, codes, slot_t=None, slot_add=0, buf=0,
                        q_out=None, file=None, mask_alphabet=None):
-        """act_inc of timestep t on inputs_pair[buf] AND encode of timestep t + 1 into inputs_pair[buf ^ 1] (31 x 31 windows: into
+        """act_inc of timestep t on inputs_pair[buf] AND encode of timestep t + 1 into inputs_pair[buf ^ 1] (several bands: into
         the band sums) as ONE launch (ssd_policy_head_inc_encode): the pipelined rollout's third launch of a timestep.  `codes` /
         slot_t / slot_add as in encode(): the observation the env step of t just produced (storage slot *slot_t + slot_add)."""
         assert self.fused and self.inc_encode

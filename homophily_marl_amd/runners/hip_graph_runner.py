@@ -134,6 +134,11 @@ class HipGraphRunner(HipVecRunner):
                          and getattr(a, "pipeline_encode", True) and (K % 2 == 0 or not use_graph)
                          and (self.obs_fmt == abi.OBS_CODE or self._want_code))
         self.rng_copy = th.zeros(1, dtype=th.long, device=dev)          # pipelined: the env head's copy of rng_ctr for the inc head
+        if self.pipe and self.fast.V not in (15, 31):
+            # pipeline_any_view changes the launches of a timestep, not its draws: in the four-launch timestep the encoder advances
+            # the draw counter BEFORE the heads of that timestep read it, in the pipelined one the inc head advances it AFTER they
+            # did -- so the counter starts one ahead here and both runners draw the same exploration (15 / 31 keep their sequence)
+            self.rng_ctr.fill_(1)
         self._par = 0
         self._ready = True
 

@@ -808,8 +808,10 @@ int ssd_policy_encode(const ssd_policy_encode_args* args, void* stream);
 /* ssd_policy_head_inc(inc_args) and ssd_policy_encode(enc_args) as ONE launch -- the pipelined rollout's third launch of a timestep:
  * both follow the env step of t and share no data (the inc head reads the input rows of t, the encoder reads the observation of slot
  * t + 1 and must write a DIFFERENT `inputs` buffer / `part`), so one launch-to-launch gap of the timestep disappears.  enc_args: no
- * act, no slot_t_copy / counter_inc (the heads hand the counters over, see ssd_policy_head); same precision as inc_args.  Instantiated
- * for 15 x 15 / 31 x 31 windows; other edges: ssd_policy_encode + ssd_policy_head_inc (SSD_ERR_UNSUPPORTED here). */
+ * act, no slot_t_copy / counter_inc (the heads hand the counters over, see ssd_policy_head); same precision as inc_args.  Every
+ * window edge ssd_policy_encode takes: 15 x 15 / 31 x 31 under either layout (their own instantiations), every other odd edge
+ * 3 .. 63 under SSD_ENCODE_LAYOUT_LUT (one run-time-geometry instantiation per precision, action count and looped / unlooped
+ * head).  The Toeplitz layout at another edge, an even edge or one outside 3 .. 63: SSD_ERR_UNSUPPORTED. */
 int ssd_policy_head_inc_encode(const ssd_policy_head* inc_args, const ssd_policy_encode_args* enc_args, void* stream);
 /* conv_b (f32 [6]): read only for the range bound of the conv activations (see SSD_ERRBIT_F16_RANGE). */
 /* conv_w f32 [6, 3, 3, 3], conv_b [6], lin_w [32, 6 (V-2)^2] -> the images of SSD_ENCODE_LAYOUT_LUT: table (SSD_ENCODE_LUT_TABLE_BYTES,
