@@ -936,16 +936,11 @@ __device__ __forceinline__ T cold_kernarg(int offset) {
 // as SCALAR kernel arguments in front of the struct: built with -mllvm -amdgpu-kernarg-preload-count=14 they arrive in SGPRs with
 // the wave (gfx950 kernarg preload; struct arguments are not preloaded), so the state loads are requested before the first
 // scalar-memory trip to the kernarg segment has returned.  Without the flag they are ordinary arguments.
-#ifdef SSD_ENV_WPE      // experiment knob: tell the register allocator / scheduler how many waves per SIMD the launch really has
-#define SSD_ENV_OCC __attribute__((amdgpu_waves_per_eu(SSD_ENV_WPE, SSD_ENV_WPE)))
-#else
-#define SSD_ENV_OCC
-#endif
 // REC (render mode, ssd_set_render; instantiated for MODE_STEP / MODE_STEP_OBS with OV_ANY only): the step also writes every agent's
 // beam record to EnvArgs::beam_rec [N, n] (beam_record).  The other instantiations never read it.
 template <int MODE, int NT, bool TAPE, int OV = OV_ANY, bool REC = false>
-__global__ __launch_bounds__(kBlock) SSD_ENV_OCC void k_env(EnvHdr* p_hdr, uint2* p_agents, uint8_t* p_grid, const int32_t* p_actions, const DevSpec* p_spec,
-                                                int p_N, int p_GS, int p_PMS, int p_lds_stride, const EnvArgs A) {
+__global__ __launch_bounds__(kBlock) void k_env(EnvHdr* p_hdr, uint2* p_agents, uint8_t* p_grid, const int32_t* p_actions, const DevSpec* p_spec,
+                                    int p_N, int p_GS, int p_PMS, int p_lds_stride, const EnvArgs A) {
     const DevHead& hd = A.hd;
     const DevSpec* __restrict__ S = p_spec;
     DevState st;
@@ -965,14 +960,12 @@ __global__ __launch_bounds__(kBlock) SSD_ENV_OCC void k_env(EnvHdr* p_hdr, uint2
     // Speed only (never correctness): the 4 waves that share a SIMD get distinct static priorities from their hardware
     // wave slot, so they drift apart and their 16-byte store bursts are spread over the kernel instead of hitting the
     // per-CU store path all at once at the end (profiles/: stores and compute otherwise do not overlap at all).
-#ifndef SSD_NO_SETPRIO
     if (MODE == MODE_STEP_OBS || MODE == MODE_OBS) {
         const uint32_t slot = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 4) & 3u;   // HW_REG_HW_ID.WAVE_ID[1:0]
         if (slot == 0) __builtin_amdgcn_s_setprio(3);
         else if (slot == 1) __builtin_amdgcn_s_setprio(2);
         else if (slot == 2) __builtin_amdgcn_s_setprio(1);
     }
-#endif
 
     Env E;
     E.S = S; E.h = h; E.lane = lane; E.n = NT ? NT : h->n; E.W = h->W; E.HW = h->HW; E.GS = p_GS;

@@ -20,10 +20,34 @@
 // lane-local.  Weight fragments are pre-swizzled by the pack kernels below so that one ds_read_b128 / global_load_dwordx4 per
 // lane fetches a whole A operand.
 #include "ssd_policy_common.h"
+#include <type_traits>
 
 namespace ssd {
 #define SSD_GLOBAL __attribute__((address_space(1)))    // a pointer type that carries the global address space
 
+// ---- host side: what every launcher below is built from ------------------------------------------------------------------------
+// Run-time value -> template argument: calls f(int_c<V>{}) for the V among Vs that equals v and returns what it returns, or `none`.
+// The launchers nest one step per template parameter of their kernel; there is no table of kernels and no position in one.
+template <int V> using int_c = std::integral_constant<int, V>;
+template <int... Vs, typename R, typename F>
+static R pick(int v, R none, F&& f) {
+    R r = none;
+    ((v == Vs ? (void)(r = f(int_c<Vs>{})) : (void)0), ...);
+    return r;
+}
+
+// Raises the dynamic-LDS limit of `count` kernels to `bytes`, once per device (the attribute is per device; `done`: the caller's flags,
+// one set per kernel or per table of kernels).  0, or -1: no current device / the runtime refused.
+static int raise_lds_limit(const void* const* fns, int count, size_t bytes, bool (&done)[64]) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
+    if (done[dev]) return 0;
+    for (int i = 0; i < count; ++i)
+        if (hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return -1;
+    done[dev] = true;
+    return 0;
+}
+static int raise_lds_limit(const void* fn, size_t bytes, bool (&done)[64]) { return raise_lds_limit(&fn, 1, bytes, done); }
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
@@ -1092,20 +1116,11 @@ __device__ __forceinline__ void head_body(const HeadK& a_entry, uint8_t* lds_raw
 
 // the standalone heads: 8 tiles per workgroup + the loader wave (Cleanup-5 x 4096 envs: 256 tiles per agent -> 32 workgroups per agent, 160 in
 // all; measured 4 / 6 / 8 / 11 compute waves: 19.1 / 14.8 / 14.2 / 17.4 us)
-#ifndef SSD_HEAD_WAVES
-#define SSD_HEAD_WAVES 8
-#endif
-constexpr int HEAD_WAVES = SSD_HEAD_WAVES;
-#ifndef SSD_HEAD_WAVES_LOOP
-#define SSD_HEAD_WAVES_LOOP 8
-#endif
-constexpr int HEAD_WAVES_LOOP = SSD_HEAD_WAVES_LOOP;   // (round 3: 6, when the looped instantiations filled the register file; 160-168 registers now)
+constexpr int HEAD_WAVES = 8;
+constexpr int HEAD_WAVES_LOOP = 8;                     // (round 3: 6, when the looped instantiations filled the register file; 160-168 registers now)
 // GEN = 2 holds 16 more registers through fc1 (the gathered sum) and up to 48 while a gather group is in flight: 7 compute waves + the
 // loader = two waves per SIMD and the 256-register budget k_inc_encode's head half has
-#ifndef SSD_HEAD_WAVES_GATHER
-#define SSD_HEAD_WAVES_GATHER 7
-#endif
-constexpr int HEAD_WAVES_GATHER = SSD_HEAD_WAVES_GATHER;
+constexpr int HEAD_WAVES_GATHER = 7;
 constexpr int head_waves(bool loop, int gen = 0) { return gen >= 2 ? HEAD_WAVES_GATHER : loop ? HEAD_WAVES_LOOP : HEAD_WAVES; }
 // The leading scalar arguments repeat what a compute wave needs for its largest loads (the tile's state and input rows): built
 // with -amdgpu-kernarg-preload-count they arrive in SGPRs with the wave (struct arguments are not preloaded).  The looped
@@ -1138,7 +1153,8 @@ static int chip_cus() {
     }
     return cus[dev];
 }
-static void head_args(const ssd_policy_head* p, HeadK& k, HeadCold& c, int waves = HEAD_WAVES) {
+// every argument but HeadK::bpa, which is the launch plan's (plan_head)
+static void head_args(const ssd_policy_head* p, HeadK& k, HeadCold& c) {
     k.N = p->n_env; k.n = p->n_agents; k.A = p->n_actions; k.inp = p->input_shape;
     k.pos_scale = p->pos_scale; k.seed = p->seed; k.env_id_base = p->env_id_base;
     k.inputs = p->inputs; k.h = p->h; k.weights = static_cast<const uint8_t*>(p->weights); k.avail = p->avail; k.eps = p->epsilon; k.step = p->step;
@@ -1179,22 +1195,46 @@ static void head_args(const ssd_policy_head* p, HeadK& k, HeadCold& c, int waves
     c.next_step = p->next_step_out; c.t_copy = p->t_copy_out; c.step_copy = p->step_copy_out;
     c.numeric_err = numeric_err_word();
     PSTAMP_SET(k);
-    // workgroups per agent: one 16-row tile per wave while that grid fits the chip (no back edge in the kernel); larger jobs get one
-    // workgroup per CU and waves that walk several tiles (the LOOP instantiations)
-    const int tiles = (k.N + 15) / 16;
-    k.bpa = (tiles + waves - 1) / waves;
-    static const bool no_loop = getenv("SSD_HEAD_NO_LOOP") != nullptr;       // experiment: grids larger than the chip instead of looping waves
-    if (k.n * k.bpa > chip_cus() && !no_loop) { k.bpa = chip_cus() / k.n; if (k.bpa < 1) k.bpa = 1; }
 }
-static bool head_loops(const HeadK& k, int waves) { return k.bpa * waves < (k.N + 15) / 16; }
-// the standalone heads: one tile per wave while that grid fits the chip (the kernels without a back edge), else the looped instantiation
-// (the generic-layout kernels exist as looped instantiations only).  Returns the compute waves per workgroup; `looped` = which kernel.
-static int head_plan(const ssd_policy_head* p, HeadK& k, HeadCold& c, bool gen, bool& looped) {
-    head_args(p, k, c, gen ? HEAD_WAVES_LOOP : HEAD_WAVES);
-    looped = gen || head_loops(k, HEAD_WAVES);
-    if (!looped) return HEAD_WAVES;
-    head_args(p, k, c, HEAD_WAVES_LOOP);
-    return HEAD_WAVES_LOOP;
+// How a head launch of N envs x n agents is cut.  Workgroups per agent: one 16-row tile per wave while that grid fits the chip (no back
+// edge in the kernel); larger jobs get one workgroup per CU and waves that walk several tiles (the LOOP instantiations).
+static int head_bpa(int tiles, int waves, int agents, int cus) {
+    const int bpa = (tiles + waves - 1) / waves;
+    if (agents * bpa <= cus) return bpa;
+    return cus / agents < 1 ? 1 : cus / agents;
+}
+struct HeadPlan { int bpa, waves; bool looped; };       // workgroups per agent, compute waves per workgroup, which instantiation
+// waves / waves_looped: the compute waves of the instantiation without / with the back edge; the looped one is taken when the grid of
+// the other does not cover the tiles (or always: the kernels that exist looped only)
+static HeadPlan plan_head(int N, int n, int waves, int waves_looped, bool always_looped = false) {
+    const int tiles = (N + 15) / 16, cus = chip_cus();
+    HeadPlan pl = {head_bpa(tiles, waves, n, cus), waves, always_looped};
+    if (pl.bpa * waves < tiles) pl.looped = true;
+    if (pl.looped && waves_looped != waves) pl = {head_bpa(tiles, waves_looped, n, cus), waves_looped, true};
+    return pl;
+}
+static HeadPlan plan_head_standalone(int N, int n, int gen) { return plan_head(N, n, head_waves(false, gen), head_waves(true, gen), gen == 1); }
+
+// The standalone head kernel of (GEN, action count, precision, inc, looped), nullptr where there is none: GEN 1 (the generic tail
+// layout) is instantiated for the env head and looped only, and serves any grid.
+static const void* head_kernel(int gen, int A, int prec, int inc, int looped) {
+    const void* const none = nullptr;
+    return pick<0, 1, 2, 3>(gen, none, [&](auto g) { return pick<9, 8>(A, none, [&](auto at) { return pick<2, 1>(prec, none, [&](auto pr) {
+        return pick<0, 1>(inc, none, [&](auto i) { return pick<0, 1>(looped, none, [&](auto l) -> const void* {
+            constexpr int GEN = decltype(g)::value, AT = decltype(at)::value, PREC = decltype(pr)::value, INC = decltype(i)::value;
+            constexpr bool LOOP = decltype(l)::value != 0;
+            if constexpr (GEN == 1 && (INC || !LOOP)) return nullptr;
+            else return reinterpret_cast<const void*>(&k_head<INC, PREC, AT, GEN, LOOP>);
+        }); }); }); }); });
+}
+// the LDS limit of ALL kernels of a GEN (16, GEN 1: 4) is raised together at the GEN's first launch on a device
+static int raise_head_lds_limit(int gen) {
+    static bool done[4][64] = {};
+    const void* fns[16];
+    int count = 0;
+    for (int A : {9, 8}) for (int prec : {2, 1}) for (int inc : {0, 1}) for (int looped : {0, 1})
+        if (const void* f = head_kernel(gen, A, prec, inc, looped)) fns[count++] = f;
+    return raise_lds_limit(fns, count, (size_t)head_lds_bytes(cmax(head_waves(false, gen), head_waves(true, gen)), 2), done[gen]);
 }
 
 int launch_policy_head(const ssd_policy_head* p, int inc, hipStream_t s) {
@@ -1202,75 +1242,22 @@ int launch_policy_head(const ssd_policy_head* p, int inc, hipStream_t s) {
     HeadCold c;
     const bool onehot = head_gathers_onehot(p);
     const bool gather = onehot || head_gathers(p);
-    const bool gen = !gather && !inc && p->input_flags && (p->input_flags & ~SSD_INPUT_EXPLICIT) != (uint32_t)SSD_INPUT_FLAGS_SHIPPED;
-    bool looped = false;
-    int waves;
-    if (gather) {           // one tile per wave while that grid fits the chip, else the looped instantiation: both exist
-        head_args(p, k, c, HEAD_WAVES_GATHER);
-        looped = head_loops(k, HEAD_WAVES_GATHER);
-        waves = HEAD_WAVES_GATHER;
+    const int gen = onehot ? 3 : gather ? 2 : (!inc && p->input_flags && (p->input_flags & ~SSD_INPUT_EXPLICIT) != (uint32_t)SSD_INPUT_FLAGS_SHIPPED) ? 1 : 0;
+    head_args(p, k, c);
+    const HeadPlan pl = plan_head_standalone(k.N, k.n, gen);
+    k.bpa = pl.bpa;
+    if (gather) {
         const void* g3[3] = {onehot ? p->onehot_rows : p->others_rows, p->prev_record, p->prev_record_out};      // (see gather_slots)
         __builtin_memcpy(reinterpret_cast<uint8_t*>(&c) + (inc ? gather_slots<1>() : gather_slots<0>()), g3, inc ? 16 : 24);
-    } else waves = head_plan(p, k, c, gen, looped);
+    }
     const int prec = p->precision == 1 ? 1 : 2;
-    const int bpa = k.bpa;
-    const size_t lds = (size_t)head_lds_bytes(waves, prec);
     if (k.A != 9 && k.A != 8) return -3;                               // instantiated for Cleanup (9 actions) and Harvest (8)
-    static bool attr_done_dev[64] = {};                               // the attribute is per device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
-    const void* fns[16] = {reinterpret_cast<const void*>(&k_head<0, 2, 9>), reinterpret_cast<const void*>(&k_head<1, 2, 9>),
-                           reinterpret_cast<const void*>(&k_head<0, 1, 9>), reinterpret_cast<const void*>(&k_head<1, 1, 9>),
-                           reinterpret_cast<const void*>(&k_head<0, 2, 8>), reinterpret_cast<const void*>(&k_head<1, 2, 8>),
-                           reinterpret_cast<const void*>(&k_head<0, 1, 8>), reinterpret_cast<const void*>(&k_head<1, 1, 8>),
-                           reinterpret_cast<const void*>(&k_head<0, 2, 9, 0, true>), reinterpret_cast<const void*>(&k_head<1, 2, 9, 0, true>),
-                           reinterpret_cast<const void*>(&k_head<0, 1, 9, 0, true>), reinterpret_cast<const void*>(&k_head<1, 1, 9, 0, true>),
-                           reinterpret_cast<const void*>(&k_head<0, 2, 8, 0, true>), reinterpret_cast<const void*>(&k_head<1, 2, 8, 0, true>),
-                           reinterpret_cast<const void*>(&k_head<0, 1, 8, 0, true>), reinterpret_cast<const void*>(&k_head<1, 1, 8, 0, true>)};
-    if (!attr_done_dev[dev]) {
-        const size_t l2 = (size_t)head_lds_bytes(HEAD_WAVES, 2);
-        for (const void* f : fns)
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2) != hipSuccess) return -1;
-        attr_done_dev[dev] = true;
-    }
-    const void* gen_fns[4] = {reinterpret_cast<const void*>(&k_head<0, 2, 9, 1, true>), reinterpret_cast<const void*>(&k_head<0, 1, 9, 1, true>),
-                              reinterpret_cast<const void*>(&k_head<0, 2, 8, 1, true>), reinterpret_cast<const void*>(&k_head<0, 1, 8, 1, true>)};      // (any grid)
-    static bool gen_attr_done_dev[64] = {};
-    if (gen && !gen_attr_done_dev[dev]) {
-        const size_t l2 = (size_t)head_lds_bytes(HEAD_WAVES, 2);
-        for (const void* f : gen_fns)
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2) != hipSuccess) return -1;
-        gen_attr_done_dev[dev] = true;
-    }
-#define SSD_G2(I, P, AT_) reinterpret_cast<const void*>(&k_head<I, P, AT_, 2, false>), reinterpret_cast<const void*>(&k_head<I, P, AT_, 2, true>)
-    const void* gather_fns[16] = {SSD_G2(0, 2, 9), SSD_G2(1, 2, 9), SSD_G2(0, 1, 9), SSD_G2(1, 1, 9),      // [A == 8][prec == 1][inc][looped]
-                                  SSD_G2(0, 2, 8), SSD_G2(1, 2, 8), SSD_G2(0, 1, 8), SSD_G2(1, 1, 8)};
-#undef SSD_G2
-#define SSD_G3(I, P, AT_) reinterpret_cast<const void*>(&k_head<I, P, AT_, 3, false>), reinterpret_cast<const void*>(&k_head<I, P, AT_, 3, true>)
-    const void* onehot_fns[16] = {SSD_G3(0, 2, 9), SSD_G3(1, 2, 9), SSD_G3(0, 1, 9), SSD_G3(1, 1, 9),      // (the same order)
-                                  SSD_G3(0, 2, 8), SSD_G3(1, 2, 8), SSD_G3(0, 1, 8), SSD_G3(1, 1, 8)};
-#undef SSD_G3
-    static bool onehot_attr_done_dev[64] = {};
-    if (onehot && !onehot_attr_done_dev[dev]) {
-        const size_t l2 = (size_t)head_lds_bytes(HEAD_WAVES_GATHER, 2);
-        for (const void* f : onehot_fns)
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2) != hipSuccess) return -1;
-        onehot_attr_done_dev[dev] = true;
-    }
-    static bool gather_attr_done_dev[64] = {};
-    if (gather && !onehot && !gather_attr_done_dev[dev]) {
-        const size_t l2 = (size_t)head_lds_bytes(HEAD_WAVES_GATHER, 2);
-        for (const void* f : gather_fns)
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2) != hipSuccess) return -1;
-        gather_attr_done_dev[dev] = true;
-    }
+    if (raise_head_lds_limit(gen)) return -1;
     if (k.N >= (1 << 24) || k.n >= 256) return -1;
     uint32_t nn = (uint32_t)k.N | ((uint32_t)k.n << 24);
     void* args[10] = {&nn, &k.bpa, &k.h, &k.inputs, &k.prev_actions, &k.prev_reward, &k.recv, &k.pos, &k, &c};
-    const void* fn = gather ? (onehot ? onehot_fns : gather_fns)[(k.A == 8 ? 8 : 0) + (prec == 1 ? 4 : 0) + (inc ? 2 : 0) + (looped ? 1 : 0)]
-                   : gen ? gen_fns[(k.A == 8 ? 2 : 0) + (prec == 1 ? 1 : 0)]
-                         : fns[(looped ? 8 : 0) + (k.A == 8 ? 4 : 0) + (prec == 1 ? 2 : 0) + (inc ? 1 : 0)];
-    if (hipLaunchKernel(fn, dim3(k.n * bpa), dim3((waves + 1) * 64), args, lds, s) != hipSuccess) return -1;
+    const void* fn = head_kernel(gen, k.A, prec, inc ? 1 : 0, pl.looped);
+    if (hipLaunchKernel(fn, dim3(k.n * pl.bpa), dim3((pl.waves + 1) * 64), args, (size_t)head_lds_bytes(pl.waves, prec), s) != hipSuccess) return -1;
     return 0;
 }
 
@@ -1380,14 +1367,15 @@ __global__ __launch_bounds__(256) void k_pack_head_onehot(ssd_policy_head_params
 void launch_pack_head(const ssd_policy_head_params* p, int prec, void* image, hipStream_t s) {
     const dim3 grid((HF_TOT * 512 + 255) / 256, p->n_agents);
     int32_t* err = numeric_err_word();
-    if (p->input_flags & SSD_INPUT_GATHER_ONEHOT) {           // the grid covers the table too (at most 1 + 2 A + n A rows of 64 floats)
-        if (prec == 2) hipLaunchKernelGGL(k_pack_head_onehot<2>, grid, dim3(256), 0, s, *p, static_cast<uint8_t*>(image), err);
-        else hipLaunchKernelGGL(k_pack_head_onehot<1>, grid, dim3(256), 0, s, *p, static_cast<uint8_t*>(image), err);
-    } else if (p->input_flags & SSD_INPUT_OTHERS_LAST_ACTION) {      // the grid covers the block's n A x 64 floats too (29 696 threads per agent)
-        if (prec == 2) hipLaunchKernelGGL(k_pack_head_others<2>, grid, dim3(256), 0, s, *p, static_cast<uint8_t*>(image), err);
-        else hipLaunchKernelGGL(k_pack_head_others<1>, grid, dim3(256), 0, s, *p, static_cast<uint8_t*>(image), err);
-    } else if (prec == 2) hipLaunchKernelGGL(k_pack_head<2>, grid, dim3(256), 0, s, *p, static_cast<uint8_t*>(image), err);
-    else hipLaunchKernelGGL(k_pack_head<1>, grid, dim3(256), 0, s, *p, static_cast<uint8_t*>(image), err);
+    // the grid covers the gathered rows too: the one-hot table (at most 1 + 2 A + n A rows of 64 floats), the others' block (n A rows)
+    const int mode = (p->input_flags & SSD_INPUT_GATHER_ONEHOT) ? 2 : (p->input_flags & SSD_INPUT_OTHERS_LAST_ACTION) ? 1 : 0;
+    pick<2, 1>(prec == 2 ? 2 : 1, 0, [&](auto pr) {
+        constexpr int PREC = decltype(pr)::value;
+        if (mode == 2) hipLaunchKernelGGL(k_pack_head_onehot<PREC>, grid, dim3(256), 0, s, *p, static_cast<uint8_t*>(image), err);
+        else if (mode == 1) hipLaunchKernelGGL(k_pack_head_others<PREC>, grid, dim3(256), 0, s, *p, static_cast<uint8_t*>(image), err);
+        else hipLaunchKernelGGL(k_pack_head<PREC>, grid, dim3(256), 0, s, *p, static_cast<uint8_t*>(image), err);
+        return 0;
+    });
 }
 
 // ===========================================================================================================================
@@ -1405,10 +1393,7 @@ static_assert(Geo<15>::R == SSD_ENCODE_BAND_ROWS(15) && Geo<15>::NB == SSD_ENCOD
 // (a template parameter BT of the kernels: 4 for 15 x 15 windows at up to 32 768 rows -- Cleanup-5 x 4096: 320 workgroups balance the
 // chip better behind the inc heads, k_inc_encode 32.4 -> 30.5 us -- else 5, which moves fewer Linear fragments per row)
 constexpr int ENC_BT_MAX = 5;                      // batch tiles (16 rows each) per workgroup: Linear weights are fetched once per 80 rows
-#ifndef SSD_ENC_WAVES
-#define SSD_ENC_WAVES 8
-#endif
-constexpr int ENC_WAVES = SSD_ENC_WAVES;                     // 2 per SIMD: one wave's LDS / VALU work overlaps its partner's MFMAs
+constexpr int ENC_WAVES = 8;                       // 2 per SIMD: one wave's LDS / VALU work overlaps its partner's MFMAs
 // LDS record of (batch row, input row): [plane R: CP one-hot bytes][plane G][plane B][tail: NXT x 8 bytes].  tail[k] = cells 8 (k + 1)
 // and 8 (k + 1) + 1 of the three planes (+ 2 zero bytes): the 4th K-quarter of position tile k, so that every lane's B operand is
 // ONE 8-byte LDS read.  The per-batch-row stride is padded to 8 * odd (mod 256): the 16 rows of a read hit 16 different bank pairs.
@@ -1848,10 +1833,7 @@ __device__ __forceinline__ void encode_body_lut(const EncK& a, uint8_t* lds_raw,
     u32x4 la[2][PREC], la_next[2][PREC];
     if (s_begin < s_end) load_la(s_begin, la_next);
     const uint32_t* my_rows = packed + m * PRW;
-#ifndef SSD_LUT_UNROLL
-#define SSD_LUT_UNROLL 1
-#endif
-#pragma unroll SSD_LUT_UNROLL
+#pragma unroll 1
     for (int sl = s_begin; sl < s_end; ++sl) {
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
@@ -1951,10 +1933,11 @@ __global__ __launch_bounds__(ENC_WAVES * 64) void k_encode_lut(EncK a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     encode_body_lut<V, PREC, BT>(a, lds_raw, (int)blockIdx.x, (int)blockIdx.y);
 }
-static int enc_bt(int V, int rows) {
-    static const char* force = getenv("SSD_ENC_BT");                  // diagnostics: force the batch tiles per workgroup (4 | 5) for 15 x 15 windows
-    if (force && V == 15) return force[0] == '4' ? 4 : 5;
-    return (V == 15 && rows <= 32768) ? 4 : 5;
+// the BT of a launch as a template argument (see ENC_BT_MAX; a 31 x 31 window has no BT = 4 instantiation)
+template <int V, typename F>
+static int enc_bt(int rows, F&& f) {
+    if constexpr (V == 15) { if (rows <= 32768) return f(int_c<4>{}); }
+    return f(int_c<5>{});
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -2147,13 +2130,7 @@ static int launch_encode_lut_any(const EncK& k, int V, hipStream_t s) {
     constexpr size_t lds_max = enc_lut_any_lds_bytes(SSD_ENCODE_EDGE_MAX);
     static_assert(lds_max >= enc_lut_any_lds_bytes(15) && lds_max <= 160 * 1024, "LDS of the run-time-edge encoder");
     static bool done[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
-    if (!done[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_encode_lut_any<PREC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max) != hipSuccess)
-            return -1;
-        done[dev] = true;
-    }
+    if (raise_lds_limit(reinterpret_cast<const void*>(&k_encode_lut_any<PREC>), lds_max, done)) return -1;
     const int groups = (k.rows + ENC_ANY_BT * 16 - 1) / (ENC_ANY_BT * 16);
     hipLaunchKernelGGL(k_encode_lut_any<PREC>, dim3(groups, SSD_ENCODE_BANDS(V)), dim3(ENC_WAVES * 64), enc_lut_any_lds_bytes(V), s, k, V);
     return 0;
@@ -2167,22 +2144,15 @@ static int launch_encode_lut_any(const EncK& k, int V, hipStream_t s) {
 // starts on each CU the moment its head workgroup retires.  Workgroups [0, heads) run head_body, the rest encode_body with the
 // (x, band) index unfolded; EncK sits behind the two head arguments (the heads' cold-argument offsets are unchanged).
 // ---------------------------------------------------------------------------------------------------------------------------
-#ifndef SSD_FUSED_WAVES
-#define SSD_FUSED_WAVES SSD_ENC_WAVES
-#endif
-constexpr int FUSED_WAVES = SSD_FUSED_WAVES;    // k_inc_encode: one block size for both bodies (waves past ENC_WAVES leave an encoder workgroup at once)
-static_assert(FUSED_WAVES >= ENC_WAVES, "the encoder body needs its waves");
+// (measured without effect: 10 / 12 waves per fused workgroup, with 8- or 12-wave encoder bodies)
+constexpr int FUSED_WAVES = ENC_WAVES;          // k_inc_encode: one block size for both bodies
 template <int PREC, int AT, int V, bool LOOP, int BT, bool LUT = false>
 __global__ __launch_bounds__(FUSED_WAVES * 64) void k_inc_encode(int heads, int enc_groups, int p_N, int p_n, int p_bpa, int p_pad, float* p_h, float* p_inputs,
                                                                  const uint8_t* p_codes, const int64_t* p_slot_t, HeadK a, HeadCold cold_unused, EncK e) {
     // (leading scalars: which body a workgroup runs, then what each body's first requests need -- see k_head)
     constexpr int LEAD = 6 * 4 + 4 * 8;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
-#ifndef SSD_ENC_FIRST
-#define SSD_ENC_FIRST 0
-#endif
-    const int total = (int)gridDim.x;
-    const int b = SSD_ENC_FIRST ? ((int)blockIdx.x + heads) % total : (int)blockIdx.x;      // (which body the first workgroups run)
+    const int b = (int)blockIdx.x;
     if (b < heads) {
         if constexpr (LOOP) head_body<1, PREC, AT, 0, FUSED_WAVES - 1, LOOP, LEAD>(a, lds_raw, b);
         else {
@@ -2192,7 +2162,6 @@ __global__ __launch_bounds__(FUSED_WAVES * 64) void k_inc_encode(int heads, int 
         }
     } else {
         const int i = b - heads, by = i / enc_groups;
-        if (FUSED_WAVES > ENC_WAVES && (int)threadIdx.x >= ENC_WAVES * 64) return;
         EncK el = e;
         el.codes = p_codes; el.slot_t = p_slot_t;
         if constexpr (LUT) encode_body_lut<V, PREC, BT>(el, lds_raw, i - by * enc_groups, by);
@@ -2203,13 +2172,14 @@ __global__ __launch_bounds__(FUSED_WAVES * 64) void k_inc_encode(int heads, int 
 // k_inc_encode_any: the same launch for every other odd window edge 3 .. 63 under the class-LUT layout -- the head half does not
 // depend on V, the encoder half is encode_body_lut_any with V a run-time value (the LAST argument: everything in front of it sits
 // where k_inc_encode has it, so the heads' cold-argument offsets and refetch_head_args hold).  8 instantiations for all 29 edges.
+// (The two kernels are written out twice: sharing their text through a __forceinline__ function -- with the encoder half as a
+// template argument or as a lambda, arguments by reference or by value -- reorders instructions in all 56 instantiations.)
 template <int PREC, int AT, bool LOOP>
 __global__ __launch_bounds__(FUSED_WAVES * 64) void k_inc_encode_any(int heads, int enc_groups, int p_N, int p_n, int p_bpa, int p_pad, float* p_h, float* p_inputs,
                                                                      const uint8_t* p_codes, const int64_t* p_slot_t, HeadK a, HeadCold cold_unused, EncK e, int V) {
     constexpr int LEAD_ANY = 6 * 4 + 4 * 8;                           // (= k_inc_encode's LEAD)
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
-    const int total = (int)gridDim.x;
-    const int b = SSD_ENC_FIRST ? ((int)blockIdx.x + heads) % total : (int)blockIdx.x;
+    const int b = (int)blockIdx.x;
     if (b < heads) {
         if constexpr (LOOP) head_body<1, PREC, AT, 0, FUSED_WAVES - 1, LOOP, LEAD_ANY>(a, lds_raw, b);
         else {
@@ -2219,53 +2189,36 @@ __global__ __launch_bounds__(FUSED_WAVES * 64) void k_inc_encode_any(int heads, 
         }
     } else {
         const int i = b - heads, by = i / enc_groups;
-        if (FUSED_WAVES > ENC_WAVES && (int)threadIdx.x >= ENC_WAVES * 64) return;
         EncK el = e;
         el.codes = p_codes; el.slot_t = p_slot_t;
         encode_body_lut_any<PREC>(el, V, lds_raw, i - by * enc_groups, by);
     }
 }
 
-template <int V, int PREC, bool ACT, int BT>
-static int launch_encode_bt(const EncK& k, hipStream_t s) {
-    using G = Geo<V>;
-    constexpr size_t lds = enc_lds_bytes<V, PREC, BT>();
-    static bool done[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
-    if (!done[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_encode<V, PREC, ACT, BT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-        done[dev] = true;
-    }
-    const int groups = (k.rows + BT * 16 - 1) / (BT * 16);
-    hipLaunchKernelGGL((k_encode<V, PREC, ACT, BT>), dim3(groups, G::NB), dim3(ENC_WAVES * 64), lds, s, k);
-    return 0;
-}
+// (the `done` flags of the launchers below are statics of a generic lambda's body: one set per BT, that is per kernel)
 template <int V, int PREC, bool ACT>
-static int launch_encode_t(const EncK& k, hipStream_t s) {
-    if constexpr (V == 15) { if (enc_bt(V, k.rows) == 4) return launch_encode_bt<V, PREC, ACT, 4>(k, s); }
-    return launch_encode_bt<V, PREC, ACT, 5>(k, s);
-}
-
-template <int V, int PREC, int BT>
-static int launch_encode_lut_bt(const EncK& k, hipStream_t s) {
-    using G = Geo<V>;
-    constexpr size_t lds = enc_lut_lds_bytes<V, PREC, BT>();
-    static bool done[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
-    if (!done[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_encode_lut<V, PREC, BT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-        done[dev] = true;
-    }
-    const int groups = (k.rows + BT * 16 - 1) / (BT * 16);
-    hipLaunchKernelGGL((k_encode_lut<V, PREC, BT>), dim3(groups, G::NB), dim3(ENC_WAVES * 64), lds, s, k);
-    return 0;
+static int launch_encode(const EncK& k, hipStream_t s) {
+    return enc_bt<V>(k.rows, [&](auto bt) {
+        constexpr int BT = decltype(bt)::value;
+        constexpr size_t lds = enc_lds_bytes<V, PREC, BT>();
+        static bool done[64] = {};
+        if (raise_lds_limit(reinterpret_cast<const void*>(&k_encode<V, PREC, ACT, BT>), lds, done)) return -1;
+        const int groups = (k.rows + BT * 16 - 1) / (BT * 16);
+        hipLaunchKernelGGL((k_encode<V, PREC, ACT, BT>), dim3(groups, Geo<V>::NB), dim3(ENC_WAVES * 64), lds, s, k);
+        return 0;
+    });
 }
 template <int V, int PREC>
-static int launch_encode_lut_t(const EncK& k, hipStream_t s) {
-    if constexpr (V == 15) { if (enc_bt(V, k.rows) == 4) return launch_encode_lut_bt<V, PREC, 4>(k, s); }
-    return launch_encode_lut_bt<V, PREC, 5>(k, s);
+static int launch_encode_lut(const EncK& k, hipStream_t s) {
+    return enc_bt<V>(k.rows, [&](auto bt) {
+        constexpr int BT = decltype(bt)::value;
+        constexpr size_t lds = enc_lut_lds_bytes<V, PREC, BT>();
+        static bool done[64] = {};
+        if (raise_lds_limit(reinterpret_cast<const void*>(&k_encode_lut<V, PREC, BT>), lds, done)) return -1;
+        const int groups = (k.rows + BT * 16 - 1) / (BT * 16);
+        hipLaunchKernelGGL((k_encode_lut<V, PREC, BT>), dim3(groups, Geo<V>::NB), dim3(ENC_WAVES * 64), lds, s, k);
+        return 0;
+    });
 }
 
 static void encode_args(const ssd_policy_encode_args* p, EncK& k) {
@@ -2278,32 +2231,22 @@ static void encode_args(const ssd_policy_encode_args* p, EncK& k) {
     PSTAMP_SET(k);
 }
 
-template <int PREC, int AT, int V, bool LOOP, int BT, bool LUT>
-static int launch_inc_encode_bt(HeadK& k, HeadCold& c, EncK& e, hipStream_t s) {
-    const size_t lh = (size_t)head_lds_bytes(FUSED_WAVES - 1, PREC), le = LUT ? enc_lut_lds_bytes<V, PREC, BT>() : enc_lds_bytes<V, PREC, BT>();
-    const size_t lds = lh > le ? lh : le;
-    static bool done[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
-    const void* fn = reinterpret_cast<const void*>(&k_inc_encode<PREC, AT, V, LOOP, BT, LUT>);
-    if (!done[dev]) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-        done[dev] = true;
-    }
-    int heads = k.n * k.bpa, groups = (e.rows + BT * 16 - 1) / (BT * 16);
-    int pad = 0;
-    void* args[13] = {&heads, &groups, &k.N, &k.n, &k.bpa, &pad, &k.h, &k.inputs, &e.codes, &e.slot_t, &k, &c, &e};
-    if (hipLaunchKernel(fn, dim3(heads + groups * Geo<V>::NB), dim3(FUSED_WAVES * 64), args, lds, s) != hipSuccess) return -1;
-    return 0;
-}
 template <int PREC, int AT, int V, bool LOOP>
-static int launch_inc_encode_t(HeadK& k, HeadCold& c, EncK& e, hipStream_t s) {
-    if (e.layout == SSD_ENCODE_LAYOUT_LUT) {
-        if constexpr (V == 15) { if (enc_bt(V, e.rows) == 4) return launch_inc_encode_bt<PREC, AT, V, LOOP, 4, true>(k, c, e, s); }
-        return launch_inc_encode_bt<PREC, AT, V, LOOP, 5, true>(k, c, e, s);
-    }
-    if constexpr (V == 15) { if (enc_bt(V, e.rows) == 4) return launch_inc_encode_bt<PREC, AT, V, LOOP, 4, false>(k, c, e, s); }
-    return launch_inc_encode_bt<PREC, AT, V, LOOP, 5, false>(k, c, e, s);
+static int launch_inc_encode(HeadK& k, HeadCold& c, EncK& e, hipStream_t s) {
+    return pick<0, 1>(e.layout == SSD_ENCODE_LAYOUT_LUT, -2, [&](auto lut) { return enc_bt<V>(e.rows, [&](auto bt) {
+        constexpr int BT = decltype(bt)::value;
+        constexpr bool LUT = decltype(lut)::value != 0;
+        const size_t lh = (size_t)head_lds_bytes(FUSED_WAVES - 1, PREC), le = LUT ? enc_lut_lds_bytes<V, PREC, BT>() : enc_lds_bytes<V, PREC, BT>();
+        const size_t lds = lh > le ? lh : le;
+        static bool done[64] = {};
+        const void* fn = reinterpret_cast<const void*>(&k_inc_encode<PREC, AT, V, LOOP, BT, LUT>);
+        if (raise_lds_limit(fn, lds, done)) return -1;
+        int heads = k.n * k.bpa, groups = (e.rows + BT * 16 - 1) / (BT * 16);
+        int pad = 0;
+        void* args[13] = {&heads, &groups, &k.N, &k.n, &k.bpa, &pad, &k.h, &k.inputs, &e.codes, &e.slot_t, &k, &c, &e};
+        if (hipLaunchKernel(fn, dim3(heads + groups * Geo<V>::NB), dim3(FUSED_WAVES * 64), args, lds, s) != hipSuccess) return -1;
+        return 0;
+    }); });
 }
 
 constexpr size_t inc_encode_any_lds_max(int prec) {
@@ -2318,13 +2261,8 @@ static int launch_inc_encode_any(HeadK& k, HeadCold& c, EncK& e, int V, hipStrea
     const size_t lh = (size_t)head_lds_bytes(FUSED_WAVES - 1, PREC), le = enc_lut_any_lds_bytes(V);
     const size_t lds = lh > le ? lh : le;
     static bool done[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
     const void* fn = reinterpret_cast<const void*>(&k_inc_encode_any<PREC, AT, LOOP>);
-    if (!done[dev]) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max) != hipSuccess) return -1;
-        done[dev] = true;
-    }
+    if (raise_lds_limit(fn, lds_max, done)) return -1;
     int heads = k.n * k.bpa, groups = (e.rows + ENC_ANY_BT * 16 - 1) / (ENC_ANY_BT * 16);
     int pad = 0;
     void* args[14] = {&heads, &groups, &k.N, &k.n, &k.bpa, &pad, &k.h, &k.inputs, &e.codes, &e.slot_t, &k, &c, &e, &V};
@@ -2335,19 +2273,9 @@ static int launch_inc_encode_any(HeadK& k, HeadCold& c, EncK& e, int V, hipStrea
 // How a head launch of (n_env, n_agents) is cut: workgroups per agent, compute waves per workgroup, and the number of 16-row tiles the
 // busiest wave walks (1 = the kernel without a back edge; > 1 = the LOOP instantiation).  fused: the inc head inside k_inc_encode.
 void policy_head_plan(int n_env, int n_agents, int fused, int* wg_per_agent, int* waves_out, int* tiles_per_wave) {
-    HeadK k = {};
-    k.N = n_env; k.n = n_agents;
-    const int tiles = (n_env + 15) / 16;
-    int waves = fused ? FUSED_WAVES - 1 : HEAD_WAVES;
-    auto size = [&](int w) {
-        k.bpa = (tiles + w - 1) / w;
-        static const bool no_loop = getenv("SSD_HEAD_NO_LOOP") != nullptr;
-        if (k.n * k.bpa > chip_cus() && !no_loop) { k.bpa = chip_cus() / k.n; if (k.bpa < 1) k.bpa = 1; }
-    };
-    size(waves);
-    if (!fused && head_loops(k, waves)) { waves = HEAD_WAVES_LOOP; size(waves); }
-    *wg_per_agent = k.bpa; *waves_out = waves;
-    *tiles_per_wave = (tiles + k.bpa * waves - 1) / (k.bpa * waves);
+    const HeadPlan pl = fused ? plan_head(n_env, n_agents, FUSED_WAVES - 1, FUSED_WAVES - 1) : plan_head_standalone(n_env, n_agents, 0);
+    *wg_per_agent = pl.bpa; *waves_out = pl.waves;
+    *tiles_per_wave = ((n_env + 15) / 16 + pl.bpa * pl.waves - 1) / (pl.bpa * pl.waves);
 }
 
 // inc head (timestep t) + encoder (timestep t + 1) as one launch; -2: no instance for this window size / layout, -3: for this action count
@@ -2355,44 +2283,38 @@ int launch_policy_inc_encode(const ssd_policy_head* ph, const ssd_policy_encode_
     HeadK k;
     HeadCold c;
     EncK e;
-    head_args(ph, k, c, FUSED_WAVES - 1);
+    head_args(ph, k, c);
+    const HeadPlan pl = plan_head(k.N, k.n, FUSED_WAVES - 1, FUSED_WAVES - 1);
+    k.bpa = pl.bpa;
     encode_args(pe, e);
     const int prec = ph->precision == 1 ? 1 : 2, V = pe->view_edge;
     if (k.A != 9 && k.A != 8) return -3;
-    const bool loops = head_loops(k, FUSED_WAVES - 1);
-    if (V != 15 && V != 31) {       // every other odd edge 3 .. 63: the run-time-geometry encoder half, class-LUT images only
-        if (V < SSD_ENCODE_EDGE_MIN || V > SSD_ENCODE_EDGE_MAX || !(V & 1) || e.layout != SSD_ENCODE_LAYOUT_LUT) return -2;
-#define SSD_IEA(P_, A_) if (prec == P_ && k.A == A_) return loops ? launch_inc_encode_any<P_, A_, true>(k, c, e, V, s) : launch_inc_encode_any<P_, A_, false>(k, c, e, V, s)
-        SSD_IEA(2, 9); SSD_IEA(2, 8); SSD_IEA(1, 9); SSD_IEA(1, 8);
-#undef SSD_IEA
-        return -2;
-    }
-#define SSD_IE(P_, A_, V_) if (prec == P_ && k.A == A_ && V == V_) return loops ? launch_inc_encode_t<P_, A_, V_, true>(k, c, e, s) : launch_inc_encode_t<P_, A_, V_, false>(k, c, e, s)
-    SSD_IE(2, 9, 15); SSD_IE(2, 9, 31); SSD_IE(2, 8, 15); SSD_IE(2, 8, 31);
-    SSD_IE(1, 9, 15); SSD_IE(1, 9, 31); SSD_IE(1, 8, 15); SSD_IE(1, 8, 31);
-#undef SSD_IE
-    return -2;
+    // every odd edge 3 .. 63 but 15 and 31: the run-time-geometry encoder half, class-LUT images only
+    if (V != 15 && V != 31 && (V < SSD_ENCODE_EDGE_MIN || V > SSD_ENCODE_EDGE_MAX || !(V & 1) || e.layout != SSD_ENCODE_LAYOUT_LUT)) return -2;
+    return pick<2, 1>(prec, -2, [&](auto pr) { return pick<9, 8>(k.A, -2, [&](auto at) { return pick<0, 1>(pl.looped, -2, [&](auto l) {
+        constexpr int PREC = decltype(pr)::value, AT = decltype(at)::value;
+        constexpr bool LOOP = decltype(l)::value != 0;
+        if (V != 15 && V != 31) return launch_inc_encode_any<PREC, AT, LOOP>(k, c, e, V, s);
+        return pick<15, 31>(V, -2, [&](auto v) { return launch_inc_encode<PREC, AT, decltype(v)::value, LOOP>(k, c, e, s); });
+    }); }); });
 }
 
 int launch_policy_encode(const ssd_policy_encode_args* p, hipStream_t s) {
     EncK k;
     encode_args(p, k);
-    const int prec = p->precision == 1 ? 1 : 2;
-    if (p->act && p->layout == SSD_ENCODE_LAYOUT_LUT)   // the learner's forward at the other window edges (the class-LUT body writes `act`)
-        return prec == 2 ? launch_encode_lut_any<2>(k, p->view_edge, s) : launch_encode_lut_any<1>(k, p->view_edge, s);
-    if (p->act) {       // the learner's forward (also emits LeakyReLU(conv)): f32-equivalent, or the labelled bf16 variant
-        if (p->view_edge == 15) return prec == 2 ? launch_encode_t<15, 2, true>(k, s) : launch_encode_t<15, 1, true>(k, s);
-        if (p->view_edge == 31) return prec == 2 ? launch_encode_t<31, 2, true>(k, s) : launch_encode_t<31, 1, true>(k, s);
-        return -2;
-    }
-    if (p->layout == SSD_ENCODE_LAYOUT_LUT) {
-        if (p->view_edge == 15) return prec == 2 ? launch_encode_lut_t<15, 2>(k, s) : launch_encode_lut_t<15, 1>(k, s);
-        if (p->view_edge == 31) return prec == 2 ? launch_encode_lut_t<31, 2>(k, s) : launch_encode_lut_t<31, 1>(k, s);
-        return prec == 2 ? launch_encode_lut_any<2>(k, p->view_edge, s) : launch_encode_lut_any<1>(k, p->view_edge, s);
-    }
-    if (p->view_edge == 15) return prec == 2 ? launch_encode_t<15, 2, false>(k, s) : launch_encode_t<15, 1, false>(k, s);
-    if (p->view_edge == 31) return prec == 2 ? launch_encode_t<31, 2, false>(k, s) : launch_encode_t<31, 1, false>(k, s);
-    return -2;
+    const int V = p->view_edge;
+    const bool lut = p->layout == SSD_ENCODE_LAYOUT_LUT;
+    return pick<2, 1>(p->precision == 1 ? 1 : 2, -2, [&](auto pr) {
+        constexpr int PREC = decltype(pr)::value;
+        // the run-time-geometry class-LUT body: the other window edges, and (it writes `act`) the learner's forward under that layout at every edge
+        if (lut && (p->act || (V != 15 && V != 31))) return launch_encode_lut_any<PREC>(k, V, s);
+        return pick<15, 31>(V, -2, [&](auto v) {
+            constexpr int VE = decltype(v)::value;
+            if (lut) return launch_encode_lut<VE, PREC>(k, s);
+            // act: the learner's forward (also emits LeakyReLU(conv)): f32-equivalent, or the labelled bf16 variant
+            return p->act ? launch_encode<VE, PREC, true>(k, s) : launch_encode<VE, PREC, false>(k, s);
+        });
+    });
 }
 
 // ---- pack: conv_w f32 [6, 3, 3, 3], lin_w f32 [32, 6 P] -> fragment images ------------------------------------------------------
@@ -2517,33 +2439,27 @@ int launch_pack_encoder_lut(const float* cw, const float* cb, const float* lw, i
     float* t = static_cast<float*>(table);
     uint8_t* l = static_cast<uint8_t*>(lin_frags);
     int32_t* err = numeric_err_word();
-#define SSD_PACKL(V_, P_)                                                                                                    \
-    do {                                                                                                                     \
-        const int total = 3 * LUT_DY_F + SSD_ENCODE_LUT_KSTEPS(V_) * 2 * 512;                                                 \
-        hipLaunchKernelGGL((k_pack_encoder_lut<V_, P_>), dim3((total + 255) / 256), dim3(256), 0, s, cw, cb, lw, t, l, err);  \
-    } while (0)
-    if (V == 15) { if (prec == 2) SSD_PACKL(15, 2); else SSD_PACKL(15, 1); return 0; }
-    if (V == 31) { if (prec == 2) SSD_PACKL(31, 2); else SSD_PACKL(31, 1); return 0; }
-#undef SSD_PACKL
-    if (V < SSD_ENCODE_EDGE_MIN || V > SSD_ENCODE_EDGE_MAX || !(V & 1)) return -2;
-    const int total = 3 * LUT_DY_F + SSD_ENCODE_LUT_KSTEPS(V) * 2 * 512;
-    if (prec == 2) hipLaunchKernelGGL(k_pack_encoder_lut_any<2>, dim3((total + 255) / 256), dim3(256), 0, s, cw, cb, lw, t, l, err, V);
-    else hipLaunchKernelGGL(k_pack_encoder_lut_any<1>, dim3((total + 255) / 256), dim3(256), 0, s, cw, cb, lw, t, l, err, V);
-    return 0;
+    if (V != 15 && V != 31 && (V < SSD_ENCODE_EDGE_MIN || V > SSD_ENCODE_EDGE_MAX || !(V & 1))) return -2;
+    const dim3 grid((3 * LUT_DY_F + SSD_ENCODE_LUT_KSTEPS(V) * 2 * 512 + 255) / 256);
+    return pick<2, 1>(prec == 2 ? 2 : 1, -2, [&](auto pr) {
+        constexpr int PREC = decltype(pr)::value;
+        if (V != 15 && V != 31) { hipLaunchKernelGGL(k_pack_encoder_lut_any<PREC>, grid, dim3(256), 0, s, cw, cb, lw, t, l, err, V); return 0; }
+        return pick<15, 31>(V, -2, [&](auto v) {
+            hipLaunchKernelGGL((k_pack_encoder_lut<decltype(v)::value, PREC>), grid, dim3(256), 0, s, cw, cb, lw, t, l, err);
+            return 0;
+        });
+    });
 }
 
 int launch_pack_encoder(const float* cw, const float* cb, const float* lw, int V, int prec, void* conv_frags, void* lin_frags, hipStream_t s) {
     uint8_t *c = static_cast<uint8_t*>(conv_frags), *l = static_cast<uint8_t*>(lin_frags);
     int32_t* err = numeric_err_word();
-#define SSD_PACK(V_, P_)                                                                                                     \
-    do {                                                                                                                     \
-        const int total = 9 * 512 + SSD_ENCODE_UNITS(V_) * 2 * 512;                                  \
-        hipLaunchKernelGGL((k_pack_encoder<V_, P_>), dim3((total + 255) / 256), dim3(256), 0, s, cw, cb, lw, c, l, err);     \
-    } while (0)
-    if (V == 15) { if (prec == 2) SSD_PACK(15, 2); else SSD_PACK(15, 1); return 0; }
-    if (V == 31) { if (prec == 2) SSD_PACK(31, 2); else SSD_PACK(31, 1); return 0; }
-#undef SSD_PACK
-    return -2;
+    return pick<15, 31>(V, -2, [&](auto v) { return pick<2, 1>(prec == 2 ? 2 : 1, -2, [&](auto pr) {
+        constexpr int VE = decltype(v)::value;
+        const dim3 grid((9 * 512 + SSD_ENCODE_UNITS(VE) * 2 * 512 + 255) / 256);
+        hipLaunchKernelGGL((k_pack_encoder<VE, decltype(pr)::value>), grid, dim3(256), 0, s, cw, cb, lw, c, l, err);
+        return 0;
+    }); });
 }
 
 }  // namespace ssd

@@ -28,7 +28,7 @@ with th.no_grad():
 dense = th.nn.functional.pad(codes.reshape(N, n, V * V), (0, abi.code_agent_stride(V) - V * V)).contiguous()
 fp.encode(None, codes=dense, mask_alphabet=False)
 out = fp.inputs[..., :32].clone()
-print("rows", N * n, "SSD_ENC_BT", os.environ.get("SSD_ENC_BT"))
+print("rows", N * n)
 print("kernel  vs f64: %.3e" % (out.double() - ref64).abs().max().item())
 print("torch32 vs f64: %.3e" % (ref32.double() - ref64).abs().max().item())
 print("torch32 (128-env chunks) vs f64: %.3e" % (chunks.double() - ref64).abs().max().item())
