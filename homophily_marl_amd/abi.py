@@ -172,7 +172,8 @@ class SsdPolicyHead(C.Structure):
                 ("lin_b", C.c_void_p), ("input_flags", C.c_uint32),
                 ("next_step_out", C.c_void_p), ("t_copy_out", C.c_void_p), ("step_copy_out", C.c_void_p),
                 ("recv_inc", C.c_void_p), ("recv_inc_out", C.c_void_p), ("avail_bits", C.c_uint32),
-                ("others_rows", C.c_void_p), ("prev_record", C.c_void_p), ("prev_record_out", C.c_void_p), ("onehot_rows", C.c_void_p)]
+                ("others_rows", C.c_void_p), ("prev_record", C.c_void_p), ("prev_record_out", C.c_void_p), ("onehot_rows", C.c_void_p),
+                ("pipeline_gather", C.c_int32)]
 
 
 class SsdPolicyHeadParams(C.Structure):

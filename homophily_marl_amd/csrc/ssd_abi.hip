@@ -886,7 +886,30 @@ static int policy_head(const ssd_policy_head* a, int inc, void* stream) {
     if (rc) return fail(SSD_ERR_DEVICE, "ssd_policy_head: launch / hipFuncSetAttribute(max dynamic LDS) failed");
     return launched();
 }
+// the same launch for the gathered head layouts (k_inc_encode_gather): ssd_policy_head.pipeline_gather asks for it
+static int policy_head_inc_encode_gather(const ssd_policy_head* h, const ssd_policy_encode_args* e, void* stream) {
+    if (!e) return fail(SSD_ERR_INVALID, "bad argument");
+    if (!h->input_flags || !(h->input_flags & (SSD_INPUT_OTHERS_LAST_ACTION | SSD_INPUT_GATHER_ONEHOT)))
+        return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_head_inc_encode: pipeline_gather is for SSD_INPUT_OTHERS_LAST_ACTION / SSD_INPUT_GATHER_ONEHOT heads; every other input set leaves it zero");
+    if (const int bad = check_head(h, 1)) return bad;
+    if (!encode_edge_ok(e->view_edge)) return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_head_inc_encode (pipeline_gather)" SSD_EDGE_MSG);
+    if (e->layout == SSD_ENCODE_LAYOUT_TOEPLITZ)
+        return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_head_inc_encode: pipeline_gather takes SSD_ENCODE_LAYOUT_LUT at every edge (the Toeplitz layout: ssd_policy_encode + ssd_policy_head_inc)");
+    if (const int bad = check_encode(e)) return bad;
+    if (e->act || e->slot_t_copy || e->counter_inc) return fail(SSD_ERR_INVALID, "ssd_policy_head_inc_encode: no act / slot_t_copy / counter_inc");
+    if ((h->precision == 1) != (e->precision == 1)) return fail(SSD_ERR_INVALID, "ssd_policy_head_inc_encode: one precision for both halves");
+    if (e->out == h->inputs) return fail(SSD_ERR_INVALID, "ssd_policy_head_inc_encode: the encoder must write the other inputs buffer");
+    if (e->slot_t && (e->slot_t == h->next_t_out))
+        return fail(SSD_ERR_INVALID, "ssd_policy_head_inc_encode: the encoder must not read the scalar the inc head writes");
+    if (h->n_actions != 9 && h->n_actions != 8)
+        return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_head_inc_encode (pipeline_gather) is instantiated for n_actions 9 (Cleanup) and 8 (Harvest)");
+    const int rc = launch_policy_inc_encode_gather(h, e, (hipStream_t)stream);
+    if (rc == -3 || rc == -2) return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_head_inc_encode (pipeline_gather): no instance for this action count / edge / layout");
+    if (rc) return fail(SSD_ERR_DEVICE, "ssd_policy_head_inc_encode: launch / hipFuncSetAttribute(max dynamic LDS) failed");
+    return launched();
+}
 int ssd_policy_head_inc_encode(const ssd_policy_head* h, const ssd_policy_encode_args* e, void* stream) {
+    if (h && h->pipeline_gather) return policy_head_inc_encode_gather(h, e, stream);
     if (h && h->input_flags && (h->input_flags & SSD_INPUT_GATHER_ONEHOT))
         return fail(SSD_ERR_UNSUPPORTED, "ssd_policy_head_inc_encode: SSD_INPUT_GATHER_ONEHOT takes ssd_policy_encode + ssd_policy_head_inc");
     if (h && h->input_flags && (h->input_flags & SSD_INPUT_OTHERS_LAST_ACTION))

@@ -2195,6 +2195,36 @@ __global__ __launch_bounds__(FUSED_WAVES * 64) void k_inc_encode_any(int heads, 
     }
 }
 
+// k_inc_encode_gather: the same launch for the gathered head layouts -- GEN 2 (obs_others_last_action) and GEN 3
+// (SSD_INPUT_GATHER_ONEHOT) -- at EVERY odd window edge 3 .. 63, 15 and 31 included: the head half is head_body<1, .., GEN> with the
+// 7 compute waves HEAD_WAVES_GATHER was sized for, the encoder half encode_body_lut_any.  The arguments are k_inc_encode_any's, byte
+// for byte: the gather pointers travel in HeadCold (gather_slots<1>), which sits where the heads' cold offsets expect it.
+// A third kernel and not a GEN parameter of the two above, for the reason given there.  Instantiated looped only (as GEN 1's env head:
+// the looped head serves any grid -- a wave whose first tile is past the end only hands the counters over): 8 instantiations.
+template <int PREC, int AT, int GEN, bool LOOP>
+__global__ __launch_bounds__(FUSED_WAVES * 64) void k_inc_encode_gather(int heads, int enc_groups, int p_N, int p_n, int p_bpa, int p_pad, float* p_h,
+                                                                        float* p_inputs, const uint8_t* p_codes, const int64_t* p_slot_t, HeadK a,
+                                                                        HeadCold cold_unused, EncK e, int V) {
+    static_assert(GEN == 2 || GEN == 3, "the gathered layouts");
+    static_assert(FUSED_WAVES - 1 == HEAD_WAVES_GATHER, "the gather head's register budget: 7 compute waves + the loader");
+    constexpr int LEAD_GATHER = 6 * 4 + 4 * 8;                        // (= k_inc_encode's LEAD)
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+    const int b = (int)blockIdx.x;
+    if (b < heads) {
+        if constexpr (LOOP) head_body<1, PREC, AT, GEN, FUSED_WAVES - 1, LOOP, LEAD_GATHER>(a, lds_raw, b);
+        else {
+            HeadK al = a;
+            al.N = p_N; al.n = p_n; al.bpa = p_bpa; al.h = p_h; al.inputs = p_inputs;
+            head_body<1, PREC, AT, GEN, FUSED_WAVES - 1, LOOP, LEAD_GATHER>(al, lds_raw, b);
+        }
+    } else {
+        const int i = b - heads, by = i / enc_groups;
+        EncK el = e;
+        el.codes = p_codes; el.slot_t = p_slot_t;
+        encode_body_lut_any<PREC>(el, V, lds_raw, i - by * enc_groups, by);
+    }
+}
+
 // (the `done` flags of the launchers below are statics of a generic lambda's body: one set per BT, that is per kernel)
 template <int V, int PREC, bool ACT>
 static int launch_encode(const EncK& k, hipStream_t s) {
@@ -2269,6 +2299,23 @@ static int launch_inc_encode_any(HeadK& k, HeadCold& c, EncK& e, int V, hipStrea
     if (hipLaunchKernel(fn, dim3(heads + groups * SSD_ENCODE_BANDS(V)), dim3(FUSED_WAVES * 64), args, lds, s) != hipSuccess) return -1;
     return 0;
 }
+// the gathered heads' launch: LDS = the larger of the GEN >= 2 head half (the image + 7 waves' scratch, as the standalone gather heads) and
+// the encoder half at this edge
+template <int PREC, int AT, int GEN>
+static int launch_inc_encode_gather(HeadK& k, HeadCold& c, EncK& e, int V, hipStream_t s) {
+    constexpr size_t lds_max = inc_encode_any_lds_max(PREC);
+    static_assert(lds_max <= 160 * 1024, "LDS of the gathered fused launch");
+    const size_t lh = (size_t)head_lds_bytes(FUSED_WAVES - 1, PREC), le = enc_lut_any_lds_bytes(V);
+    const size_t lds = lh > le ? lh : le;
+    static bool done[64] = {};
+    const void* fn = reinterpret_cast<const void*>(&k_inc_encode_gather<PREC, AT, GEN, true>);
+    if (raise_lds_limit(fn, lds_max, done)) return -1;
+    int heads = k.n * k.bpa, groups = (e.rows + ENC_ANY_BT * 16 - 1) / (ENC_ANY_BT * 16);
+    int pad = 0;
+    void* args[14] = {&heads, &groups, &k.N, &k.n, &k.bpa, &pad, &k.h, &k.inputs, &e.codes, &e.slot_t, &k, &c, &e, &V};
+    if (hipLaunchKernel(fn, dim3(heads + groups * SSD_ENCODE_BANDS(V)), dim3(FUSED_WAVES * 64), args, lds, s) != hipSuccess) return -1;
+    return 0;
+}
 
 // How a head launch of (n_env, n_agents) is cut: workgroups per agent, compute waves per workgroup, and the number of 16-row tiles the
 // busiest wave walks (1 = the kernel without a back edge; > 1 = the LOOP instantiation).  fused: the inc head inside k_inc_encode.
@@ -2296,6 +2343,26 @@ int launch_policy_inc_encode(const ssd_policy_head* ph, const ssd_policy_encode_
         constexpr bool LOOP = decltype(l)::value != 0;
         if (V != 15 && V != 31) return launch_inc_encode_any<PREC, AT, LOOP>(k, c, e, V, s);
         return pick<15, 31>(V, -2, [&](auto v) { return launch_inc_encode<PREC, AT, decltype(v)::value, LOOP>(k, c, e, s); });
+    }); }); });
+}
+
+// the same launch for the gathered head layouts (GEN 2 / 3): class-LUT images, any odd edge 3 .. 63; -2 / -3 as above
+int launch_policy_inc_encode_gather(const ssd_policy_head* ph, const ssd_policy_encode_args* pe, hipStream_t s) {
+    HeadK k;
+    HeadCold c;
+    EncK e;
+    const bool onehot = head_gathers_onehot(ph);
+    if (!onehot && !head_gathers(ph)) return -2;
+    head_args(ph, k, c);
+    k.bpa = plan_head(k.N, k.n, FUSED_WAVES - 1, FUSED_WAVES - 1).bpa;        // (the kernel is the looped one at any grid)
+    const void* g2[2] = {onehot ? ph->onehot_rows : ph->others_rows, ph->prev_record};      // (see gather_slots)
+    __builtin_memcpy(reinterpret_cast<uint8_t*>(&c) + gather_slots<1>(), g2, 16);
+    encode_args(pe, e);
+    const int prec = ph->precision == 1 ? 1 : 2, V = pe->view_edge;
+    if (k.A != 9 && k.A != 8) return -3;
+    if (V < SSD_ENCODE_EDGE_MIN || V > SSD_ENCODE_EDGE_MAX || !(V & 1) || e.layout != SSD_ENCODE_LAYOUT_LUT) return -2;
+    return pick<2, 1>(prec, -2, [&](auto pr) { return pick<9, 8>(k.A, -2, [&](auto at) { return pick<2, 3>(onehot ? 3 : 2, -2, [&](auto g) {
+        return launch_inc_encode_gather<decltype(pr)::value, decltype(at)::value, decltype(g)::value>(k, c, e, V, s);
     }); }); });
 }
 

@@ -68,9 +68,13 @@ class FastPolicy:
             and (shipped or self.enc_layout == abi.ENCODE_LAYOUT_LUT)
         # act_inc_encode (inc head of t + encoder of t + 1 as one launch: the pipelined rollout): 15 / 31 always; every other edge
         # with the opt-in key pipeline_any_view under the class-LUT layout (k_inc_encode_any), else the standalone encoder and
-        # inc-head launches
+        # inc-head launches.  The gathered layouts (others / gather): with the opt-in key pipeline_gathered under the class-LUT layout
+        # at every supported edge (k_inc_encode_gather), else the four standalone launches
         any_view = bool(getattr(a, "pipeline_any_view", False)) and self.enc_layout == abi.ENCODE_LAYOUT_LUT
-        self.inc_encode = self.fused_enc and (shipped or any_view) and not self.others and not self.gather     # (gathered layouts: the four standalone launches)
+        if self.others or self.gather:
+            self.inc_encode = self.fused_enc and bool(getattr(a, "pipeline_gathered", False)) and self.enc_layout == abi.ENCODE_LAYOUT_LUT
+        else:
+            self.inc_encode = self.fused_enc and (shipped or any_view)
         self.bands = abi.encode_bands(self.V) if self.fused_enc else 1
         # bf16 MFMA products an f32-equivalent product costs (bench.py's roofline accounting); conv: the planes are exact, 2
         self.n_products = dict(encode_conv=2, encode_lin=3, head_env=3, head_inc=3) if precision == 2 else \
@@ -379,13 +383,15 @@ class FastPolicy:
 
     @th.no_grad()
     def act_inc_encode(self, actions, pos, orient, reward, clean_num, apple_den, eps, step, codes, slot_t=None, slot_add=0, buf=0,
-                       q_out=None, file=None, mask_alphabet=None):
+                       q_out=None, file=None, mask_alphabet=None, par=None):
         """act_inc of timestep t on inputs_pair[buf] AND encode of timestep t + 1 into inputs_pair[buf ^ 1] (several bands: into
-        the band sums) as ONE launch (ssd_policy_head_inc_encode): the pipelined rollout's third launch of a timestep.  `codes` /
-        slot_t / slot_add as in encode(): the observation the env step of t just produced (storage slot *slot_t + slot_add)."""
+        the band sums) as ONE launch (ssd_policy_head_inc_encode; the gathered layouts: with ssd_policy_head.pipeline_gather set): the
+        pipelined rollout's third launch of a timestep.  `codes` / slot_t / slot_add as in encode(): the observation the env step of t
+        just produced (storage slot *slot_t + slot_add).  `par` as in act_inc (the gathered layouts read prev_rec[par])."""
         assert self.fused and self.inc_encode
-        ha = self._inc_args(actions, pos, orient, reward, clean_num, apple_den, eps, step, q_out=q_out, file=file, buf=buf)
+        ha = self._inc_args(actions, pos, orient, reward, clean_num, apple_den, eps, step, q_out=q_out, file=file, buf=buf, par=par)
         ea, codes = self._encode_args(None, codes, slot_t, mask_alphabet, buf=buf ^ 1, slot_add=slot_add)
+        ha.pipeline_gather = int(self.others or self.gather)         # the gathered layouts ask for their own fused launch
         abi.check(self.lib, self.lib.ssd_policy_head_inc_encode(C.byref(ha), C.byref(ea), self._stream()))
         self._keep_codes = codes
         return self.actions_inc

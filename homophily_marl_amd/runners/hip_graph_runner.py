@@ -14,7 +14,10 @@ mechanics that make a timestep capturable and replayable for every t:
     groups or an odd number of timesteps per graph take the four standalone launches (k_encode, k_head<env>, env, k_head<inc>).
     obs_others_last_action with fused_others_last_action takes the same four launches (the heads gather fc1's rows; the previous actions
     of all agents travel in FastPolicy.prev_rec, a buffer pair indexed by the parity of t like the input rows).  fused_onehot_gather:
-    the same four launches for ANY flag set at any team size (every one-hot block is gathered; the same record pair).
+    the same four launches for ANY flag set at any team size (every one-hot block is gathered; the same record pair).  With
+    pipeline_gathered both take the three pipelined launches at every window edge, the third being k_inc_encode_gather: the env head of
+    t reads prev_rec[t & 1] and writes the other buffer, the inc head inside the third launch reads prev_rec[t & 1]; the exploration
+    draws are those of the four-launch timestep.
     Other configurations (obs_others_last_action without that key, fast_policy=False) take the generic torch timestep, captured the same way;
   * epsilon is a device scalar; exploration uses the package's counter generator (no multinomial, no host sync).
 The first episode runs eagerly (warm-up of hipBLASLt plans and the allocator); graphs are captured from the second on.
@@ -134,10 +137,11 @@ class HipGraphRunner(HipVecRunner):
                          and getattr(a, "pipeline_encode", True) and (K % 2 == 0 or not use_graph)
                          and (self.obs_fmt == abi.OBS_CODE or self._want_code))
         self.rng_copy = th.zeros(1, dtype=th.long, device=dev)          # pipelined: the env head's copy of rng_ctr for the inc head
-        if self.pipe and self.fast.V not in (15, 31):
-            # pipeline_any_view changes the launches of a timestep, not its draws: in the four-launch timestep the encoder advances
-            # the draw counter BEFORE the heads of that timestep read it, in the pipelined one the inc head advances it AFTER they
-            # did -- so the counter starts one ahead here and both runners draw the same exploration (15 / 31 keep their sequence)
+        if self.pipe and (self.fast.V not in (15, 31) or self.fast.prev_rec is not None):
+            # pipeline_any_view / pipeline_gathered change the launches of a timestep, not its draws: in the four-launch timestep the
+            # encoder advances the draw counter BEFORE the heads of that timestep read it, in the pipelined one the inc head advances it
+            # AFTER they did -- so the counter starts one ahead here and both runners draw the same exploration (the dense layouts at
+            # 15 / 31 keep their sequence; the gathered ones had no pipelined sequence before the key, so the rule holds there too)
             self.rng_ctr.fill_(1)
         self._par = 0
         self._ready = True
@@ -228,7 +232,7 @@ class HipGraphRunner(HipVecRunner):
 
             def env_head_p():
                 self.fast.head_env(self.prev_actions, self.prev_reward, self.prev_inc, pos, self.eps, self.rng_ctr, file=bundle.file_env,
-                                   orient=orient, actions_i32=self.actions_i32, pos_copy=pos_t, orient_copy=orient_t, buf=par)
+                                   orient=orient, actions_i32=self.actions_i32, pos_copy=pos_t, orient_copy=orient_t, buf=par, par=par)
 
             def env_step_p():
                 self.env.step_batch(self.actions_i32, observe=True, fmt=self.obs_fmt, out=self.cur)
@@ -236,11 +240,11 @@ class HipGraphRunner(HipVecRunner):
             def inc_encode_p():
                 out = self.env.native.out
                 self.fast.act_inc_encode(actions, pos_t, orient_t, out["reward"], out["clean_num"], out["apple_den"], self.eps, self.rng_copy,
-                                         codes, slot_t=self.t_store, slot_add=1, buf=par, file=bundle.file_inc)
+                                         codes, slot_t=self.t_store, slot_add=1, buf=par, file=bundle.file_inc, par=par)
 
             def inc_last_p():      # slot T: zeros for reward / clean_num / apple_den, nothing left to encode
                 z = self._zeros_nn
-                self.fast.act_inc(actions, pos_t, orient_t, z, z, z, self.eps, self.rng_copy, file=bundle.file_inc_last, buf=par)
+                self.fast.act_inc(actions, pos_t, orient_t, z, z, z, self.eps, self.rng_copy, file=bundle.file_inc_last, buf=par, par=par)
 
             if store_env_step:
                 return [("ssd::k_head<env>", "head_env", env_head_p), ("ssd::k_env<MODE_STEP_OBS>", "env", env_step_p),

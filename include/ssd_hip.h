@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SSD_ABI_VERSION 10
+#define SSD_ABI_VERSION 10   /* (still 10 with ssd_policy_head.pipeline_gather appended: zero = as before) */
 
 #define SSD_MAX_AGENTS 10   /* maps hold at most 10 spawn points; agent ids >= 10 break the reference (map_env.py:370) */
 #define SSD_MAX_CELLS 1024  /* H*W upper bound (largest reference map is 48x18 = 864) */
@@ -644,7 +644,7 @@ typedef struct ssd_policy_head {
      *                    launch, and the inc head of this timestep still reads it afterwards.
      * Missing others_rows / prev_record, n_agents > SSD_MAX_AGENTS, prev_record_out on the inc head or equal to prev_record:
      * SSD_ERR_INVALID.  ssd_policy_head_inc_encode refuses the flag (SSD_ERR_UNSUPPORTED): these configurations take the four
-     * standalone launches per timestep. */
+     * standalone launches per timestep, or ssd_policy_head_inc_encode with pipeline_gather as their third of three. */
     const float* others_rows;
     const uint8_t* prev_record;
     uint8_t* prev_record_out;
@@ -663,8 +663,11 @@ typedef struct ssd_policy_head {
      *                 input row), 0xFF / any value outside [0, n_actions) adds zeros.  others_rows is not used.
      * Missing onehot_rows / prev_record, misalignment, n_agents > SSD_MAX_AGENTS, prev_record_out on the inc head or equal to
      * prev_record: SSD_ERR_INVALID.  input_shape != 32 + the widths of all flagged blocks: SSD_ERR_UNSUPPORTED.
-     * ssd_policy_head_inc_encode refuses the bit (SSD_ERR_UNSUPPORTED). */
+     * ssd_policy_head_inc_encode refuses the bit (SSD_ERR_UNSUPPORTED) unless pipeline_gather is set. */
     const float* onehot_rows;
+    /* ---- appended for the pipelined launch of the gathered layouts (zero = as before) ---- */
+    int32_t pipeline_gather;       /* read by ssd_policy_head_inc_encode only: nonzero = take the gathered fused launch (declared below
+                                      the encoder's arguments) for a head that carries one of the two gather bits */
 } ssd_policy_head;
 #define SSD_INPUT_LAST_ACTION 1u   /* obs_last_action: one-hot of the previous env action, n_actions columns */
 #define SSD_INPUT_AGENT_ID    2u   /* obs_agent_id: one-hot of the agent, n columns */
@@ -692,7 +695,8 @@ int ssd_policy_head_env(const ssd_policy_head* args, void* stream);
 int ssd_policy_head_inc(const ssd_policy_head* args, void* stream);
 /* How a head launch of (n_env, n_agents) is cut on the current device: workgroups per agent, compute waves per workgroup (a 16-row
  * tile each) and the number of tiles the busiest wave walks -- 1 while the grid fits the chip (the kernels without a back edge),
- * more beyond (Cleanup-10 x 8192: the looped instantiations).  fused_with_encoder: the inc head inside ssd_policy_head_inc_encode. */
+ * more beyond (Cleanup-10 x 8192: the looped instantiations).  fused_with_encoder: the inc head inside ssd_policy_head_inc_encode
+ * (with pipeline_gather: the same cut, always walked by the looped head). */
 int ssd_policy_head_plan(int32_t n_env, int32_t n_agents, int32_t fused_with_encoder, int32_t* workgroups_per_agent, int32_t* compute_waves,
                          int32_t* tiles_per_wave);
 /* The inc head of timestep t and ssd_policy_encode of timestep t + 1 as ONE launch (declared below the encoder's arguments):
@@ -813,6 +817,14 @@ int ssd_policy_encode(const ssd_policy_encode_args* args, void* stream);
  * 3 .. 63 under SSD_ENCODE_LAYOUT_LUT (one run-time-geometry instantiation per precision, action count and looped / unlooped
  * head).  The Toeplitz layout at another edge, an even edge or one outside 3 .. 63: SSD_ERR_UNSUPPORTED. */
 int ssd_policy_head_inc_encode(const ssd_policy_head* inc_args, const ssd_policy_encode_args* enc_args, void* stream);
+/* The same launch for the gathered head layouts, asked for by inc_args->pipeline_gather != 0: inc_args carries
+ * SSD_INPUT_OTHERS_LAST_ACTION or SSD_INPUT_GATHER_ONEHOT (with others_rows / onehot_rows and prev_record as ssd_policy_head_inc takes
+ * them; prev_record_out null), enc_args SSD_ENCODE_LAYOUT_LUT at any odd edge 3 .. 63, 15 and 31 included (the run-time-geometry
+ * encoder half at every edge; its features are bit for bit those of ssd_policy_encode).  One instantiation per precision, action
+ * count (9 / 8) and layout: the head half is the looped gather head at any grid.  pipeline_gather on a head without either bit, the
+ * Toeplitz layout, an even edge or one outside 3 .. 63, another action count: SSD_ERR_UNSUPPORTED.  Everything ssd_policy_head_inc /
+ * ssd_policy_encode refuse, act / slot_t_copy / counter_inc, two precisions, enc_args->out == inc_args->inputs, enc_args->slot_t ==
+ * inc_args->next_t_out: SSD_ERR_INVALID.  With pipeline_gather zero both bits are refused as before (SSD_ERR_UNSUPPORTED). */
 /* conv_b (f32 [6]): read only for the range bound of the conv activations (see SSD_ERRBIT_F16_RANGE). */
 /* conv_w f32 [6, 3, 3, 3], conv_b [6], lin_w [32, 6 (V-2)^2] -> the images of SSD_ENCODE_LAYOUT_LUT: table (SSD_ENCODE_LUT_TABLE_BYTES,
  * 16-byte aligned) and lin_frags (SSD_ENCODE_LUT_LIN_BYTES(V, precision)); V odd, 3 .. 63. */
