@@ -244,10 +244,11 @@ def policy_frag_piece(precision, F, term):
 
 def policy_head_plan(n_env, n_agents, fused_with_encoder=False):
     """(workgroups per agent, compute waves per workgroup, tiles the busiest wave walks) of a head launch on the current device
-    (ssd_policy_head_plan); tiles > 1 = the looped kernel instantiations."""
+    (ssd_policy_head_plan); tiles > 1 = the looped kernel instantiations.  fused_with_encoder: 0 / False = the standalone dense heads,
+    1 / True = the inc head inside the fused launch, 2 = the standalone gathered heads (others' last action / one-hot gather)."""
     lib = load_library()
     a, b, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)
-    check(lib, lib.ssd_policy_head_plan(n_env, n_agents, int(bool(fused_with_encoder)), C.byref(a), C.byref(b), C.byref(c)))
+    check(lib, lib.ssd_policy_head_plan(n_env, n_agents, int(fused_with_encoder), C.byref(a), C.byref(b), C.byref(c)))
     return a.value, b.value, c.value
 
 

@@ -930,6 +930,8 @@ int ssd_policy_head_plan(int32_t n_env, int32_t n_agents, int32_t fused_with_enc
                          int32_t* tiles_per_wave) {
     if (!workgroups_per_agent || !compute_waves || !tiles_per_wave) return fail(SSD_ERR_INVALID, "null argument");
     if (n_env < 1 || n_agents < 1) return fail(SSD_ERR_INVALID, "ssd_policy_head_plan: n_env, n_agents >= 1");
+    if (fused_with_encoder < 0 || fused_with_encoder > 2)
+        return fail(SSD_ERR_INVALID, "ssd_policy_head_plan: the third argument is 0 (standalone dense heads), 1 (fused with the encoder) or 2 (standalone gathered heads)");
     int a = 0, b = 0, c = 0;
     policy_head_plan(n_env, n_agents, fused_with_encoder, &a, &b, &c);
     *workgroups_per_agent = a; *compute_waves = b; *tiles_per_wave = c;

@@ -2318,9 +2318,10 @@ static int launch_inc_encode_gather(HeadK& k, HeadCold& c, EncK& e, int V, hipSt
 }
 
 // How a head launch of (n_env, n_agents) is cut: workgroups per agent, compute waves per workgroup, and the number of 16-row tiles the
-// busiest wave walks (1 = the kernel without a back edge; > 1 = the LOOP instantiation).  fused: the inc head inside k_inc_encode.
-void policy_head_plan(int n_env, int n_agents, int fused, int* wg_per_agent, int* waves_out, int* tiles_per_wave) {
-    const HeadPlan pl = fused ? plan_head(n_env, n_agents, FUSED_WAVES - 1, FUSED_WAVES - 1) : plan_head_standalone(n_env, n_agents, 0);
+// busiest wave walks (1 = the kernel without a back edge; > 1 = the LOOP instantiation).  mode 0: the standalone dense heads (GEN 0),
+// 1: the inc head inside k_inc_encode, 2: the standalone gathered heads (GEN 2 / 3: HEAD_WAVES_GATHER compute waves).
+void policy_head_plan(int n_env, int n_agents, int mode, int* wg_per_agent, int* waves_out, int* tiles_per_wave) {
+    const HeadPlan pl = mode == 1 ? plan_head(n_env, n_agents, FUSED_WAVES - 1, FUSED_WAVES - 1) : plan_head_standalone(n_env, n_agents, mode == 2 ? 2 : 0);
     *wg_per_agent = pl.bpa; *waves_out = pl.waves;
     *tiles_per_wave = ((n_env + 15) / 16 + pl.bpa * pl.waves - 1) / (pl.bpa * pl.waves);
 }

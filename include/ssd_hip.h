@@ -695,8 +695,10 @@ int ssd_policy_head_env(const ssd_policy_head* args, void* stream);
 int ssd_policy_head_inc(const ssd_policy_head* args, void* stream);
 /* How a head launch of (n_env, n_agents) is cut on the current device: workgroups per agent, compute waves per workgroup (a 16-row
  * tile each) and the number of tiles the busiest wave walks -- 1 while the grid fits the chip (the kernels without a back edge),
- * more beyond (Cleanup-10 x 8192: the looped instantiations).  fused_with_encoder: the inc head inside ssd_policy_head_inc_encode
- * (with pipeline_gather: the same cut, always walked by the looped head). */
+ * more beyond (Cleanup-10 x 8192: the looped instantiations).  fused_with_encoder selects the launch: 0 = the standalone heads of
+ * the dense input layouts (8 compute waves), 1 = the inc head inside ssd_policy_head_inc_encode (7; with pipeline_gather: the same
+ * cut, always walked by the looped head), 2 = the standalone heads of the gathered layouts (SSD_INPUT_OTHERS_LAST_ACTION /
+ * SSD_INPUT_GATHER_ONEHOT: 7 compute waves, so they loop from a smaller n_env on).  Any other value is SSD_ERR_INVALID. */
 int ssd_policy_head_plan(int32_t n_env, int32_t n_agents, int32_t fused_with_encoder, int32_t* workgroups_per_agent, int32_t* compute_waves,
                          int32_t* tiles_per_wave);
 /* The inc head of timestep t and ssd_policy_encode of timestep t + 1 as ONE launch (declared below the encoder's arguments):

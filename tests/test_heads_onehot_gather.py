@@ -77,7 +77,8 @@ def test_onehot_gather_heads_match_the_torch_controller(kind, map_, n, N, flags)
     if (kind, n) == ("cleanup", 6):
         assert mac.input_shape == 57
     if N == 4112:
-        assert abi.policy_head_plan(N, n)[2] > 1
+        wg, waves, walks = abi.policy_head_plan(N, n, 2)          # the gathered heads' own plan: 7 compute waves
+        assert waves == 7 and walks > 1 and wg * waves * walks >= (N + 15) // 16
     env.reset_batch()
     g = th.Generator(device="cuda").manual_seed(0)
     ok_actions = th.nonzero(env.avail_actions_batch[0, 0]).squeeze(-1).to(th.int32)
