@@ -18,10 +18,14 @@ t reads [t & 1]) -- no launch reads what a sibling workgroup writes.  fused_oneh
 abi.INPUT_GATHER_ONEHOT): every one-hot block is gathered that way -- the own last action, the agent id, the inc head's one-hot action,
 the others' block if flagged -- from one table per head (onehot_<head>); the image keeps 32 + sign r + sign inc + distances + pos, which
 fits at any team size.  The own previous action is then read from prev_rec as well.
+Which of these a controller takes -- fused heads or per-layer, gathered blocks, encoder layout, fused encoder, the pipelined launch -- is
+decided in one place, plan_rollout (pure: the runners and the host tests call it without a device); FastPolicy takes its values from there.
 Action RNG: the package's counter generator (not torch's Philox) keyed by the GLOBAL env id (env_id_base + local env), so env
 shards draw what the unsharded job draws; exploration draws are not parity-pinned against torch.
 """
 import ctypes as C
+import os
+from dataclasses import dataclass
 
 import torch as th
 import torch.nn.functional as F
@@ -29,53 +33,82 @@ import torch.nn.functional as F
 from . import abi
 
 
+@dataclass(frozen=True)
+class RolloutPlan:
+    """Which rollout kernels a controller takes (plan_rollout): every choice FastPolicy and the runners make from the controller alone."""
+    supported: bool         # the rollout kernels build this controller's input layout (on the fused heads or the per-layer path)
+    fused: bool             # one launch per head (csrc/ssd_policy_mfma.hip); else the per-layer composition
+    flags: object           # the controller's rollout flag word (None: a set the kernels do not take)
+    others: bool            # the others' last-action block is gathered (INPUT_OTHERS_LAST_ACTION)
+    gather: bool            # every one-hot block is gathered (INPUT_GATHER_ONEHOT)
+    inp_dense: int          # columns of the 64-column image / of `inputs`
+    V: int                  # window edge
+    enc_layout: int         # abi.ENCODE_LAYOUT_LUT / _TOEPLITZ
+    fused_enc: bool         # the fused encoder reads class codes
+    inc_encode: bool        # act_inc_encode exists: the pipelined rollout's third launch
+    bands: int              # bands the fused encoder cuts the output rows into
+    needs_prev_rec: bool    # the heads read the previous actions of all agents from the record pair (FastPolicy.prev_rec)
+
+
+def plan_rollout(mac, fused=True, environ=os.environ):
+    """The RolloutPlan of controller `mac` (fused: the caller allows the fused heads).  Pure: no device, no library, no allocation.
+    supported: the shipped flag set on either path, any other combination of the _build_inputs flags (homophily_controller.py:137-184)
+    on the fused heads as long as the DENSE inputs (+ the inc head's one-hot action) fit the 64-column weight image.
+    obs_others_last_action is not dense -- the heads gather fc1's rows for it -- and is taken when the controller opts in
+    (rollout_input_flags holds bit 64; else its flag word is None).  Under abi.INPUT_GATHER_ONEHOT (config key fused_onehot_gather) no
+    one-hot block is dense and every flag set fits (32 + sign r + sign inc + distances + pos <= 46 at n <= abi.MAX_AGENTS)."""
+    a = mac.args
+    n, H, A = mac.n_agents, a.rnn_hidden_dim, a.n_actions
+    flags = getattr(mac, "rollout_input_flags", mac.input_flags)
+    others = flags is not None and bool(flags & abi.INPUT_OTHERS_LAST_ACTION)
+    gather = flags is not None and bool(flags & abi.INPUT_GATHER_ONEHOT)
+    inp_dense = mac.input_shape - (n * A if others else 0)
+    if gather:     # every one-hot block is gathered: the inc head's action too (nothing follows the dense columns)
+        inp_dense -= (A if flags & abi.INPUT_LAST_ACTION else 0) + (n if flags & abi.INPUT_AGENT_ID else 0)
+    V = int(a.obs_dims[0])
+    # fused: one launch per head (csrc/ssd_policy_mfma.hip), inputs padded to 64 columns; otherwise the per-layer composition
+    # (batched hipBLASLt GEMMs + the small kernels of csrc/ssd_policy.hip), which assembles the shipped input layout only
+    fused = bool(fused) and H == 64 and inp_dense + (0 if gather else A) <= 64 and A + 7 <= 16 and flags is not None
+    supported = bool(mac.shipped_flags) or (fused and (not gather or n <= abi.MAX_AGENTS))
+    # encoder images: the class-LUT layout (conv as a table sum, no conv MFMAs: include/ssd_hip.h SSD_ENCODE_LAYOUT_LUT) unless
+    # enc_layout / SSD_ENC_LAYOUT asks for round 3's Toeplitz fragments (kept as the cross-check and for the training forward)
+    lay = getattr(a, "enc_layout", None) or environ.get("SSD_ENC_LAYOUT", "lut")
+    enc_layout = abi.ENCODE_LAYOUT_TOEPLITZ if str(lay).lower() in ("toeplitz", "0") else abi.ENCODE_LAYOUT_LUT
+    lut = enc_layout == abi.ENCODE_LAYOUT_LUT
+    # the fused encoder: the class-LUT layout for every odd window edge 3 .. 63 (view_size 1 .. 31), the Toeplitz layout for
+    # 15 x 15 and 31 x 31 windows (view_size 7 / 15: the shipped configurations)
+    shipped = V in (15, 31)
+    fused_enc = fused and abi.encode_edge_supported(V) and tuple(a.obs_dims) == (V, V) and (shipped or lut)
+    # act_inc_encode (inc head of t + encoder of t + 1 as one launch: the pipelined rollout): 15 / 31 always; every other edge
+    # with the opt-in key pipeline_any_view under the class-LUT layout (k_inc_encode_any), else the standalone encoder and
+    # inc-head launches.  The gathered layouts (others / gather): with the opt-in key pipeline_gathered under the class-LUT layout
+    # at every supported edge (k_inc_encode_gather), else the four standalone launches
+    if others or gather:
+        inc_encode = fused_enc and bool(getattr(a, "pipeline_gathered", False)) and lut
+    else:
+        inc_encode = fused_enc and (shipped or (bool(getattr(a, "pipeline_any_view", False)) and lut))
+    return RolloutPlan(supported=supported, fused=fused, flags=flags, others=others, gather=gather, inp_dense=inp_dense, V=V,
+                       enc_layout=enc_layout, fused_enc=fused_enc, inc_encode=inc_encode, bands=abi.encode_bands(V) if fused_enc else 1,
+                       needs_prev_rec=others or gather)
+
+
 class FastPolicy:
-    def __init__(self, mac, n_env, avail_mask_u8, seed=0, actions_out=None, actions_inc_out=None, share_packs_from=None, fused=True,
-                 precision=2, env_id_base=0):
+    def __init__(self, mac, n_env, avail_mask_u8, seed=0, fused=True, precision=2, env_id_base=0):
         self.mac, self.agent, self.a = mac, mac.agent, mac.args
         a = self.a
         assert a.rgb_input and a.conv_out == 6 and a.obs_dim_net == 32 and a.conv_kernel == 3 and a.conv_stride == 1
         assert precision in (1, 2)
+        self.plan = plan = plan_rollout(mac, fused)
+        assert plan.supported, "FastPolicy: this _build_inputs flag set needs the fused heads (FastPolicy.supports)"
+        self.fused, self.flags, self.others, self.gather, self.inp_dense = plan.fused, plan.flags, plan.others, plan.gather, plan.inp_dense
+        self.V, self.enc_layout, self.fused_enc, self.inc_encode, self.bands = plan.V, plan.enc_layout, plan.fused_enc, plan.inc_encode, plan.bands
         self.lib = abi.load_library()
         self.N, self.n, self.H, self.A = n_env, mac.n_agents, a.rnn_hidden_dim, a.n_actions
         self.dev = next(self.agent.parameters()).device
         self.inp = mac.input_shape
-        flags = getattr(mac, "rollout_input_flags", mac.input_flags)
-        self.flags = flags
-        self.others = flags is not None and bool(flags & abi.INPUT_OTHERS_LAST_ACTION)
-        self.gather = flags is not None and bool(flags & abi.INPUT_GATHER_ONEHOT)
-        self.inp_dense = self.inp - (self.n * self.A if self.others else 0)     # columns of the 64-column image / of `inputs`
-        if self.gather:     # every one-hot block is gathered: the inc head's action too (nothing follows the dense columns)
-            self.inp_dense -= (self.A if flags & abi.INPUT_LAST_ACTION else 0) + (self.n if flags & abi.INPUT_AGENT_ID else 0)
-        self.V = int(a.obs_dims[0])
         self.precision, self.env_id_base = int(precision), int(env_id_base) & 0xFFFFFFFF
         n, N, H = self.n, self.N, self.H
         f32 = dict(dtype=th.float32, device=self.dev)
-        # fused: one launch per head (csrc/ssd_policy_mfma.hip), inputs padded to 64 columns; otherwise the per-layer
-        # composition below (batched hipBLASLt GEMMs + the small kernels of csrc/ssd_policy.hip)
-        self.fused = bool(fused) and H == 64 and self.inp_dense + (0 if self.gather else self.A) <= 64 and self.A + 7 <= 16 and flags is not None
-        # the per-layer composition assembles the shipped input layout only (ssd_build_inputs)
-        assert self.fused or mac.shipped_flags, "FastPolicy: this _build_inputs flag set needs the fused heads (FastPolicy.supports)"
-        # encoder images: the class-LUT layout (conv as a table sum, no conv MFMAs: include/ssd_hip.h SSD_ENCODE_LAYOUT_LUT) unless
-        # enc_layout / SSD_ENC_LAYOUT asks for round 3's Toeplitz fragments (kept as the cross-check and for the training forward)
-        import os
-        lay = getattr(a, "enc_layout", None) or os.environ.get("SSD_ENC_LAYOUT", "lut")
-        self.enc_layout = abi.ENCODE_LAYOUT_TOEPLITZ if str(lay).lower() in ("toeplitz", "0") else abi.ENCODE_LAYOUT_LUT
-        # the fused encoder: the class-LUT layout for every odd window edge 3 .. 63 (view_size 1 .. 31), the Toeplitz layout for
-        # 15 x 15 and 31 x 31 windows (view_size 7 / 15: the shipped configurations)
-        shipped = self.V in (15, 31)
-        self.fused_enc = self.fused and abi.encode_edge_supported(self.V) and tuple(a.obs_dims) == (self.V, self.V) \
-            and (shipped or self.enc_layout == abi.ENCODE_LAYOUT_LUT)
-        # act_inc_encode (inc head of t + encoder of t + 1 as one launch: the pipelined rollout): 15 / 31 always; every other edge
-        # with the opt-in key pipeline_any_view under the class-LUT layout (k_inc_encode_any), else the standalone encoder and
-        # inc-head launches.  The gathered layouts (others / gather): with the opt-in key pipeline_gathered under the class-LUT layout
-        # at every supported edge (k_inc_encode_gather), else the four standalone launches
-        any_view = bool(getattr(a, "pipeline_any_view", False)) and self.enc_layout == abi.ENCODE_LAYOUT_LUT
-        if self.others or self.gather:
-            self.inc_encode = self.fused_enc and bool(getattr(a, "pipeline_gathered", False)) and self.enc_layout == abi.ENCODE_LAYOUT_LUT
-        else:
-            self.inc_encode = self.fused_enc and (shipped or any_view)
-        self.bands = abi.encode_bands(self.V) if self.fused_enc else 1
         # bf16 MFMA products an f32-equivalent product costs (bench.py's roofline accounting); conv: the planes are exact, 2
         self.n_products = dict(encode_conv=2, encode_lin=3, head_env=3, head_inc=3) if precision == 2 else \
             dict(encode_conv=1, encode_lin=1, head_env=1, head_inc=1)
@@ -89,20 +122,15 @@ class FastPolicy:
         self.feat_part = th.zeros(self.bands, n * N, 32, **f32) if self.bands > 1 else None
         self.h_env = th.zeros(n, N, H, **f32)
         self.h_inc = th.zeros(n, N, H, **f32)
-        # outputs may be slices of a caller-owned full-batch buffer (env groups evaluated on separate streams)
-        self.actions = th.zeros(N, n, dtype=th.long, device=self.dev) if actions_out is None else actions_out
-        self.actions_inc = th.zeros(N, n, n, dtype=th.long, device=self.dev) if actions_inc_out is None else actions_inc_out
-        assert self.actions.is_contiguous() and self.actions_inc.is_contiguous()
+        self.actions = th.zeros(N, n, dtype=th.long, device=self.dev)
+        self.actions_inc = th.zeros(N, n, n, dtype=th.long, device=self.dev)
         self.avail = avail_mask_u8.to(device=self.dev, dtype=th.uint8).contiguous()
         self._avail_bits = 0x80000000 | sum(1 << k for k, v in enumerate(avail_mask_u8.detach().cpu().reshape(-1).tolist()[:31]) if v)   # ssd_policy_head.avail_bits
         self.seed = seed & 0xFFFFFFFF
         self.arange_n = th.arange(n, device=self.dev).unsqueeze(1)
         # every agent's previous env action, one byte per agent (0xFF = none), 16 bytes per env, as a pair selected by the timestep's parity
-        self.prev_rec = th.full((2, N, abi.PREV_RECORD_BYTES), 0xFF, dtype=th.uint8, device=self.dev) if (self.others or self.gather) else None
-        if share_packs_from is not None:
-            self.p = share_packs_from.p          # same weights: one packed copy serves every group
-        else:
-            self.pack()
+        self.prev_rec = th.full((2, N, abi.PREV_RECORD_BYTES), 0xFF, dtype=th.uint8, device=self.dev) if plan.needs_prev_rec else None
+        self.pack()
 
     def _stream(self):
         return th.cuda.current_stream(self.dev).cuda_stream
@@ -182,21 +210,8 @@ class FastPolicy:
 
     @staticmethod
     def supports(mac, fused=True):
-        """Whether the rollout kernels build this controller's input layout: the shipped flag set on either path, any other
-        combination of the _build_inputs flags (homophily_controller.py:137-184) on the fused heads as long as the DENSE inputs (+ the
-        inc head's one-hot action) fit the 64-column weight image.  obs_others_last_action is not dense -- the heads gather fc1's rows
-        for it -- and is taken when the controller opts in (rollout_input_flags holds bit 64; else its flag word is None).  Under
-        abi.INPUT_GATHER_ONEHOT (config key fused_onehot_gather) no one-hot block is dense and every flag set fits."""
-        a = mac.args
-        if mac.shipped_flags:
-            return True
-        flags = getattr(mac, "rollout_input_flags", mac.input_flags)
-        if flags is None:
-            return False
-        if flags & abi.INPUT_GATHER_ONEHOT:     # dense: 32 + sign r + sign inc + distances + pos <= 46 at n <= 10
-            return bool(fused) and a.rnn_hidden_dim == 64 and a.n_actions + 7 <= 16 and mac.n_agents <= abi.MAX_AGENTS
-        dense = mac.input_shape - (mac.n_agents * a.n_actions if flags & abi.INPUT_OTHERS_LAST_ACTION else 0)
-        return bool(fused) and a.rnn_hidden_dim == 64 and dense + a.n_actions <= 64 and a.n_actions + 7 <= 16
+        """Whether the rollout kernels build this controller's input layout (plan_rollout)."""
+        return plan_rollout(mac, fused).supported
 
     def _head_params(self, head):
         """ssd_policy_head_params of one head: pointers to the reference-shaped parameters (homophily_agent.py:37-125)."""

@@ -10,8 +10,8 @@ mechanics that make a timestep capturable and replayable for every t:
   * with FastPolicy's fused kernels (default) a timestep is 3 launches (pipelined): k_head<env> on the features the previous
     timestep's launch left, the fused env step + observe (writes obs[:, t + 1] of the storage), and k_inc_encode = k_head<inc> of
     t together with k_encode of slot t + 1 (they share no data; the input rows live in a buffer pair indexed by the parity of t);
-    the heads file actions / pose / rewards in slot t, carry the runner state and hand the device-side counters over.  Several env
-    groups or an odd number of timesteps per graph take the four standalone launches (k_encode, k_head<env>, env, k_head<inc>).
+    the heads file actions / pose / rewards in slot t, carry the runner state and hand the device-side counters over.  An odd number
+    of timesteps per graph takes the four standalone launches (k_encode, k_head<env>, env, k_head<inc>).
     obs_others_last_action with fused_others_last_action takes the same four launches (the heads gather fc1's rows; the previous actions
     of all agents travel in FastPolicy.prev_rec, a buffer pair indexed by the parity of t like the input rows).  fused_onehot_gather:
     the same four launches for ANY flag set at any team size (every one-hot block is gathered; the same record pair).  With
@@ -20,11 +20,14 @@ mechanics that make a timestep capturable and replayable for every t:
     draws are those of the four-launch timestep.
     Other configurations (obs_others_last_action without that key, fast_policy=False) take the generic torch timestep, captured the same way;
   * epsilon is a device scalar; exploration uses the package's counter generator (no multinomial, no host sync).
+Which of these a runner takes is decided once, on the host: plan_rollout (fast_policy.py) for the controller, plan_runner below for
+the storage format, the graph length and the config keys.
 The first episode runs eagerly (warm-up of hipBLASLt plans and the allocator); graphs are captured from the second on.
 The returned EpisodeBatch is the persistent storage: consume it (buffer.insert_episode_batch) before the next run(), as the
 training loop does (run.py:184-185).
 """
 import ctypes as C
+from typing import NamedTuple
 
 import torch as th
 import torch.nn.functional as F
@@ -32,7 +35,49 @@ import torch.nn.functional as F
 from .. import abi, ops
 
 from ..components.episode_buffer import EpisodeBatch
+from ..fast_policy import FastPolicy, plan_rollout
 from .hip_vec_runner import HipVecRunner
+
+
+class RunnerPlan(NamedTuple):
+    fast: bool              # the FastPolicy kernels; else the generic torch timestep
+    direct_obs: bool        # fused encoder: the env kernel writes obs[:, t + 1] of the storage itself (and the class codes the encoder reads)
+    fold_store: bool        # the two heads file their results in the storage themselves: no store-step launch
+    graph_steps: int        # timesteps per rollout hipGraph; 0: eager timesteps
+    pipe: bool              # the pipelined timestep of 3 launches
+    counter_start: int      # what the exploration draw counter starts at
+
+
+def plan_runner(plan, args, episode_limit, obs_fmt):
+    """The runner's own choices for a controller whose RolloutPlan is `plan` (computed with fused = fused_policy and the simplified
+    palette).  Pure: it is called before anything is allocated."""
+    a = args
+    fast = bool(getattr(a, "fast_policy", True)) and plan.supported
+    direct_obs = fast and plan.fused_enc
+    fold_store = direct_obs and bool(getattr(a, "fold_store", True))
+    if obs_fmt == abi.OBS_CODE and not direct_obs:
+        # class-code storage is consumed by the fused encoder only; windows it does not take (view 0) take the generic timestep
+        # (the torch controller expands the codes itself)
+        fast = False
+    # Pipelined timestep (3 launches): env head -> env step -> [inc head of t + encoder of t + 1] as one launch
+    # (FastPolicy.act_inc_encode).  The encoder writes the OTHER buffer of FastPolicy.inputs_pair, so the buffer of a timestep is
+    # its parity -- baked into the captured graph, hence an even number of timesteps per graph.
+    K = max(1, int(getattr(a, "steps_per_graph", 10)))
+    while episode_limit % K:
+        K -= 1
+    if fast and plan.needs_prev_rec and K % 2:
+        # the previous-action records alternate with the parity of t, which a captured graph bakes in: an even number of timesteps
+        # per graph, or (odd episode lengths) eager timesteps
+        K = max([k for k in range(2, K, 2) if episode_limit % k == 0], default=0)
+    use_graph = bool(getattr(a, "rollout_graph", True))
+    # (fold_store implies that the encoder has class codes to read: the storage's under OBS_CODE, else the env's side buffer)
+    pipe = bool(fold_store and plan.fused and plan.inc_encode and getattr(a, "pipeline_encode", True) and (K % 2 == 0 or not use_graph))
+    # pipeline_any_view / pipeline_gathered change the launches of a timestep, not its draws: in the four-launch timestep the
+    # encoder advances the draw counter BEFORE the heads of that timestep read it, in the pipelined one the inc head advances it
+    # AFTER they did -- so the counter starts one ahead there and both runners draw the same exploration (the dense layouts at
+    # 15 / 31 keep their sequence; the gathered ones had no pipelined sequence before the key, so the rule holds there too)
+    ahead = pipe and (plan.V not in (15, 31) or plan.needs_prev_rec)
+    return RunnerPlan(fast=fast, direct_obs=direct_obs, fold_store=fold_store, graph_steps=K, pipe=pipe, counter_start=int(ahead))
 
 
 class HipGraphRunner(HipVecRunner):
@@ -65,8 +110,11 @@ class HipGraphRunner(HipVecRunner):
                                and self.obs_fmt != abi.OBS_CODE and abi.encode_edge_supported(self.env.native.V))
         self._dense_cur = self.env.native.obs_buffers(self.obs_fmt, want_code=self._want_code)   # obs / pos / orient written by the env kernel
         self.cur = self._dense_cur
+        use_fused = bool(getattr(a, "fused_policy", True)) and simplified
+        rp = plan_runner(plan_rollout(self.mac, use_fused), a, self.episode_limit, self.obs_fmt)
+        self.direct_obs, self.fold_store, self.pipe, self._graph_steps_planned = rp.direct_obs, rp.fold_store, rp.pipe, rp.graph_steps
         self.t_dev = th.zeros(1, dtype=th.long, device=dev)
-        self.rng_ctr = th.zeros(1, dtype=th.long, device=dev)          # never reset: exploration draws differ between episodes
+        self.rng_ctr = th.full((1,), rp.counter_start, dtype=th.long, device=dev)   # never reset: exploration draws differ between episodes
         self.prev_actions = th.full((N, n), -1, dtype=th.long, device=dev)
         self.prev_reward = th.zeros(N, n, device=dev)
         self.prev_inc = th.zeros(N, n, n, dtype=th.long, device=dev)
@@ -82,67 +130,16 @@ class HipGraphRunner(HipVecRunner):
         self.avail_mask = self.env.avail_actions_batch                  # [N, n, A]
         self.inc_mask = (1 - th.eye(n, device=dev, dtype=th.long)).reshape(1, n, n)
         self.fast = None
-        self.direct_obs = self.fold_store = False
-        from ..fast_policy import FastPolicy
-        use_fused = bool(getattr(a, "fused_policy", True)) and simplified
-        if getattr(a, "fast_policy", True) and FastPolicy.supports(self.mac, use_fused):   # else: the generic captured timestep
-            # Optionally the policy work of a timestep is evaluated per env GROUP on separate streams (fork/join inside the
-            # captured graph) around the single full-batch env launch.  Measured on MI355X / ROCm 7.2: no gain (the graph
-            # runs the branches back to back), so the default is one group.
-            G = int(getattr(a, "policy_groups", 1))
-            if N % G or N // G < 1:
-                G = 1
-            self.groups, hsz = G, N // G
-            self.actions_full = th.zeros(N, n, dtype=th.long, device=dev)
-            self.actions_inc_full = th.zeros(N, n, n, dtype=th.long, device=dev)
-            seed = int(self.env.native.cfg.seed) * 2654435761 + 12345
-            prec = 1 if str(getattr(a, "qnet_dtype", "fp32")).lower() in ("bf16", "bfloat16") else 2
-            base = int(self.env.native.cfg.env_id_base)
-            self.fasts = []
-            for g in range(G):
-                sl = slice(g * hsz, (g + 1) * hsz)
-                # one exploration seed for every group and rank: the draws are keyed by the GLOBAL env id (env_id_base + local env)
-                self.fasts.append(FastPolicy(self.mac, hsz, avail, seed=seed, actions_out=self.actions_full[sl],
-                                             actions_inc_out=self.actions_inc_full[sl],
-                                             share_packs_from=self.fasts[0] if g else None,
-                                             fused=use_fused, precision=prec,
-                                             env_id_base=base + g * hsz))
-            self.fast = self.fasts[0]
-            self.gslices = [slice(g * hsz, (g + 1) * hsz) for g in range(G)]
-            self.side_streams = [th.cuda.Stream(device=dev) for _ in range(G)] if G > 1 else []
+        if rp.fast:         # else: the generic captured timestep
+            # one exploration seed for every rank: the draws are keyed by the GLOBAL env id (env_id_base + local env)
+            self.fast = FastPolicy(self.mac, N, avail, seed=int(self.env.native.cfg.seed) * 2654435761 + 12345, fused=use_fused,
+                                   precision=1 if str(getattr(a, "qnet_dtype", "fp32")).lower() in ("bf16", "bfloat16") else 2,
+                                   env_id_base=int(self.env.native.cfg.env_id_base))
             self._zeros_nn = th.zeros(N, n, device=dev)
             self.pos_t, self.orient_t = th.zeros(N, n, 2, device=dev), th.zeros(N, n, 2, device=dev)   # pose before the env step
             self.actions_i32 = th.zeros(N, n, dtype=th.int32, device=dev)
             self.t_store = th.zeros(1, dtype=th.long, device=dev)     # the encoder's copy of t_dev, read by the store-step launch
-            # fused encoder: the env kernel writes obs[:, t + 1] of the storage itself (and the class codes the encoder reads)
-            self.direct_obs = self.fast.fused_enc and self.obs_fmt in (abi.OBS_F32, abi.OBS_CODE)
-            self.fold_store = self.direct_obs and G == 1 and bool(getattr(a, "fold_store", True))
-            if self.obs_fmt == abi.OBS_CODE and not self.direct_obs:
-                # class-code storage is consumed by the fused encoder only; windows it does not take (view 0) take the generic timestep
-                # (the torch controller expands the codes itself)
-                self.fast, self.fasts, self.fold_store = None, [], False
-        # Pipelined timestep (3 launches): env head -> env step -> [inc head of t + encoder of t + 1] as one launch
-        # (FastPolicy.act_inc_encode).  The encoder writes the OTHER buffer of FastPolicy.inputs_pair, so the buffer of a timestep is
-        # its parity -- baked into the captured graph, hence an even number of timesteps per graph.
-        K = max(1, int(getattr(a, "steps_per_graph", 10)))
-        while self.episode_limit % K:
-            K -= 1
-        if self.fast is not None and self.fast.prev_rec is not None and K % 2:
-            # the previous-action records alternate with the parity of t, which a captured graph bakes in: an even number of timesteps
-            # per graph, or (odd episode lengths) eager timesteps
-            K = max([k for k in range(2, K, 2) if self.episode_limit % k == 0], default=0)
-        self._graph_steps_planned = K
-        use_graph = bool(getattr(a, "rollout_graph", True))
-        self.pipe = bool(self.fast is not None and self.fold_store and self.fast.fused and self.fast.inc_encode and self.groups == 1
-                         and getattr(a, "pipeline_encode", True) and (K % 2 == 0 or not use_graph)
-                         and (self.obs_fmt == abi.OBS_CODE or self._want_code))
         self.rng_copy = th.zeros(1, dtype=th.long, device=dev)          # pipelined: the env head's copy of rng_ctr for the inc head
-        if self.pipe and (self.fast.V not in (15, 31) or self.fast.prev_rec is not None):
-            # pipeline_any_view / pipeline_gathered change the launches of a timestep, not its draws: in the four-launch timestep the
-            # encoder advances the draw counter BEFORE the heads of that timestep read it, in the pipelined one the inc head advances it
-            # AFTER they did -- so the counter starts one ahead here and both runners draw the same exploration (the dense layouts at
-            # 15 / 31 keep their sequence; the gathered ones had no pipelined sequence before the key, so the rule holds there too)
-            self.rng_ctr.fill_(1)
         self._par = 0
         self._ready = True
 
@@ -170,14 +167,14 @@ class HipGraphRunner(HipVecRunner):
                                       dst_actions=st["actions"].data_ptr(), dst_actions_onehot=st["actions_onehot"].data_ptr(),
                                       prev_actions_out=self.prev_actions.data_ptr())
                     b.file_inc_last = dict(common, dst_actions_inc=st["actions_inc"].data_ptr())
-                    if self.recv_inc is not None and self.groups == 1:
+                    if self.recv_inc is not None:
                         b.file_env = dict(b.file_env, recv_inc=self.recv_inc.data_ptr())
                     b.file_inc = dict(b.file_inc_last, prev_actions_inc_out=self.prev_inc.data_ptr(), dst_reward=st["reward"].data_ptr(),
                                       dst_clean_num=st["clean_num"].data_ptr(), dst_apple_den=st["apple_den"].data_ptr(),
                                       dst_terminated=st["terminated"].data_ptr(), terminated=out["terminated"].data_ptr(),
                                       prev_reward_out=self.prev_reward.data_ptr(), ep_return=self.ep_return.data_ptr(),
                                       next_t_out=self.t_dev.data_ptr())
-                    if self.recv_inc is not None and self.groups == 1:
+                    if self.recv_inc is not None:
                         b.file_inc = dict(b.file_inc, recv_inc_out=self.recv_inc.data_ptr())
                     if self.pipe:
                         # counter hand-over without a launch writing a scalar it reads: the env head reads the masters (t_dev, rng_ctr)
@@ -199,72 +196,36 @@ class HipGraphRunner(HipVecRunner):
         rand = idx_table[r] if idx_table is not None else r
         return th.where(u < self.eps, rand, greedy)
 
-    def _fork(self, fn):
-        """run fn(g) for every env group, each on its own stream, then join (capturable fork/join)."""
-        if self.groups == 1:
-            fn(0)
-            return
-        main = th.cuda.current_stream(self.env.device)
-        for g, s in enumerate(self.side_streams):
-            s.wait_stream(main)
-            with th.cuda.stream(s):
-                fn(g)
-        for s in self.side_streams:
-            main.wait_stream(s)
-
     def _fast_stages(self, store_env_step):
         """The launches of one timestep with the FastPolicy kernels, in order, as (kernel name, key, closure).  Fused path
         (default): k_encode reads obs[:, t] from the storage where the env kernel put it, the two head kernels file actions / pose /
         rewards into slot t and carry the previous-step inputs, return and counters themselves -- a timestep is 4 launches
         (encode, env head, env step+observe, inc head), or 3 when pipelined (self.pipe: env head, env step+observe, inc head of t +
-        encoder of t + 1 as one launch).  Otherwise one store-step launch writes the nine small fields."""
+        encoder of t + 1 as one launch).  Otherwise one store-step launch writes the nine small fields.
+        The pipelined timestep differs from the four-launch one in three things only: no encoder launch of its own, the input buffer
+        `buf` (its parity instead of 0) and the draw counter the inc head reads (the env head's copy instead of the master)."""
         st = self.store.data.transition_data
         td = self.t_dev
+        fast, bundle, pipe, fused = self.fast, self._bundle, self.pipe, self.fast.fused
         obs, pos, orient = self.cur["obs"], self.cur["pos"], self.cur["orient"]
-        fused = self.fast.fused
-        actions = self.actions_full
+        codes = st["obs"] if self.obs_fmt == abi.OBS_CODE else self.cur.get("code")     # what the fused encoder reads
+        actions = fast.actions
         pos_t, orient_t = self.pos_t, self.orient_t                     # forward_inc sees the PRE-step pose (controller :78-82)
-        bundle = self._bundle
+        par = self._par
+        buf = par if pipe else 0                                        # pipelined: the buffer of a timestep is its parity
+        inc_step = self.rng_copy if pipe else self.rng_ctr
+        inc_encode = pipe and store_env_step                            # slot T: nothing left to encode
 
-        if self.pipe:
-            par = self._par                                             # buffer of this timestep = its parity
-            codes = st["obs"] if self.obs_fmt == abi.OBS_CODE else self.cur["code"]
-
-            def env_head_p():
-                self.fast.head_env(self.prev_actions, self.prev_reward, self.prev_inc, pos, self.eps, self.rng_ctr, file=bundle.file_env,
-                                   orient=orient, actions_i32=self.actions_i32, pos_copy=pos_t, orient_copy=orient_t, buf=par, par=par)
-
-            def env_step_p():
-                self.env.step_batch(self.actions_i32, observe=True, fmt=self.obs_fmt, out=self.cur)
-
-            def inc_encode_p():
-                out = self.env.native.out
-                self.fast.act_inc_encode(actions, pos_t, orient_t, out["reward"], out["clean_num"], out["apple_den"], self.eps, self.rng_copy,
-                                         codes, slot_t=self.t_store, slot_add=1, buf=par, file=bundle.file_inc, par=par)
-
-            def inc_last_p():      # slot T: zeros for reward / clean_num / apple_den, nothing left to encode
-                z = self._zeros_nn
-                self.fast.act_inc(actions, pos_t, orient_t, z, z, z, self.eps, self.rng_copy, file=bundle.file_inc_last, buf=par, par=par)
-
-            if store_env_step:
-                return [("ssd::k_head<env>", "head_env", env_head_p), ("ssd::k_env<MODE_STEP_OBS>", "env", env_step_p),
-                        ("ssd::k_inc_encode", "inc_encode", inc_encode_p)]
-            return [("ssd::k_head<env>", "head_env", env_head_p), ("ssd::k_head<inc>", "head_inc", inc_last_p)]
-
-        def encode(g):
-            sl = self.gslices[g]
+        def encode():
             if self.direct_obs:     # the observation is already in the storage; the encoder reads its class codes
-                code_store = self.obs_fmt == abi.OBS_CODE
-                self.fasts[g].encode(None, codes=(st["obs"] if code_store else self.cur["code"])[sl], slot_t=td,
-                                     t_copy=self.t_store if g == 0 else None, counter_inc=self.rng_ctr if self.fold_store else None)
+                fast.encode(None, codes=codes, slot_t=td, t_copy=self.t_store, counter_inc=self.rng_ctr if self.fold_store else None)
             else:
-                self.fasts[g].encode(obs[sl], codes=self.cur["code"][sl] if "code" in self.cur else None, store_obs=st["obs"][sl], store_t=td)
+                fast.encode(obs, codes=codes, store_obs=st["obs"], store_t=td)
 
-        def env_head(g):
-            sl = self.gslices[g]
-            extra = dict(orient=orient[sl], actions_i32=self.actions_i32[sl], pos_copy=pos_t[sl], orient_copy=orient_t[sl]) if fused else {}
-            self.fasts[g].head_env(self.prev_actions[sl], self.prev_reward[sl], self.prev_inc[sl], pos[sl], self.eps, self.rng_ctr,
-                                   file=bundle.file_env, par=self._par, **extra)
+        def env_head():
+            extra = dict(orient=orient, actions_i32=self.actions_i32, pos_copy=pos_t, orient_copy=orient_t) if fused else {}
+            fast.head_env(self.prev_actions, self.prev_reward, self.prev_inc, pos, self.eps, self.rng_ctr, file=bundle.file_env,
+                          buf=buf, par=par, **extra)
 
         def env_step():
             if not fused:
@@ -273,20 +234,22 @@ class HipGraphRunner(HipVecRunner):
             if store_env_step:
                 self.env.step_batch(self.actions_i32, observe=True, fmt=self.obs_fmt, out=self.cur if self.direct_obs else None)
 
-        def inc_head(g):
-            sl = self.gslices[g]
+        def inc_head():
             if store_env_step:
                 out = self.env.native.out
                 reward, clean, den = out["reward"], out["clean_num"], out["apple_den"]
-            else:
+            else:       # slot T: zeros for reward / clean_num / apple_den
                 reward = clean = den = self._zeros_nn
-            self.fasts[g].act_inc(actions[sl], pos_t[sl], orient_t[sl], reward[sl], clean[sl], den[sl], self.eps, self.rng_ctr,
-                                  file=bundle.file_inc if store_env_step else bundle.file_inc_last, par=self._par)
+            file = bundle.file_inc if store_env_step else bundle.file_inc_last
+            if inc_encode:
+                fast.act_inc_encode(actions, pos_t, orient_t, reward, clean, den, self.eps, inc_step, codes, slot_t=self.t_store, slot_add=1,
+                                    buf=buf, file=file, par=par)
+            else:
+                fast.act_inc(actions, pos_t, orient_t, reward, clean, den, self.eps, inc_step, file=file, buf=buf, par=par)
 
-        return [("ssd::k_encode", "encode", lambda: self._fork(encode)),
-                ("ssd::k_head<env>", "head_env", lambda: self._fork(env_head)),
-                ("ssd::k_env<MODE_STEP_OBS>", "env", env_step),
-                ("ssd::k_head<inc>", "head_inc", lambda: self._fork(inc_head))]
+        return ([] if pipe else [("ssd::k_encode", "encode", encode)]) + [("ssd::k_head<env>", "head_env", env_head)] + \
+            ([("ssd::k_env<MODE_STEP_OBS>", "env", env_step)] if store_env_step or not pipe else []) + \
+            [("ssd::k_inc_encode", "inc_encode", inc_head) if inc_encode else ("ssd::k_head<inc>", "head_inc", inc_head)]
 
     def timestep_launches(self):
         """(kernel name, key, closure) of the launches of one rollout timestep on the live buffers -- what the rollout hipGraph was
@@ -317,7 +280,7 @@ class HipGraphRunner(HipVecRunner):
         ss = abi.SsdStoreStep()
         ss.t_index = self.t_dev.data_ptr()
         ss.n_env, ss.n_agents, ss.n_actions, ss.t_slots = self.batch_size, self.args.n_agents, self.args.n_actions, self.episode_limit + 1
-        ss.actions, ss.actions_inc = self.actions_full.data_ptr(), self.actions_inc_full.data_ptr()
+        ss.actions, ss.actions_inc = fp.actions.data_ptr(), fp.actions_inc.data_ptr()
         ss.pos, ss.orient = self.pos_t.data_ptr(), self.orient_t.data_ptr()
         ss.dst_pos, ss.dst_orient = st["agent_pos"].data_ptr(), st["agent_orientation"].data_ptr()
         if self.direct_obs:
@@ -442,10 +405,10 @@ class HipGraphRunner(HipVecRunner):
         self.env.observe_batch(self.obs_fmt, out=self.cur if getattr(self, "direct_obs", False) else None)   # fills self.cur (or obs[:, 0])
         # the runner state an episode opens with, as ONE launch: time index, previous actions (-1) / reward / incentive actions, the
         # episode returns, the hidden states (the generic timestep's, or FastPolicy's own)
-        hidden = [self.h_env, self.h_inc] if self.fast is None else [h for fp in self.fasts for h in (fp.h_env, fp.h_inc)]
+        hidden = [self.h_env, self.h_inc] if self.fast is None else [self.fast.h_env, self.fast.h_inc]
         ops.fill_blocks([(self.t_dev, 0), (self.prev_actions, 0xFFFFFFFF), (self.prev_reward, 0), (self.prev_inc, 0), (self.ep_return, 0)]
                         + ([(self.recv_inc, 0)] if self.recv_inc is not None else []) + [(h, 0) for h in hidden]
-                        + [(fp.prev_rec, 0xFFFFFFFF) for fp in (self.fasts if self.fast is not None else []) if fp.prev_rec is not None])
+                        + ([(self.fast.prev_rec, 0xFFFFFFFF)] if self.fast is not None and self.fast.prev_rec is not None else []))
         if self.fast is not None:
             if in_capture:
                 self.fast._pack_eager()   # the learner may have stepped the weights since the last episode (packs are shared)

@@ -133,6 +133,22 @@ def n_actions(kind):
     return 8 if kind == "harvest" else 9
 
 
+SHIPPED_WORD = 1 | 2 | 4 | 8 | 32             # the shipped _build_inputs flag set as a flag word
+
+
+def host_plan(V, flags=SHIPPED_WORD, **keys):
+    """plan_rollout (fast_policy.py) over a stand-in controller of 5 agents and 9 actions with window edge V, the shipped input set plus
+    the gather bits of the rollout flag word `flags` (64: the others' last actions, 0x100: gathered one-hots) and the config keys `keys`:
+    the host tests read the plan's fields without a device."""
+    from types import SimpleNamespace
+    from homophily_marl_amd.fast_policy import plan_rollout
+    n, A, others = 5, 9, bool(flags & 64)
+    args = SimpleNamespace(rnn_hidden_dim=64, n_actions=A, obs_dims=(V, V), **keys)
+    mac = SimpleNamespace(args=args, n_agents=n, input_shape=32 + A + n + 4 + (n * A if others else 0),
+                          input_flags=None if others else SHIPPED_WORD, rollout_input_flags=flags, shipped_flags=not others)
+    return plan_rollout(mac)
+
+
 def gen_of(flags, inc):
     """launch_policy_head: GEN 3 = SSD_INPUT_GATHER_ONEHOT, GEN 2 = the others' block gathered, GEN 1 = an env head whose dense flag
     set is not the shipped one, GEN 0 = everything else (the inc head of a GEN 1 set included)"""

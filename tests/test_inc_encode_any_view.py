@@ -2,7 +2,7 @@
 pipeline_any_view: k_inc_encode_any = the inc head of timestep t and the run-time-geometry class-LUT encoder of t + 1 as one launch.
 
 CPU: the kernel-argument layout the compiler emitted for the new kernels (the heads read part of their arguments by offset), the
-argument refusals of ssd_policy_head_inc_encode that return before any launch, and the truth table of FastPolicy.inc_encode.
+argument refusals of ssd_policy_head_inc_encode that return before any launch, and the truth table of plan_rollout's inc_encode.
 GPU: the fused launch against the two standalone launches bit for bit (one to six bands, ragged tiles, both action counts, both
 precisions, the looped head), and the pipelined hip_graph runner against the four-launch runner field by field, replayed on the CPU
 oracle."""
@@ -11,13 +11,13 @@ import functools
 import os
 import re
 import sys
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch as th
 
 from homophily_marl_amd import abi
+from tests.policy_cases import host_plan as _host_policy      # plan_rollout over a stand-in controller: the shipped input set
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 ODD_EDGES = list(range(3, 64, 2))
@@ -100,17 +100,6 @@ def test_fused_launch_refuses_the_toeplitz_layout_at_other_edges_before_any_laun
     e = _enc(13, abi.ENCODE_LAYOUT_LUT)
     e.out = h.inputs
     assert lib.ssd_policy_head_inc_encode(C.byref(h), C.byref(e), None) == abi.SSD_ERR_INVALID and b"other inputs buffer" in lib.ssd_last_error()
-
-
-def _host_policy(V, **keys):
-    """FastPolicy on the CPU over a stand-in controller with the shipped input set (no packs: nothing is launched)."""
-    from homophily_marl_amd.fast_policy import FastPolicy
-    n, A = 5, 9
-    args = SimpleNamespace(rgb_input=True, conv_out=6, obs_dim_net=32, conv_kernel=3, conv_stride=1, rnn_hidden_dim=64, n_actions=A,
-                           obs_dims=(V, V), **keys)
-    mac = SimpleNamespace(agent=th.nn.Linear(1, 1), args=args, n_agents=n, input_shape=32 + A + n + 4, input_flags=1 | 2 | 4 | 8 | 32,
-                          shipped_flags=True)
-    return FastPolicy(mac, 16, th.ones(A, dtype=th.uint8), share_packs_from=SimpleNamespace(p=None))
 
 
 def test_inc_encode_truth_table(monkeypatch):

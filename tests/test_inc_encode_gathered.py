@@ -4,7 +4,7 @@ encoder of t + 1 as one launch (ssd_policy_head_inc_encode with ssd_policy_head.
 15 and 31 included.
 
 CPU: the kernel-argument layout the compiler emitted for the new kernels (the heads read the gather pointers by offset), the argument
-refusals of the entry point under the new field that return before any launch, and the truth table of FastPolicy.inc_encode.
+refusals of the entry point under the new field that return before any launch, and the truth table of plan_rollout's inc_encode.
 GPU: the fused launch against the two standalone launches bit for bit (both layouts, ragged tiles, one to three bands, both action
 counts, both precisions, the looped grid; V = 15 / 31: the run-time-geometry encoder half against the compile-time kernels the standalone
 launch takes there), the pipelined hip_graph runner against the four-launch runner field by field, replayed on the CPU oracle, and the
@@ -12,13 +12,13 @@ reference's Q-values (bar 1e-5, DESIGN section 2 "Bars") through act_env / act_i
 import ctypes as C
 import os
 import sys
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch as th
 
 from homophily_marl_amd import abi
+from tests.policy_cases import host_plan as _host_policy      # plan_rollout over a stand-in controller: a rollout flag word with a gather bit
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 ODD_EDGES = list(range(3, 64, 2))
@@ -141,17 +141,6 @@ def test_gathered_launch_refuses_bad_arguments_before_any_launch(flags):
     assert (b"SSD_INPUT_GATHER_ONEHOT" if flags & GATHER else b"obs_others_last_action") in lib.ssd_last_error()
 
 
-def _host_policy(V, flags, **keys):
-    """FastPolicy on the CPU over a stand-in controller whose rollout flag word carries a gather bit (no packs: nothing is launched)."""
-    from homophily_marl_amd.fast_policy import FastPolicy
-    n, A = 5, 9
-    args = SimpleNamespace(rgb_input=True, conv_out=6, obs_dim_net=32, conv_kernel=3, conv_stride=1, rnn_hidden_dim=64, n_actions=A,
-                           obs_dims=(V, V), **keys)
-    mac = SimpleNamespace(agent=th.nn.Linear(1, 1), args=args, n_agents=n, input_shape=32 + A + n + 4 + (n * A if flags & OTHERS else 0),
-                          input_flags=None if flags & OTHERS else SHIPPED, rollout_input_flags=flags, shipped_flags=not flags & OTHERS)
-    return FastPolicy(mac, 16, th.ones(A, dtype=th.uint8), share_packs_from=SimpleNamespace(p=None))
-
-
 @pytest.mark.parametrize("flags", HEAD_FLAGS)
 def test_inc_encode_truth_table_of_the_gathered_layouts(flags, monkeypatch):
     """key off: False at every edge (15 / 31 and pipeline_any_view included); key on under the class-LUT layout: True at every odd
@@ -159,7 +148,7 @@ def test_inc_encode_truth_table_of_the_gathered_layouts(flags, monkeypatch):
     monkeypatch.delenv("SSD_ENC_LAYOUT", raising=False)
     for V in ODD_EDGES:
         fp = _host_policy(V, flags)
-        assert fp.fused and fp.fused_enc and fp.prev_rec is not None and (fp.gather or fp.others)
+        assert fp.fused and fp.fused_enc and fp.needs_prev_rec and (fp.gather or fp.others)
         assert not fp.inc_encode, V
         assert not _host_policy(V, flags, pipeline_gathered=False, pipeline_any_view=True).inc_encode, V
         assert _host_policy(V, flags, pipeline_gathered=True).inc_encode, V
@@ -174,12 +163,8 @@ def test_inc_encode_truth_table_of_the_gathered_layouts(flags, monkeypatch):
 def test_the_key_leaves_the_dense_layouts_alone(monkeypatch):
     """pipeline_gathered says nothing about a controller without a gather bit: 15 / 31 pipelined, the rest by pipeline_any_view."""
     monkeypatch.delenv("SSD_ENC_LAYOUT", raising=False)
-    from homophily_marl_amd.fast_policy import FastPolicy
     for V in (7, 15, 31):
-        args = SimpleNamespace(rgb_input=True, conv_out=6, obs_dim_net=32, conv_kernel=3, conv_stride=1, rnn_hidden_dim=64, n_actions=9,
-                               obs_dims=(V, V), pipeline_gathered=True)
-        mac = SimpleNamespace(agent=th.nn.Linear(1, 1), args=args, n_agents=5, input_shape=50, input_flags=SHIPPED, shipped_flags=True)
-        assert FastPolicy(mac, 16, th.ones(9, dtype=th.uint8), share_packs_from=SimpleNamespace(p=None)).inc_encode == (V in (15, 31))
+        assert _host_policy(V, SHIPPED, pipeline_gathered=True).inc_encode == (V in (15, 31))
 
 
 # ---- GPU -------------------------------------------------------------------------------------------------------------------------

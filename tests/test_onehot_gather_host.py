@@ -20,7 +20,7 @@ import numpy as np
 import torch as th
 
 from homophily_marl_amd import abi
-from homophily_marl_amd.fast_policy import FastPolicy
+from homophily_marl_amd.fast_policy import FastPolicy, plan_rollout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["obs_last_action", "obs_agent_id", "obs_reward", "obs_inc_reward", "obs_distance", "obs_agent_pos", "obs_others_last_action"]
@@ -60,12 +60,12 @@ def test_supports_truth_table_with_and_without_the_key():
             assert off.input_shape == full
             assert off.rollout_input_flags == off.input_flags == (None if on[6] else word)
             today = off.shipped_flags or (not on[6] and full + A <= 64)
-            assert FastPolicy.supports(off) == today, (n, on)
+            assert plan_rollout(off).supported == today, (n, on)
             mac = mk(True)
             assert mac.input_shape == full and mac.input_flags == off.input_flags            # untouched by the key
             assert mac.rollout_input_flags == ((word | GATHER) if word & (1 | 2 | 64) else word), (n, on)
-            assert FastPolicy.supports(mac) is True, (n, on)
-            assert FastPolicy.supports(mac, fused=False) == mac.shipped_flags
+            assert plan_rollout(mac).supported is True, (n, on)
+            assert plan_rollout(mac, fused=False).supported == mac.shipped_flags
             needs_feature += not today
     assert needs_feature > 4 * 64                                                         # every set with bit 64, and the wide dense ones
     on = [True] * 7

@@ -19,7 +19,7 @@ import pytest
 import torch as th
 
 from homophily_marl_amd import abi
-from homophily_marl_amd.fast_policy import FastPolicy
+from homophily_marl_amd.fast_policy import plan_rollout
 
 NAMES = ["obs_last_action", "obs_agent_id", "obs_reward", "obs_inc_reward", "obs_distance", "obs_agent_pos", "obs_others_last_action"]
 BITS = [1, 2, 4, 8, 16, 32, 64]
@@ -53,13 +53,13 @@ def test_rollout_flag_word_and_support_for_every_flag_combination(name):
         assert mac.input_shape == full
         assert mac.rollout_input_flags == word and mac.input_flags_all == word
         assert mac.input_flags == (None if on[6] else word)                    # untouched by the key
-        assert FastPolicy.supports(mac) == (mac.shipped_flags or dense + A <= 64), (on, dense)
-        assert FastPolicy.supports(mac, fused=False) == mac.shipped_flags
+        assert plan_rollout(mac).supported == (mac.shipped_flags or dense + A <= 64), (on, dense)
+        assert plan_rollout(mac, fused=False).supported == mac.shipped_flags
         off = mk(False)
         assert off.input_flags == (None if on[6] else word) and off.rollout_input_flags == off.input_flags
-        assert FastPolicy.supports(off) == (off.shipped_flags or (not on[6] and full + A <= 64)), on
+        assert plan_rollout(off).supported == (off.shipped_flags or (not on[6] and full + A <= 64)), on
         assert lib.ssd_build_inputs_width(n, A, abi.INPUT_EXPLICIT | word) == full - 32
-        seen += on[6] and FastPolicy.supports(mac)
+        seen += on[6] and plan_rollout(mac).supported
     assert seen == 64                      # n = 5: every set with the block fits (dense <= 55)
 
 
