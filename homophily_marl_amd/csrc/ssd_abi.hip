@@ -594,6 +594,8 @@ int ssd_dueling_pick(const float* av, int32_t rows, int32_t n_actions, const uin
                      void* stream) {
     if (!av || !epsilon || !step || !actions || rows < 1 || n_actions < 1 || n_agents < 1 || batch < 1) return fail(SSD_ERR_INVALID, "bad argument");
     if (rows != (pairs ? n_agents * batch * n_agents : n_agents * batch)) return fail(SSD_ERR_INVALID, "rows must be n*B (or n*B*n for pairs)");
+    // the availability mask is gathered into 16 bits (avail_to_bits) and the draw's pick walks one 32-bit word
+    if (n_actions > 16) return fail(SSD_ERR_UNSUPPORTED, "ssd_dueling_pick: n_actions must be 1 .. 16");
     launch_dueling_pick(av, rows, n_actions, avail, epsilon, step, seed, n_agents, batch, pairs, actions, q_out, env_id_base, (hipStream_t)stream);
     return launched();
 }

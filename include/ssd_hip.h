@@ -378,7 +378,8 @@ int ssd_td_sim_loss(const ssd_td_loss_args* args, int32_t mode, void* stream);
  *   mask avail u8[n_actions] (NULL = all).  epsilon f32 and step i64 are device scalars; rows are agent-major (i, b) or, with
  *   pairs = 1, (i, b, j) with the diagonal i == j forced to 0 (homophily_controller.py:44-46); actions are written env-major
  *   [batch, n] / [batch, n, n].  q_out (nullable) receives q [rows, n_actions].  The exploration draw of a row is keyed by
- *   (seed, *step, (env_id_base + b) * n + i [, * n + j]): the GLOBAL env id, so env shards draw what the unsharded job draws. */
+ *   (seed, *step, (env_id_base + b) * n + i [, * n + j]): the GLOBAL env id, so env shards draw what the unsharded job draws.
+ *   n_actions 1 .. 16 (the mask is gathered into 16 bits; SSD_ERR_UNSUPPORTED above that, like K of ssd_dueling_q_*). */
 int ssd_encoder(const float* obs, int32_t rows, int32_t view_edge, int32_t conv_out, int32_t feat_out, const float* conv_w,
                 const float* conv_b, const float* lin_w, const float* lin_b, float* out, int32_t out_stride, int32_t n_agents,
                 int32_t agent_major, float* store_obs, int64_t store_env_stride, const int64_t* store_t, void* stream);
@@ -552,7 +553,23 @@ int ssd_conv_wgrad_codes(const uint8_t* codes, const float* d_conv, float* parti
  * Activations are agent-major: inputs f32 [n, n_env, 64] (columns 0..31 = encoder output; the env head fills 32..63: tail then
  * zeros), h f32 [n, n_env, 64] updated in place. q_out (nullable): env f32 [n, n_env, n_actions]; inc f32 [n, n_env, n, 3].
  * Exploration draws: the package's counter generator keyed by (seed, *step, GLOBAL env id = env_id_base + env, agent[, j]) --
- * a shard of a larger job draws what the unsharded job draws for the same envs (ssd_dueling_pick uses the same key). */
+ * a shard of a larger job draws what the unsharded job draws for the same envs (ssd_dueling_pick uses the same key).
+ * The generator (csrc/ssd_policy_common.h: dueling_pick_bits; restated on the host by tests/explore_util.py, which every pick site
+ * equals bit for bit -- tests/test_exploration_draws.py), all arithmetic in uint32 unless said otherwise:
+ *   mix32p(x): x ^= x>>17; x *= 0xed5ad4bb; x ^= x>>11; x *= 0xac4c1b51; x ^= x>>15; x *= 0x31848bab; x ^= x>>14
+ *   x0 = mix32p(seed ^ mix32p(u32(step) * 0x9E3779B9 + key));   x1 = mix32p(x0 ^ 0x85EBCA6B)
+ *   explore  <=>  f32(x0 >> 8) * 2^-24 < eps           (f32 compare; eps is the f32 device scalar: never for eps <= 0 or NaN,
+ *                                                       always for eps >= 1)
+ *   pick = (u64(x1) * popcount(live)) >> 32  ->  the pick-th lowest AVAILABLE action;  no action available: the greedy result
+ *   key  = (env_id_base + b) * n + i                    env head
+ *   key  = ((env_id_base + b) * n + i) * n + j          inc head (diagonal forced to 0 afterwards, draw or not)
+ *   seed = ssd_policy_head.seed (FastPolicy: its seed for the env head, seed ^ 0x5bd1e995 for the inc head);  step = *step mod 2^32
+ *   greedy = first maximum of v + a_k - mean(a) over the available k (action 0 when none is available)
+ * The rollout advances *step once per timestep slot, the closing slot T included, and never resets it: the four-launch timestep's
+ * encoder before the heads read it (ssd_policy_encode_args.counter_inc), the pipelined timestep's inc head after they did
+ * (next_step_out) from a counter that starts at RunnerPlan.counter_start -- one ahead wherever a four-launch sequence exists to
+ * be matched (every window edge but 15 / 31, and the gathered layouts), so that slot t of episode e draws at step
+ * 1 + e (T + 1) + t in both; the pipelined dense timestep at 15 / 31 starts at 0 and draws at e (T + 1) + t. */
 #define SSD_POLICY_HEAD_FRAGS 58
 #define SSD_POLICY_HEAD_TAIL_FLOATS (464 + 64)
 #define SSD_POLICY_TAIL_PIECES 3
