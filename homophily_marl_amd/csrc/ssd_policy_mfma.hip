@@ -1424,6 +1424,41 @@ struct EncK {
     PSTAMP_DECL
 };
 
+// The epilogue of every encoder body: add the waves' partial sums of the Linear in a fixed order (deterministic) and finish -- the
+// band's partial sums to `part`, or LeakyReLU(sum + bias) to `out`.  The scratch aliases the staging LDS (planes / packed rows,
+// fragments / table), which the leading barrier frees: every wave is done with it.
+template <int BT>
+__device__ __forceinline__ void enc_reduce_finish(const EncK& a, uint8_t* lds_raw, const f32x4 (&accl)[BT][2], int row0, int band, float INV, int tid, int lane,
+                                                  int wave) {
+    __syncthreads();
+    f32x4* red = reinterpret_cast<f32x4*>(lds_raw);                    // [wave][bt][mt][lane]
+#pragma unroll
+    for (int bt = 0; bt < BT; ++bt)
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) red[((wave * BT + bt) * 2 + mt) * 64 + lane] = accl[bt][mt];
+    __syncthreads();
+    for (int it = tid; it < BT * 2 * 64; it += ENC_WAVES * 64) {
+        const int l = it & 63, mt = (it >> 6) & 1, bt = it >> 7;
+        f32x4 sum = red[((0 * BT + bt) * 2 + mt) * 64 + l];
+#pragma unroll
+        for (int w = 1; w < ENC_WAVES; ++w) sum += red[((w * BT + bt) * 2 + mt) * 64 + l];
+        const int row = row0 + bt * 16 + (l & 15), f0 = 16 * mt + 4 * (l >> 4);
+        if (row < a.rows) {
+            const int b = row / a.n, i = row - b * a.n;
+            const size_t orow = a.agent_major ? (size_t)i * (a.rows / a.n) + b : (size_t)row;
+            if (a.part) {
+                f32x4 o;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) o[r] = sum[r] * INV;
+                *reinterpret_cast<f32x4*>(a.part + ((size_t)band * a.rows + orow) * 32 + f0) = o;
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) a.out[orow * a.out_stride + f0 + r] = leaky(fmaf(sum[r], INV, a.lin_b[f0 + r]));
+            }
+        }
+    }
+}
+
 template <int V, int PREC, bool ACT, int BT>
 __device__ __forceinline__ void encode_body(const EncK& a, uint8_t* lds_raw, const int block_x, const int block_y) {
     using G = Geo<V>;
@@ -1628,7 +1663,7 @@ __device__ __forceinline__ void encode_body(const EncK& a, uint8_t* lds_raw, con
             u32x4 xh, xl;
             if constexpr (ACT || PREC != 2) split8<PREC>(v, xh, xl);
             else leaky_split8(accc[0][bt], accc[1][bt], xh, xl);
-            if (PREC == 2) {
+            if (PREC == 2) {                                           // (the three products, written out in each body: see above k_inc_encode_any)
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt) accl[bt][mt] = mma<PREC>(la[mt][PREC - 1], xh, accl[bt][mt]);
 #pragma unroll
@@ -1640,33 +1675,7 @@ __device__ __forceinline__ void encode_body(const EncK& a, uint8_t* lds_raw, con
     }
     PSTAMP(2);
     // ---- add the waves' partial sums in a fixed order (deterministic), finish ------------------------------------------------------
-    __syncthreads();                                                   // every wave is done with the planes: reuse them
-    f32x4* red = reinterpret_cast<f32x4*>(lds_raw);                    // [wave][bt][mt][lane]
-#pragma unroll
-    for (int bt = 0; bt < BT; ++bt)
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) red[((wave * BT + bt) * 2 + mt) * 64 + lane] = accl[bt][mt];
-    __syncthreads();
-    for (int it = tid; it < BT * 2 * 64; it += ENC_WAVES * 64) {
-        const int l = it & 63, mt = (it >> 6) & 1, bt = it >> 7;
-        f32x4 sum = red[((0 * BT + bt) * 2 + mt) * 64 + l];
-#pragma unroll
-        for (int w = 1; w < ENC_WAVES; ++w) sum += red[((w * BT + bt) * 2 + mt) * 64 + l];
-        const int row = row0 + bt * 16 + (l & 15), f0 = 16 * mt + 4 * (l >> 4);
-        if (row < a.rows) {
-            const int b = row / a.n, i = row - b * a.n;
-            const size_t orow = a.agent_major ? (size_t)i * (a.rows / a.n) + b : (size_t)row;
-            if (a.part) {
-                f32x4 o;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[r] = sum[r] * INV;
-                *reinterpret_cast<f32x4*>(a.part + ((size_t)band * a.rows + orow) * 32 + f0) = o;
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) a.out[orow * a.out_stride + f0 + r] = leaky(fmaf(sum[r], INV, a.lin_b[f0 + r]));
-            }
-        }
-    }
+    enc_reduce_finish<BT>(a, lds_raw, accl, row0, band, INV, tid, lane, wave);
     PSTAMP(3);
     PSTAMP_REAL(15);
 }
@@ -1796,7 +1805,7 @@ __device__ __forceinline__ void encode_body_lut(const EncK& a, uint8_t* lds_raw,
             for (int h = 0; h < NQ; ++h) {
                 u32x4 c = cw[k][h];
                 if (h == NQ - 1) c[3] &= 0x00FFFFFFu;                  // byte 16 NQ - 1 is cell V (the next row's first cell)
-                uint32_t word = 0u;
+                uint32_t word = 0u;                                    // (this loop is written out in encode_body_lut_any too: see above k_inc_encode_any)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     uint32_t cls = c[e] & 0x03030303u;                 // SSD_OBS_CODE classes 0..3
@@ -1880,7 +1889,7 @@ __device__ __forceinline__ void encode_body_lut(const EncK& a, uint8_t* lds_raw,
                 v[6] = 0.f; v[7] = 0.f;
                 split8<PREC>(v, xh, xl);
             }
-            if (PREC == 2) {
+            if (PREC == 2) {                                           // (the three products, written out in each body: see above k_inc_encode_any)
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt) accl[bt][mt] = mma<PREC>(la[mt][PREC - 1], xh, accl[bt][mt]);
 #pragma unroll
@@ -1892,33 +1901,7 @@ __device__ __forceinline__ void encode_body_lut(const EncK& a, uint8_t* lds_raw,
     }
     PSTAMP(2);
     // ---- add the waves' partial sums in a fixed order (deterministic), finish ------------------------------------------------------
-    __syncthreads();                                                   // every wave is done with the packed rows and the table: reuse them
-    f32x4* red = reinterpret_cast<f32x4*>(lds_raw);                    // [wave][bt][mt][lane]
-#pragma unroll
-    for (int bt = 0; bt < BT; ++bt)
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) red[((wave * BT + bt) * 2 + mt) * 64 + lane] = accl[bt][mt];
-    __syncthreads();
-    for (int it = tid; it < BT * 2 * 64; it += ENC_WAVES * 64) {
-        const int l = it & 63, mt = (it >> 6) & 1, bt = it >> 7;
-        f32x4 sum = red[((0 * BT + bt) * 2 + mt) * 64 + l];
-#pragma unroll
-        for (int w = 1; w < ENC_WAVES; ++w) sum += red[((w * BT + bt) * 2 + mt) * 64 + l];
-        const int row = row0 + bt * 16 + (l & 15), f0 = 16 * mt + 4 * (l >> 4);
-        if (row < a.rows) {
-            const int b = row / a.n, i = row - b * a.n;
-            const size_t orow = a.agent_major ? (size_t)i * (a.rows / a.n) + b : (size_t)row;
-            if (a.part) {
-                f32x4 o;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[r] = sum[r] * INV;
-                *reinterpret_cast<f32x4*>(a.part + ((size_t)band * a.rows + orow) * 32 + f0) = o;
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) a.out[orow * a.out_stride + f0 + r] = leaky(fmaf(sum[r], INV, a.lin_b[f0 + r]));
-            }
-        }
-    }
+    enc_reduce_finish<BT>(a, lds_raw, accl, row0, band, INV, tid, lane, wave);
     PSTAMP(3);
     PSTAMP_REAL(15);
 }
@@ -2005,6 +1988,7 @@ __device__ __forceinline__ void encode_body_lut_any(const EncK& a, const int V, 
                     }
                 }
                 // (bytes past the row's V cells belong to the next row: no position reads them)
+                // (the loop of encode_body_lut, written out again: see above k_inc_encode_any)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     uint32_t cls = c[e] & 0x03030303u;
@@ -2080,7 +2064,7 @@ __device__ __forceinline__ void encode_body_lut_any(const EncK& a, const int V, 
             }
             u32x4 xh, xl;
             split8<PREC>(v, xh, xl);
-            if (PREC == 2) {
+            if (PREC == 2) {                                           // (the three products, written out in each body: see above k_inc_encode_any)
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt) accl[bt][mt] = mma<PREC>(la[mt][PREC - 1], xh, accl[bt][mt]);
 #pragma unroll
@@ -2091,49 +2075,12 @@ __device__ __forceinline__ void encode_body_lut_any(const EncK& a, const int V, 
         }
     }
     // ---- add the waves' partial sums in a fixed order (deterministic), finish ----------------------------------------------------------
-    __syncthreads();
-    f32x4* red = reinterpret_cast<f32x4*>(lds_raw);                    // [wave][bt][mt][lane]
-#pragma unroll
-    for (int bt = 0; bt < BT; ++bt)
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) red[((wave * BT + bt) * 2 + mt) * 64 + lane] = accl[bt][mt];
-    __syncthreads();
-    for (int it = tid; it < BT * 2 * 64; it += ENC_WAVES * 64) {
-        const int l = it & 63, mt = (it >> 6) & 1, bt = it >> 7;
-        f32x4 sum = red[((0 * BT + bt) * 2 + mt) * 64 + l];
-#pragma unroll
-        for (int w = 1; w < ENC_WAVES; ++w) sum += red[((w * BT + bt) * 2 + mt) * 64 + l];
-        const int row = row0 + bt * 16 + (l & 15), f0 = 16 * mt + 4 * (l >> 4);
-        if (row < a.rows) {
-            const int b = row / a.n, i = row - b * a.n;
-            const size_t orow = a.agent_major ? (size_t)i * (a.rows / a.n) + b : (size_t)row;
-            if (a.part) {
-                f32x4 o;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[r] = sum[r] * INV;
-                *reinterpret_cast<f32x4*>(a.part + ((size_t)band * a.rows + orow) * 32 + f0) = o;
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) a.out[orow * a.out_stride + f0 + r] = leaky(fmaf(sum[r], INV, a.lin_b[f0 + r]));
-            }
-        }
-    }
+    enc_reduce_finish<BT>(a, lds_raw, accl, row0, band, INV, tid, lane, wave);
 }
 template <int PREC>
 __global__ __launch_bounds__(ENC_WAVES * 64) void k_encode_lut_any(EncK a, int V) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     encode_body_lut_any<PREC>(a, V, lds_raw, (int)blockIdx.x, (int)blockIdx.y);
-}
-
-template <int PREC>
-static int launch_encode_lut_any(const EncK& k, int V, hipStream_t s) {
-    constexpr size_t lds_max = enc_lut_any_lds_bytes(SSD_ENCODE_EDGE_MAX);
-    static_assert(lds_max >= enc_lut_any_lds_bytes(15) && lds_max <= 160 * 1024, "LDS of the run-time-edge encoder");
-    static bool done[64] = {};
-    if (raise_lds_limit(reinterpret_cast<const void*>(&k_encode_lut_any<PREC>), lds_max, done)) return -1;
-    const int groups = (k.rows + ENC_ANY_BT * 16 - 1) / (ENC_ANY_BT * 16);
-    hipLaunchKernelGGL(k_encode_lut_any<PREC>, dim3(groups, SSD_ENCODE_BANDS(V)), dim3(ENC_WAVES * 64), enc_lut_any_lds_bytes(V), s, k, V);
-    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -2174,6 +2121,9 @@ __global__ __launch_bounds__(FUSED_WAVES * 64) void k_inc_encode(int heads, int 
 // where k_inc_encode has it, so the heads' cold-argument offsets and refetch_head_args hold).  8 instantiations for all 29 edges.
 // (The two kernels are written out twice: sharing their text through a __forceinline__ function -- with the encoder half as a
 // template argument or as a lambda, arguments by reference or by value -- reorders instructions in all 56 instantiations.)
+// (The same holds inside the encoder bodies.  Their epilogue is shared -- enc_reduce_finish leaves every instruction stream as it was
+// but one commuted operand pair in the BT = 4 kernels -- while a helper for the class-code packing loop or for the Linear's three
+// products re-scheduled 62 kernels by up to hundreds of instructions, unmeasured: those copies stay, until a change that is timed.)
 template <int PREC, int AT, bool LOOP>
 __global__ __launch_bounds__(FUSED_WAVES * 64) void k_inc_encode_any(int heads, int enc_groups, int p_N, int p_n, int p_bpa, int p_pad, float* p_h, float* p_inputs,
                                                                      const uint8_t* p_codes, const int64_t* p_slot_t, HeadK a, HeadCold cold_unused, EncK e, int V) {
@@ -2225,17 +2175,23 @@ __global__ __launch_bounds__(FUSED_WAVES * 64) void k_inc_encode_gather(int head
     }
 }
 
-// (the `done` flags of the launchers below are statics of a generic lambda's body: one set per BT, that is per kernel)
+// One encoder launch: (groups of bt * 16 rows) x bands workgroups.  V: the run-time edge, the second argument of k_encode_lut_any
+// (nullptr: the kernels of a compiled edge).  `done` belongs to the kernel `fn`: the wrappers below keep one set per kernel (for those
+// that walk enc_bt, a static of a generic lambda's body: one set per BT).
+static int launch_encode_kernel(const void* fn, const EncK& k, int* V, int bands, int bt, size_t lds, size_t lds_limit, bool (&done)[64], hipStream_t s) {
+    if (raise_lds_limit(fn, lds_limit, done)) return -1;
+    const int groups = (k.rows + bt * 16 - 1) / (bt * 16);
+    void* args[2] = {const_cast<EncK*>(&k), V};
+    (void)hipLaunchKernel(fn, dim3(groups, bands), dim3(ENC_WAVES * 64), args, lds, s);
+    return 0;
+}
 template <int V, int PREC, bool ACT>
 static int launch_encode(const EncK& k, hipStream_t s) {
     return enc_bt<V>(k.rows, [&](auto bt) {
         constexpr int BT = decltype(bt)::value;
         constexpr size_t lds = enc_lds_bytes<V, PREC, BT>();
         static bool done[64] = {};
-        if (raise_lds_limit(reinterpret_cast<const void*>(&k_encode<V, PREC, ACT, BT>), lds, done)) return -1;
-        const int groups = (k.rows + BT * 16 - 1) / (BT * 16);
-        hipLaunchKernelGGL((k_encode<V, PREC, ACT, BT>), dim3(groups, Geo<V>::NB), dim3(ENC_WAVES * 64), lds, s, k);
-        return 0;
+        return launch_encode_kernel(reinterpret_cast<const void*>(&k_encode<V, PREC, ACT, BT>), k, nullptr, Geo<V>::NB, BT, lds, lds, done, s);
     });
 }
 template <int V, int PREC>
@@ -2244,11 +2200,16 @@ static int launch_encode_lut(const EncK& k, hipStream_t s) {
         constexpr int BT = decltype(bt)::value;
         constexpr size_t lds = enc_lut_lds_bytes<V, PREC, BT>();
         static bool done[64] = {};
-        if (raise_lds_limit(reinterpret_cast<const void*>(&k_encode_lut<V, PREC, BT>), lds, done)) return -1;
-        const int groups = (k.rows + BT * 16 - 1) / (BT * 16);
-        hipLaunchKernelGGL((k_encode_lut<V, PREC, BT>), dim3(groups, Geo<V>::NB), dim3(ENC_WAVES * 64), lds, s, k);
-        return 0;
+        return launch_encode_kernel(reinterpret_cast<const void*>(&k_encode_lut<V, PREC, BT>), k, nullptr, Geo<V>::NB, BT, lds, lds, done, s);
     });
+}
+template <int PREC>
+static int launch_encode_lut_any(const EncK& k, int V, hipStream_t s) {
+    constexpr size_t lds_max = enc_lut_any_lds_bytes(SSD_ENCODE_EDGE_MAX);
+    static_assert(lds_max >= enc_lut_any_lds_bytes(15) && lds_max <= 160 * 1024, "LDS of the run-time-edge encoder");
+    static bool done[64] = {};
+    return launch_encode_kernel(reinterpret_cast<const void*>(&k_encode_lut_any<PREC>), k, &V, SSD_ENCODE_BANDS(V), ENC_ANY_BT, enc_lut_any_lds_bytes(V), lds_max,
+                                done, s);
 }
 
 static void encode_args(const ssd_policy_encode_args* p, EncK& k) {
@@ -2261,60 +2222,51 @@ static void encode_args(const ssd_policy_encode_args* p, EncK& k) {
     PSTAMP_SET(k);
 }
 
+// One fused launch: n * bpa head workgroups, then (groups of bt * 16 rows) x bands encoder workgroups.  V: the run-time edge, the
+// last argument of k_inc_encode_any / k_inc_encode_gather (nullptr: k_inc_encode, which has 13).  `done` belongs to the kernel `fn`.
+static int launch_fused_kernel(const void* fn, HeadK& k, HeadCold& c, EncK& e, int* V, int bands, int bt, size_t lds, size_t lds_limit, bool (&done)[64],
+                               hipStream_t s) {
+    if (raise_lds_limit(fn, lds_limit, done)) return -1;
+    int heads = k.n * k.bpa, groups = (e.rows + bt * 16 - 1) / (bt * 16);
+    int pad = 0;
+    void* args[14] = {&heads, &groups, &k.N, &k.n, &k.bpa, &pad, &k.h, &k.inputs, &e.codes, &e.slot_t, &k, &c, &e, V};
+    if (hipLaunchKernel(fn, dim3(heads + groups * bands), dim3(FUSED_WAVES * 64), args, lds, s) != hipSuccess) return -1;
+    return 0;
+}
+// LDS of a fused launch: the larger of the head half (the image + 7 waves' scratch) and the encoder half
+constexpr size_t fused_lds_bytes(int prec, size_t enc) {
+    const size_t head = (size_t)head_lds_bytes(FUSED_WAVES - 1, prec);
+    return head > enc ? head : enc;
+}
+constexpr size_t inc_encode_any_lds_max(int prec) {
+    size_t m = 0;
+    for (int V = SSD_ENCODE_EDGE_MIN; V <= SSD_ENCODE_EDGE_MAX; V += 2) m = enc_lut_any_lds_bytes(V) > m ? enc_lut_any_lds_bytes(V) : m;
+    return fused_lds_bytes(prec, m);
+}
+static_assert(inc_encode_any_lds_max(1) <= 160 * 1024 && inc_encode_any_lds_max(2) <= 160 * 1024, "LDS of the run-time-edge fused launches");
+
 template <int PREC, int AT, int V, bool LOOP>
 static int launch_inc_encode(HeadK& k, HeadCold& c, EncK& e, hipStream_t s) {
     return pick<0, 1>(e.layout == SSD_ENCODE_LAYOUT_LUT, -2, [&](auto lut) { return enc_bt<V>(e.rows, [&](auto bt) {
         constexpr int BT = decltype(bt)::value;
         constexpr bool LUT = decltype(lut)::value != 0;
-        const size_t lh = (size_t)head_lds_bytes(FUSED_WAVES - 1, PREC), le = LUT ? enc_lut_lds_bytes<V, PREC, BT>() : enc_lds_bytes<V, PREC, BT>();
-        const size_t lds = lh > le ? lh : le;
+        constexpr size_t lds = fused_lds_bytes(PREC, LUT ? enc_lut_lds_bytes<V, PREC, BT>() : enc_lds_bytes<V, PREC, BT>());
         static bool done[64] = {};
-        const void* fn = reinterpret_cast<const void*>(&k_inc_encode<PREC, AT, V, LOOP, BT, LUT>);
-        if (raise_lds_limit(fn, lds, done)) return -1;
-        int heads = k.n * k.bpa, groups = (e.rows + BT * 16 - 1) / (BT * 16);
-        int pad = 0;
-        void* args[13] = {&heads, &groups, &k.N, &k.n, &k.bpa, &pad, &k.h, &k.inputs, &e.codes, &e.slot_t, &k, &c, &e};
-        if (hipLaunchKernel(fn, dim3(heads + groups * Geo<V>::NB), dim3(FUSED_WAVES * 64), args, lds, s) != hipSuccess) return -1;
-        return 0;
+        return launch_fused_kernel(reinterpret_cast<const void*>(&k_inc_encode<PREC, AT, V, LOOP, BT, LUT>), k, c, e, nullptr, Geo<V>::NB, BT, lds, lds, done, s);
     }); });
-}
-
-constexpr size_t inc_encode_any_lds_max(int prec) {
-    size_t m = (size_t)head_lds_bytes(FUSED_WAVES - 1, prec);
-    for (int V = SSD_ENCODE_EDGE_MIN; V <= SSD_ENCODE_EDGE_MAX; V += 2) m = enc_lut_any_lds_bytes(V) > m ? enc_lut_any_lds_bytes(V) : m;
-    return m;
 }
 template <int PREC, int AT, bool LOOP>
 static int launch_inc_encode_any(HeadK& k, HeadCold& c, EncK& e, int V, hipStream_t s) {
-    constexpr size_t lds_max = inc_encode_any_lds_max(PREC);
-    static_assert(lds_max <= 160 * 1024, "LDS of the run-time-edge fused launch");
-    const size_t lh = (size_t)head_lds_bytes(FUSED_WAVES - 1, PREC), le = enc_lut_any_lds_bytes(V);
-    const size_t lds = lh > le ? lh : le;
     static bool done[64] = {};
-    const void* fn = reinterpret_cast<const void*>(&k_inc_encode_any<PREC, AT, LOOP>);
-    if (raise_lds_limit(fn, lds_max, done)) return -1;
-    int heads = k.n * k.bpa, groups = (e.rows + ENC_ANY_BT * 16 - 1) / (ENC_ANY_BT * 16);
-    int pad = 0;
-    void* args[14] = {&heads, &groups, &k.N, &k.n, &k.bpa, &pad, &k.h, &k.inputs, &e.codes, &e.slot_t, &k, &c, &e, &V};
-    if (hipLaunchKernel(fn, dim3(heads + groups * SSD_ENCODE_BANDS(V)), dim3(FUSED_WAVES * 64), args, lds, s) != hipSuccess) return -1;
-    return 0;
+    return launch_fused_kernel(reinterpret_cast<const void*>(&k_inc_encode_any<PREC, AT, LOOP>), k, c, e, &V, SSD_ENCODE_BANDS(V), ENC_ANY_BT,
+                               fused_lds_bytes(PREC, enc_lut_any_lds_bytes(V)), inc_encode_any_lds_max(PREC), done, s);
 }
-// the gathered heads' launch: LDS = the larger of the GEN >= 2 head half (the image + 7 waves' scratch, as the standalone gather heads) and
-// the encoder half at this edge
+// the gathered heads' launch (the GEN >= 2 head half: the image + 7 waves' scratch as well, as the standalone gather heads)
 template <int PREC, int AT, int GEN>
 static int launch_inc_encode_gather(HeadK& k, HeadCold& c, EncK& e, int V, hipStream_t s) {
-    constexpr size_t lds_max = inc_encode_any_lds_max(PREC);
-    static_assert(lds_max <= 160 * 1024, "LDS of the gathered fused launch");
-    const size_t lh = (size_t)head_lds_bytes(FUSED_WAVES - 1, PREC), le = enc_lut_any_lds_bytes(V);
-    const size_t lds = lh > le ? lh : le;
     static bool done[64] = {};
-    const void* fn = reinterpret_cast<const void*>(&k_inc_encode_gather<PREC, AT, GEN, true>);
-    if (raise_lds_limit(fn, lds_max, done)) return -1;
-    int heads = k.n * k.bpa, groups = (e.rows + ENC_ANY_BT * 16 - 1) / (ENC_ANY_BT * 16);
-    int pad = 0;
-    void* args[14] = {&heads, &groups, &k.N, &k.n, &k.bpa, &pad, &k.h, &k.inputs, &e.codes, &e.slot_t, &k, &c, &e, &V};
-    if (hipLaunchKernel(fn, dim3(heads + groups * SSD_ENCODE_BANDS(V)), dim3(FUSED_WAVES * 64), args, lds, s) != hipSuccess) return -1;
-    return 0;
+    return launch_fused_kernel(reinterpret_cast<const void*>(&k_inc_encode_gather<PREC, AT, GEN, true>), k, c, e, &V, SSD_ENCODE_BANDS(V), ENC_ANY_BT,
+                               fused_lds_bytes(PREC, enc_lut_any_lds_bytes(V)), inc_encode_any_lds_max(PREC), done, s);
 }
 
 // How a head launch of (n_env, n_agents) is cut: workgroups per agent, compute waves per workgroup, and the number of 16-row tiles the
@@ -2326,22 +2278,33 @@ void policy_head_plan(int n_env, int n_agents, int mode, int* wg_per_agent, int*
     *tiles_per_wave = ((n_env + 15) / 16 + pl.bpa * pl.waves - 1) / (pl.bpa * pl.waves);
 }
 
+// What the two fused launches share: the arguments of both halves, the cut of the inc head, and the refusals in their order.
+// -3: no instance for this action count; then -2: none for this window edge / layout -- any odd edge 3 .. 63 under the class-LUT
+// images, and with `shipped_any_layout` 15 and 31 under either layout (launch_inc_encode picks the body).
+static int inc_encode_args(const ssd_policy_head* ph, const ssd_policy_encode_args* pe, bool shipped_any_layout, HeadK& k, HeadCold& c, EncK& e, HeadPlan& pl) {
+    head_args(ph, k, c);
+    pl = plan_head(k.N, k.n, FUSED_WAVES - 1, FUSED_WAVES - 1);
+    k.bpa = pl.bpa;
+    encode_args(pe, e);
+    const int V = pe->view_edge;
+    if (k.A != 9 && k.A != 8) return -3;
+    if (shipped_any_layout && (V == 15 || V == 31)) return 0;
+    if (V < SSD_ENCODE_EDGE_MIN || V > SSD_ENCODE_EDGE_MAX || !(V & 1) || e.layout != SSD_ENCODE_LAYOUT_LUT) return -2;
+    return 0;
+}
+
 // inc head (timestep t) + encoder (timestep t + 1) as one launch; -2: no instance for this window size / layout, -3: for this action count
 int launch_policy_inc_encode(const ssd_policy_head* ph, const ssd_policy_encode_args* pe, hipStream_t s) {
     HeadK k;
     HeadCold c;
     EncK e;
-    head_args(ph, k, c);
-    const HeadPlan pl = plan_head(k.N, k.n, FUSED_WAVES - 1, FUSED_WAVES - 1);
-    k.bpa = pl.bpa;
-    encode_args(pe, e);
+    HeadPlan pl;
+    if (const int rc = inc_encode_args(ph, pe, true, k, c, e, pl)) return rc;
     const int prec = ph->precision == 1 ? 1 : 2, V = pe->view_edge;
-    if (k.A != 9 && k.A != 8) return -3;
-    // every odd edge 3 .. 63 but 15 and 31: the run-time-geometry encoder half, class-LUT images only
-    if (V != 15 && V != 31 && (V < SSD_ENCODE_EDGE_MIN || V > SSD_ENCODE_EDGE_MAX || !(V & 1) || e.layout != SSD_ENCODE_LAYOUT_LUT)) return -2;
     return pick<2, 1>(prec, -2, [&](auto pr) { return pick<9, 8>(k.A, -2, [&](auto at) { return pick<0, 1>(pl.looped, -2, [&](auto l) {
         constexpr int PREC = decltype(pr)::value, AT = decltype(at)::value;
         constexpr bool LOOP = decltype(l)::value != 0;
+        // every odd edge 3 .. 63 but 15 and 31: the run-time-geometry encoder half
         if (V != 15 && V != 31) return launch_inc_encode_any<PREC, AT, LOOP>(k, c, e, V, s);
         return pick<15, 31>(V, -2, [&](auto v) { return launch_inc_encode<PREC, AT, decltype(v)::value, LOOP>(k, c, e, s); });
     }); }); });
@@ -2352,16 +2315,13 @@ int launch_policy_inc_encode_gather(const ssd_policy_head* ph, const ssd_policy_
     HeadK k;
     HeadCold c;
     EncK e;
+    HeadPlan pl;                                                               // (only its bpa: the kernel is the looped one at any grid)
     const bool onehot = head_gathers_onehot(ph);
     if (!onehot && !head_gathers(ph)) return -2;
-    head_args(ph, k, c);
-    k.bpa = plan_head(k.N, k.n, FUSED_WAVES - 1, FUSED_WAVES - 1).bpa;        // (the kernel is the looped one at any grid)
+    if (const int rc = inc_encode_args(ph, pe, false, k, c, e, pl)) return rc;
     const void* g2[2] = {onehot ? ph->onehot_rows : ph->others_rows, ph->prev_record};      // (see gather_slots)
     __builtin_memcpy(reinterpret_cast<uint8_t*>(&c) + gather_slots<1>(), g2, 16);
-    encode_args(pe, e);
     const int prec = ph->precision == 1 ? 1 : 2, V = pe->view_edge;
-    if (k.A != 9 && k.A != 8) return -3;
-    if (V < SSD_ENCODE_EDGE_MIN || V > SSD_ENCODE_EDGE_MAX || !(V & 1) || e.layout != SSD_ENCODE_LAYOUT_LUT) return -2;
     return pick<2, 1>(prec, -2, [&](auto pr) { return pick<9, 8>(k.A, -2, [&](auto at) { return pick<2, 3>(onehot ? 3 : 2, -2, [&](auto g) {
         return launch_inc_encode_gather<decltype(pr)::value, decltype(at)::value, decltype(g)::value>(k, c, e, V, s);
     }); }); });
@@ -2386,6 +2346,32 @@ int launch_policy_encode(const ssd_policy_encode_args* p, hipStream_t s) {
 }
 
 // ---- pack: conv_w f32 [6, 3, 3, 3], lin_w f32 [32, 6 P] -> fragment images ------------------------------------------------------
+// The conv ACTIVATIONS are split at the scale CS inside the encoder's loop, where a range check per value would cost ~4 % of
+// the kernel: they are bounded by the pack kernels instead (precision 2, one thread per output channel e < 6).  A window cell lights
+// at most one plane, so for output channel e
+// |conv| <= |b| + 255/256 * sum over the 9 taps of max_ch |w[e, ch, dy, dx]| -- the exact worst case over all observations.
+__device__ __forceinline__ void check_conv_range(const float* __restrict__ cw, const float* __restrict__ cb, int e, float CS, int32_t* err) {
+    float bound = fabsf(cb[e]);
+    for (int tap = 0; tap < 9; ++tap) {
+        float mx = 0.f;
+        for (int ch = 0; ch < 3; ++ch) mx = fmaxf(mx, fabsf(cw[(e * 3 + ch) * 9 + tap]));
+        bound += mx * (255.f / 256.f);
+    }
+    if (!(bound * CS <= F16_MAX)) atomicOr(err, ERR_F16_RANGE);
+}
+// Entry e of the class-LUT table f32 [3][64][6], at the conv activations' split scale CS:
+// T[dy][idx][c] = (dy == 0 ? b[c] : 0) + 255/256 * sum over dx of w[c][plane(class of cell dx)][dy][dx]; classes (SSD_OBS_CODE):
+// 2 = waste -> R (plane 0), 1 = apple -> G (plane 1), 3 = wall / agent -> B (plane 2), 0 = nothing
+__device__ __forceinline__ float lut_table_entry(const float* __restrict__ cw, const float* __restrict__ cb, int e, float CS) {
+    const int dy = e / LUT_DY_F, idx = (e / LUT_ENTRY_F) % 64, c = e % LUT_ENTRY_F;
+    double v = dy == 0 ? (double)cb[c] : 0.0;
+    for (int dx = 0; dx < 3; ++dx) {
+        const int cls = (idx >> (2 * dx)) & 3;
+        const int plane = cls == 2 ? 0 : (cls == 1 ? 1 : (cls == 3 ? 2 : -1));
+        if (plane >= 0) v += (double)cw[((c * 3 + plane) * 3 + dy) * 3 + dx] * (255.0 / 256.0);
+    }
+    return (float)(v * (double)CS);
+}
 template <int V, int PREC>
 __global__ __launch_bounds__(256) void k_pack_encoder(const float* __restrict__ cw, const float* __restrict__ cb, const float* __restrict__ lw, uint8_t* conv_frags,
                                                       uint8_t* lin_frags, int32_t* err) {
@@ -2394,18 +2380,7 @@ __global__ __launch_bounds__(256) void k_pack_encoder(const float* __restrict__ 
     constexpr int NCONV = 9 * 512, NLIN = UNITS * 2 * 512;
     constexpr float CS = PREC == 2 ? ENC_CSCALE : 2.f, LS = PREC == 2 ? ENC_LSCALE : 1.f;   // PREC 1: the plane value is 0.5
     const int e = blockIdx.x * 256 + threadIdx.x;
-    if (PREC == 2 && e < 6 && err) {
-        // The conv ACTIVATIONS are split at the scale CS inside the encoder's loop, where a range check per value would cost ~4 % of
-        // the kernel: they are bounded here instead.  A window cell lights at most one plane, so for output channel e
-        // |conv| <= |b| + 255/256 * sum over the 9 taps of max_ch |w[e, ch, dy, dx]| -- the exact worst case over all observations.
-        float bound = fabsf(cb[e]);
-        for (int tap = 0; tap < 9; ++tap) {
-            float mx = 0.f;
-            for (int ch = 0; ch < 3; ++ch) mx = fmaxf(mx, fabsf(cw[(e * 3 + ch) * 9 + tap]));
-            bound += mx * (255.f / 256.f);
-        }
-        if (!(bound * CS <= F16_MAX)) atomicOr(err, ERR_F16_RANGE);
-    }
+    if (PREC == 2 && e < 6 && err) check_conv_range(cw, cb, e, CS, err);
     if (e < NCONV) {
         // fragment (s, dy): row m = (o2 = m >> 3, position p = m & 7); quarter q < 3: plane q, cells 0..7; quarter 3: the tail
         // [R 8, R 9, G 8, G 9, B 8, B 9, 0, 0]; the tap index is d = cell - p
@@ -2435,26 +2410,9 @@ __global__ __launch_bounds__(256) void k_pack_encoder_lut(const float* __restric
     constexpr int NTAB = 3 * LUT_DY_F, NLIN = KSTEPS * 2 * 512;
     constexpr float CS = PREC == 2 ? ENC_CSCALE : 1.f, LS = PREC == 2 ? ENC_LSCALE : 1.f;
     const int e = blockIdx.x * 256 + threadIdx.x;
-    if (PREC == 2 && e < 6 && err) {      // range of the conv ACTIVATIONS at the scale CS (they are split inside the encoder): exact worst case, see k_pack_encoder
-        float bound = fabsf(cb[e]);
-        for (int tap = 0; tap < 9; ++tap) {
-            float mx = 0.f;
-            for (int ch = 0; ch < 3; ++ch) mx = fmaxf(mx, fabsf(cw[(e * 3 + ch) * 9 + tap]));
-            bound += mx * (255.f / 256.f);
-        }
-        if (!(bound * CS <= F16_MAX)) atomicOr(err, ERR_F16_RANGE);
-    }
+    if (PREC == 2 && e < 6 && err) check_conv_range(cw, cb, e, CS, err);
     if (e < NTAB) {
-        // T[dy][idx][c] = (dy == 0 ? b[c] : 0) + 255/256 * sum over dx of w[c][plane(class of cell dx)][dy][dx]; classes (SSD_OBS_CODE):
-        // 2 = waste -> R (plane 0), 1 = apple -> G (plane 1), 3 = wall / agent -> B (plane 2), 0 = nothing
-        const int dy = e / LUT_DY_F, idx = (e / LUT_ENTRY_F) % 64, c = e % LUT_ENTRY_F;
-        double v = dy == 0 ? (double)cb[c] : 0.0;
-        for (int dx = 0; dx < 3; ++dx) {
-            const int cls = (idx >> (2 * dx)) & 3;
-            const int plane = cls == 2 ? 0 : (cls == 1 ? 1 : (cls == 3 ? 2 : -1));
-            if (plane >= 0) v += (double)cw[((c * 3 + plane) * 3 + dy) * 3 + dx] * (255.0 / 256.0);
-        }
-        table[e] = (float)(v * (double)CS);
+        table[e] = lut_table_entry(cw, cb, e, CS);
     } else if (e < NTAB + NLIN) {
         const int i = e - NTAB, mt = (i >> 9) & 1, gs = i >> 10, lane = (i >> 3) & 63, j = i & 7, q = lane >> 4, m = lane & 15;
         int band = 0, base = 0;                                        // the band this K-step belongs to
@@ -2475,24 +2433,9 @@ __global__ __launch_bounds__(256) void k_pack_encoder_lut_any(const float* __res
     const int NTAB = 3 * LUT_DY_F, NLIN = KSTEPS * 2 * 512, KF = (R * O + 3) / 4;     // KF: K-steps of a full band
     constexpr float CS = PREC == 2 ? ENC_CSCALE : 1.f, LS = PREC == 2 ? ENC_LSCALE : 1.f;
     const int e = blockIdx.x * 256 + threadIdx.x;
-    if (PREC == 2 && e < 6 && err) {      // range of the conv activations at the scale CS: see k_pack_encoder
-        float bound = fabsf(cb[e]);
-        for (int tap = 0; tap < 9; ++tap) {
-            float mx = 0.f;
-            for (int ch = 0; ch < 3; ++ch) mx = fmaxf(mx, fabsf(cw[(e * 3 + ch) * 9 + tap]));
-            bound += mx * (255.f / 256.f);
-        }
-        if (!(bound * CS <= F16_MAX)) atomicOr(err, ERR_F16_RANGE);
-    }
-    if (e < NTAB) {                       // the table: as k_pack_encoder_lut
-        const int dy = e / LUT_DY_F, idx = (e / LUT_ENTRY_F) % 64, c = e % LUT_ENTRY_F;
-        double v = dy == 0 ? (double)cb[c] : 0.0;
-        for (int dx = 0; dx < 3; ++dx) {
-            const int cls = (idx >> (2 * dx)) & 3;
-            const int plane = cls == 2 ? 0 : (cls == 1 ? 1 : (cls == 3 ? 2 : -1));
-            if (plane >= 0) v += (double)cw[((c * 3 + plane) * 3 + dy) * 3 + dx] * (255.0 / 256.0);
-        }
-        table[e] = (float)(v * (double)CS);
+    if (PREC == 2 && e < 6 && err) check_conv_range(cw, cb, e, CS, err);
+    if (e < NTAB) {
+        table[e] = lut_table_entry(cw, cb, e, CS);
     } else if (e < NTAB + NLIN) {
         const int i = e - NTAB, mt = (i >> 9) & 1, gs = i >> 10, lane = (i >> 3) & 63, j = i & 7, q = lane >> 4, m = lane & 15;
         const int band = gs / KF < NB - 1 ? gs / KF : NB - 1, base = band * KF;

@@ -9,6 +9,7 @@ Keys are the kernels' template argument lists as a demangler prints them, withou
 The ledger (test_every_policy_kernel_is_held_by_a_case_or_argued_unreachable) covers LEDGER_PREFIXES.  An encoder or pack kernel counts
 as held where the case compares what it produced with a reference: the features (or the q-values computed from them) against the
 torch encoder / controller.  A case that only compares kernel with kernel (the older two-launch tests) holds none of them."""
+import functools
 import re
 from collections import namedtuple
 
@@ -147,6 +148,66 @@ def host_plan(V, flags=SHIPPED_WORD, **keys):
     mac = SimpleNamespace(args=args, n_agents=n, input_shape=32 + A + n + 4 + (n * A if others else 0),
                           input_flags=None if others else SHIPPED_WORD, rollout_input_flags=flags, shipped_flags=not others)
     return plan_rollout(mac)
+
+
+# ---- dummy arguments of the host refusal tests, and what the GPU tests of the run-time window edges ask of the env -------------------
+def dummy_head(flags=None, n=5, A=9, pipe=1):
+    """A head's arguments with dummy addresses (non-null, 16-byte aligned, never read): every refusal under test returns from the
+    argument checks, a launch would fault.  flags None: the shipped input set without a flag word, every pointer of the dense heads
+    set.  Else the explicit flag word `flags` with the gather pointers its bits ask for and `pipe` as pipeline_gather (which asks
+    ssd_policy_head_inc_encode for the gathered fused launch); the previous-step pointers the gathered heads do not read stay null."""
+    from homophily_marl_amd import abi
+    a = abi.SsdPolicyHead()
+    P = 1 << 20
+    others, gather = abi.INPUT_OTHERS_LAST_ACTION, abi.INPUT_GATHER_ONEHOT
+    a.n_env, a.n_agents, a.n_actions, a.pos_scale = 16, n, A, 1.0
+    a.input_shape = 32 + A + n + 4 + (n * A if flags is not None and flags & others else 0)
+    fields = ("inputs", "h", "weights", "epsilon", "step", "out_actions", "actions", "pos_pre", "orient_pre", "reward", "clean_num", "apple_den")
+    if flags is None:
+        fields += ("prev_actions", "prev_reward", "prev_actions_inc", "pos")
+    else:
+        a.input_flags, a.pipeline_gather = abi.INPUT_EXPLICIT | flags, pipe
+        if flags & gather:
+            a.onehot_rows, a.prev_record = P, P
+        elif flags & others:
+            a.others_rows, a.prev_record = P, P
+    for f in fields:
+        setattr(a, f, P)
+    return a
+
+
+def dummy_encode_args(V, layout=None, n=5):
+    """The encoder arguments of 16 * n rows at window edge V with dummy addresses (layout None: the class-LUT images)"""
+    from homophily_marl_amd import abi
+    P = 1 << 20
+    ea = abi.SsdPolicyEncodeArgs()
+    ea.codes, ea.code_bytes, ea.env_stride, ea.agent_stride = P, 1 << 24, n * V * V, V * V
+    ea.rows, ea.view_edge, ea.n_agents, ea.precision, ea.layout = 16 * n, V, n, 2, abi.ENCODE_LAYOUT_LUT if layout is None else layout
+    ea.conv_frags, ea.lin_frags, ea.conv_b, ea.lin_b = P, P, P, P
+    if 3 <= V <= 63 and V & 1 and abi.encode_bands(V) > 1:
+        ea.part = P + (1 << 16)
+    else:
+        ea.out, ea.out_stride = P + (1 << 16), 64
+    return ea
+
+
+def env_map(kind, n):
+    return "default10" if (kind == "harvest" or n == 10) else "default5"
+
+
+@functools.lru_cache(maxsize=None)
+def v_max(kind, mapname, n):
+    """The largest view ssd_create accepts for this map and team size (found by creating)."""
+    from homophily_marl_amd import abi
+    from homophily_marl_amd.envs.native import NativeEnv
+    for v in range(31, -1, -1):
+        try:
+            e = NativeEnv(kind, device=0, map=mapname, num_agents=n, n_env=1, view_size=v)
+        except abi.SsdError:
+            continue
+        e.close()
+        return v
+    raise AssertionError("no view accepted")
 
 
 def gen_of(flags, inc):
@@ -311,7 +372,7 @@ def existing_cases():
         out.append(Case("mfma-fused", "fused", kind, map_of(kind, n), n, N, view, (2,), SHIPPED, None, LUT, None, 3, False))
     for kind, n, view, N, prec in av.LAUNCH_CASES:
         if view != "max":                         # the largest view a map takes is found by creating an env: not on the CPU
-            out.append(Case("any-view", "fused", kind, av._map(kind, n), n, N, view, (prec,), SHIPPED, "pipeline_any_view", LUT, None, 3, False))
+            out.append(Case("any-view", "fused", kind, env_map(kind, n), n, N, view, (prec,), SHIPPED, "pipeline_any_view", LUT, None, 3, False))
     for kind, map_, n, view, N, prec, flags in ga.LAUNCH_CASES:
         out.append(Case("gathered", "fused", kind, map_, n, N, view, (prec,), flags, "pipeline_gathered", LUT, None, 3, False))
     return out

@@ -13,6 +13,7 @@ import torch as th
 import torch.nn.functional as F
 
 from homophily_marl_amd import abi
+from tests.policy_cases import v_max as _v_max
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 ODD_EDGES = list(range(3, 64, 2))
@@ -63,19 +64,6 @@ def test_encoder_entry_points_refuse_unsupported_edges(V):
 
 
 # ---- GPU -------------------------------------------------------------------------------------------------------------------------
-def _v_max(env_name, mapname, n):
-    """The largest view ssd_create accepts for this map and team size (found by creating)."""
-    from homophily_marl_amd.envs.native import NativeEnv
-    for v in range(31, -1, -1):
-        try:
-            e = NativeEnv(env_name, device=0, map=mapname, num_agents=n, n_env=1, view_size=v)
-        except abi.SsdError:
-            continue
-        e.close()
-        return v
-    raise AssertionError("no view accepted")
-
-
 def _ctx(kind, n, N, view, **over):
     from homophily_marl_amd.run import load_config, setup
     cfg = load_config(kind, overrides=dict(dict(runner="hip_vec", batch_size_run=N, batch_size=8, buffer_size=N, buffer_cpu_only=False,

@@ -7,7 +7,6 @@ GPU: the fused launch against the two standalone launches bit for bit (one to si
 precisions, the looped head), and the pipelined hip_graph runner against the four-launch runner field by field, replayed on the CPU
 oracle."""
 import ctypes as C
-import functools
 import os
 import re
 import sys
@@ -17,6 +16,7 @@ import pytest
 import torch as th
 
 from homophily_marl_amd import abi
+from tests.policy_cases import dummy_encode_args as _enc, dummy_head as _head, env_map as _map, v_max as _v_max
 from tests.policy_cases import host_plan as _host_policy      # plan_rollout over a stand-in controller: the shipped input set
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
@@ -50,29 +50,6 @@ def test_kernel_arguments_of_the_any_edge_launch_sit_where_the_heads_read_them()
         block = text[text.index(".amdhsa_kernel " + name):]
         block = block[:block.index(".end_amdhsa_kernel")]
         assert ".amdhsa_user_sgpr_kernarg_preload_length 14" in block, name
-
-
-def _head(n=5, A=9):
-    a = abi.SsdPolicyHead()
-    P = 1 << 20                                                                 # a non-null, 16-byte aligned address that is never read
-    a.n_env, a.n_agents, a.n_actions, a.pos_scale, a.input_shape = 16, n, A, 1.0, 32 + A + n + 4      # the shipped input set
-    for f in ("inputs", "h", "weights", "epsilon", "step", "out_actions", "prev_actions", "prev_reward", "prev_actions_inc", "pos", "actions",
-              "pos_pre", "orient_pre", "reward", "clean_num", "apple_den"):
-        setattr(a, f, P)
-    return a
-
-
-def _enc(V, layout, n=5):
-    P = 1 << 20
-    ea = abi.SsdPolicyEncodeArgs()
-    ea.codes, ea.code_bytes, ea.env_stride, ea.agent_stride = P, 1 << 24, n * V * V, V * V
-    ea.rows, ea.view_edge, ea.n_agents, ea.precision, ea.layout = 16 * n, V, n, 2, layout
-    ea.conv_frags, ea.lin_frags, ea.conv_b, ea.lin_b = P, P, P, P
-    if 3 <= V <= 63 and V & 1 and abi.encode_bands(V) > 1:
-        ea.part = P + (1 << 16)
-    else:
-        ea.out, ea.out_stride = P + (1 << 16), 64
-    return ea
 
 
 @pytest.mark.parametrize("V", [1, 2, 16, 20, 64, 65])
@@ -119,24 +96,6 @@ def test_inc_encode_truth_table(monkeypatch):
 
 
 # ---- GPU -------------------------------------------------------------------------------------------------------------------------
-def _map(kind, n):
-    return "default10" if (kind == "harvest" or n == 10) else "default5"
-
-
-@functools.lru_cache(maxsize=None)
-def _v_max(kind, mapname, n):
-    """The largest view ssd_create accepts for this map and team size (found by creating)."""
-    from homophily_marl_amd.envs.native import NativeEnv
-    for v in range(31, -1, -1):
-        try:
-            e = NativeEnv(kind, device=0, map=mapname, num_agents=n, n_env=1, view_size=v)
-        except abi.SsdError:
-            continue
-        e.close()
-        return v
-    raise AssertionError("no view accepted")
-
-
 def _ctx(kind, n, N, view, **over):
     from homophily_marl_amd.run import load_config, setup
     cfg = load_config(kind, overrides=dict(dict(runner="hip_vec", batch_size_run=N, batch_size=8, buffer_size=N, buffer_cpu_only=False,

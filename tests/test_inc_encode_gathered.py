@@ -18,6 +18,7 @@ import pytest
 import torch as th
 
 from homophily_marl_amd import abi
+from tests.policy_cases import dummy_encode_args as _enc, dummy_head as _head
 from tests.policy_cases import host_plan as _host_policy      # plan_rollout over a stand-in controller: a rollout flag word with a gather bit
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
@@ -52,36 +53,6 @@ def test_kernel_arguments_of_the_gathered_launch_sit_where_the_heads_read_them()
         block = text[text.index(".amdhsa_kernel " + name):]
         block = block[:block.index(".end_amdhsa_kernel")]
         assert ".amdhsa_user_sgpr_kernarg_preload_length 14" in block, name
-
-
-def _head(flags, n=5, A=9, pipe=1):
-    """an inc head's arguments with dummy addresses (non-null, 16-byte aligned, never read) for the flag word `flags`; pipe: the field
-    pipeline_gather that asks ssd_policy_head_inc_encode for the gathered fused launch"""
-    a = abi.SsdPolicyHead()
-    P = 1 << 20
-    a.n_env, a.n_agents, a.n_actions, a.pos_scale = 16, n, A, 1.0
-    a.input_shape = 32 + A + n + 4 + (n * A if flags & OTHERS else 0)
-    a.input_flags, a.pipeline_gather = abi.INPUT_EXPLICIT | flags, pipe
-    for f in ("inputs", "h", "weights", "epsilon", "step", "out_actions", "actions", "pos_pre", "orient_pre", "reward", "clean_num", "apple_den"):
-        setattr(a, f, P)
-    if flags & GATHER:
-        a.onehot_rows, a.prev_record = P, P
-    elif flags & OTHERS:
-        a.others_rows, a.prev_record = P, P
-    return a
-
-
-def _enc(V, layout=abi.ENCODE_LAYOUT_LUT, n=5):
-    P = 1 << 20
-    ea = abi.SsdPolicyEncodeArgs()
-    ea.codes, ea.code_bytes, ea.env_stride, ea.agent_stride = P, 1 << 24, n * V * V, V * V
-    ea.rows, ea.view_edge, ea.n_agents, ea.precision, ea.layout = 16 * n, V, n, 2, layout
-    ea.conv_frags, ea.lin_frags, ea.conv_b, ea.lin_b = P, P, P, P
-    if 3 <= V <= 63 and V & 1 and abi.encode_bands(V) > 1:
-        ea.part = P + (1 << 16)
-    else:
-        ea.out, ea.out_stride = P + (1 << 16), 64
-    return ea
 
 
 HEAD_FLAGS = [SHIPPED | OTHERS, SHIPPED | GATHER, SHIPPED | OTHERS | GATHER]

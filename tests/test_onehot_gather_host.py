@@ -21,6 +21,7 @@ import torch as th
 
 from homophily_marl_amd import abi
 from homophily_marl_amd.fast_policy import FastPolicy, plan_rollout
+from tests.policy_cases import dummy_head as _head
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["obs_last_action", "obs_agent_id", "obs_reward", "obs_inc_reward", "obs_distance", "obs_agent_pos", "obs_others_last_action"]
@@ -74,23 +75,13 @@ def test_supports_truth_table_with_and_without_the_key():
     assert mac.input_shape == 155 and FastPolicy.supports(mac)                             # the row that fails without the feature
 
 
-def _head(n=6, A=9):
-    a = abi.SsdPolicyHead()
-    P = 1 << 20                                                                 # a non-null, 16-byte aligned address that is never read
-    a.n_env, a.n_agents, a.n_actions, a.pos_scale = 16, n, A, 1.0
-    for f in ("inputs", "h", "weights", "epsilon", "step", "out_actions", "prev_actions", "prev_reward", "prev_actions_inc", "pos", "actions",
-              "pos_pre", "orient_pre", "reward", "clean_num", "apple_den"):
-        setattr(a, f, P)
-    return a
-
-
 def test_heads_refuse_bad_gather_arguments_before_any_launch():
     """Every row returns from the argument check: the addresses are dummies, so a launch would fault."""
     lib = abi.load_library()
     P = 1 << 20
     wide = 32 + 9 + 6 + 1 + 1 + 6 + 2                                           # shipped + distance at n = 6: 57 columns, 66 with the inc one-hot
     for fn, inc in ((lib.ssd_policy_head_env, False), (lib.ssd_policy_head_inc, True)):
-        a = _head()
+        a = _head(n=6)
         a.input_flags, a.input_shape = abi.INPUT_EXPLICIT | SHIPPED | 16, wide
         assert fn(C.byref(a), None) == abi.SSD_ERR_UNSUPPORTED                 # dense, as before: does not fit
         a.input_flags |= GATHER
@@ -117,7 +108,7 @@ def test_heads_refuse_bad_gather_arguments_before_any_launch():
         a.input_flags, a.n_agents = (a.input_flags & ~128), 11
         a.input_shape = 32 + 9 + 11 + 1 + 1 + 11 + 2
         assert fn(C.byref(a), None) == abi.SSD_ERR_INVALID                     # more agents than a record holds
-    a = _head()
+    a = _head(n=6)
     a.input_flags, a.input_shape, a.onehot_rows, a.prev_record = abi.INPUT_EXPLICIT | SHIPPED | 16 | GATHER, wide, P, P
     e = abi.SsdPolicyEncodeArgs()
     assert lib.ssd_policy_head_inc_encode(C.byref(a), C.byref(e), None) == abi.SSD_ERR_UNSUPPORTED

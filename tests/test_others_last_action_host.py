@@ -20,6 +20,7 @@ import torch as th
 
 from homophily_marl_amd import abi
 from homophily_marl_amd.fast_policy import plan_rollout
+from tests.policy_cases import dummy_head as _head
 
 NAMES = ["obs_last_action", "obs_agent_id", "obs_reward", "obs_inc_reward", "obs_distance", "obs_agent_pos", "obs_others_last_action"]
 BITS = [1, 2, 4, 8, 16, 32, 64]
@@ -61,16 +62,6 @@ def test_rollout_flag_word_and_support_for_every_flag_combination(name):
         assert lib.ssd_build_inputs_width(n, A, abi.INPUT_EXPLICIT | word) == full - 32
         seen += on[6] and plan_rollout(mac).supported
     assert seen == 64                      # n = 5: every set with the block fits (dense <= 55)
-
-
-def _head(n=5, A=9):
-    a = abi.SsdPolicyHead()
-    P = 1 << 20                                                                 # a non-null, 16-byte aligned address that is never read
-    a.n_env, a.n_agents, a.n_actions, a.pos_scale = 16, n, A, 1.0
-    for f in ("inputs", "h", "weights", "epsilon", "step", "out_actions", "prev_actions", "prev_reward", "prev_actions_inc", "pos", "actions",
-              "pos_pre", "orient_pre", "reward", "clean_num", "apple_den"):
-        setattr(a, f, P)
-    return a
 
 
 SHIPPED = 1 | 2 | 4 | 8 | 32
