@@ -427,10 +427,26 @@ struct TileIn {
                                    // the four lane quarters of a row share the givers between them (summed over q in prepare)
     uint32_t rv;                   // env, receiver-major bytes given: givers 4 q .. 4 q + 3 as one dword
     float pr, p0, p1, o0, o1;      // env: last reward, pose
-    int aj[3];                     // inc epilogue items (row, j) = lane + 64 k: action of j and its 7 features
+    int aj[3];                     // inc epilogue item lane + 64 k = a partner pair (row, j), see IncItems: action of j, its 7 features
     float f[3][7];
     float own[3], ep;              // inc, lanes < 16 (row = lane): this agent's reward / clean_num / apple_den of the step, its return so far
     int term;                      // inc, agent 0: the env's terminated flag
+};
+
+// The inc head's epilogue items: the 16 (n - 1) PARTNER pairs (row, j != agent) of a tile, 64 per pass.  The self pair of a row is a
+// constant 0 (no self incentive) that lanes < 16 store without evaluating anything, so n = 5 is exactly one pass (it was one full pass,
+// one of 16 live lanes and a dead one that still issued its loads).  Item it -> row = it / (n - 1), jj = it % (n - 1), j = jj + (jj >=
+// agent).  n = 1: no item, no pass, no division.  Three passes cover n <= 10 (16 * 9 = 144 <= 192).
+struct IncItems {
+    int n1, count;                 // partners per row, items per tile
+    uint32_t magic;                // it / n1 for it < 192, n1 <= 9
+    __device__ __forceinline__ explicit IncItems(int n) : n1(n - 1), count(16 * (n - 1)), magic((65536u + (uint32_t)(n > 1 ? n - 1 : 1) - 1u) / (uint32_t)(n > 1 ? n - 1 : 1)) {}
+    __device__ __forceinline__ bool pass(int k) const { return count > 64 * k; }   // wave-uniform
+    __device__ __forceinline__ void pair(int it, int agent, int& row, int& j) const {
+        row = (int)(((uint32_t)it * magic) >> 16);
+        const int jj = it - row * n1;
+        j = jj + (jj >= agent ? 1 : 0);
+    }
 };
 
 // Addresses are 32-bit element offsets from the (scalar) base pointers -- every array here has far fewer than 2^31 elements (the ABI
@@ -542,12 +558,17 @@ __device__ __forceinline__ void load_tile(const HeadK& a, int tile, int agent, i
             for (int ct = 0; ct < 4; ++ct) in.x[ct] = ldg128(a.inputs, (size_t)((ro + 16u * ct) * 4u));
         }
         in.act = (int)ld32(reinterpret_cast<const int32_t*>(a.actions), 2u * ((uint32_t)bc * (uint32_t)n + (uint32_t)agent));
+        const IncItems items(n);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const int it = lane + 64 * k, row = it / n, j = it - row * n, bb = tile * 16 + row;
+            if (!items.pass(k)) break;                                 // (wave-uniform: a pass without an item requests nothing)
+            int row, j;
+            const int it = lane + 64 * k;
+            items.pair(it, agent, row, j);
+            const int bb = tile * 16 + row;
             // other_j = [one-hot(a_j), pos_j / scale, orient_j, r_j, clean_j, apple_den_j] (homophily_agent.py:194-201); items past the
             // tile (or the batch) read the batch's last row and are never used
-            const bool live = it < 16 * n && bb < N;
+            const bool live = it < items.count && bb < N;
             const uint32_t ej = live ? (uint32_t)bb * (uint32_t)n + (uint32_t)j : (uint32_t)N * (uint32_t)n - 1u;
             in.aj[k] = (int)ld32(reinterpret_cast<const int32_t*>(a.actions), 2u * ej);
             typedef float f32x2v __attribute__((ext_vector_type(2)));
@@ -1029,22 +1050,14 @@ __device__ __forceinline__ void head_body(const HeadK& a_entry, uint8_t* lds_raw
             auto q_out = ca.q_out;
             auto recv_out = COLD(uint8_t, recv_out);
             if (first) PSTAMP(9);
-            const uint32_t n_magic = (65536u + (uint32_t)n - 1u) / (uint32_t)n;      // it / n for it < 192, n <= 10
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                if (first && k == 1) PSTAMP(10);
-                if (first && k == 2) PSTAMP(11);
-                const int it = lane + 64 * k;
-                const int row = (int)(((uint32_t)it * n_magic) >> 16), j = it - row * n, bb = tile * 16 + row;
-                if (it >= 16 * n || bb >= N) continue;
-                const int aj = in.aj[k];
+            // the pair's three advantages + value: fc2's row of `row` + the extra features' columns (av[3] = the value)
+            auto pair_q = [&](int row, int aj, const float (&fj)[7], float (&av)[4]) {
                 float f[7];
-                f[0] = in.f[k][0] / a.pos_scale; f[1] = in.f[k][1] / a.pos_scale;
+                f[0] = fj[0] / a.pos_scale; f[1] = fj[1] / a.pos_scale;
 #pragma unroll
-                for (int e = 2; e < 7; ++e) f[e] = in.f[k][e];
+                for (int e = 2; e < 7; ++e) f[e] = fj[e];
                 const f32x4 sc = *reinterpret_cast<const f32x4*>(scratch + row * 16);
                 const f32x4 wa = *reinterpret_cast<const f32x4*>(w2o + aj * 4);
-                float av[4];
 #pragma unroll
                 for (int o = 0; o < 4; ++o) av[o] = sc[o] + wa[o];
 #pragma unroll
@@ -1053,24 +1066,81 @@ __device__ __forceinline__ void head_body(const HeadK& a_entry, uint8_t* lds_raw
 #pragma unroll
                     for (int o = 0; o < 4; ++o) av[o] = fmaf(f[e], we[o], av[o]);
                 }
+            };
+            const IncItems items(n);                                   // the partner pairs only (see IncItems)
+            // (an opaque copy of the lane id: the items' (row, j) are a few integer operations, formed again here -- as the same
+            // expressions as in load_tile they would be kept in registers through the whole tile chain, which has none to spare)
+            int lane_items = lane;
+#if defined(__HIP_DEVICE_COMPILE__)
+            asm volatile("" : "+v"(lane_items));
+#endif
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                if (!items.pass(k)) break;                             // (wave-uniform)
+                if (first && k == 1) PSTAMP(10);
+                if (first && k == 2) PSTAMP(11);
+                const int it = lane_items + 64 * k;
+                int row, j;
+                items.pair(it, agent, row, j);
+                const int bb = tile * 16 + row;
+                if (it >= items.count || bb >= N) continue;
+                float av[4];
+                pair_q(row, in.aj[k], in.f[k], av);
                 const uint32_t rq = (uint32_t)((agent * N + bb) * n + j);
                 const uint32_t rk = ((a.env_id_base + (uint32_t)bb) * (uint32_t)n + (uint32_t)agent) * (uint32_t)n + (uint32_t)j;
-                int act = dueling_pick_bits<3>(av, av[3], 3, 0xFFFFFFFFu, eps, step, a.seed, rk, q_out ? q_out + (size_t)rq * 3 : (decltype(q_out))nullptr);
-                if (j == agent) act = 0;                               // no self incentive (homophily_controller.py:44-46)
+                const int act = dueling_pick_bits<3>(av, av[3], 3, 0xFFFFFFFFu, eps, step, a.seed, rk, q_out ? q_out + (size_t)rq * 3 : (decltype(q_out))nullptr);
                 const size_t pair = ((size_t)bb * n + agent) * n + j;
                 out_actions[pair] = act;
                 if (p_inc) p_inc[pair] = act;
                 if (recv_out) recv_out[((size_t)j * N + bb) * 16 + agent] = (uint8_t)act;      // receiver-major byte (the next env head's input)
                 if (d_actions_inc && file) d_actions_inc[(((size_t)bb * a.slots + slot_t) * n + agent) * n + j] = act;
             }
-            // once per (env, agent), lanes < 16 (row = lane): this step's outcome of the agent itself, read with the tile's inputs
+            // once per (env, agent), lanes < 16 (row = lane)
             const int br = tile * 16 + lane;
+            if (lane < 16 && br < N) {
+                // the self pair: no self incentive (homophily_controller.py:44-46) -- a constant 0 wherever a pick is stored
+                const size_t self = ((size_t)br * n + agent) * n + agent;
+                out_actions[self] = 0;
+                if (p_inc) p_inc[self] = 0;
+                if (recv_out) recv_out[((size_t)agent * N + br) * 16 + agent] = (uint8_t)0;
+                if (d_actions_inc && file) d_actions_inc[(((size_t)br * a.slots + slot_t) * n + agent) * n + agent] = 0;
+            }
+            // ... and this step's outcome of the agent itself, read with the tile's inputs
             if (lane < 16 && br < N && cb.d_reward) {
                 const size_t ea = (size_t)br * n + agent, sr = ((size_t)br * a.slots + slot_t) * n + agent;
                 if (file) { cb.d_reward[sr] = in.own[0]; cb.d_clean[sr] = in.own[1]; cb.d_den[sr] = in.own[2]; }
                 if (cb.p_rew) cb.p_rew[ea] = in.own[0];
                 if (cb.ep_ret) cb.ep_ret[ea] = in.ep + in.own[0];
                 if (agent == 0 && cb.d_term && file) cb.d_term[(size_t)br * a.slots + slot_t] = (uint8_t)in.term;
+            }
+            // q_out given (tests; the rollout passes null -- a wave-uniform branch): the self pairs' Q values are part of q_out, evaluated
+            // here, loads and all.  Last of the epilogue, with every input and pointer fetched again (the pointers from the kernarg
+            // segment) and its own copy of the lane id: nothing of this path is live through the tile chain or beside the filing
+            // pointers -- the looped kernels have no register to spare (sharing the agent's own reward / clean_num / apple_den with the
+            // filing above, or the row index, spills one in k_head<1, 2, *, 0, true>).
+            if (q_out) {
+                int lane_q = lane;                                     // (opaque, like lane_items)
+#if defined(__HIP_DEVICE_COMPILE__)
+                asm volatile("" : "+v"(lane_q));
+#endif
+                const int br_q = tile * 16 + lane_q;
+                if (lane_q < 16 && br_q < N) {
+                    const uint32_t ea = (uint32_t)br_q * (uint32_t)n + (uint32_t)agent;
+                    typedef float f32x2v __attribute__((ext_vector_type(2)));
+                    auto acts = cold_ptr<const int32_t>(KOFF, (int)offsetof(HeadK, actions));
+                    auto pos_pre = cold_ptr<const f32x2v>(KOFF, (int)offsetof(HeadK, pos_pre));
+                    auto orient_pre = cold_ptr<const f32x2v>(KOFF, (int)offsetof(HeadK, orient_pre));
+                    auto rew = cold_ptr<const float>(KOFF, (int)offsetof(HeadK, reward));
+                    auto cln = cold_ptr<const float>(KOFF, (int)offsetof(HeadK, clean));
+                    auto den = cold_ptr<const float>(KOFF, (int)offsetof(HeadK, den));
+                    const int a_self = (int)acts[2u * ea];
+                    const f32x2v pj = pos_pre[ea], oj = orient_pre[ea];
+                    const float fs[7] = {pj.x, pj.y, oj.x, oj.y, rew[ea], cln[ea], den[ea]};
+                    float av[4];
+                    pair_q(lane_q, a_self, fs, av);
+                    const uint32_t rq = (uint32_t)((agent * N + br_q) * n + agent);
+                    (void)dueling_pick_bits<3>(av, av[3], 3, 0xFFFFFFFFu, 0.f, step, a.seed, 0u, q_out + (size_t)rq * 3);
+                }
             }
         }
         __builtin_amdgcn_wave_barrier();                               // scratch is reused by the next tile
@@ -1430,31 +1500,52 @@ struct EncK {
 template <int BT>
 __device__ __forceinline__ void enc_reduce_finish(const EncK& a, uint8_t* lds_raw, const f32x4 (&accl)[BT][2], int row0, int band, float INV, int tid, int lane,
                                                   int wave) {
+    // Thread tid finishes the items tid + 512 u: lane l = lane, output half mt = wave & 1, batch tile bt = (wave >> 1) + 4 u.  Nothing
+    // of an item's address depends on the sums, so the bias (one 16-byte load at any dword address: f0 is the same for every u), the
+    // row's division and its output offset are done HERE, in front of the barriers: behind the last one stand only the LDS reads,
+    // the adds and ONE 16-byte store per item (rows of `out` start at any dword: out_stride is free) -- no load whose result a store
+    // would have to wait for (`out` and `lin_b` may alias for the compiler, which made the tail bias load / wait / store, four times).
+    constexpr int NU = (BT * 2 * 64 + ENC_WAVES * 64 - 1) / (ENC_WAVES * 64);
+    static_assert(ENC_WAVES == 8, "an item's (lane, mt, bt) from (lane, wave)");
+    typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));
+    const int mt = wave & 1, f0 = 16 * mt + 4 * (lane >> 4);
+    const bool to_part = a.part != nullptr;                            // (wave-uniform)
+    f32x4 bias = {0.f, 0.f, 0.f, 0.f};
+    if (!to_part) bias = *reinterpret_cast<const f32x4_u SSD_GLOBAL*>((const float SSD_GLOBAL*)a.lin_b + f0);
+    size_t off[NU];                                                    // float offset of the item's four outputs in `part` / `out`
+    bool on[NU];
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+        const int bt = (wave >> 1) + 4 * u, row = row0 + bt * 16 + (lane & 15);
+        on[u] = bt < BT && row < a.rows;
+        const int b = row / a.n, i = row - b * a.n;
+        const size_t orow = a.agent_major ? (size_t)i * (a.rows / a.n) + b : (size_t)row;
+        off[u] = to_part ? ((size_t)band * a.rows + orow) * 32 + f0 : orow * a.out_stride + f0;
+    }
     __syncthreads();
     f32x4* red = reinterpret_cast<f32x4*>(lds_raw);                    // [wave][bt][mt][lane]
 #pragma unroll
     for (int bt = 0; bt < BT; ++bt)
 #pragma unroll
-        for (int mt = 0; mt < 2; ++mt) red[((wave * BT + bt) * 2 + mt) * 64 + lane] = accl[bt][mt];
+        for (int mt2 = 0; mt2 < 2; ++mt2) red[((wave * BT + bt) * 2 + mt2) * 64 + lane] = accl[bt][mt2];
     __syncthreads();
-    for (int it = tid; it < BT * 2 * 64; it += ENC_WAVES * 64) {
-        const int l = it & 63, mt = (it >> 6) & 1, bt = it >> 7;
-        f32x4 sum = red[((0 * BT + bt) * 2 + mt) * 64 + l];
 #pragma unroll
-        for (int w = 1; w < ENC_WAVES; ++w) sum += red[((w * BT + bt) * 2 + mt) * 64 + l];
-        const int row = row0 + bt * 16 + (l & 15), f0 = 16 * mt + 4 * (l >> 4);
-        if (row < a.rows) {
-            const int b = row / a.n, i = row - b * a.n;
-            const size_t orow = a.agent_major ? (size_t)i * (a.rows / a.n) + b : (size_t)row;
-            if (a.part) {
-                f32x4 o;
+    for (int u = 0; u < NU; ++u) {
+        const int bt = (wave >> 1) + 4 * u;
+        if (u > 0 && bt >= BT) break;                                  // (wave-uniform: BT = 5 leaves a second item to waves 0 and 1)
+        f32x4 sum = red[((0 * BT + bt) * 2 + mt) * 64 + lane];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) o[r] = sum[r] * INV;
-                *reinterpret_cast<f32x4*>(a.part + ((size_t)band * a.rows + orow) * 32 + f0) = o;
-            } else {
+        for (int w = 1; w < ENC_WAVES; ++w) sum += red[((w * BT + bt) * 2 + mt) * 64 + lane];
+        if (!on[u]) continue;
+        f32x4 o;
+        if (to_part) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) a.out[orow * a.out_stride + f0 + r] = leaky(fmaf(sum[r], INV, a.lin_b[f0 + r]));
-            }
+            for (int r = 0; r < 4; ++r) o[r] = sum[r] * INV;
+            *reinterpret_cast<f32x4 SSD_GLOBAL*>((float SSD_GLOBAL*)a.part + off[u]) = o;
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o[r] = leaky(fmaf(sum[r], INV, bias[r]));
+            *reinterpret_cast<f32x4_u SSD_GLOBAL*>((float SSD_GLOBAL*)a.out + off[u]) = o;
         }
     }
 }
@@ -2121,9 +2212,10 @@ __global__ __launch_bounds__(FUSED_WAVES * 64) void k_inc_encode(int heads, int 
 // where k_inc_encode has it, so the heads' cold-argument offsets and refetch_head_args hold).  8 instantiations for all 29 edges.
 // (The two kernels are written out twice: sharing their text through a __forceinline__ function -- with the encoder half as a
 // template argument or as a lambda, arguments by reference or by value -- reorders instructions in all 56 instantiations.)
-// (The same holds inside the encoder bodies.  Their epilogue is shared -- enc_reduce_finish leaves every instruction stream as it was
-// but one commuted operand pair in the BT = 4 kernels -- while a helper for the class-code packing loop or for the Linear's three
-// products re-scheduled 62 kernels by up to hundreds of instructions, unmeasured: those copies stay, until a change that is timed.)
+// (The same holds inside the encoder bodies.  Their epilogue is shared -- enc_reduce_finish, when it was introduced, left every
+// instruction stream as it was but one commuted operand pair in the BT = 4 kernels -- while a helper for the class-code packing loop
+// or for the Linear's three products re-scheduled 62 kernels by up to hundreds of instructions, unmeasured: those copies stay, until a
+// change that is timed.)
 template <int PREC, int AT, bool LOOP>
 __global__ __launch_bounds__(FUSED_WAVES * 64) void k_inc_encode_any(int heads, int enc_groups, int p_N, int p_n, int p_bpa, int p_pad, float* p_h, float* p_inputs,
                                                                      const uint8_t* p_codes, const int64_t* p_slot_t, HeadK a, HeadCold cold_unused, EncK e, int V) {
