@@ -200,7 +200,7 @@ class SsdTdLossArgs(C.Structure):
                 ("double_q", C.c_int32),
                 ("gamma_env", C.c_float), ("gamma_inc", C.c_float), ("reward_scale", C.c_float), ("incentive_ratio", C.c_float),
                 ("incentive_cost", C.c_float), ("incentive", C.c_float), ("seq_len", C.c_float), ("sim_threshold", C.c_float),
-                ("sim_loss_weight", C.c_float),
+                ("sim_loss_weight", C.c_float), ("td_lambda", C.c_float),
                 ("q_env", C.c_void_p), ("q_inc", C.c_void_p), ("tq_env", C.c_void_p), ("tq_inc", C.c_void_p),
                 ("actions", C.c_void_p), ("actions_inc", C.c_void_p), ("avail", C.c_void_p), ("reward", C.c_void_p), ("clean_num", C.c_void_p),
                 ("terminated", C.c_void_p), ("filled", C.c_void_p), ("dens", C.c_void_p),

@@ -534,6 +534,7 @@ int ssd_td_sim_loss(const ssd_td_loss_args* a, int32_t mode, void* stream) {
     if (mode && (!a->q_env || !a->q_inc || !a->tq_env || !a->tq_inc || !a->actions || !a->actions_inc || !a->avail || !a->dens || !a->dq_env || !a->dq_inc))
         return fail(SSD_ERR_INVALID, "null argument");
     if (!(a->seq_len > 0.f) || !(a->reward_scale != 0.f)) return fail(SSD_ERR_INVALID, "seq_len / reward_scale");
+    if (mode && !(a->td_lambda >= 0.f && a->td_lambda <= 1.f)) return fail(SSD_ERR_INVALID, "ssd_td_sim_loss: td_lambda outside [0, 1]");
     launch_td_sim_loss(a, mode ? 1 : 0, (hipStream_t)stream);
     return launched();
 }

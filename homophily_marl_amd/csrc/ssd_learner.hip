@@ -3,7 +3,9 @@
 //   k_incentive_transfer  incentive reward transfer         (learners/homophily_learner.py:94-115)
 //   k_td_sim_loss         double-Q TD losses of both heads + similarity loss, forward AND the gradient w.r.t. the Q-values in one
 //                         launch (learners/homophily_learner.py:94-217)
-// All are elementwise / row kernels over [B(*T)*n] rows; one thread per output element / row.
+//   k_td_lambda_loss      the same loss with TD(lambda) targets for both heads (td_lambda > 0): one workgroup per (episode, agent),
+//                         a backward weighted scan over t
+// All but the last are elementwise / row kernels over [B(*T)*n] rows; one thread per output element / row.
 #include "ssd_device.h"
 
 namespace ssd {
@@ -296,6 +298,214 @@ __global__ __launch_bounds__(128) void k_td_sim_loss(ssd_td_loss_args a) {
     out[2] = (td_env * mask) * (td_env * mask); out[3] = (td_inc * mask) * (td_inc * mask); out[4] = sim_num;
     out[5] = chosen_env; out[6] = q_inc_taken; out[7] = (float)give; out[8] = rv;
     out[9] = clean * rv; out[10] = clean; out[11] = r * rv; out[12] = r;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// k_td_lambda_loss: the same loss with TD(lambda) targets for both heads (td_lambda > 0; the reference ships the recursion as
+// utils/rl_utils.py:4-14, build_td_lambda_targets).  With a_h = lambda gamma_h and, per row t of one (episode b, agent i),
+//   b_h,t = mask_t (r_h,t + (1 - lambda) gamma_h V_h,t+1 live_t)          V = tmax_env / sum_tmax, the one-step bootstrap values
+//   G_h,T = V_h,T (1 - sum_{t<T} terminated[b, t]),   G_h,t = a_h G_h,t+1 + b_h,t,   td_h,t = chosen_h,t - G_h,t
+// One workgroup per (b, i), one thread per row; the episode is walked in chunks of 256 rows from its END backwards (thread 255 of
+// the first chunk is row T - 1, so G_T enters as that chunk's carry and any T works).  Per chunk: every thread evaluates its row's
+// one-step pieces with the expressions and operation order of k_td_sim_loss<1>; a weighted suffix scan S_p = sum_{q >= p} a^(q-p) b_q
+// inside each wave (six __shfl_down steps with the weights a, a^2, a^4 .. a^32); lane 0 of every wave publishes its S through LDS and
+// every thread chains the four of them behind the incoming carry in the same fixed order (C_3 = carry, C_w = S_head[w+1] + a^64
+// C_w+1), so G_p = S_p + a^(64 - lane) C_wave and the next chunk's carry is G of thread 0.  No atomics, nothing crosses workgroups.
+// With -ffp-contract=off a row's b_h,t is mask times the bits of the one-step target, and for a lambda whose a^2 underflows
+// (2^-100) td is the one-step td wherever mask is 1.  partials columns 0 .. 12 as k_td_sim_loss<1>, 13 / 14 = G_env,t / G_inc,t.
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_td_lambda_loss(ssd_td_loss_args a) {
+    __shared__ float s_head[2][4], s_boot[2];
+    __shared__ int s_term[4];
+    const int T1 = a.t_slots, T = T1 - 1, n = a.n_agents, A = a.n_actions;
+    const int b = blockIdx.x / n, i = blockIdx.x - b * n;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // the bootstrap slot: its Q-values enter the targets only (no gradient)
+    {
+        const size_t itT = ((size_t)b * T1 + T) * n + i;
+        for (int k = tid; k < A; k += 256) a.dq_env[itT * A + k] = 0.f;
+        for (int k = tid; k < n * 3; k += 256) a.dq_inc[itT * n * 3 + k] = 0.f;
+    }
+    // 1 - sum_{t < T} terminated[b, t]: the flags are 0 / 1, so the sum is exact in any order
+    int nterm = 0;
+    for (int t = tid; t < T; t += 256) nterm += (int)a.terminated[(size_t)b * T1 + t];
+    for (int d = 32; d; d >>= 1) nterm += __shfl_down(nterm, d);
+    if (lane == 0) s_term[wave] = nterm;
+    // a_h^(2^j), j = 0 .. 6, and this lane's a_h^(64 - lane)
+    const float lam = a.td_lambda;
+    const float c_env = (1.f - lam) * a.gamma_env, c_inc = (1.f - lam) * a.gamma_inc;
+    float we[7], wi[7];
+    we[0] = lam * a.gamma_env; wi[0] = lam * a.gamma_inc;
+    for (int j = 1; j < 7; ++j) { we[j] = we[j - 1] * we[j - 1]; wi[j] = wi[j - 1] * wi[j - 1]; }
+    float pe = 1.f, pi = 1.f;
+    for (int j = 0; j < 7; ++j)
+        if (((64 - lane) >> j) & 1) { pe *= we[j]; pi *= wi[j]; }
+    const float den0 = a.dens[0], den1 = 1.f + a.dens[1];
+    const bool others = a.consider_others_inc != 0;
+    float carry_env = 0.f, carry_inc = 0.f;
+    for (int c1 = T; c1 > 0; c1 -= 256) {                                       // rows [c1 - 256, c1), thread 255 = row c1 - 1
+        const int t = c1 - 256 + tid;
+        const bool valid = t >= 0;
+        const int bt = b * T1 + (valid ? t : 0), it = bt * n + i;
+        const size_t row = (size_t)bt * n;                                      // (b, t, agent 0)
+        const int64_t* ainc = a.actions_inc + row * n;                          // [giver][receiver] at (b, t)
+        const size_t qi = (size_t)it * n * 3, qi1 = qi + (size_t)n * n * 3;
+        float mask = 0.f, sim_sum = 0.f, r = 0.f, clean = 0.f, rv = 0.f, chosen_env = 0.f, sum_chosen = 0.f, q_inc_taken = 0.f;
+        float b_env = 0.f, b_inc = 0.f;
+        uint32_t cn_bits = 0, rw_bits = 0;
+        int give = 0, a_t = 0, cl_i = 0, idle_i = 0;
+        // sim(i, k) = [cluster_i == cluster_k] idle_i idle_k  (0, 1, 2 or 4)
+        auto sim_ik = [&](int k) -> float {
+            const int cn_k = (cn_bits >> k) & 1, rw_k = (rw_bits >> k) & 1;
+            return (2 * rw_k + cn_k == cl_i) ? (float)(idle_i * (cn_k + rw_k)) : 0.f;
+        };
+        auto recv_of = [&](const int64_t* acts, int j, float& r0, float& r1, float& r2) {
+            int p = 0, m = 0;
+            for (int g = 0; g < n; ++g) {
+                if (g == j) continue;
+                const int64_t x = acts[(size_t)g * n + j];
+                p += x == 1; m += x == 2;
+            }
+            r0 = (float)(n - 1 - p - m); r1 = (float)p; r2 = (float)m;
+        };
+        if (valid) {
+            mask = (float)a.filled[bt] * (t ? 1.f - (float)a.terminated[bt - 1] : 1.f);   // :62-64
+            // ---- similarity mask: window flags of every agent (:184-191), cluster / idle (:194-206) --------------------------------
+            const int t_lo = t - a.sim_horizon + 1 > 0 ? t - a.sim_horizon + 1 : 0;
+            for (int k = 0; k < n; ++k) {
+                float cn = 0.f, rw = 0.f;
+                for (int tau = t_lo; tau <= t; ++tau) {
+                    const size_t e = ((size_t)b * T1 + tau) * n + k;
+                    cn += a.clean_num[e] > 0.f ? 1.f : 0.f;
+                    rw += a.reward[e] / a.reward_scale;
+                }
+                cn_bits |= (cn > 0.f ? 1u : 0u) << k; rw_bits |= (rw > 0.f ? 1u : 0u) << k;
+            }
+            const int cn_i = (cn_bits >> i) & 1, rw_i = (rw_bits >> i) & 1;
+            cl_i = 2 * rw_i + cn_i; idle_i = cn_i + rw_i;
+            for (int k = 0; k < n; ++k) { if (k != i) sim_sum += sim_ik(k) * (float)(n - 2); }   // receivers j != i, j != k
+            // ---- incentive transfer (:94-115) ------------------------------------------------------------------------------------------
+            int rp = 0, rn = 0;
+            for (int j = 0; j < n; ++j) {
+                if (j == i) continue;
+                give += ainc[(size_t)i * n + j] != 0;
+                const int64_t x = ainc[(size_t)j * n + i];
+                rp += x == 1; rn += x == 2;
+            }
+            r = a.reward[row + i] / a.reward_scale;
+            clean = a.clean_num[row + i] > 0.f ? 1.f : 0.f;
+            rv = (float)(rp - rn);
+            const float r_env = (r + rv * a.incentive_ratio * a.incentive) / a.seq_len;
+            const float r_inc = (r - (float)give * a.incentive_cost * a.incentive) / a.seq_len;
+            const float live = 1.f - (float)a.terminated[bt];
+            // ---- env head: chosen value and bootstrap value (:118-177) -------------------------------------------------------------------
+            const size_t qe = (size_t)it * A, qe1 = qe + (size_t)n * A;             // (b, t, i) and (b, t + 1, i)
+            a_t = (int)a.actions[row + i];
+            chosen_env = a.q_env[qe + a_t];
+            float bq = -INFINITY, tmax_env = kNeg;
+            for (int k = 0; k < A; ++k) {
+                const bool ok = a.avail[qe1 + k] != 0;
+                const float q = a.double_q ? (ok ? a.q_env[qe1 + k] : kNeg) : (ok ? a.tq_env[qe1 + k] : kNeg);
+                if (q > bq) { bq = q; tmax_env = ok ? a.tq_env[qe1 + k] : kNeg; }    // first maximum
+            }
+            // ---- inc head over the receivers j != i --------------------------------------------------------------------------------------
+            const int64_t* ainc1 = ainc + (size_t)n * n;                            // (b, t + 1)
+            float sum_tmax = 0.f;
+            for (int j = 0; j < n; ++j) {
+                const int c = (int)ainc[(size_t)i * n + j];
+                const float qc = a.q_inc[qi + j * 3 + c];
+                q_inc_taken += qc;
+                if (j == i) continue;
+                const float* sel = (a.double_q ? a.q_inc : a.tq_inc) + qi1 + j * 3;
+                const int best = sel[1] > sel[0] ? (sel[2] > sel[1] ? 2 : 1) : (sel[2] > sel[0] ? 2 : 0);   // first maximum
+                const float* tq = a.tq_inc + qi1 + j * 3;
+                if (others) {
+                    const float* q = a.q_inc + qi + j * 3;
+                    float r0, r1, r2;
+                    recv_of(ainc, j, r0, r1, r2);
+                    sum_chosen += (q[0] * r0 + q[1] * r1 + q[2] * r2) / (float)(n - 1);
+                    recv_of(ainc1, j, r0, r1, r2);
+                    const float other = tq[0] * r0 + tq[1] * r1 + tq[2] * r2;
+                    sum_tmax += (tq[best] + other - tq[(int)ainc1[(size_t)i * n + j]]) / (float)(n - 1);
+                } else {
+                    sum_chosen += qc;
+                    sum_tmax += tq[best];
+                }
+            }
+            b_env = mask * (r_env + c_env * tmax_env * live);
+            b_inc = mask * (r_inc + c_inc * sum_tmax * live);
+            if (t == T - 1) { s_boot[0] = tmax_env; s_boot[1] = sum_tmax; }       // V_h,T: first chunk, thread 255
+        }
+        // ---- weighted suffix scan inside the wave -------------------------------------------------------------------------------------
+        float s_env = b_env, s_inc = b_inc;
+        for (int j = 0; j < 6; ++j) {
+            const int d = 1 << j;
+            const float oe = __shfl_down(s_env, d), oi = __shfl_down(s_inc, d);
+            if (lane + d < 64) { s_env += we[j] * oe; s_inc += wi[j] * oi; }
+        }
+        if (lane == 0) { s_head[0][wave] = s_env; s_head[1][wave] = s_inc; }
+        __syncthreads();
+        // ---- the four waves behind the carry, fixed order ---------------------------------------------------------------------------
+        if (c1 == T) {
+            const float not_term = 1.f - (float)(((s_term[0] + s_term[1]) + s_term[2]) + s_term[3]);
+            carry_env = s_boot[0] * not_term; carry_inc = s_boot[1] * not_term;
+        }
+        float cw_env = carry_env, cw_inc = carry_inc;                               // C_3
+        for (int w = 3; w >= 0; --w) {
+            if (w == wave) { s_env += pe * cw_env; s_inc += pi * cw_inc; }        // G of this row
+            cw_env = s_head[0][w] + we[6] * cw_env; cw_inc = s_head[1][w] + wi[6] * cw_inc;
+        }
+        carry_env = cw_env; carry_inc = cw_inc;                                     // G of thread 0: the next chunk's carry
+        __syncthreads();                                                            // s_head is rewritten by the next chunk
+        if (!valid) continue;
+        // ---- td, gradient rows, partials ---------------------------------------------------------------------------------------------
+        float* out = a.partials + ((size_t)(b * T + t) * n + i) * SSD_TD_LOSS_PARTIALS;
+        float* dqe = a.dq_env + (size_t)it * A;
+        float* dqi = a.dq_inc + qi;
+        const float td_env = chosen_env - s_env;
+        const float g_env = 2.f * td_env * mask * mask / den0;
+        for (int k = 0; k < A; ++k) dqe[k] = k == a_t ? g_env : 0.f;
+        const float td_inc = sum_chosen - s_inc;
+        const float g_inc = 2.f * td_inc * mask * mask / den0;
+        // d chosen_ij / d q_inc[t, i, j, x]: 1 at the taken action, or recv_x,j(t) / (n - 1) with consider_others_inc
+        const float gd = g_inc / (float)(n - 1);
+        // ---- similarity loss (:208-217) and the inc gradient rows ------------------------------------------------------------------------
+        float sim_num = 0.f;
+        const float wsim = a.sim_loss_weight / den1;
+        for (int j = 0; j < n; ++j) {
+            const float q0 = a.q_inc[qi + j * 3], q1 = a.q_inc[qi + j * 3 + 1], q2 = a.q_inc[qi + j * 3 + 2];
+            const float mx = fmaxf(q0, fmaxf(q1, q2));
+            const float e0 = expf(q0 - mx), e1 = expf(q1 - mx), e2 = expf(q2 - mx), es = e0 + e1 + e2;
+            const float p[3] = {e0 / es, e1 / es, e2 / es};
+            float g[3] = {0.f, 0.f, 0.f};
+            if (j != i) {
+                for (int k = 0; k < n; ++k) {
+                    if (k == i || k == j) continue;
+                    const float sm = sim_ik(k);
+                    if (sm == 0.f) continue;
+                    const int c = (int)ainc[(size_t)k * n + j];                     // the incentive action k actually gave j
+                    const float nl = -logf(c == 0 ? p[0] : c == 1 ? p[1] : p[2]);
+                    sim_num += fmaxf(nl, a.sim_threshold) * sm;
+                    if (nl >= a.sim_threshold) {                                    // clamp_min passes the gradient where input >= min
+                        g[0] += sm * (p[0] - (c == 0 ? 1.f : 0.f)); g[1] += sm * (p[1] - (c == 1 ? 1.f : 0.f)); g[2] += sm * (p[2] - (c == 2 ? 1.f : 0.f));
+                    }
+                }
+            }
+            const int cij = (int)ainc[(size_t)i * n + j];
+            if (others && j != i) {
+                float r0, r1, r2;
+                recv_of(ainc, j, r0, r1, r2);
+                dqi[j * 3] = wsim * g[0] + gd * r0; dqi[j * 3 + 1] = wsim * g[1] + gd * r1; dqi[j * 3 + 2] = wsim * g[2] + gd * r2;
+            } else {
+                for (int x = 0; x < 3; ++x) dqi[j * 3 + x] = wsim * g[x] + ((j != i && x == cij) ? g_inc : 0.f);
+            }
+        }
+        out[0] = mask; out[1] = sim_sum;
+        out[2] = (td_env * mask) * (td_env * mask); out[3] = (td_inc * mask) * (td_inc * mask); out[4] = sim_num;
+        out[5] = chosen_env; out[6] = q_inc_taken; out[7] = (float)give; out[8] = rv;
+        out[9] = clean * rv; out[10] = clean; out[11] = r * rv; out[12] = r;
+        out[13] = s_env; out[14] = s_inc;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -708,7 +918,8 @@ void launch_column_sums(const float* x, float* out, int G, int R, int C, float* 
 void launch_td_sim_loss(const ssd_td_loss_args* a, int mode, hipStream_t stream) {
     const int total = a->batch * a->t_slots * a->n_agents;
     const dim3 grid((total + 127) / 128), block(128);
-    if (mode) hipLaunchKernelGGL(k_td_sim_loss<1>, grid, block, 0, stream, *a);
+    if (mode && a->td_lambda > 0.f) hipLaunchKernelGGL(k_td_lambda_loss, dim3(a->batch * a->n_agents), dim3(256), 0, stream, *a);
+    else if (mode) hipLaunchKernelGGL(k_td_sim_loss<1>, grid, block, 0, stream, *a);
     else hipLaunchKernelGGL(k_td_sim_loss<0>, grid, block, 0, stream, *a);
 }
 

@@ -24,6 +24,22 @@ from ..controllers import REGISTRY as mac_REGISTRY
 NEG = -9999999
 
 
+def lambda_returns(r, terminated, mask, v, gamma, lam):
+    """TD(lambda) targets G [B, T, n] of one head, f32 on the tensors' device.  r, mask [B, T, n]: the head's rewards and the TD mask;
+    terminated [B, T] (or [B, T, 1]); v [B, T + 1, n]: slot t + 1 is the bootstrap value of row t (slot 0 is never read).
+        G_T = v_T (1 - sum_t terminated_t),   G_t = lam gamma G_t+1 + mask_t (r_t + (1 - lam) gamma v_t+1 (1 - terminated_t))
+    walked from the episode's end -- the recursion the loss kernel evaluates as a scan (csrc/ssd_learner.hip: k_td_lambda_loss), and
+    PyMARL's forward-view recursion (the reference ships it unused, utils/rl_utils.py:4-14)."""
+    r, mask, v = r.float(), mask.float(), v.float()
+    term = terminated.float().reshape(r.shape[0], r.shape[1], 1)
+    g = v[:, -1] * (1 - term.sum(dim=1))
+    out = th.empty_like(r)
+    for t in range(r.shape[1] - 1, -1, -1):
+        g = lam * gamma * g + mask[:, t] * (r[:, t] + (1 - lam) * gamma * v[:, t + 1] * (1 - term[:, t]))
+        out[:, t] = g
+    return out
+
+
 class _FusedLogs(Mapping):
     """The nine logged scalars of a train step (homophily_learner.py:228-246) as a read-only mapping over the loss kernel's sums:
     a quotient is formed when it is read (the logger reads every learner_log_interval steps), not as ~14 scalar launches per step.
@@ -81,6 +97,10 @@ class HomophilyLearner:
         self.inc_sim_mask = (1 - eye).reshape(1, 1, n, 1, n).to(self.device)
         self.oth_sim_mask = (1 - eye).reshape(1, 1, 1, n, n).to(self.device)
         self.sim_horizon = args.sim_horizon
+        # td_lambda (not a key of the reference's config; absent or 0: its one-step targets): TD(lambda) targets for both heads
+        lam = float(getattr(args, "td_lambda", 0.0) or 0.0)
+        if not 0.0 <= lam <= 1.0:                      # (NaN fails both comparisons)
+            raise ValueError("td_lambda must lie in [0, 1], got %r" % (getattr(args, "td_lambda", None),))
         self.params = list(mac.parameters())
         self.params_env = mac.parameters_env()
         self.params_inc = mac.parameters_inc()
@@ -316,6 +336,14 @@ class HomophilyLearner:
 
         targets_env = rewards_for_env + a.gamma_env * (1 - terminated) * tmax_env.sum(dim=-1)
         targets_inc = rewards_for_inc + a.gamma_inc * (1 - terminated) * (tmax_inc * self.inc_mask).sum(dim=-1)
+        lam = float(getattr(a, "td_lambda", 0.0) or 0.0)
+        if lam > 0:                                    # TD(lambda) targets replace the one-step ones (a device batch takes the kernel)
+            ops._leaving_kernels("td_sim_loss", rewards, "td_lambda > 0 with the tensor-op loss")
+            with th.no_grad():
+                pad = lambda x: th.cat([th.zeros_like(x[:, :1]), x], dim=1)        # row t's bootstrap value at slot t + 1
+                targets_env = lambda_returns(rewards_for_env, terminated, mask, pad(tmax_env.sum(dim=-1)), a.gamma_env, lam)
+                targets_inc = lambda_returns(rewards_for_inc, terminated, mask, pad((tmax_inc * self.inc_mask).sum(dim=-1)), a.gamma_inc, lam)
+            self.last_lambda_returns = (targets_env, targets_inc)                  # [B, T, n] each (the tests pin them to the reference)
         td_env = chosen_env.sum(dim=-1) - targets_env.detach()
         td_inc = (chosen_inc * self.inc_mask).sum(dim=-1) - targets_inc.detach()
         value_loss_env = ((td_env * mask) ** 2).sum() / dens[0]

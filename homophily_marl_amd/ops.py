@@ -166,6 +166,7 @@ def _td_loss_args(batch, a, n_actions, partials):
     t.incentive_ratio, t.incentive_cost, t.incentive = float(a.incentive_ratio), float(a.incentive_cost), float(a.incentive)
     t.seq_len, t.sim_threshold, t.sim_loss_weight = float(T1), float(a.sim_threshold), float(a.sim_loss_weight)
     t.consider_others_inc = int(bool(a.consider_others_inc))
+    t.td_lambda = float(getattr(a, "td_lambda", 0.0) or 0.0)
     for k, v in keep.items():
         setattr(t, k, v.data_ptr())
     t.partials = partials.data_ptr()
@@ -219,7 +220,8 @@ def td_sim_loss_grads(q_env, q_inc, tq_env, tq_inc, dens, batch, a):
     """(dL/dq_env, dL/dq_inc, column sums of the per-row partials) of the same loss from the same launch, WITHOUT an autograd node:
     the learner seeds the backward pass of the two Q tensors with the gradients directly (th.autograd.grad(..., grad_outputs=...)) --
     the loss scalar is a logged quantity only (_FusedLogs forms it when it is read), so the six scalar launches that assembled it and
-    the two multiplications by d loss / d loss = 1 of the autograd form are gone.  Columns 13..15 of the partials are never written or read."""
+    the two multiplications by d loss / d loss = 1 of the autograd form are gone.  Columns 13..15 of the partials are never read
+    (13 / 14 are written only with td_lambda > 0: the rows' lambda-returns)."""
     lib = abi.load_library()
     B, T, n = batch.batch_size, batch.max_seq_length - 1, q_env.shape[2]
     q_env, q_inc, tq_env, tq_inc = q_env.detach().contiguous(), q_inc.detach().contiguous(), tq_env.contiguous(), tq_inc.contiguous()

@@ -350,11 +350,25 @@ int ssd_clip_adam_step(const ssd_clip_adam_args* args, void* stream);
  *         plain-max selection; dq_inc[t,i,j,c] = (similarity part) + g_inc recv_c,j(t) / (n-1).  The logged q_inc taken stays the
  *         gather at a_inc.
  * Refused (SSD_ERR_INVALID): n_agents outside 2 .. SSD_MAX_AGENTS (the agents' window flags are bits of one word), batch * t_slots *
- * n_agents over SSD_ROWS32_MAX (32-bit thread index).  partials columns 13 .. 15 are never written. */
+ * n_agents over SSD_ROWS32_MAX (32-bit thread index), in mode 1 a td_lambda below 0, above 1 or NaN.  partials columns 13 .. 15 are
+ * never written while td_lambda is 0.
+ * td_lambda (learner config key of the same name, default 0; mode 0 ignores it): 0 = the one-step targets above, same kernel, same
+ *         numbers.  In (0, 1] both heads take TD(lambda) targets from one launch of a second kernel (one workgroup per (episode,
+ *         agent), a backward scan over t; any T): with T = t_slots - 1, V_h,t+1 the bootstrap value the one-step target of row t uses
+ *         (env: the selected tq_env[t+1]; inc: sum_{j != i} of the selected / consider_others_inc value), r_h,t the head's reward,
+ *         mask_t and live_t = 1 - terminated[b, t] as above,
+ *             G_h,T = V_h,T (1 - sum_{t < T} terminated[b, t]),
+ *             G_h,t = td_lambda gamma_h G_h,t+1 + mask_t (r_h,t + (1 - td_lambda) gamma_h live_t V_h,t+1),   t = T-1 .. 0,
+ *         and td_h,t = chosen_h,t - G_h,t; everything downstream (squared errors, gradient rows, similarity loss, columns 0 .. 12) is
+ *         unchanged in form.  partials column 13 = G_env,t and 14 = G_inc,t of the row; column 15 is still never written.
+ *         The member follows sim_loss_weight, in the four bytes that were padding in front of the first pointer (the fifteen 4-byte
+ *         scalars end at byte 60, q_env sits at 64): sizeof and the offset of every other member are unchanged, and
+ *         consider_others_inc stays the last member. */
 #define SSD_TD_LOSS_PARTIALS 16
 typedef struct ssd_td_loss_args {
     int32_t batch, t_slots, n_agents, n_actions, sim_horizon, double_q;
     float gamma_env, gamma_inc, reward_scale, incentive_ratio, incentive_cost, incentive, seq_len, sim_threshold, sim_loss_weight;
+    float td_lambda;
     const float *q_env, *q_inc, *tq_env, *tq_inc;
     const int64_t *actions, *actions_inc;
     const int32_t* avail;

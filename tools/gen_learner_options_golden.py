@@ -76,7 +76,8 @@ def max_keeps_action_axis():
         th.Tensor.max = orig
 
 
-def run_case(base, overrides):
+def build_case(base, overrides):
+    """(args, batch, mac, learner) of the REFERENCE on the base fixture's batch and weights, the target net set apart by PERTURB."""
     z = np.load(os.path.join(GOLDEN, base))
     meta = json.loads(bytes(z["meta"]).decode())
     cfg = {}
@@ -124,6 +125,11 @@ def run_case(base, overrides):
     with th.no_grad():
         for name, v in perturbed({k: v.numpy() for k, v in tsd.items()}).items():
             tsd[name].copy_(th.as_tensor(v))
+    return args, batch, mac, learner
+
+
+def run_case(base, overrides):
+    args, batch, mac, learner = build_case(base, overrides)
     out = {}
     for step in range(2):
         with (contextlib.nullcontext() if args.double_q else max_keeps_action_axis()):
