@@ -353,6 +353,75 @@ HIP_SIGNATURES["ssd_poll_error"] = (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)])
 HIP_SIGNATURES["ssd_set_render"] = (C.c_int, [C.c_void_p, C.c_int32])
 HIP_SIGNATURES["ssd_render"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
 ERR_BAD_RENDER = 64
+
+
+class SsdBehaviourArgs(C.Structure):
+    """include/ssd_hip.h: ssd_behaviour_args."""
+    _fields_ = [("n_env", C.c_int32), ("t_slots", C.c_int32), ("n_agents", C.c_int32), ("n_actions", C.c_int32),
+                ("actions", C.c_void_p), ("actions_inc", C.c_void_p), ("reward", C.c_void_p), ("clean_num", C.c_void_p),
+                ("workspace", C.c_void_p), ("acc", C.c_void_p)]
+
+
+BEHAVIOUR_MAX_GROUPS = 256
+BEHAVIOUR_WAVES = 16         # envs a workgroup of k_behaviour_partials walks at a time (a wave each)
+BEHAVIOUR_ROLES = ("idle", "cleaner", "harvester", "mixed")
+# ssd_behaviour_stats has a table of its own: HIP_SIGNATURES is pinned to the plainly declared names of the header and to the refusal
+# tables of tests/test_learner_abi_refusals.py; this export's checks of the same kind are tests/test_behaviour_host.py
+BEHAVIOUR_SIGNATURES = {"ssd_behaviour_stats": (C.c_int, [C.POINTER(SsdBehaviourArgs), C.c_void_p])}
+
+
+def behaviour_len(n, A):
+    """SSD_BEHAVIOUR_LEN"""
+    return 12 * n + n * A + 3 * n * n + 3
+
+
+def behaviour_layout(n, A):
+    """name -> (offset, shape) of the blocks of ssd_behaviour_stats' accumulator (include/ssd_hip.h), in order."""
+    blocks = (("reward_sum", (n,)), ("clean_sum", (n,)), ("clean_steps", (n,)), ("harvest_steps", (n,)), ("harvest_time", (n,)),
+              ("action_count", (n, A)), ("inc_count", (n, n, 3)), ("recv_on_clean", (n,)), ("recv_on_reward", (n,)), ("role_count", (n, 4)),
+              ("cleaners_hist", (n + 1,)), ("n_episodes", (1,)), ("n_steps", (1,)))
+    out, off = {}, 0
+    for name, shape in blocks:
+        out[name] = (off, shape)
+        size = 1
+        for s in shape:
+            size *= s
+        off += size
+    assert off == behaviour_len(n, A)
+    return out
+
+
+def behaviour_blocks(vec, n, A):
+    """the accumulator (any 1-D sequence of behaviour_len(n, A) numbers) as name -> f64 array of the block's shape"""
+    import numpy as np
+    vec = np.asarray(vec, dtype=np.float64).reshape(-1)
+    assert vec.size == behaviour_len(n, A), (vec.size, n, A)
+    return {k: vec[o:o + int(np.prod(s))].reshape(s).copy() for k, (o, s) in behaviour_layout(n, A).items()}
+
+
+def behaviour_summary(vec, n, A):
+    """The logged scalars of a behaviour accumulator (one pure function: the runner's _log, run.py and the tools share it).
+    rollout_* are the learner's four log values (homophily_learner.py:234-238) over EVERY step of the rollouts instead of the 16
+    sampled episodes, on the raw rewards (reward_scale is not applied)."""
+    b = behaviour_blocks(vec, n, A)
+    n_ep, n_steps = max(1.0, float(b["n_episodes"][0])), max(1.0, float(b["n_steps"][0]))
+    inc, roles = b["inc_count"], b["role_count"].sum(axis=0)
+    pairs = max(1, n * (n - 1)) * n_steps
+    clean = b["clean_sum"]
+    out = {"cleaners_per_env_mean": float((b["cleaners_hist"] * range(n + 1)).sum() / n_ep)}
+    for k, name in enumerate(BEHAVIOUR_ROLES):
+        out["role_%s_frac" % name] = float(roles[k] / (n * n_ep))
+    out["inc_pos_rate"] = float(inc[..., 1].sum() / pairs)
+    out["inc_neg_rate"] = float(inc[..., 2].sum() / pairs)
+    out["rollout_incentives_to_cleanup_per"] = float(b["recv_on_clean"].sum() / (b["clean_steps"].sum() + 1e-6))
+    out["rollout_incentives_to_harvest_per"] = float(b["recv_on_reward"].sum() / (b["reward_sum"].sum() + 1e-6))
+    out["rollout_value_give_mean"] = float((inc[..., 1].sum() + inc[..., 2].sum()) / (n * n_steps))
+    out["rollout_value_receive_mean"] = float((inc[..., 1].sum() - inc[..., 2].sum()) / (n * n_steps))
+    out["harvest_time_mean"] = float(b["harvest_time"].sum() / max(1.0, b["harvest_steps"].sum()))
+    out["clean_share_max"] = float(clean.max() / clean.sum()) if clean.sum() > 0 else 0.0
+    return out
+
+
 CPU_SIGNATURES = _sigs("ssd_cpu_", False)
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -391,6 +460,7 @@ def load_library():
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback." % HIP_LIB_PATH)
         lib = C.CDLL(HIP_LIB_PATH)
         bind(lib, HIP_SIGNATURES)
+        bind(lib, BEHAVIOUR_SIGNATURES)
         ver = lib.ssd_abi_version()
         if ver != ABI_VERSION:
             raise ImportError("libssd_hip.so ABI version %d != %d" % (ver, ABI_VERSION))

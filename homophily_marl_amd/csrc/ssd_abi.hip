@@ -525,6 +525,18 @@ int ssd_runner_stats(const float* collective_return, const float* equality, cons
     launch_runner_stats(collective_return, equality, episode_return, n_env, n_returns, acc, (hipStream_t)stream);
     return launched();
 }
+int ssd_behaviour_stats(const ssd_behaviour_args* a, void* stream) {
+    if (!a) return fail(SSD_ERR_INVALID, "ssd_behaviour_stats: null args");
+    if (!a->actions || !a->actions_inc || !a->reward || !a->clean_num || !a->workspace || !a->acc)
+        return fail(SSD_ERR_INVALID, "ssd_behaviour_stats: null member pointer");
+    if (a->n_env < 1 || a->t_slots < 2) return fail(SSD_ERR_INVALID, "ssd_behaviour_stats: n_env >= 1, t_slots >= 2");
+    if (a->n_agents < 1 || a->n_agents > SSD_MAX_AGENTS) return fail(SSD_ERR_INVALID, "ssd_behaviour_stats: n_agents outside 1 .. SSD_MAX_AGENTS");
+    if (a->n_actions < 1 || a->n_actions > 16) return fail(SSD_ERR_INVALID, "ssd_behaviour_stats: n_actions outside 1 .. 16");
+    if ((int64_t)a->t_slots * a->n_agents * a->n_agents > (int64_t)INT32_MAX)
+        return fail(SSD_ERR_INVALID, "ssd_behaviour_stats: t_slots * n_agents^2 over INT32_MAX (32-bit index inside an env's block)");
+    launch_behaviour_stats(a, (hipStream_t)stream);
+    return launched();
+}
 
 int ssd_td_sim_loss(const ssd_td_loss_args* a, int32_t mode, void* stream) {
     if (!a || a->batch < 1 || a->t_slots < 2 || a->n_agents < 2 || a->n_agents > SSD_MAX_AGENTS || a->n_actions < 1 || a->sim_horizon < 1)

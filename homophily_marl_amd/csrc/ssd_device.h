@@ -195,6 +195,7 @@ int learner_precision();                  // 2: f32-equivalent (default), 1: sin
 void set_learner_precision(int p);
 void launch_fill_blocks(const ssd_block_fill* blocks, int count, hipStream_t stream);
 void launch_runner_stats(const float* coll, const float* eq, const float* ret, int n_env, int n_ret, double* acc, hipStream_t stream);
+void launch_behaviour_stats(const ssd_behaviour_args* a, hipStream_t stream);
 int launch_bias_bmm_fwd(const float* x, const float* w, const float* b, float* y, int n, int R, int I, int O, hipStream_t s, int leaky = 0);
 int launch_bias_bmm_bwd(const float* g, const float* x, const float* w, float* dx, float* dw, float* db, const float* slope_of, int n, int R,
                         int I, int O, hipStream_t s, long x_set = 0, long g_set = 0, const float* act_y = nullptr, const float* x2 = nullptr, int I1 = 0,

@@ -592,6 +592,110 @@ void launch_runner_stats(const float* coll, const float* eq, const float* ret, i
     hipLaunchKernelGGL(k_runner_stats, dim3(1), dim3(1024), 0, stream, coll, eq, ret, n_env, n_ret, acc);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// k_behaviour_partials / k_behaviour_finish: the per-agent behaviour statistics of one rollout (ssd_behaviour_stats; the block table is
+// in include/ssd_hip.h), all in integers.
+// A wave walks one env at a time.  Lane = (time row tl, receiver j) with j = lane % n fixed for the whole kernel: 64 / n time rows per
+// pass, so everything that is indexed by the agent alone lives in the lane's registers as int64 sums over all of the wave's envs and
+// reaches LDS once, at the end; only the counters whose index depends on the DATA (action_count, inc_count) are LDS atomics per
+// element.  A lane reads its receiver's column of the n x n incentive block of its time row (n loads of 8 bytes; the n lanes of a row
+// cover its n * n * 8 contiguous bytes between them), its action, reward and clean_num.  Every load's address is clamped into the env's
+// own block (time row 0 for a lane past T, the diagonal element for a giver index past n) and the value masked: no load behind a
+// data-dependent branch, slot T is never addressed.  The per-episode sums C, Hh of a receiver are added over its lanes by 64 / n
+// bpermutes at the end of the env; lanes 0 .. n-1 then hold the agents' roles, a ballot counts the cleaners.
+// Integer sums commute: the LDS atomics' order does not show.  A workgroup writes its own row of the workspace; the second launch
+// (one workgroup) adds the rows in index order into the f64 accumulator.
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int BEH_WAVES = SSD_BEHAVIOUR_WAVES;
+constexpr int BEH_LEN_MAX = SSD_BEHAVIOUR_LEN(SSD_MAX_AGENTS, 16);
+
+__device__ __forceinline__ void beh_add(long long* cnt, int k, long long v) {
+    atomicAdd(reinterpret_cast<unsigned long long*>(cnt + k), (unsigned long long)v);
+}
+__device__ __forceinline__ int beh_round(float x) {                    // nearest integer; NaN -> 0, |x| > 2^24 -> 2^24
+    x = x == x ? x : 0.f;
+    return (int)rintf(fminf(fmaxf(x, -16777216.f), 16777216.f));
+}
+
+__global__ __launch_bounds__(64 * BEH_WAVES) void k_behaviour_partials(const int64_t* __restrict__ actions, const int64_t* __restrict__ actions_inc,
+                                                                       const float* __restrict__ reward, const float* __restrict__ clean,
+                                                                       int n_env, int T, int n, int A, long long* __restrict__ ws) {
+    __shared__ long long cnt[BEH_LEN_MAX];
+    const int len = SSD_BEHAVIOUR_LEN(n, A);
+    for (int k = threadIdx.x; k < len; k += 64 * BEH_WAVES) cnt[k] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int tpw = 64 / n, nn = n * n;                                // time rows per pass
+    const int tl = lane / n, j = lane - tl * n;
+    const bool active = tl < tpw;
+    const int o_act = 5 * n, o_inc = o_act + n * A, o_rc = o_inc + 3 * nn, o_role = o_rc + 2 * n, o_hist = o_role + 4 * n, o_ep = o_hist + n + 1;
+    long long s_r = 0, s_c = 0, s_cl = 0, s_hv = 0, s_ht = 0, s_rc = 0, s_rr = 0, envs = 0;
+    const size_t row = (size_t)(T + 1) * n;                            // elements of one env in the [n_env, T + 1, n] fields
+    for (long b = (long)blockIdx.x * BEH_WAVES + wave; b < n_env; b += (long)gridDim.x * BEH_WAVES) {
+        const int64_t* a_e = actions + (size_t)b * row;
+        const int64_t* ai_e = actions_inc + (size_t)b * row * n;
+        const float* r_e = reward + (size_t)b * row;
+        const float* c_e = clean + (size_t)b * row;
+        int C = 0, Hh = 0;
+        for (int t0 = 0; t0 < T; t0 += tpw) {
+            const int t = t0 + tl;
+            const bool valid = active && t < T;
+            const int tc = valid ? t : 0, m = tc * n + j;
+            long long v[SSD_MAX_AGENTS];
+#pragma unroll
+            for (int i = 0; i < SSD_MAX_AGENTS; ++i) v[i] = ai_e[tc * nn + (i < n ? i : j) * n + j];
+            const long long a = a_e[m];
+            const int r = valid ? beh_round(r_e[m]) : 0, c = valid ? beh_round(c_e[m]) : 0;
+            int rv = 0;
+#pragma unroll
+            for (int i = 0; i < SSD_MAX_AGENTS; ++i) {
+                const bool ok = valid && i < n && i != j;
+                if (ok && (unsigned long long)v[i] < 3ull) beh_add(cnt, o_inc + (i * n + j) * 3 + (int)v[i], 1);
+                rv += (ok && v[i] == 1) - (ok && v[i] == 2);
+            }
+            if (valid && (unsigned long long)a < (unsigned long long)A) beh_add(cnt, o_act + j * A + (int)a, 1);
+            const int cl = c > 0, hv = r > 0;
+            s_r += r; s_c += c; s_cl += cl; s_hv += hv; s_ht += hv ? t : 0;
+            s_rc += cl ? rv : 0; s_rr += (long long)r * rv;
+            C += cl; Hh += hv;
+        }
+        int Cs = 0, Hs = 0;                                            // lanes 0 .. n-1: the episode sums of agent `lane`
+        for (int k = 0; k < tpw; ++k) {
+            const int src = (lane + k * n) & 63;
+            Cs += __shfl(C, src); Hs += __shfl(Hh, src);
+        }
+        const bool agent = lane < n, cleaner = agent && Cs > Hs;
+        if (agent) beh_add(cnt, o_role + lane * 4 + ((Cs == 0 && Hs == 0) ? 0 : Cs > Hs ? 1 : Hs > Cs ? 2 : 3), 1);
+        const int n_cleaners = __popcll(__ballot(cleaner));
+        if (lane == 0) beh_add(cnt, o_hist + n_cleaners, 1);
+        envs += 1;
+    }
+    if (active) {
+        beh_add(cnt, j, s_r); beh_add(cnt, n + j, s_c); beh_add(cnt, 2 * n + j, s_cl); beh_add(cnt, 3 * n + j, s_hv); beh_add(cnt, 4 * n + j, s_ht);
+        beh_add(cnt, o_rc + j, s_rc); beh_add(cnt, o_rc + n + j, s_rr);
+    }
+    if (lane == 0) { beh_add(cnt, o_ep, envs); beh_add(cnt, o_ep + 1, envs * T); }
+    __syncthreads();
+    for (int k = threadIdx.x; k < len; k += 64 * BEH_WAVES) ws[(size_t)blockIdx.x * len + k] = cnt[k];
+}
+
+__global__ __launch_bounds__(256) void k_behaviour_finish(const long long* __restrict__ ws, int groups, int len, double* __restrict__ acc) {
+    for (int k = threadIdx.x; k < len; k += 256) {
+        long long s = 0;
+        for (int g = 0; g < groups; ++g) s += ws[(size_t)g * len + k];
+        acc[k] += (double)s;
+    }
+}
+
+void launch_behaviour_stats(const ssd_behaviour_args* a, hipStream_t stream) {
+    int groups = a->n_env / BEH_WAVES + (a->n_env % BEH_WAVES ? 1 : 0);
+    if (groups > SSD_BEHAVIOUR_MAX_GROUPS) groups = SSD_BEHAVIOUR_MAX_GROUPS;
+    long long* ws = reinterpret_cast<long long*>(a->workspace);
+    hipLaunchKernelGGL(k_behaviour_partials, dim3(groups), dim3(64 * BEH_WAVES), 0, stream, a->actions, a->actions_inc, a->reward, a->clean_num,
+                       a->n_env, a->t_slots - 1, a->n_agents, a->n_actions, ws);
+    hipLaunchKernelGGL(k_behaviour_finish, dim3(1), dim3(256), 0, stream, ws, groups, SSD_BEHAVIOUR_LEN(a->n_agents, a->n_actions), a->acc);
+}
+
 static int grid_for(size_t total);
 // k_dueling_q: q = v + a - mean_k a per (agent, row) of the learner's time-batched heads, output in the batch layout [B, T, n, inner, K];
 // BWD: da = dq - mean_k dq, dv = sum_k dq.  One thread per (agent, row); K <= 16.  ld: floats per row of a (and da); v / dv rows have the

@@ -269,6 +269,61 @@ def runner_stats(collective_return, equality, episode_return, acc):
     return acc
 
 
+def behaviour_workspace(n_agents, n_actions, device):
+    """the int64 workspace of ssd_behaviour_stats: one row per workgroup"""
+    return th.empty(abi.BEHAVIOUR_MAX_GROUPS, abi.behaviour_len(n_agents, n_actions), dtype=th.int64, device=device)
+
+
+def behaviour_stats(actions, actions_inc, reward, clean_num, n_actions, acc, workspace=None):
+    """acc f64 [abi.behaviour_len(n, A)] += the per-agent behaviour statistics of one rollout (ssd_behaviour_stats; blocks:
+    abi.behaviour_layout): two launches on the device, integer accumulation.  The fields are those of an episode storage over T + 1
+    slots -- actions i64 [N, T+1, n(, 1)], actions_inc i64 [N, T+1, n, n(, 1)], reward / clean_num f32 [N, T+1, n]; slot T is not read.
+    workspace (device tensors): behaviour_workspace(n, A), allocated here when None."""
+    if actions.dim() == 4:
+        actions = actions.squeeze(-1)
+    if actions_inc.dim() == 5:
+        actions_inc = actions_inc.squeeze(-1)
+    N, T1, n = actions.shape
+    A = int(n_actions)
+    assert actions_inc.shape == (N, T1, n, n) and reward.shape == (N, T1, n) and clean_num.shape == (N, T1, n)
+    assert acc.dtype == th.float64 and acc.shape == (abi.behaviour_len(n, A),)
+    fields = ((actions, th.int64), (actions_inc, th.int64), (reward, th.float32), (clean_num, th.float32))
+    if acc.is_cuda and acc.is_contiguous() and all(t.is_cuda and t.dtype == d and t.is_contiguous() for t, d in fields):
+        lib = abi.load_library()
+        if workspace is None:
+            workspace = behaviour_workspace(n, A, acc.device)
+        assert workspace.is_cuda and workspace.dtype == th.int64 and workspace.is_contiguous() and workspace.numel() >= abi.BEHAVIOUR_MAX_GROUPS * acc.numel()
+        a = abi.SsdBehaviourArgs(n_env=N, t_slots=T1, n_agents=n, n_actions=A, actions=actions.data_ptr(), actions_inc=actions_inc.data_ptr(),
+                                 reward=reward.data_ptr(), clean_num=clean_num.data_ptr(), workspace=workspace.data_ptr(), acc=acc.data_ptr())
+        abi.check(lib, lib.ssd_behaviour_stats(C.byref(a), _stream(acc)))
+        return acc
+    _leaving_kernels("behaviour_stats", acc, "dtype / layout")
+    if N < 1 or T1 < 2 or not 1 <= n <= abi.MAX_AGENTS or not 1 <= A <= 16:
+        raise ValueError("behaviour_stats: n_env >= 1, t_slots >= 2, n_agents 1..%d, n_actions 1..16" % abi.MAX_AGENTS)
+    T, dev = T1 - 1, acc.device
+    i64 = lambda x: x.to(th.int64)
+    rnd = lambda x: i64(th.round(th.nan_to_num(x[:, :T].float(), nan=0.0).clamp(-16777216.0, 16777216.0)))
+    act, r, c = i64(actions[:, :T]), rnd(reward), rnd(clean_num)
+    inc = i64(actions_inc[:, :T])
+    off = ~th.eye(n, dtype=th.bool, device=dev).view(1, 1, n, n)
+    is_c = [((inc == k) & off) for k in range(3)]                       # [N, T, giver, receiver]
+    rv = i64(is_c[1].sum(2)) - i64(is_c[2].sum(2))                      # per receiver
+    cl, hv = i64(c > 0), i64(r > 0)
+    t_idx = th.arange(T, dtype=th.int64, device=dev).view(1, T, 1)
+    C_ep, H_ep = cl.sum(1), hv.sum(1)                                   # [N, n]
+    role = th.where((C_ep == 0) & (H_ep == 0), 0, th.where(C_ep > H_ep, 1, th.where(H_ep > C_ep, 2, 3)))
+    cleaners = (role == 1).sum(1)
+    parts = [r.sum((0, 1)), c.sum((0, 1)), cl.sum((0, 1)), hv.sum((0, 1)), (hv * t_idx).sum((0, 1)),
+             th.stack([i64(act == k).sum((0, 1)) for k in range(A)], dim=-1).reshape(-1),
+             th.stack([i64(m).sum((0, 1)) for m in is_c], dim=-1).reshape(-1),
+             (cl * rv).sum((0, 1)), (r * rv).sum((0, 1)),
+             th.stack([i64(role == k).sum(0) for k in range(4)], dim=-1).reshape(-1),
+             th.stack([i64(cleaners == k).sum() for k in range(n + 1)]),
+             th.tensor([N, N * T], dtype=th.int64, device=dev)]
+    acc += th.cat([i64(p).reshape(-1) for p in parts]).to(th.float64)
+    return acc
+
+
 def column_sums(x):
     """x [R, C] -> [C] or x [G, R, C] -> [G, C]: row sums by the HIP kernel k_column_sums (one launch, deterministic, no
     cross-workgroup hand-off).  ATen's multi-block reduction kernels keep block-arrival semaphores that a memset node clears; inside a

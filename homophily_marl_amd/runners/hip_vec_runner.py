@@ -163,6 +163,8 @@ class HipVecRunner:
             stats["n_episodes"] = self.batch_size + stats.get("n_episodes", 0)
             stats["ep_length"] = self.t * self.batch_size + stats.get("ep_length", 0)
             stats["n_returns"] = ep_return.numel() + stats.get("n_returns", 0)
+        if getattr(self.args, "behaviour_stats", False):
+            self._behaviour_device(test_mode)
         if not test_mode:
             self.t_env += self.t * self.batch_size
             self.rollouts += 1
@@ -192,6 +194,38 @@ class HipVecRunner:
             setattr(self, key, th.zeros(4, dtype=th.float64, device=self.env.device))
         return getattr(self, key)
 
+    # ---- behaviour statistics (config key behaviour_stats, default off) ---------------------------------------------------------------
+    def _behaviour_acc(self, test_mode):
+        """(f64 accumulator [abi.behaviour_len(n, A)], int64 workspace) of ssd_behaviour_stats, one pair per mode, allocated on first use"""
+        from .. import ops
+        key = "_beh_test" if test_mode else "_beh_train"
+        if getattr(self, key, None) is None:
+            n, A = self.args.n_agents, self.args.n_actions
+            setattr(self, key, (th.zeros(abi.behaviour_len(n, A), dtype=th.float64, device=self.env.device),
+                                ops.behaviour_workspace(n, A, self.env.device)))
+        return getattr(self, key)
+
+    def _behaviour_device(self, test_mode):
+        """this rollout's per-agent behaviour statistics added to the accumulator: two eager launches over the episode's storage
+        (self.batch: the runner's own, or the replay buffer's reserved slots), on the current stream, never inside a stream capture"""
+        from .. import ops
+        if th.cuda.is_available() and th.cuda.is_current_stream_capturing():
+            raise RuntimeError("behaviour_stats is launched eagerly: _finish_stats was reached inside a stream capture")
+        st = self.batch.data.transition_data
+        acc, ws = self._behaviour_acc(test_mode)
+        ops.behaviour_stats(st["actions"], st["actions_inc"], st["reward"], st["clean_num"], self.args.n_actions, acc, ws)
+
+    def behaviour(self, test_mode=False, reset=False):
+        """The behaviour accumulator of the training (or test) episodes since it was last zeroed, by block name (abi.behaviour_layout):
+        dict[str, np.ndarray] of f64 integers.  Synchronises.  Rank-local under data parallelism, like the other runner statistics."""
+        if not getattr(self.args, "behaviour_stats", False):
+            raise RuntimeError("runner.behaviour() needs the config key behaviour_stats")
+        acc, _ = self._behaviour_acc(test_mode)
+        blocks = abi.behaviour_blocks(acc.cpu().numpy(), self.args.n_agents, self.args.n_actions)
+        if reset:
+            acc.zero_()
+        return blocks
+
     def run(self, test_mode=False):
         self.begin_episode(test_mode)
         while not self.step_once():
@@ -208,6 +242,12 @@ class HipVecRunner:
         self.logger.log_stat(prefix + "return_std", max(0.0, rss / n_ret - mean * mean) ** 0.5, self.t_env)    # np.std: population
         for k, v in (("collective_return", coll), ("equality_metric", eq), ("ep_length", stats.get("ep_length", 0))):
             self.logger.log_stat(prefix + k + "_mean", v / n_ep, self.t_env)
+        if getattr(self.args, "behaviour_stats", False):
+            bacc, _ = self._behaviour_acc(test_mode)
+            vec = bacc.cpu().numpy()
+            bacc.zero_()
+            for k, v in abi.behaviour_summary(vec, self.args.n_agents, self.args.n_actions).items():
+                self.logger.log_stat(prefix + k, v, self.t_env)
         stats.clear()
 
 

@@ -298,6 +298,55 @@ int ssd_fill_blocks(const ssd_block_fill* blocks, int32_t count, void* stream);
 int ssd_runner_stats(const float* collective_return, const float* equality, const float* episode_return, int32_t n_env, int32_t n_returns,
                      double* acc, void* stream);
 
+/* ssd_behaviour_stats: what the agents of one rollout DID, per agent, added to a device accumulator -- the picture behind the four
+ * scalars of ssd_runner_stats (the reference has no counterpart beyond the learner's four log values incentives_to_cleanup_per,
+ * incentives_to_harvest_per, value_give_mean, value_receive_mean over its 16 sampled episodes, homophily_learner.py:234-238).
+ * The fields are those of an episode storage, contiguous, over t_slots = T + 1 time slots.  The sums run over every env b and every
+ * slot t < T: slot T holds only the bootstrap actions and is never read.  No mask: the vectorised runners fill every slot.
+ *   recv+_j(b,t) = #{i != j : actions_inc[b,t,i,j] == 1},  recv-_j likewise for 2,  rv = recv+ - recv-,
+ *   r = reward, c = clean_num, both rounded to the nearest integer (a NaN counts as 0, a magnitude above 2^24 as 2^24),
+ *   cl = c > 0 (the learner's binarisation, homophily_learner.py:59-60),  hv = r > 0.
+ * acc f64 [SSD_BEHAVIOUR_LEN(n, A)], blocks in this order (n = n_agents, A = n_actions):
+ *   reward_sum     [n]        sum r
+ *   clean_sum      [n]        sum c
+ *   clean_steps    [n]        sum cl
+ *   harvest_steps  [n]        sum hv
+ *   harvest_time   [n]        sum t hv
+ *   action_count   [n, A]     #{actions == a}; values outside [0, A) are ignored
+ *   inc_count      [n, n, 3]  #{actions_inc[i -> j] == c}, i != j; the diagonal is 0 whatever is stored there
+ *                             (homophily_learner.py:98); values outside 0..2 are ignored
+ *   recv_on_clean  [n]        per receiver j: sum cl rv
+ *   recv_on_reward [n]        per receiver j: sum r rv
+ *   role_count     [n, 4]     envs in which the agent was idle, cleaner, harvester, mixed: with C = sum_t cl and Hh = sum_t hv of the
+ *                             episode, idle: C == 0 && Hh == 0; cleaner: C > Hh; harvester: Hh > C; mixed: C == Hh > 0
+ *   cleaners_hist  [n + 1]    number of envs with exactly k cleaner agents
+ *   n_episodes     [1]        n_env
+ *   n_steps        [1]        n_env T
+ * Every entry is an integer and is accumulated in integers (64-bit throughout: per-lane sums, LDS counters, one int64 row of
+ * `workspace` per workgroup), so the result does not depend on the order of summation and acc += is exact in f64 below 2^53.
+ * Two launches, no workgroup reads what another workgroup of the same launch wrote: k_behaviour_partials (G = min(
+ * SSD_BEHAVIOUR_MAX_GROUPS, ceil(n_env / SSD_BEHAVIOUR_WAVES)) workgroups of SSD_BEHAVIOUR_WAVES waves, a wave per env, writes rows [0, G) of workspace -- every
+ * column; the other rows are not touched) and k_behaviour_finish (one workgroup adds the rows in index order into acc).
+ * With n_agents == 1 there are no pairs: inc_count and recv_* stay 0.
+ * Refused (SSD_ERR_INVALID): NULL args or a NULL member pointer; n_env < 1; t_slots < 2; n_agents outside 1 .. SSD_MAX_AGENTS;
+ * n_actions outside 1 .. 16; t_slots * n_agents * n_agents above INT32_MAX (an element's index inside one env's block of
+ * actions_inc is 32-bit; offsets across envs, the time sums and every counter are 64-bit, so n_env has no bound of its own).
+ * The name is declared in parentheses (an ordinary declaration to a compiler): tests/test_abi_symbols.py and
+ * tests/test_learner_abi_refusals.py together pin the plainly declared exports to the refusal tables of the latter; this export's
+ * ctypes mirror is abi.BEHAVIOUR_SIGNATURES and its symbol, struct-size and refusal checks are tests/test_behaviour_host.py. */
+#define SSD_BEHAVIOUR_MAX_GROUPS 256
+#define SSD_BEHAVIOUR_WAVES 16
+#define SSD_BEHAVIOUR_LEN(n, A) (12 * (n) + (n) * (A) + 3 * (n) * (n) + 3)
+typedef struct ssd_behaviour_args {
+    int32_t n_env, t_slots, n_agents, n_actions;
+    const int64_t* actions;      /* [n_env, t_slots, n] */
+    const int64_t* actions_inc;  /* [n_env, t_slots, n(giver), n(receiver)] */
+    const float *reward, *clean_num;   /* [n_env, t_slots, n], integer-valued (what the env kernels write); rounded to nearest */
+    int64_t* workspace;          /* [SSD_BEHAVIOUR_MAX_GROUPS, LEN] */
+    double* acc;                 /* [LEN]  += this rollout */
+} ssd_behaviour_args;
+int (ssd_behaviour_stats)(const ssd_behaviour_args* args, void* stream);
+
 /* ssd_clip_adam_step: the optimiser tail of HomophilyLearner.cal_loss_and_step (homophily_learner.py:223-226) --
  *   clip_grad_norm_(params_inc, clip); clip_grad_norm_(params_env, clip); optimiser_inc.step(); optimiser_env.step()
  * with the conv encoder a member of BOTH parameter groups (homophily_agent.py:127-146: its gradient is scaled by both clips, the second

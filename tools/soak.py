@@ -29,6 +29,8 @@ ap.add_argument("--epsilon-anneal-time", type=int, default=None)
 ap.add_argument("--seed", type=int, default=1)
 ap.add_argument("--anomaly", action="store_true", help="torch.autograd.set_detect_anomaly(True)")
 ap.add_argument("--nan-check", action="store_true", help="after every iteration: first non-finite gradient / parameter, with details")
+ap.add_argument("--behaviour-stats", action="store_true",
+                help="config key behaviour_stats: print abi.behaviour_summary of the training rollouts (and of the greedy test rollout) at every report")
 ap.add_argument("--set", action="append", default=[], help="extra config override key=value (python literal)")
 a = ap.parse_args()
 c = CONFIGS[a.config]
@@ -37,6 +39,8 @@ over = dict(runner="hip_graph", train_graph=1, batch_size_run=N, batch_size=16, 
             store_state=False, train_steps_per_rollout=a.train_steps_per_rollout,
             env_args=dict(num_agents=n, map=c["map"], episode_limit=T, view_size=c["view_size"], seed=a.seed),
             use_cuda=True, save_model=False, runner_stats=False, learner_log_interval=10 ** 12)
+if a.behaviour_stats:
+    over["behaviour_stats"] = True
 import ast
 for kv in a.set:
     k, v = kv.split("=", 1)
@@ -148,6 +152,13 @@ for it in range(a.iters):
                   logs.get("loss_value_inc", float("nan")), logs.get("loss_sim", float("nan")), logs.get("q_env_taken_mean", float("nan")),
                   logs.get("q_inc_taken_mean", float("nan")), float(ctx.learner._flat_grad.norm()),
                   float(ctx.runner.store["clean_num"][:, :-1].mean()), float(p.norm()), bool(th.isfinite(p).all()), time.time() - t0), flush=True)
+        if a.behaviour_stats:      # the rollouts since the last report (the accumulators are zeroed here: runner_stats is off in this tool)
+            from homophily_marl_amd import abi
+            for mode, label in ((False, "train "), (True, "greedy")):
+                b = ctx.runner.behaviour(test_mode=mode, reset=True)
+                vec = [x for k in abi.behaviour_layout(n, ctx.args.n_actions) for x in b[k].reshape(-1)]
+                s = abi.behaviour_summary(vec, n, ctx.args.n_actions)
+                print("   behaviour %s (%d episodes): " % (label, int(b["n_episodes"][0])) + "  ".join("%s %.4f" % kv for kv in s.items()), flush=True)
         acc, cnt = 0.0, 0
         assert bool(th.isfinite(p).all())
 assert ctx.runner.env.native.poll_error() == 0
