@@ -370,6 +370,19 @@ BEHAVIOUR_ROLES = ("idle", "cleaner", "harvester", "mixed")
 BEHAVIOUR_SIGNATURES = {"ssd_behaviour_stats": (C.c_int, [C.POINTER(SsdBehaviourArgs), C.c_void_p])}
 
 
+class SsdWindowField(C.Structure):
+    """ssd_window_field (include/ssd_hip.h): one field of ssd_gather_windows."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("slot_bytes", C.c_int64), ("filled", C.c_int32), ("reserved", C.c_int32)]
+
+
+# the two exports of training on sampled time windows, in a table of their own like ssd_behaviour_stats (their checks:
+# tests/test_train_window_host.py)
+WINDOW_SIGNATURES = {
+    "ssd_sample_windows": (C.c_int, [C.c_uint64, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ssd_gather_windows": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+}
+
+
 def behaviour_len(n, A):
     """SSD_BEHAVIOUR_LEN"""
     return 12 * n + n * A + 3 * n * n + 3
@@ -461,6 +474,7 @@ def load_library():
         lib = C.CDLL(HIP_LIB_PATH)
         bind(lib, HIP_SIGNATURES)
         bind(lib, BEHAVIOUR_SIGNATURES)
+        bind(lib, WINDOW_SIGNATURES)
         ver = lib.ssd_abi_version()
         if ver != ABI_VERSION:
             raise ImportError("libssd_hip.so ABI version %d != %d" % (ver, ABI_VERSION))

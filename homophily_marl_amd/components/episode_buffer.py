@@ -166,6 +166,10 @@ class ReplayBuffer(EpisodeBatch):
         self._sample_seed = None
         self._sample_calls = 0
         self._sample_ids = None
+        # time windows (sample_windows): "episode" | "window", the length a window batch's rewards are divided by (gather_windows)
+        self.window_norm = "episode"
+        self._window_draws = None
+        self.last_window_ids = self.last_window_t0 = None
 
     def reserve(self, n):
         """A view over the next n episode slots, for producers that write whole episodes in place (vectorised runners): hand
@@ -228,6 +232,74 @@ class ReplayBuffer(EpisodeBatch):
                     th.index_select(v, 0, ids, out=dst)
             return out
         return self[ids]
+
+    # ---- time windows (config keys train_window / train_burn_in / train_window_norm) -------------------------------------------
+    def gather_windows(self, ids, t0, window, burn_in, out=None):
+        """An EpisodeBatch of window + 1 slots: row e holds slots [t0[e], t0[e] + window] of episode ids[e] (slot t0 + window is the
+        bootstrap slot, as slot T of a whole episode).  The first K_e rows carry no loss, K_e = burn_in if t0[e] > 0 and 0 if
+        t0[e] == 0 (there the zero hidden state is the true state), expressed through `filled` alone: filled[e, r] = the stored value
+        * (r >= K_e).  The batch carries `reward_norm`, the length the learner divides the rewards by: the episode's slot count
+        (window_norm "episode": targets keep their scale whatever the window) or window + 1 ("window": the reference run on the
+        slice).  Device buffers: every field in ONE launch (ssd_gather_windows), ids / t0 stay on the device; out: an EpisodeBatch
+        of that shape on the buffer's device that receives the windows (a learner's static batch).  The caller guarantees ids within
+        the stored episodes and t0 + window < max_seq_length on device tensors; host indices are checked."""
+        T = self.max_seq_length - 1
+        if not 1 <= window <= T or not 0 <= burn_in < window:
+            raise ValueError("gather_windows: window %r outside 1 .. %d or burn_in %r outside 0 .. window - 1" % (window, T, burn_in))
+        W = window + 1
+        as_idx = lambda x: x.to(device=self.device, dtype=th.long) if isinstance(x, th.Tensor) else th.as_tensor(np.asarray(x), dtype=th.long, device=self.device)
+        ids, t0 = as_idx(ids), as_idx(t0)
+        B = ids.numel()
+        src = self.data.transition_data
+        if out is not None and not (out.batch_size == B and out.max_seq_length == W and not self.data.episode_data
+                                    and all(out.data.transition_data[k].device == v.device for k, v in src.items())):
+            raise ValueError("gather_windows: out is not a batch of %d windows of %d slots on the buffer's device" % (B, W))
+        if out is None:
+            nd = SimpleNamespace(transition_data={k: th.empty((B, W) + tuple(v.shape[2:]), dtype=v.dtype, device=v.device) for k, v in src.items()},
+                                 episode_data={k: v[ids] for k, v in self.data.episode_data.items()})
+            out = EpisodeBatch(self.scheme, self.groups, B, W, data=nd, device=self.device)
+        out.reward_norm = float(self.max_seq_length if self.window_norm == "episode" else W)
+        keys = list(src)
+        pairs = [(src[k], out.data.transition_data[k]) for k in keys]
+        if ids.is_cuda and ops.gather_windows(pairs, ids, t0, self.max_seq_length, W, burn_in, keys.index("filled")):
+            return out
+        ops._leaving_kernels("gather_windows", ids, "fields that do not qualify for ssd_gather_windows")
+        if not ids.is_cuda and B and not (0 <= int(ids.min()) and int(ids.max()) < self.buffer_size and 0 <= int(t0.min()) and int(t0.max()) + W <= self.max_seq_length):
+            raise IndexError("gather_windows: ids or t0 outside the buffer")
+        rows = th.arange(W, device=ids.device)
+        slots = t0.unsqueeze(1) + rows
+        for k, (v, dst) in zip(keys, pairs):
+            dst.copy_(v[ids.unsqueeze(1), slots])
+        keep = rows.unsqueeze(0) >= th.where(t0 > 0, burn_in, 0).unsqueeze(1)
+        out.data.transition_data["filled"].mul_(keep.reshape((B, W) + (1,) * (src["filled"].dim() - 2)).to(src["filled"].dtype))
+        return out
+
+    def sample_windows(self, batch_size, window, burn_in, out=None):
+        """batch_size windows of `window` transitions, one per sampled episode: the episodes sample() would draw (device buffers:
+        the ids of ssd_sample_ids for the same seed and call) and a start t0 uniform on 0 .. T - window each, gathered by
+        gather_windows.  Device buffers draw both in ONE launch (ssd_sample_windows); host buffers use numpy's generator.  The drawn
+        (ids, t0) stay in last_window_ids / last_window_t0.  With exactly batch_size episodes stored the ids are 0 .. batch_size - 1,
+        as in sample(); the starts are still drawn."""
+        assert self.can_sample(batch_size)
+        n_starts = self.max_seq_length - window
+        if n_starts < 1:
+            raise ValueError("sample_windows: window %r outside 1 .. %d" % (window, self.max_seq_length - 1))
+        if th.device(self.device).type == "cuda" and batch_size <= ops.abi.SAMPLE_IDS_MAX:
+            if self._sample_seed is None:
+                self._sample_seed = int(np.random.randint(0, 2 ** 31 - 1)) | (int(np.random.randint(0, 2 ** 31 - 1)) << 32)
+            if self._window_draws is None or self._window_draws.shape[1] != batch_size:
+                self._window_draws = th.empty(2, batch_size, dtype=th.long, device=self.device)
+            ids, t0 = ops.sample_windows(self._sample_seed, self._sample_calls, self.episodes_in_buffer, batch_size, n_starts,
+                                         self._window_draws[0], self._window_draws[1])
+            if self.episodes_in_buffer == batch_size:
+                ids.copy_(th.arange(batch_size, device=self.device))
+        else:
+            ep_ids = np.arange(batch_size) if self.episodes_in_buffer == batch_size else np.random.choice(self.episodes_in_buffer, batch_size, replace=False)
+            ids = th.as_tensor(ep_ids, dtype=th.long, device=self.device)
+            t0 = th.as_tensor(np.random.randint(0, n_starts, batch_size), dtype=th.long, device=self.device)
+        self._sample_calls += 1
+        self.last_window_ids, self.last_window_t0 = ids, t0
+        return self.gather_windows(ids, t0, window, burn_in, out=out)
 
     def sample_latest(self, batch_size):
         ep_ids = np.arange(self.buffer_index - batch_size, self.buffer_index) % self.buffer_size

@@ -525,6 +525,37 @@ int ssd_runner_stats(const float* collective_return, const float* equality, cons
     launch_runner_stats(collective_return, equality, episode_return, n_env, n_returns, acc, (hipStream_t)stream);
     return launched();
 }
+int ssd_sample_windows(uint64_t seed, uint32_t call, int32_t population, int32_t count, int32_t n_starts, int64_t* ids, int64_t* t0, void* stream) {
+    if (!ids || !t0) return fail(SSD_ERR_INVALID, "ssd_sample_windows: null pointer");
+    if (count < 1 || count > SSD_SAMPLE_IDS_MAX || population < count) return fail(SSD_ERR_INVALID, "ssd_sample_windows: 1 <= count <= min(population, SSD_SAMPLE_IDS_MAX)");
+    if (n_starts < 1) return fail(SSD_ERR_INVALID, "ssd_sample_windows: n_starts >= 1");
+    launch_sample_windows(seed, call, population, count, n_starts, ids, t0, (hipStream_t)stream);
+    return SSD_OK;
+}
+
+int ssd_gather_windows(const ssd_window_field* fields, int32_t count, const int64_t* ids, const int64_t* t0, int32_t n_ids, int32_t src_slots,
+                       int32_t win_slots, int32_t burn_in, void* stream) {
+    if (!fields || !ids || !t0) return fail(SSD_ERR_INVALID, "ssd_gather_windows: null pointer");
+    if (count < 1 || count > SSD_COPY_BLOCKS_MAX) return fail(SSD_ERR_INVALID, "ssd_gather_windows: 1..SSD_COPY_BLOCKS_MAX fields");
+    if (n_ids < 1 || n_ids > 65535) return fail(SSD_ERR_INVALID, "ssd_gather_windows: n_ids outside 1 .. 65535");
+    if (win_slots < 2 || win_slots > src_slots) return fail(SSD_ERR_INVALID, "ssd_gather_windows: win_slots outside 2 .. src_slots");
+    if (burn_in < 0 || burn_in > win_slots - 2) return fail(SSD_ERR_INVALID, "ssd_gather_windows: burn_in outside 0 .. win_slots - 2");
+    int n_filled = 0;
+    for (int i = 0; i < count; ++i) {
+        const ssd_window_field& f = fields[i];
+        if (!f.src || !f.dst || f.slot_bytes < 1) return fail(SSD_ERR_INVALID, "ssd_gather_windows: bad field (null pointer or slot_bytes < 1)");
+        // the grid is one workgroup per 8 KiB of destination: 64 GiB per field keeps the sum over 32 fields inside a 32-bit grid
+        if (f.slot_bytes > (int64_t)(1ll << 36) / ((int64_t)n_ids * win_slots)) return fail(SSD_ERR_INVALID, "ssd_gather_windows: a field's destination is over 64 GiB");
+        if (f.filled) {
+            ++n_filled;
+            if (n_filled > 1 || f.slot_bytes != 8 || (reinterpret_cast<uintptr_t>(f.src) & 7) || (reinterpret_cast<uintptr_t>(f.dst) & 7))
+                return fail(SSD_ERR_INVALID, "ssd_gather_windows: at most one filled field, of 8-byte slots at 8-byte aligned pointers");
+        }
+    }
+    launch_gather_windows(fields, count, ids, t0, n_ids, src_slots, win_slots, burn_in, (hipStream_t)stream);
+    return SSD_OK;
+}
+
 int ssd_behaviour_stats(const ssd_behaviour_args* a, void* stream) {
     if (!a) return fail(SSD_ERR_INVALID, "ssd_behaviour_stats: null args");
     if (!a->actions || !a->actions_inc || !a->reward || !a->clean_num || !a->workspace || !a->acc)

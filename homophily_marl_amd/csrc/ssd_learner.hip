@@ -811,6 +811,164 @@ void launch_sample_ids(uint64_t seed, uint32_t call, int population, int count, 
     hipLaunchKernelGGL(k_sample_ids, dim3(1), dim3(64), 0, stream, (uint32_t)seed, (uint32_t)(seed >> 32), call, population, count, out);
 }
 
+// k_sample_windows: the ids of k_sample_ids (the same draws, the same Floyd and Fisher-Yates steps) and one window start per id from the
+// draws the ids do not use: t0[e] = floor(draw(2 count + e) n_starts / 2^32) (include/ssd_hip.h).  One wave.  Every draw depends on
+// its index alone, so the lanes form all of them first: the Floyd candidates t_i and the Fisher-Yates partners k_i go to LDS, the
+// starts straight out.  What stays serial is the chain over the picks, and that runs in registers: pick s * 64 + l lives in p[s] of
+// lane l (S = ceil(count / 64) slots, -1 while unset), "already picked" is S compares per lane and a ballot, a swap two readlanes
+// and two predicated moves; the next step's t / k is fetched from LDS a step ahead.  (One thread walking the picks in LDS, as
+// k_sample_ids does at its 16 ids, took 41 us at 64 ids and 118 us at 128: the compares are quadratic in count.)
+template <int S>
+__global__ __launch_bounds__(64) void k_sample_windows(uint32_t s0, uint32_t s1, uint32_t call, int population, int count, int n_starts,
+                                                       int64_t* __restrict__ ids, int64_t* __restrict__ t0) {
+    __shared__ int32_t tv[SSD_SAMPLE_IDS_MAX], kv[SSD_SAMPLE_IDS_MAX];
+    if (blockIdx.x != 0) return;
+    const int lane = threadIdx.x;
+    for (int i = lane; i < count; i += 64) {
+        tv[i] = (int)(((uint64_t)sample_draw(s0, s1, call, (uint32_t)i) * (uint32_t)(population - count + i + 1)) >> 32);
+        kv[i] = (int)(((uint64_t)sample_draw(s0, s1, call, (uint32_t)(count + i)) * (uint32_t)(i + 1)) >> 32);      // (kv[0] is never used)
+        t0[i] = (int64_t)(((uint64_t)sample_draw(s0, s1, call, (uint32_t)(2 * count + i)) * (uint32_t)n_starts) >> 32);
+    }
+    __syncthreads();
+    int32_t p[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) p[s] = -1;
+    int t = tv[0];
+    for (int i = 0; i < count; ++i) {                                    // Floyd: pick[i] = t_i, or j = population - count + i if t_i is taken
+        const int t_next = tv[i + 1 < count ? i + 1 : i];
+        bool found = false;
+#pragma unroll
+        for (int s = 0; s < S; ++s) found |= p[s] == t;
+        const int v = __ballot(found) ? population - count + i : t;
+#pragma unroll
+        for (int s = 0; s < S; ++s)
+            if (s == (i >> 6) && lane == (i & 63)) p[s] = v;
+        t = t_next;
+    }
+    int k = kv[count - 1];
+    for (int i = count - 1; i > 0; --i) {                                // Fisher-Yates: swap(pick[i], pick[k_i])
+        const int k_next = kv[i - 1];
+        const int ku = __builtin_amdgcn_readfirstlane(k);
+        int va = 0, vb = 0;
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            va = s == (i >> 6) ? p[s] : va;
+            vb = s == (ku >> 6) ? p[s] : vb;
+        }
+        const int a = __builtin_amdgcn_readlane(va, i & 63), b = __builtin_amdgcn_readlane(vb, ku & 63);
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            if (s == (i >> 6) && lane == (i & 63)) p[s] = b;
+            if (s == (ku >> 6) && lane == (ku & 63)) p[s] = a;
+        }
+        k = k_next;
+    }
+#pragma unroll
+    for (int s = 0; s < S; ++s)
+        if (s * 64 + lane < count) ids[s * 64 + lane] = (int64_t)p[s];
+}
+void launch_sample_windows(uint64_t seed, uint32_t call, int population, int count, int n_starts, int64_t* ids, int64_t* t0, hipStream_t stream) {
+    const uint32_t s0 = (uint32_t)seed, s1 = (uint32_t)(seed >> 32);
+    if (count <= 64) hipLaunchKernelGGL(k_sample_windows<1>, dim3(1), dim3(64), 0, stream, s0, s1, call, population, count, n_starts, ids, t0);
+    else if (count <= 128) hipLaunchKernelGGL(k_sample_windows<2>, dim3(1), dim3(64), 0, stream, s0, s1, call, population, count, n_starts, ids, t0);
+    else if (count <= 256) hipLaunchKernelGGL(k_sample_windows<4>, dim3(1), dim3(64), 0, stream, s0, s1, call, population, count, n_starts, ids, t0);
+    else hipLaunchKernelGGL(k_sample_windows<SSD_SAMPLE_IDS_MAX / 64>, dim3(1), dim3(64), 0, stream, s0, s1, call, population, count, n_starts, ids, t0);
+}
+
+// k_gather_windows: windows [t0[e], t0[e] + win_slots) of rows ids[e] of up to SSD_COPY_BLOCKS_MAX fields into consecutive rows of
+// their destinations (ssd_gather_windows).  One 1-D grid: field f owns the workgroups [block0[f], block0[f + 1]).
+// A copied field's destination is ONE dense byte range [dst, dst + n_ids W), W = win_slots slot_bytes, cut into the 16-byte-aligned
+// granules of its absolute address.  A thread takes GATHER_UNROLL granules.  A granule that lies inside the range and inside one
+// window is one 16-byte load at the source's alignment (t0 slot_bytes lands anywhere) and one aligned 16-byte store; the loads of a
+// thread's granules are all issued before its first store.  The other granules -- the range's two ends, and wherever a window ends
+// inside a granule (W = 2 for `terminated` at win_slots 2: eight windows per granule) -- go byte by byte, each byte from its own
+// window.  Which way a granule goes depends on the launch's arguments only, never on ids or t0.
+// The `filled` field goes by int64 slots: the load is unconditional and the burn-in rule a multiplication.
+constexpr int GATHER_UNROLL = 2;
+struct WindowField { const uint8_t* src; uint8_t* dst; int64_t slot_bytes; int32_t block0, filled; };
+struct WindowTable { WindowField f[SSD_COPY_BLOCKS_MAX]; };
+struct __attribute__((packed, aligned(1))) u128_unaligned { uint32_t v[4]; };
+__global__ __launch_bounds__(256) void k_gather_windows(WindowTable t, int count, const int64_t* __restrict__ ids, const int64_t* __restrict__ t0,
+                                                        int n_ids, int src_slots, int win_slots, int burn_in) {
+    int fi = 0;
+    for (int i = 1; i < count; ++i) fi = (int)blockIdx.x >= t.f[i].block0 ? i : fi;
+    const WindowField f = t.f[fi];
+    const int blk = (int)blockIdx.x - f.block0;
+    if (f.filled) {
+        const int64_t total = (int64_t)n_ids * win_slots;
+        const int64_t i = (int64_t)blk * 256 + threadIdx.x;
+        if (i < total) {
+            const int e = (int)(i / win_slots), r = (int)(i - (int64_t)e * win_slots);
+            const int64_t start = t0[e];
+            const int64_t v = reinterpret_cast<const int64_t*>(f.src)[(ids[e] * src_slots + start) + r];
+            reinterpret_cast<int64_t*>(f.dst)[i] = v * (int64_t)(r >= (start > 0 ? burn_in : 0));
+        }
+        return;
+    }
+    const uint64_t W = (uint64_t)win_slots * (uint64_t)f.slot_bytes, D = (uint64_t)n_ids * W;
+    const uint64_t row = (uint64_t)src_slots * (uint64_t)f.slot_bytes;
+    const uint64_t d0 = reinterpret_cast<uint64_t>(f.dst), dA = d0 & ~(uint64_t)15;
+    const uint64_t granules = (d0 + D - dA + 15) >> 4;
+    uint64_t first[GATHER_UNROLL], w[GATHER_UNROLL];
+    const uint8_t* s[GATHER_UNROLL];
+    int e[GATHER_UNROLL], len[GATHER_UNROLL];
+    bool wide[GATHER_UNROLL];
+#pragma unroll
+    for (int u = 0; u < GATHER_UNROLL; ++u) {
+        const uint64_t g = ((uint64_t)blk * GATHER_UNROLL + u) * 256 + threadIdx.x;
+        const uint64_t lo = dA + (g << 4);
+        uint64_t a = lo < d0 ? d0 : lo, b = lo + 16 < d0 + D ? lo + 16 : d0 + D;
+        if (g >= granules) a = b = d0;                                   // past the field's last granule: nothing to do
+        first[u] = a - d0;
+        len[u] = (int)(b - a);
+        const uint64_t o = len[u] > 0 ? first[u] : 0;
+        e[u] = (int)(o / W);
+        w[u] = o - (uint64_t)e[u] * W;
+        wide[u] = len[u] == 16 && w[u] + 16 <= W;
+    }
+#pragma unroll
+    for (int u = 0; u < GATHER_UNROLL; ++u)                              // e < n_ids always (o < D, or o = 0)
+        s[u] = f.src + ((uint64_t)ids[e[u]] * row + (uint64_t)t0[e[u]] * (uint64_t)f.slot_bytes);
+    u128_unaligned v[GATHER_UNROLL];
+#pragma unroll
+    for (int u = 0; u < GATHER_UNROLL; ++u)
+        if (wide[u]) v[u] = *reinterpret_cast<const u128_unaligned*>(s[u] + w[u]);
+#pragma unroll
+    for (int u = 0; u < GATHER_UNROLL; ++u)
+        if (wide[u]) *reinterpret_cast<uint4*>(f.dst + first[u]) = make_uint4(v[u].v[0], v[u].v[1], v[u].v[2], v[u].v[3]);
+#pragma unroll
+    for (int u = 0; u < GATHER_UNROLL; ++u) {
+        if (wide[u] || len[u] <= 0) continue;
+        int ee = e[u];
+        uint64_t ww = w[u];
+        const uint8_t* ss = s[u];
+        for (int k = 0; k < len[u]; ++k) {
+            f.dst[first[u] + k] = ss[ww];
+            if (++ww == W && k + 1 < len[u]) {                           // the next byte opens window ee + 1 (< n_ids: it lies inside the range)
+                ww = 0;
+                ++ee;
+                ss = f.src + ((uint64_t)ids[ee] * row + (uint64_t)t0[ee] * (uint64_t)f.slot_bytes);
+            }
+        }
+    }
+}
+void launch_gather_windows(const ssd_window_field* fields, int count, const int64_t* ids, const int64_t* t0, int n_ids, int src_slots,
+                           int win_slots, int burn_in, hipStream_t stream) {
+    WindowTable t;
+    int blocks = 0;
+    for (int i = 0; i < SSD_COPY_BLOCKS_MAX; ++i) {
+        const ssd_window_field& f = fields[i < count ? i : 0];
+        t.f[i] = WindowField{static_cast<const uint8_t*>(f.src), static_cast<uint8_t*>(f.dst), f.slot_bytes, blocks, f.filled};
+        if (i >= count) continue;
+        const uint64_t D = (uint64_t)n_ids * (uint64_t)win_slots * (uint64_t)f.slot_bytes;
+        // a copied field: its granules (one more when dst is not 16-byte aligned), GATHER_UNROLL per thread; `filled`: a slot per thread
+        const uint64_t items = f.filled ? (uint64_t)n_ids * (uint64_t)win_slots : ((reinterpret_cast<uint64_t>(f.dst) & 15) + D + 15) >> 4;
+        const uint64_t per_block = f.filled ? 256 : 256 * GATHER_UNROLL;
+        blocks += (int)((items + per_block - 1) / per_block);
+    }
+    hipLaunchKernelGGL(k_gather_windows, dim3(blocks), dim3(256), 0, stream, t, count, ids, t0, n_ids, src_slots, win_slots, burn_in);
+}
+
 void launch_copy_blocks(const ssd_block_copy* blocks, int count, hipStream_t stream) {
     CopyTable t;
     int most = 1;

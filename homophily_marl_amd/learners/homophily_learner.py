@@ -306,7 +306,7 @@ class HomophilyLearner:
 
         # incentive reward transfer (:94-115): HIP kernel
         give_value, recv_pos_all, recv_neg_all, recv_zero_all, rewards_for_env, rewards_for_inc = ops.incentive_transfer(
-            actions_inc_all.squeeze(-1), rewards, a.incentive_ratio, a.incentive_cost, float(a.incentive), float(batch.max_seq_length))
+            actions_inc_all.squeeze(-1), rewards, a.incentive_ratio, a.incentive_cost, float(a.incentive), ops.reward_norm(batch))
         receive_positive, receive_negative, receive_zero = recv_pos_all[:, :-1], recv_neg_all[:, :-1], recv_zero_all[:, :-1]
         receive_value = receive_positive - receive_negative
 
@@ -459,6 +459,7 @@ class HomophilyLearner:
             self._static_batch = EpisodeBatch(batch.scheme, batch.groups, batch.batch_size, batch.max_seq_length,
                                               data=SimpleNamespace(transition_data=self._static_data, episode_data={}),
                                               device=batch.device)
+            self._static_batch.reward_norm = getattr(batch, "reward_norm", None)      # a window batch's normaliser is baked into the graph
             self._static_dens = th.zeros(2, device=batch.device)
             th.cuda.synchronize()
             # the step is captured on a stream of this learner's own: per-(device, stream) kernel scratch (the row-chunked affine
@@ -473,6 +474,10 @@ class HomophilyLearner:
             with th.cuda.graph(g2, pool=g1.pool(), stream=self._capture_stream, capture_error_mode="thread_local"):
                 self.clip_and_step()
             self._graph = (g1, g2)
+        st = self._static_batch
+        if (batch.batch_size, batch.max_seq_length, ops.reward_norm(batch)) != (st.batch_size, st.max_seq_length, ops.reward_norm(st)):
+            raise ValueError("the train step was captured for %d x %d slots (reward normaliser %g), got a batch of %d x %d (%g)" % (
+                st.batch_size, st.max_seq_length, ops.reward_norm(st), batch.batch_size, batch.max_seq_length, ops.reward_norm(batch)))
         for k, v in batch.data.transition_data.items():
             dst = self._static_data[k]
             if v.data_ptr() != dst.data_ptr() or v.shape != dst.shape:      # not sampled straight into the static batch (sample_out)
@@ -503,7 +508,8 @@ class HomophilyLearner:
 
     def sample_out(self):
         """The static batch of the captured train step once it exists (else None): ReplayBuffer.sample(batch_size, out=...) gathers
-        the sampled episodes straight into it and train() then copies nothing."""
+        the sampled episodes straight into it and train() then copies nothing.  Under train_window it has the window's shape
+        (train_window + 1 slots: the step is captured on the first window batch) and ReplayBuffer.sample_windows fills it."""
         return self._static_batch if self._graph is not None else None
 
     def train(self, batch, t_env, episode_num):

@@ -152,6 +152,12 @@ def incentive_transfer(actions_inc, rewards, effect_ratio, cost_ratio, incentive
     return give, rp, rn, rz, re, ri
 
 
+def reward_norm(batch):
+    """The length the rewards are divided by (homophily_learner.py:112-115, `/ batch.max_seq_length`): the attribute a window batch
+    carries (ReplayBuffer.gather_windows; config key train_window_norm), else the batch's own slot count."""
+    return float(getattr(batch, "reward_norm", None) or batch.max_seq_length)
+
+
 def _td_loss_args(batch, a, n_actions, partials):
     """ssd_td_loss_args over the batch's tensors (contiguous copies where a view is not); returns (args, keep-alive list)."""
     c = lambda x: x.contiguous()
@@ -164,7 +170,7 @@ def _td_loss_args(batch, a, n_actions, partials):
     t.batch, t.t_slots, t.n_agents, t.n_actions, t.sim_horizon, t.double_q = B, T1, n, n_actions, int(a.sim_horizon), int(bool(a.double_q))
     t.gamma_env, t.gamma_inc, t.reward_scale = float(a.gamma_env), float(a.gamma_inc), float(a.reward_scale)
     t.incentive_ratio, t.incentive_cost, t.incentive = float(a.incentive_ratio), float(a.incentive_cost), float(a.incentive)
-    t.seq_len, t.sim_threshold, t.sim_loss_weight = float(T1), float(a.sim_threshold), float(a.sim_loss_weight)
+    t.seq_len, t.sim_threshold, t.sim_loss_weight = reward_norm(batch), float(a.sim_threshold), float(a.sim_loss_weight)
     t.consider_others_inc = int(bool(a.consider_others_inc))
     t.td_lambda = float(getattr(a, "td_lambda", 0.0) or 0.0)
     for k, v in keep.items():
@@ -518,6 +524,49 @@ def gather_rows(pairs, ids):
     for e, (src, dst) in zip(tab, pairs):
         e.src, e.dst, e.row_bytes = src.data_ptr(), dst.data_ptr(), src[0].numel() * src.element_size()
     abi.check(lib, lib.ssd_gather_rows(tab, len(pairs), ids.contiguous().data_ptr(), n, _stream(ids)))
+    return True
+
+
+def sample_windows(seed, call, population, count, n_starts, ids_out, t0_out):
+    """ids_out[0 .. count) as sample_ids gives them for the same (seed, call, population, count), and t0_out[e] uniform on
+    [0, n_starts) from the draws the ids do not use: t0[e] = floor(draw(2 count + e) n_starts / 2^32) (include/ssd_hip.h:
+    ssd_sample_windows).  Device tensors: ONE launch.  Host tensors: the same arithmetic restated.  Returns (ids_out, t0_out)."""
+    assert ids_out.dtype == th.long and t0_out.dtype == th.long and ids_out.numel() >= count and t0_out.numel() >= count
+    assert 1 <= count <= population and n_starts >= 1 and ids_out.is_cuda == t0_out.is_cuda
+    if ids_out.is_cuda:
+        assert ids_out.is_contiguous() and t0_out.is_contiguous()
+        lib = abi.load_library()
+        abi.check(lib, lib.ssd_sample_windows(seed & (2 ** 64 - 1), call & 0xFFFFFFFF, population, count, n_starts, ids_out.data_ptr(),
+                                              t0_out.data_ptr(), _stream(ids_out)))
+        return ids_out, t0_out
+    sample_ids(seed, call, population, count, ids_out)
+    t0_out[:count] = th.tensor([(_sample_draw(seed, call & 0xFFFFFFFF, 2 * count + e) * n_starts) >> 32 for e in range(count)], dtype=th.long)
+    return ids_out, t0_out
+
+
+def gather_windows(pairs, ids, t0, src_slots, win_slots, burn_in, filled_index):
+    """dst[e] = src[ids[e], t0[e] : t0[e] + win_slots] for every (src, dst) pair of contiguous device tensors [rows, src_slots, ...] ->
+    [len(ids), win_slots, ...], as ONE launch (ssd_gather_windows); pair number filled_index (None: no such pair) is the int64
+    `filled` mask and is written with the burn-in rule dst[e, r] = src[..] * (r >= K_e), K_e = burn_in if t0[e] > 0 else 0.
+    ids, t0: int64 device tensors; the caller guarantees ids within the rows and t0 + win_slots <= src_slots.
+    Returns False (nothing done) when a pair does not qualify -- the caller indexes field by field."""
+    if not pairs or len(pairs) > abi.COPY_BLOCKS_MAX or not (ids.is_cuda and t0.is_cuda) or ids.dtype != th.long or t0.dtype != th.long:
+        return False
+    n = ids.numel()
+    if n < 1 or n > 65535 or t0.numel() != n or not 2 <= win_slots <= src_slots or not 0 <= burn_in <= win_slots - 2:
+        return False
+    for k, (src, dst) in enumerate(pairs):
+        if not (src.is_cuda and dst.is_cuda and src.is_contiguous() and dst.is_contiguous() and src.dtype == dst.dtype and src.dim() >= 2
+                and src.shape[1] == src_slots and tuple(dst.shape[:2]) == (n, win_slots) and dst.shape[2:] == src.shape[2:] and src[0, 0].numel() > 0):
+            return False
+        if k == filled_index and not (src.dtype == th.long and src[0, 0].numel() == 1):
+            return False
+    lib = abi.load_library()
+    tab = (abi.SsdWindowField * len(pairs))()
+    for k, (e, (src, dst)) in enumerate(zip(tab, pairs)):
+        e.src, e.dst, e.slot_bytes, e.filled = src.data_ptr(), dst.data_ptr(), src[0, 0].numel() * src.element_size(), int(k == filled_index)
+    abi.check(lib, lib.ssd_gather_windows(tab, len(pairs), ids.contiguous().data_ptr(), t0.contiguous().data_ptr(), n, src_slots, win_slots,
+                                          burn_in, _stream(ids)))
     return True
 
 

@@ -59,6 +59,25 @@ def build_scheme(args, env_info):
     return scheme, groups, preprocess
 
 
+def _check_train_window(args, episode_limit, runner):
+    """The config keys of training on sampled time windows (absent = 0 / 0 / "episode": whole episodes), validated; returns the norm.
+    train_window L in 1 .. episode_limit: a train step sees batch_size windows of L transitions (L + 1 slots); train_burn_in K in
+    0 .. L - 1: the first K rows of a window that does not start at slot 0 carry no loss; train_window_norm: the length the rewards
+    are divided by, "episode" (episode_limit + 1) or "window" (L + 1)."""
+    L = args.train_window = int(getattr(args, "train_window", 0) or 0)
+    K = args.train_burn_in = int(getattr(args, "train_burn_in", 0) or 0)
+    norm = args.train_window_norm = getattr(args, "train_window_norm", "episode")
+    if norm not in ("episode", "window"):
+        raise ValueError('train_window_norm must be "episode" or "window", got %r' % (norm,))
+    if L < 0 or L > episode_limit:
+        raise ValueError("train_window %d outside 0 .. episode_limit = %d" % (L, episode_limit))
+    if K < 0 or (K >= L and (L > 0 or K > 0)):
+        raise ValueError("train_burn_in %d outside 0 .. train_window - 1 = %d" % (K, L - 1))
+    if L > 0 and not getattr(runner, "fixed_length_episodes", False):
+        raise ValueError("train_window > 0 needs a runner that fills every slot of an episode (the vectorised runners); runner %r does not" % (args.runner,))
+    return norm
+
+
 def setup(config, logger=None):
     """Build runner / buffer / mac / learner exactly in the order of run.py:84-135."""
     args = SimpleNamespace(**config)
@@ -85,6 +104,7 @@ def setup(config, logger=None):
     scheme, groups, preprocess = build_scheme(args, env_info)
     buffer = ReplayBuffer(scheme, groups, args.buffer_size, env_info["episode_limit"] + 1, preprocess=preprocess,
                           device="cpu" if args.buffer_cpu_only else args.device)
+    buffer.window_norm = _check_train_window(args, env_info["episode_limit"], runner)
     mac = mac_REGISTRY[args.mac](buffer.scheme, groups, args)
     runner.setup(scheme=scheme, groups=groups, preprocess=preprocess, mac=mac)
     learner = le_REGISTRY[args.learner](mac, buffer.scheme, logger, args)
@@ -114,6 +134,7 @@ def train_iteration(ctx, episode):
     reference's cadence is one).  The learner's episode counter (target sync every target_update_interval, homophily_learner.py:255-257)
     is the env-episode count under schedule_unit "env_steps" and the number of learner.train calls under "rollouts"."""
     a = ctx.args
+    window = getattr(a, "train_window", 0)
     marks = getattr(ctx, "_trace_marks", None)          # diagnostic (bench SSD_BENCH_TRACE): device events between the phases
 
     def mark(tag):
@@ -125,10 +146,14 @@ def train_iteration(ctx, episode):
     ctx.buffer.insert_episode_batch(batch)
     if ctx.buffer.can_sample(a.batch_size):
         for _ in range(a.train_steps_per_rollout):
-            sample = ctx.buffer.sample(a.batch_size, out=ctx.learner.sample_out() if hasattr(ctx.learner, "sample_out") else None)
+            out = ctx.learner.sample_out() if hasattr(ctx.learner, "sample_out") else None
+            if window > 0:                 # windows of a runner that fills every slot (setup checked): nothing to trim
+                sample = ctx.buffer.sample_windows(a.batch_size, window, a.train_burn_in, out=out)
+            else:
+                sample = ctx.buffer.sample(a.batch_size, out=out)
             # run.py:188-189 trims the sample to its longest episode; the vectorised runners always write episode_limit + 1 slots
             # (`filled` is all ones), so the trim is the identity there and the device -> host read of max_t_filled() is skipped
-            if not getattr(ctx.runner, "fixed_length_episodes", False):
+            if not window and not getattr(ctx.runner, "fixed_length_episodes", False):
                 sample = sample[:, :sample.max_t_filled()]
             if str(sample.device) != str(a.device):
                 sample.to(a.device)

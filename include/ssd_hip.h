@@ -347,6 +347,51 @@ typedef struct ssd_behaviour_args {
 } ssd_behaviour_args;
 int (ssd_behaviour_stats)(const ssd_behaviour_args* args, void* stream);
 
+/* Training on sampled time windows (config keys train_window / train_burn_in): one window of win_slots = L + 1 consecutive slots
+ * [t0, t0 + L] per sampled episode, drawn and gathered on the device.  Both names are declared in parentheses like
+ * ssd_behaviour_stats; their ctypes mirror is abi.WINDOW_SIGNATURES and their symbol, struct-size and refusal checks are
+ * tests/test_train_window_host.py.
+ *
+ * ssd_sample_windows: ids[0 .. count) exactly as ssd_sample_ids gives them for the same (seed, call, population, count) -- turning
+ * windows on does not change which episodes are sampled -- and t0[e] uniform on [0, n_starts):
+ *     t0[e] = floor(draw(2 * count + e) * n_starts / 2^32)
+ * where draw(i) is the counter generator's 32-bit draw number i of (seed, call), all arithmetic in u32 (mix32p: "Exploration draws"
+ * below), s0 / s1 the low / high 32 bits of seed:
+ *     draw(i) = mix32p(mix32p(s0 ^ (call * 0x9E3779B9)) ^ (s1 + i * 0x85EBCA6B))
+ * The ids are Floyd's subset sampling and a Fisher-Yates pass, every bounded draw floor(draw * m / 2^32):
+ *     for i = 0 .. count - 1:  j = population - count + i;  t = floor(draw(i) * (j + 1) / 2^32);  pick[i] = t already picked ? j : t
+ *     for i = count - 1 .. 1:  k = floor(draw(count + i) * (i + 1) / 2^32);  swap(pick[i], pick[k])
+ * so the id draws use i < 2 * count and the starts the indices from 2 * count on.  ONE launch; ids, t0: DEVICE int64
+ * [count].  A restatement for host tensors: ops.sample_windows.  Refused (SSD_ERR_INVALID): a NULL pointer, n_starts < 1, and what
+ * ssd_sample_ids refuses (count outside 1 .. min(population, SSD_SAMPLE_IDS_MAX)). */
+int (ssd_sample_windows)(uint64_t seed, uint32_t call, int32_t population, int32_t count, int32_t n_starts, int64_t* ids, int64_t* t0,
+                         void* stream);
+
+/* ssd_gather_windows: for every field f < count (1..SSD_COPY_BLOCKS_MAX) and every e < n_ids, win_slots * slot_bytes_f contiguous
+ * bytes from  src_f + (ids[e] * src_slots + t0[e]) * slot_bytes_f  to  dst_f + e * win_slots * slot_bytes_f, as ONE launch; ids and
+ * t0 (DEVICE int64 [n_ids]) are read on the device, nothing crosses the host boundary.  A field is a dense array of rows of src_slots
+ * slots of slot_bytes bytes, at any alignment; offsets across episodes are 64-bit.  A destination is one dense byte range: the kernel
+ * writes its 16-byte-aligned granules with one 16-byte store each (the source, whose alignment depends on t0, is read with loads of
+ * any alignment) and the granules that cross a window's end or the range's ends byte by byte.
+ * At most one field is flagged `filled` (slot_bytes 8: int64 slots, src and dst 8-byte aligned).  It is not copied but written with
+ * the burn-in rule: dst[e, r] = src[ids[e], t0[e] + r] * (r >= K_e), K_e = burn_in if t0[e] > 0, K_e = 0 if t0[e] == 0 (there the
+ * zero hidden state is the true state).
+ * The device validates neither ids nor t0: THE CALLER GUARANTEES 0 <= ids[e] < rows_f and 0 <= t0[e], t0[e] + win_slots <= src_slots.
+ * Then no load leaves [src_f, src_f + rows_f * src_slots * slot_bytes_f) and no store leaves the n_ids * win_slots destination slots.
+ * `fields` is a HOST array read during the call.  Refused (SSD_ERR_INVALID): a NULL pointer (fields, ids, t0, a field's src / dst);
+ * count outside 1 .. SSD_COPY_BLOCKS_MAX; n_ids outside 1 .. 65535; win_slots outside 2 .. src_slots; burn_in outside
+ * 0 .. win_slots - 2; slot_bytes < 1; a field whose destination is over 64 GiB; more than one `filled` field, or one whose
+ * slot_bytes != 8 or whose pointers are not 8-byte aligned. */
+typedef struct ssd_window_field {
+    const void* src;
+    void* dst;
+    int64_t slot_bytes;
+    int32_t filled;        /* 1: the `filled` mask (see above); 0: a plain copy */
+    int32_t reserved;
+} ssd_window_field;
+int (ssd_gather_windows)(const ssd_window_field* fields, int32_t count, const int64_t* ids, const int64_t* t0, int32_t n_ids,
+                         int32_t src_slots, int32_t win_slots, int32_t burn_in, void* stream);
+
 /* ssd_clip_adam_step: the optimiser tail of HomophilyLearner.cal_loss_and_step (homophily_learner.py:223-226) --
  *   clip_grad_norm_(params_inc, clip); clip_grad_norm_(params_env, clip); optimiser_inc.step(); optimiser_env.step()
  * with the conv encoder a member of BOTH parameter groups (homophily_agent.py:127-146: its gradient is scaled by both clips, the second

@@ -7,7 +7,8 @@ __global__ void k_empty(int* p) { if (p && threadIdx.x == 0 && blockIdx.x == 1u 
 int main() {
     struct { const char* name; int grid, block, lds; } cfg[] = {
         {"1 x 64, no LDS", 1, 64, 0}, {"k_env    1024 x 256, 27 KB", 1024, 256, 27648}, {"k_head    255 x 512, 136 KB", 255, 512, 139264},
-        {"k_encode  251 x 512, 60 KB", 251, 512, 61440}, {"2048 x 256, 8 KB", 2048, 256, 8192}};
+        {"k_encode  251 x 512, 60 KB", 251, 512, 61440}, {"2048 x 256, 8 KB", 2048, 256, 8192},
+        {"k_gather_windows 394 x 256", 394, 256, 0}};
     hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b);
     for (auto& c : cfg) {
         hipFuncSetAttribute((const void*)k_empty, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

@@ -31,6 +31,8 @@ ap.add_argument("--anomaly", action="store_true", help="torch.autograd.set_detec
 ap.add_argument("--nan-check", action="store_true", help="after every iteration: first non-finite gradient / parameter, with details")
 ap.add_argument("--behaviour-stats", action="store_true",
                 help="config key behaviour_stats: print abi.behaviour_summary of the training rollouts (and of the greedy test rollout) at every report")
+ap.add_argument("--train-window", type=int, default=0, help="config key train_window: train on windows of L transitions (0: whole episodes)")
+ap.add_argument("--burn-in", type=int, default=0, help="config key train_burn_in: rows of a window without loss")
 ap.add_argument("--set", action="append", default=[], help="extra config override key=value (python literal)")
 a = ap.parse_args()
 c = CONFIGS[a.config]
@@ -41,6 +43,8 @@ over = dict(runner="hip_graph", train_graph=1, batch_size_run=N, batch_size=16, 
             use_cuda=True, save_model=False, runner_stats=False, learner_log_interval=10 ** 12)
 if a.behaviour_stats:
     over["behaviour_stats"] = True
+if a.train_window:
+    over.update(train_window=a.train_window, train_burn_in=a.burn_in)
 import ast
 for kv in a.set:
     k, v = kv.split("=", 1)
