@@ -513,9 +513,10 @@ class HomophilyLearner:
         return self._static_batch if self._graph is not None else None
 
     def train(self, batch, t_env, episode_num):
-        if batch["reward"].is_cuda:
-            ops.set_learner_precision(self.precision)      # process-wide kernel selection; a captured step keeps what it was captured with
-        logs = self._graph_step(batch) if self.use_graph else self.cal_loss_and_step(batch)
+        # the kernel selection is process-wide: it is this learner's for the step only and goes back to what train() found (another
+        # learner, the eager controller and the SSD_GRAPH_CHECK re-evaluation keep theirs); a captured step keeps what it was captured with
+        with ops._precision(self.precision if batch["reward"].is_cuda else ops.LEARNER_PRECISION):
+            logs = self._graph_step(batch) if self.use_graph else self.cal_loss_and_step(batch)
         if (episode_num - self.last_target_update_episode) / self.args.target_update_interval >= 1.0:
             self._update_targets()
             self.last_target_update_episode = episode_num

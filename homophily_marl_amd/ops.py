@@ -42,8 +42,14 @@ def unroll_other(actions, pos, orient, reward, clean_num, apple_den, pos_scale, 
     """(other [T * B, n, A + 7], act_tm [n, T * B, A]) of a sampled batch on the device in ONE launch (ssd_unroll_other): the
     incentive head's per-receiver features [one-hot(a_j), pos_j / scale, orient_j, r_j, clean_j, apple_den_j] (homophily_agent.py:194-201)
     and the one-hot actions agent-major.  actions i64 [B, T, n], pos / orient [B, T, n, 2], reward / clean_num / apple_den [B, T, n]."""
-    lib = abi.load_library()
+    if actions.dtype != th.int64 or actions.dim() != 3:       # the kernel reads 8-byte indices [B, T, n]
+        raise _unfit("unroll_other", "actions", actions, "int64 [B, T, n] expected")
     B, T, n = actions.shape[:3]
+    for name, t, shape in (("pos", pos, (B, T, n, 2)), ("orient", orient, (B, T, n, 2)), ("reward", reward, (B, T, n)),
+                           ("clean_num", clean_num, (B, T, n)), ("apple_den", apple_den, (B, T, n))):
+        if t.shape != shape or t.device != actions.device:
+            raise _unfit("unroll_other", name, t, "%s on the device of actions expected" % (shape,))
+    lib = abi.load_library()
     c = lambda x: x.contiguous()
     actions, pos, orient, reward, clean_num, apple_den = c(actions), c(pos.float()), c(orient.float()), c(reward.float()), c(clean_num.float()), c(apple_den.float())
     other = th.empty(T * B, n, n_actions + 7, dtype=th.float32, device=actions.device)
@@ -66,6 +72,35 @@ def set_learner_precision(precision):
         lib = abi.load_library()
         abi.check(lib, lib.ssd_set_learner_precision(precision))
     LEARNER_PRECISION = precision
+
+
+class _precision:
+    """The learner precision for the launches of a block, what was set before restored on the way out.  Every Function whose launches
+    select on it (the affine layers, the dueling head, the encoder, the recurrence) records LEARNER_PRECISION in ctx at forward and runs
+    its backward launches under it: the precision belongs to the call, whatever the process-wide switch reads by the time the gradients
+    are asked for.  No launch, no library call when nothing changes."""
+
+    def __init__(self, precision):
+        self.precision = precision
+
+    def __enter__(self):
+        self.found = LEARNER_PRECISION
+        if self.precision != self.found:
+            set_learner_precision(self.precision)
+
+    def __exit__(self, *exc):
+        if self.precision != self.found:
+            set_learner_precision(self.found)
+
+
+def _f32_on(t, *others):
+    """every tensor f32 on t's device (the kernels read raw f32 pointers of one device)"""
+    return all(o.dtype == th.float32 and o.device == t.device for o in (t,) + others)
+
+
+def _unfit(op, arg, t, why):
+    """an argument neither the kernels nor the tensor-op statement can take: the error names it"""
+    return ValueError("ops.%s: %s %s: %s" % (op, arg, "%s %s on %s" % (tuple(t.shape), t.dtype, t.device), why))
 
 
 def set_strict(on=True):
@@ -93,6 +128,10 @@ def build_inputs_tail(out, offset, last_actions, last_reward, last_actions_inc, 
     B, n = pos.shape[0], pos.shape[1]
     A = n_actions
     if out.is_cuda:
+        for name, t, dtype in (("last_actions", last_actions, th.int64), ("last_actions_inc", last_actions_inc, th.int64),      # read as 8-byte indices
+                               ("last_reward", last_reward, th.float32), ("pos", pos, th.float32)):
+            if t is not None and (t.dtype != dtype or t.device != out.device):
+                raise _unfit("build_inputs_tail", name, t, "%s on the device of out expected" % dtype)
         lib = abi.load_library()
         cont = lambda x: None if x is None else x.contiguous()
         la, lr, li, p = cont(last_actions), cont(last_reward), cont(last_actions_inc), pos.contiguous()
@@ -131,6 +170,10 @@ def incentive_transfer(actions_inc, rewards, effect_ratio, cost_ratio, incentive
     B, T, n = actions_inc.shape[0], actions_inc.shape[1], actions_inc.shape[2]
     dev = actions_inc.device
     if actions_inc.is_cuda:
+        if actions_inc.dtype != th.int64 or actions_inc.dim() != 4 or actions_inc.shape[3] != n:       # the kernel reads 8-byte indices [B, T, n, n]
+            raise _unfit("incentive_transfer", "actions_inc", actions_inc, "int64 [B, T, n, n] expected")
+        if rewards.shape != (B, T - 1, n) or rewards.device != dev:
+            raise _unfit("incentive_transfer", "rewards", rewards, "%s on the device of actions_inc expected" % ((B, T - 1, n),))
         lib = abi.load_library()
         a = actions_inc.contiguous()
         r = rewards.contiguous().float()
@@ -335,7 +378,10 @@ def column_sums(x):
     cross-workgroup hand-off).  ATen's multi-block reduction kernels keep block-arrival semaphores that a memset node clears; inside a
     captured hipGraph they were observed to return ANOTHER reduction's partial sums on MI355X / ROCm 7.2 once other work ran
     between two replays (diverging / NaN training runs) -- so nothing inside the captured train step reduces over rows with them."""
-    if not x.is_cuda:
+    if x.dim() < 2:
+        raise _unfit("column_sums", "x", x, "[R, C] or [G, R, C] expected")
+    if not (x.is_cuda and x.dtype == th.float32 and x.dim() <= 3):      # the kernel reads f32 [G, R, C]
+        _leaving_kernels("column_sums", x, "dtype %s / rank %d" % (x.dtype, x.dim()))
         return x.sum(-2)
     lib = abi.load_library()
     x = x.contiguous()
@@ -386,10 +432,14 @@ def dueling_q(a, v, B, T, inner):
     """a [n, T * B * inner, K] (rows (t * B + b) * inner + j), v [n, T * B * inner, 1] -> q = v + a - mean_k a as [B, T, n, K]
     (inner = 1) or [B, T, n, inner, K]."""
     n, K = a.shape[0], a.shape[-1]
-    if a.is_cuda and a.dtype == th.float32 and K <= 16:
+    if a.dim() != 3 or a.shape[1] != T * B * inner:
+        raise _unfit("dueling_q", "a", a, "[n, T * B * inner = %d, K] expected" % (T * B * inner))
+    if v.shape != (n, T * B * inner, 1) or v.device != a.device:
+        raise _unfit("dueling_q", "v", v, "%s on the device of a expected" % ((n, T * B * inner, 1),))
+    if a.is_cuda and _f32_on(a, v) and K <= 16:
         q = _DuelingQ.apply(a, v, B, T, inner)
     else:
-        _leaving_kernels("dueling_q", a, "K = %d > 16 or dtype %s" % (K, a.dtype))
+        _leaving_kernels("dueling_q", a, "K = %d > 16 or dtypes %s, %s" % (K, a.dtype, v.dtype))
         q = (v + a - a.mean(dim=-1, keepdim=True)).reshape(n, T, B, inner, K).permute(2, 1, 0, 3, 4)
     return q.reshape(B, T, n, K) if inner == 1 else q
 
@@ -422,10 +472,16 @@ class _DuelingHead(th.autograd.Function):
         abi.check(lib, lib.ssd_dueling_head_fwd(y.data_ptr(), q.data_ptr(), n, T, B, inner, K, st))
         ctx.save_for_backward(h, w, *(() if other is None else (other,)))
         ctx.dims = (B, T, inner, K)
+        ctx.precision = LEARNER_PRECISION
         return q
 
     @staticmethod
     def backward(ctx, dq):
+        with _precision(ctx.precision):
+            return _DuelingHead._backward(ctx, dq)
+
+    @staticmethod
+    def _backward(ctx, dq):
         lib = abi.load_library()
         h, w = ctx.saved_tensors[:2]
         other = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
@@ -452,21 +508,33 @@ class _DuelingHead(th.autograd.Function):
             if need[0]:
                 dh = th.empty_like(h)
                 abi.check(lib, lib.ssd_bias_bmm_bwd_x(gs.data_ptr(), w.data_ptr(), dh.data_ptr(), n, TB, H, K + 1, (H + E) * (K + 1), st))
+        assert not need[1]       # no kernel emits dL/d other: dueling_head sends such a request to the tensor-op statement
         return dh, None, dw, db, None, None, None
 
 
 def dueling_head(h, other, w, b, B, T, inner):
     """q [B, T, n, K] (inner = 1, other None) or [B, T, n, inner, K] of one dueling head: h [n, T * B, H] the recurrence states (rows
     t * B + b), other [T * B, inner, E] or None, w [n, H (+ E), K + 1] = [advantage layer | value layer], b [n, 1, K + 1]."""
-    n, K = h.shape[0], w.shape[2] - 1
-    if h.is_cuda and h.dtype == th.float32 and K <= 15 and h.shape[-1] % 16 == 0:
+    if h.dim() != 3 or h.shape[1] != T * B:
+        raise _unfit("dueling_head", "h", h, "[n, T * B = %d, H] expected" % (T * B))
+    n, TB, H = h.shape
+    if other is not None and (other.dim() != 3 or tuple(other.shape[:2]) != (TB, inner) or other.device != h.device):
+        raise _unfit("dueling_head", "other", other, "[T * B = %d, inner = %d, E] on the device of h expected" % (TB, inner))
+    E = 0 if other is None else other.shape[-1]
+    if w.dim() != 3 or tuple(w.shape[:2]) != (n, H + E) or w.shape[2] < 2 or w.device != h.device:
+        raise _unfit("dueling_head", "w", w, "[n = %d, H (+ E) = %d, K + 1] on the device of h expected" % (n, H + E))
+    K = w.shape[2] - 1
+    if b.device != h.device:
+        raise _unfit("dueling_head", "b", b, "the device of h expected")
+    # the kernels: f32 throughout, b one row per weight set, the gradient of `other` not among those they emit
+    if (h.is_cuda and _f32_on(h, w, b) and K <= 15 and H % 16 == 0 and b.shape == (n, 1, K + 1) and (other is not None or inner == 1)
+            and (other is None or (other.dtype == th.float32 and E >= 1 and not (other.requires_grad and th.is_grad_enabled())))):
         q = _DuelingHead.apply(h, other, w, b, B, T, inner)
     else:
-        _leaving_kernels("dueling_head", h, "layout")
-        TB = h.shape[1]
+        _leaving_kernels("dueling_head", h, "layout / dtypes / a bias that is not [n, 1, K + 1] / other requires a gradient")
         x = h if other is None else th.cat([h.unsqueeze(2).expand(n, TB, inner, h.shape[-1]), other.unsqueeze(0).expand(n, TB, inner, other.shape[-1])],
                                           dim=-1).reshape(n, TB * inner, -1)
-        y = th.baddbmm(b, x, w)
+        y = _baddbmm(b, x, w)
         a, v = y[..., :K], y[..., K:]
         q = (v + a - a.mean(dim=-1, keepdim=True)).reshape(n, T, B, inner, K).permute(2, 1, 0, 3, 4)
     return q.reshape(B, T, n, K) if inner == 1 else q
@@ -632,8 +700,17 @@ def cat_groups(groups):
     return [th.cat(list(g), dim=-1) for g in groups]
 
 
+def _baddbmm(b, x, w):
+    """th.baddbmm(b, x, w), the tensor-op statement of the affine layers, in the operands' common dtype (baddbmm itself refuses mixed ones)"""
+    dt = th.promote_types(th.promote_types(b.dtype, x.dtype), w.dtype)
+    return th.baddbmm(b.to(dt), x.to(dt), w.to(dt))
+
+
 def _bmm_kernel_ok(x, w, b):
-    return (x.is_cuda and x.dtype == th.float32 and w.dtype == th.float32 and x.dim() == 3 and w.dim() == 3)
+    """ssd_bias_bmm_*: f32 x [n, R, I], w [n, I, O], b [n, 1, O] on one device -- the kernel reads w + g * I * O and b + g * O; any
+    other bias baddbmm broadcasts ([1, 1, O], [O], [n, R, O]) goes to the tensor-op statement."""
+    return (x.is_cuda and x.dim() == 3 and w.dim() == 3 and _f32_on(x, w, b) and w.shape[0] == x.shape[0] and w.shape[1] == x.shape[2]
+            and b.shape == (x.shape[0], 1, w.shape[2]))
 
 
 def _bias_bmm_fwd(x, w, b, leaky=False):
@@ -658,11 +735,17 @@ class _BiasBmm(th.autograd.Function):
         x, w = x.contiguous(), w.contiguous()
         y = _bias_bmm_fwd(x, w, b, leaky)
         ctx.leaky = leaky
+        ctx.precision = LEARNER_PRECISION
         ctx.save_for_backward(x, w, *((y,) if leaky else ()))
         return y
 
     @staticmethod
     def backward(ctx, g):
+        with _precision(ctx.precision):
+            return _BiasBmm._backward(ctx, g)
+
+    @staticmethod
+    def _backward(ctx, g):
         lib = abi.load_library()
         x, w = ctx.saved_tensors[:2]
         g = g.contiguous()
@@ -687,8 +770,14 @@ def bias_bmm(x, w, b, leaky=False):
         if th.is_grad_enabled() and (w.requires_grad or b.requires_grad or x.requires_grad):
             return _BiasBmm.apply(x, w, b, leaky)
         return _bias_bmm_fwd(x, w, b, leaky)
-    _leaving_kernels("bias_bmm", x, "dtype / rank")
-    y = th.baddbmm(b, x, w)
+    if x.dim() != 3:
+        raise _unfit("bias_bmm", "x", x, "[n, R, I] expected")
+    if w.dim() != 3 or tuple(w.shape[:2]) != (x.shape[0], x.shape[2]) or w.device != x.device:
+        raise _unfit("bias_bmm", "w", w, "[n = %d, I = %d, O] on the device of x expected" % (x.shape[0], x.shape[2]))
+    if b.device != x.device:
+        raise _unfit("bias_bmm", "b", b, "the device of x expected")
+    _leaving_kernels("bias_bmm", x, "dtypes %s, %s, %s / a bias that is not [n, 1, O]" % (x.dtype, w.dtype, b.dtype))
+    y = _baddbmm(b, x, w)
     return th.nn.functional.leaky_relu(y) if leaky else y
 
 
@@ -795,10 +884,16 @@ class _EncodeCodes(th.autograd.Function):
             feat = th.nn.functional.leaky_relu(column_sums(part.view(bands, R * 32)).view(R, 32) + lb)
         if need:
             ctx.save_for_backward(codes, act, feat, cw, lw)
+        ctx.precision = prec
         return feat
 
     @staticmethod
     def backward(ctx, d_feat):
+        with _precision(ctx.precision):
+            return _EncodeCodes._backward(ctx, d_feat)
+
+    @staticmethod
+    def _backward(ctx, d_feat):
         lib = abi.load_library()
         codes, act, feat, cw, lw = ctx.saved_tensors
         R = codes.shape[0]
@@ -823,8 +918,19 @@ class _EncodeCodes(th.autograd.Function):
 
 
 def encode_codes(codes, conv_w, conv_b, lin_w, lin_b):
-    """features [R, 32] of windows given as u8 class codes [R, V, V] (V odd, 3 .. 63, on the device): see _EncodeCodes."""
-    return _EncodeCodes.apply(codes, conv_w, conv_b, lin_w, lin_b)
+    """features [R, 32] of windows given as u8 class codes [R, V, V] (V odd, 3 .. 63, on the device): see _EncodeCodes.  Host tensors,
+    other edges and other integer dtypes of the codes: the layers themselves on expand_codes (homophily_agent.py:20-27,213-214)."""
+    if codes.dim() != 3 or codes.shape[-1] != codes.shape[-2] or codes.shape[-1] < 3:
+        raise _unfit("encode_codes", "codes", codes, "[R, V, V] with V >= 3 expected")
+    K = 6 * (codes.shape[-1] - 2) ** 2
+    for name, t, shape in (("conv_w", conv_w, (6, 3, 3, 3)), ("conv_b", conv_b, (6,)), ("lin_w", lin_w, (32, K)), ("lin_b", lin_b, (32,))):
+        if t.shape != shape or t.device != codes.device:       # the pack kernels read exactly these sizes
+            raise _unfit("encode_codes", name, t, "%s on the device of codes expected" % (shape,))
+    if encode_codes_supported(codes) and _f32_on(conv_w, conv_b, lin_w, lin_b):
+        return _EncodeCodes.apply(codes, conv_w, conv_b, lin_w, lin_b)
+    _leaving_kernels("encode_codes", codes, "dtype %s / edge %d" % (codes.dtype, codes.shape[-1]))
+    act = th.nn.functional.leaky_relu(th.nn.functional.conv2d(expand_codes(codes).to(conv_w.dtype), conv_w, conv_b))
+    return th.nn.functional.leaky_relu(th.nn.functional.linear(act.flatten(1), lin_w, lin_b))
 
 
 class _GruGates(th.autograd.Function):
@@ -875,10 +981,16 @@ class _GruSeq(th.autograd.Function):
         if need:
             ctx.save_for_backward(hs, rzn, ghn, wh)
             ctx.B = B
+        ctx.precision = LEARNER_PRECISION
         return hs if Bp == B else hs[:, :, :B].contiguous()
 
     @staticmethod
     def backward(ctx, dhs):
+        with _precision(ctx.precision):
+            return _GruSeq._backward(ctx, dhs)
+
+    @staticmethod
+    def _backward(ctx, dhs):
         lib = abi.load_library()
         hs, rzn, ghn, wh = ctx.saved_tensors
         T, G, Bp, H3 = rzn.shape
@@ -923,6 +1035,7 @@ class _GruSeqParts(th.autograd.Function):
             ctx.save_for_backward(hs, rzn, ghn, *whs)
             ctx.shapes = [p.shape for p in parts]
             ctx.n_w = n_w
+        ctx.precision = LEARNER_PRECISION
         ctx.set_materialize_grads(False)       # states without a gradient (the target net's) arrive as None, not as zero tensors
         spp = parts[0].shape[0]
         # one output per projection part: views of the one state buffer (slicing a single output would cost a zero-fill + copy + add per
@@ -931,6 +1044,11 @@ class _GruSeqParts(th.autograd.Function):
 
     @staticmethod
     def backward(ctx, *dhs_parts):
+        with _precision(ctx.precision):
+            return _GruSeqParts._backward(ctx, *dhs_parts)
+
+    @staticmethod
+    def _backward(ctx, *dhs_parts):
         lib = abi.load_library()
         hs, rzn, ghn = ctx.saved_tensors[:3]
         whs = ctx.saved_tensors[3:]
@@ -958,9 +1076,21 @@ class _GruSeqParts(th.autograd.Function):
                                                  dgh.data_ptr(), d_wh.data_ptr(), d_bh.data_ptr(), T, G, Gn, B, _stream(rzn)))
         d_bh_all = (column_sums(d_bh) if tiles > 1 else d_bh[:, 0]).unsqueeze(1)                    # [Gn, 1, 3H]
         spw = G // n_w
-        have = lambda k: (k + 1) * spw <= Gn                                                         # weight part k lies inside the walked sets
-        g_wh = tuple(d_wh[k * spw:(k + 1) * spw] if (need[3 + k] and have(k)) else None for k in range(n_w))       # views of the one output: no copies
-        g_bh = tuple(d_bh_all[k * spw:(k + 1) * spw] if (need[3 + n_w + k] and have(k)) else None for k in range(n_w))
+
+        def of_part(full, k):
+            """weight part k's share of a [Gn, ...] output: a view where the part lies inside the walked sets (the learner's form: no
+            copies, no launch), None where no set of it was walked, and for a part the walk ends inside (one weight tensor for live and
+            target parts) its full size with exact zeros for the sets not walked"""
+            lo, hi = k * spw, (k + 1) * spw
+            if hi <= Gn:
+                return full[lo:hi]
+            if lo >= Gn:
+                return None
+            out = full.new_zeros((spw,) + tuple(full.shape[1:]))
+            out[:Gn - lo] = full[lo:Gn]
+            return out
+        g_wh = tuple(of_part(d_wh, k) if need[3 + k] else None for k in range(n_w))
+        g_bh = tuple(of_part(d_bh_all, k) if need[3 + n_w + k] else None for k in range(n_w))
         g_parts = tuple(d_parts[k] if (k <= last and need[3 + 2 * n_w + k]) else None for k in range(n_parts))
         return (None, None, None) + g_wh + g_bh + g_parts
 
@@ -969,12 +1099,19 @@ def gru_sequence_parts(parts, T, B, wh, bh):
     """gru_sequence for projections held as equally sized set-major parts [sets, T * B, 3H] (rows t * B + b); wh [G, H, 3H], bh [G, 1, 3H]
     over all sets in part order -- each either ONE tensor or a list of 1..4 equally sized parts over the sets (no concatenation).
     Returns the states as a LIST with one tensor [sets, T, B, H] per projection part.  A weight part whose sets' states carry no
-    gradient gets none (the learner puts the target net's parts last).  """
+    gradient gets none (the learner puts the target net's parts last); one that only partly lies among the sets with a gradient gets
+    its full size, zeros for the rest."""
     H3 = parts[0].shape[-1]
     whs, bhs = (list(wh) if isinstance(wh, (list, tuple)) else [wh]), (list(bh) if isinstance(bh, (list, tuple)) else [bh])
     G = sum(p.shape[0] for p in parts)
-    if (parts[0].is_cuda and H3 == 192 and B % 16 == 0 and 1 <= len(parts) <= 4 and all(p.shape == parts[0].shape and p.dtype == th.float32 for p in parts)
-            and len(whs) == len(bhs) and 1 <= len(whs) <= 4 and all(w.shape == whs[0].shape for w in whs) and whs[0].shape[0] * len(whs) == G):
+    H = H3 // 3
+    for k, p in enumerate(parts):
+        if p.dim() != 3 or p.shape[1] != T * B or p.shape[2] != H3 or p.device != parts[0].device:
+            raise _unfit("gru_sequence_parts", "parts[%d]" % k, p, "[sets, T * B = %d, 3H = %d] on one device expected" % (T * B, H3))
+    _gru_weights_fit("gru_sequence_parts", parts[0], whs, bhs, G, H)
+    if (parts[0].is_cuda and H3 == 192 and B % 16 == 0 and 1 <= len(parts) <= 4 and all(p.shape == parts[0].shape for p in parts)
+            and _f32_on(*parts, *whs, *bhs) and 1 <= len(whs) <= 4 and all(w.shape == whs[0].shape for w in whs)
+            and all(b.shape == bhs[0].shape for b in bhs) and whs[0].shape[0] * len(whs) == G):
         return list(_GruSeqParts.apply(T, B, len(whs), *whs, *bhs, *parts))
     wh, bh = (whs[0] if len(whs) == 1 else th.cat(whs, dim=0)), (bhs[0] if len(bhs) == 1 else th.cat(bhs, dim=0))
     if H3 != 192 or parts[0].dtype != th.float32:
@@ -986,25 +1123,46 @@ def gru_sequence_parts(parts, T, B, wh, bh):
     return [hs[k * spp:(k + 1) * spp] for k in range(len(parts))]
 
 
+def _gru_weights_fit(op, like, whs, bhs, G, H):
+    """the recurrence weights as the sequence launches index them: wh parts [sets, H, 3H] and bh parts [sets, 1, 3H] on the projections'
+    device that cover the G sets, else the error names the argument"""
+    if len(whs) != len(bhs):
+        raise ValueError("ops.%s: wh comes as %d parts and bh as %d" % (op, len(whs), len(bhs)))
+    for name, ts, mid in (("wh", whs, H), ("bh", bhs, 1)):
+        for t in ts:
+            if t.dim() != 3 or tuple(t.shape[1:]) != (mid, 3 * H) or t.device != like.device:
+                raise _unfit(op, name, t, "[sets, %d, 3H = %d] on the device of the projections expected" % (mid, 3 * H))
+        if sum(t.shape[0] for t in ts) != G:
+            raise _unfit(op, name, ts[0], "%d sets in all expected, got %d" % (G, sum(t.shape[0] for t in ts)))
+
+
 def gru_sequence(gi, wh, bh):
     """hs [G, T, B, H]: the GRU states h_1..h_T for the input-side projections gi [T, G, B, 3H] from a zero initial state."""
+    if gi.dim() != 4 or gi.shape[3] % 3:
+        raise _unfit("gru_sequence", "gi", gi, "[T, G, B, 3H] expected")
     T, G, B, H3 = gi.shape
-    if gi.is_cuda and H3 == 192:
+    _gru_weights_fit("gru_sequence", gi, [wh], [bh], G, H3 // 3)
+    if gi.is_cuda and H3 == 192 and _f32_on(gi, wh, bh):
         return _GruSeq.apply(gi, wh, bh)
-    _leaving_kernels("gru_sequence", gi, "hidden size %d: the sequence kernels are instantiated for 64" % (H3 // 3))
+    _leaving_kernels("gru_sequence", gi, "hidden size %d (the sequence kernels are instantiated for 64) / dtypes %s, %s, %s" % (H3 // 3, gi.dtype, wh.dtype, bh.dtype))
     h = gi.new_zeros(G, B, H3 // 3)
     hs = []
     for t in range(T):
-        h = gru_gates(gi[t], th.baddbmm(bh, h, wh), h)
+        h = gru_gates(gi[t], _baddbmm(bh, h, wh), h)
         hs.append(h)
     return th.stack(hs, dim=1)
 
 
 def gru_gates(gi, gh, h):
     """h' from the two projections and the previous state; [..., 3H], [..., 3H], [..., H] -> [..., H]."""
-    if gi.is_cuda:
-        return _GruGates.apply(gi, gh, h)
     H = h.shape[-1]
+    if gi.shape[-1] != 3 * H or gi.shape[:-1] != h.shape[:-1] or gi.device != h.device:
+        raise _unfit("gru_gates", "gi", gi, "%s on the device of h expected" % (tuple(h.shape[:-1]) + (3 * H,),))
+    if gh.shape != gi.shape or gh.device != h.device:
+        raise _unfit("gru_gates", "gh", gh, "%s on the device of h expected" % (tuple(gi.shape),))
+    if gi.is_cuda and _f32_on(gi, gh, h):
+        return _GruGates.apply(gi, gh, h)
+    _leaving_kernels("gru_gates", gi, "dtypes %s, %s, %s" % (gi.dtype, gh.dtype, h.dtype))
     r = th.sigmoid(gi[..., :H] + gh[..., :H])
     z = th.sigmoid(gi[..., H:2 * H] + gh[..., H:2 * H])
     cand = th.tanh(gi[..., 2 * H:] + r * gh[..., 2 * H:])
