@@ -383,6 +383,30 @@ WINDOW_SIGNATURES = {
 }
 
 
+class SsdPrioritySampleArgs(C.Structure):
+    """include/ssd_hip.h: ssd_priority_sample_args."""
+    _fields_ = [("seed", C.c_uint64), ("call", C.c_uint32), ("population", C.c_int32), ("count", C.c_int32), ("n_starts", C.c_int32),
+                ("beta", C.c_float), ("table", C.c_void_p), ("ids", C.c_void_p), ("t0", C.c_void_p), ("weights", C.c_void_p), ("log", C.c_void_p)]
+
+
+class SsdPriorityUpdateArgs(C.Structure):
+    """include/ssd_hip.h: ssd_priority_update_args."""
+    _fields_ = [("batch", C.c_int32), ("t_slots", C.c_int32), ("n_agents", C.c_int32), ("n_actions", C.c_int32), ("table_len", C.c_int32),
+                ("alpha", C.c_float), ("eta", C.c_float), ("eps", C.c_float),
+                ("partials", C.c_void_p), ("ids", C.c_void_p), ("weights", C.c_void_p), ("dq_env", C.c_void_p), ("dq_inc", C.c_void_p),
+                ("q_new", C.c_void_p), ("table", C.c_void_p)]
+
+
+PRIORITY_ONE = 65536
+PRIORITY_MAX = 1 << 24
+PRIORITY_POP_MAX = 1 << 20
+# the two exports of prioritised replay, in a table of their own like ssd_behaviour_stats (their checks: tests/test_priority_host.py)
+PRIORITY_SIGNATURES = {
+    "ssd_priority_sample": (C.c_int, [C.POINTER(SsdPrioritySampleArgs), C.c_void_p]),
+    "ssd_priority_update": (C.c_int, [C.POINTER(SsdPriorityUpdateArgs), C.c_void_p]),
+}
+
+
 def behaviour_len(n, A):
     """SSD_BEHAVIOUR_LEN"""
     return 12 * n + n * A + 3 * n * n + 3
@@ -475,6 +499,7 @@ def load_library():
         bind(lib, HIP_SIGNATURES)
         bind(lib, BEHAVIOUR_SIGNATURES)
         bind(lib, WINDOW_SIGNATURES)
+        bind(lib, PRIORITY_SIGNATURES)
         ver = lib.ssd_abi_version()
         if ver != ABI_VERSION:
             raise ImportError("libssd_hip.so ABI version %d != %d" % (ver, ABI_VERSION))

@@ -170,6 +170,9 @@ class ReplayBuffer(EpisodeBatch):
         self.window_norm = "episode"
         self._window_draws = None
         self.last_window_ids = self.last_window_t0 = None
+        # prioritised replay (enable_priorities): the fixed-point priority table, one entry per slot; None = the feature is off
+        self.priority_table = None
+        self._priority_draws = None
 
     def reserve(self, n):
         """A view over the next n episode slots, for producers that write whole episodes in place (vectorised runners): hand
@@ -185,6 +188,7 @@ class ReplayBuffer(EpisodeBatch):
         n = ep_batch.batch_size
         res = getattr(ep_batch, "_reserved", None)
         if res is not None and res[0] is self and res[1] == self.buffer_index:      # written in place (reserve)
+            self._reset_priorities(self.buffer_index, n)
             self.buffer_index += n
             self.episodes_in_buffer = max(self.episodes_in_buffer, self.buffer_index)
             self.buffer_index %= self.buffer_size
@@ -193,6 +197,7 @@ class ReplayBuffer(EpisodeBatch):
             where = slice(self.buffer_index, self.buffer_index + n)
             self.update(ep_batch.data.transition_data, where, slice(0, ep_batch.max_seq_length), mark_filled=False)
             self.update(ep_batch.data.episode_data, where)
+            self._reset_priorities(self.buffer_index, n)
             self.buffer_index += n
             self.episodes_in_buffer = max(self.episodes_in_buffer, self.buffer_index)
             self.buffer_index %= self.buffer_size
@@ -300,6 +305,64 @@ class ReplayBuffer(EpisodeBatch):
         self._sample_calls += 1
         self.last_window_ids, self.last_window_t0 = ids, t0
         return self.gather_windows(ids, t0, window, burn_in, out=out)
+
+    # ---- prioritised replay (config keys prioritized_replay / per_*) --------------------------------------------------------------
+    def enable_priorities(self):
+        """Allocate the priority table: one fixed-point entry per slot (int32 storage of the u32 values of include/ssd_hip.h:
+        PRIORITY_ONE = 1.0, 0 = never trained on) on the buffer's device.  From then on every insert zeroes the slots it advances over
+        and sample_prioritized can draw."""
+        if self.buffer_size > ops.abi.PRIORITY_POP_MAX:
+            raise ValueError("prioritized replay: buffer_size %d over PRIORITY_POP_MAX = %d" % (self.buffer_size, ops.abi.PRIORITY_POP_MAX))
+        if self.priority_table is None:
+            self.priority_table = th.zeros(self.buffer_size, dtype=th.int32, device=self.device)
+        return self.priority_table
+
+    def _reset_priorities(self, start, n):
+        """the n slots from `start` hold new episodes: their priorities go back to 0 (one ssd_fill_blocks launch on the device)"""
+        if self.priority_table is not None and n > 0:
+            ops.fill_blocks([(self.priority_table[start:start + n], 0)])
+
+    def sample_prioritized(self, batch_size, window=0, burn_in=0, beta=0.4, out=None):
+        """batch_size samples drawn in proportion to the priority table (stratified, with replacement: duplicate ids are legal; no
+        episodes_in_buffer == batch_size shortcut), whole episodes (window 0) or windows of `window` transitions with a uniform start
+        each -- ONE launch on a device buffer (ssd_priority_sample), then the gather of sample() / gather_windows.  The batch comes
+        back with batch.priority = (table, ids, weights): the table, the drawn ids (int64) and the importance weights (f32,
+        (population qeff / total)^(-beta) over their maximum), and batch.priority_log (f32 [4]: mean and max priority, smallest
+        weight, distinct ids).  Ids, weights and log live in tensors that persist across calls: a captured train step sees stable
+        addresses.  The learner writes the new priorities back in its train step (ops.priority_update)."""
+        assert self.can_sample(batch_size)
+        if self.priority_table is None:
+            raise ValueError("sample_prioritized: enable_priorities() was not called")
+        if batch_size > ops.abi.SAMPLE_IDS_MAX:
+            raise ValueError("sample_prioritized: batch_size %d over SAMPLE_IDS_MAX = %d" % (batch_size, ops.abi.SAMPLE_IDS_MAX))
+        n_starts = self.max_seq_length - window if window else 1
+        if n_starts < 1 or window < 0:
+            raise ValueError("sample_prioritized: window %r outside 0 .. %d" % (window, self.max_seq_length - 1))
+        if self._sample_seed is None:
+            self._sample_seed = int(np.random.randint(0, 2 ** 31 - 1)) | (int(np.random.randint(0, 2 ** 31 - 1)) << 32)
+        d = self._priority_draws
+        if d is None or d.ids.numel() != batch_size:
+            idx = th.empty(2, batch_size, dtype=th.long, device=self.device)
+            d = self._priority_draws = SimpleNamespace(ids=idx[0], t0=idx[1], weights=th.empty(batch_size, dtype=th.float32, device=self.device),
+                                                       log=th.empty(4, dtype=th.float32, device=self.device))
+        ops.priority_sample(self._sample_seed, self._sample_calls, self.priority_table, self.episodes_in_buffer, batch_size, n_starts, beta,
+                            d.ids, d.t0, d.weights, d.log)
+        self._sample_calls += 1
+        if window:
+            self.last_window_ids, self.last_window_t0 = d.ids, d.t0
+            batch = self.gather_windows(d.ids, d.t0, window, burn_in, out=out)
+        elif (out is not None and out.batch_size == batch_size and out.max_seq_length == self.max_seq_length and not self.data.episode_data
+                and all(out.data.transition_data[k].device == v.device for k, v in self.data.transition_data.items())):
+            pairs = [(v, out.data.transition_data[k]) for k, v in self.data.transition_data.items()]
+            if not (d.ids.is_cuda and ops.gather_rows(pairs, d.ids)):
+                ops._leaving_kernels("gather_rows", d.ids, "fields that do not qualify for ssd_gather_rows")
+                for v, dst in pairs:
+                    th.index_select(v, 0, d.ids, out=dst)
+            batch = out
+        else:
+            batch = self[d.ids]
+        batch.priority, batch.priority_log = (self.priority_table, d.ids, d.weights), d.log
+        return batch
 
     def sample_latest(self, batch_size):
         ep_ids = np.arange(self.buffer_index - batch_size, self.buffer_index) % self.buffer_size

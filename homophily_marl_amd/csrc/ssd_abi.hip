@@ -556,6 +556,35 @@ int ssd_gather_windows(const ssd_window_field* fields, int32_t count, const int6
     return SSD_OK;
 }
 
+static bool unit_interval(float x) { return x >= 0.f && x <= 1.f; }          // (false for a NaN)
+int ssd_priority_sample(const ssd_priority_sample_args* a, void* stream) {
+    if (!a) return fail(SSD_ERR_INVALID, "ssd_priority_sample: null args");
+    if (!a->table || !a->ids || !a->t0 || !a->weights || !a->log) return fail(SSD_ERR_INVALID, "ssd_priority_sample: null member pointer");
+    if (a->population < 1 || a->population > SSD_PRIORITY_POP_MAX) return fail(SSD_ERR_INVALID, "ssd_priority_sample: population outside 1 .. SSD_PRIORITY_POP_MAX");
+    if (a->count < 1 || a->count > SSD_SAMPLE_IDS_MAX) return fail(SSD_ERR_INVALID, "ssd_priority_sample: count outside 1 .. SSD_SAMPLE_IDS_MAX");
+    if (a->n_starts < 1) return fail(SSD_ERR_INVALID, "ssd_priority_sample: n_starts >= 1");
+    if (!unit_interval(a->beta)) return fail(SSD_ERR_INVALID, "ssd_priority_sample: beta outside [0, 1]");
+    if (reinterpret_cast<uintptr_t>(a->table) & 3) return fail(SSD_ERR_INVALID, "ssd_priority_sample: table is not 4-byte aligned");
+    launch_priority_sample(a, (hipStream_t)stream);
+    return launched();
+}
+
+int ssd_priority_update(const ssd_priority_update_args* a, void* stream) {
+    if (!a) return fail(SSD_ERR_INVALID, "ssd_priority_update: null args");
+    if (!a->partials || !a->ids || !a->weights || !a->dq_env || !a->dq_inc || !a->q_new || !a->table)
+        return fail(SSD_ERR_INVALID, "ssd_priority_update: null member pointer");
+    if (a->batch < 1 || a->batch > SSD_SAMPLE_IDS_MAX) return fail(SSD_ERR_INVALID, "ssd_priority_update: batch outside 1 .. SSD_SAMPLE_IDS_MAX");
+    if (a->t_slots < 2 || a->n_agents < 1 || a->n_actions < 1) return fail(SSD_ERR_INVALID, "ssd_priority_update: t_slots >= 2, n_agents >= 1, n_actions >= 1");
+    if (a->table_len < 1 || a->table_len > SSD_PRIORITY_POP_MAX) return fail(SSD_ERR_INVALID, "ssd_priority_update: table_len outside 1 .. SSD_PRIORITY_POP_MAX");
+    if (!unit_interval(a->alpha) || !unit_interval(a->eta)) return fail(SSD_ERR_INVALID, "ssd_priority_update: alpha or eta outside [0, 1]");
+    if (!(a->eps > 0.f)) return fail(SSD_ERR_INVALID, "ssd_priority_update: eps <= 0");
+    if ((int64_t)a->batch * a->t_slots * a->n_agents > SSD_ROWS32_MAX) return fail(SSD_ERR_INVALID, "ssd_priority_update: batch * t_slots * n_agents over SSD_ROWS32_MAX");
+    if ((reinterpret_cast<uintptr_t>(a->partials) & 15) || (reinterpret_cast<uintptr_t>(a->dq_env) & 3) || (reinterpret_cast<uintptr_t>(a->dq_inc) & 3))
+        return fail(SSD_ERR_INVALID, "ssd_priority_update: partials not 16-byte aligned, or dq_env / dq_inc not 4-byte aligned");
+    launch_priority_update(a, (hipStream_t)stream);
+    return launched();
+}
+
 int ssd_behaviour_stats(const ssd_behaviour_args* a, void* stream) {
     if (!a) return fail(SSD_ERR_INVALID, "ssd_behaviour_stats: null args");
     if (!a->actions || !a->actions_inc || !a->reward || !a->clean_num || !a->workspace || !a->acc)

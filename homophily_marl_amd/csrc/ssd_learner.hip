@@ -969,6 +969,197 @@ void launch_gather_windows(const ssd_window_field* fields, int count, const int6
     hipLaunchKernelGGL(k_gather_windows, dim3(blocks), dim3(256), 0, stream, t, count, ids, t0, n_ids, src_slots, win_slots, burn_in);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Prioritised replay (ssd_priority_sample / ssd_priority_update; the contract is in include/ssd_hip.h).
+// k_priority_sample: one workgroup of 1024 threads.  Pass 1: the table's maximum (strided, coalesced).  Pass 2: thread t owns the
+// contiguous chunk [t chunk, (t + 1) chunk), chunk = ceil(population / 1024), and adds its qeff in u64 (16-byte loads when the chunk
+// is a multiple of four entries).  The 1024 chunk sums are scanned: six __shfl_up steps inside a wave, the sixteen wave totals
+// through LDS, every thread adding the totals of the waves before its own in index order; the inclusive sums stay in LDS.  Thread
+// e < count forms its stratum's x, finds the first chunk whose inclusive sum passes x by binary search and walks that chunk.  All
+// sums are integers: nothing depends on an order.  x rises with e, so the ids are non-decreasing and "distinct" is a count of the
+// places where neighbours differ.  The second and third reads of the table come from L2.
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int PRI_THREADS = 1024;
+__device__ __forceinline__ uint64_t pri_shfl_up(uint64_t v, int d) {
+    const uint32_t lo = __shfl_up((uint32_t)v, d), hi = __shfl_up((uint32_t)(v >> 32), d);
+    return ((uint64_t)hi << 32) | lo;
+}
+__global__ __launch_bounds__(PRI_THREADS) void k_priority_sample(ssd_priority_sample_args a) {
+    __shared__ uint64_t s_cum[PRI_THREADS];
+    __shared__ uint64_t s_wave[PRI_THREADS / 64];
+    __shared__ uint32_t s_red[PRI_THREADS];
+    __shared__ float s_w[PRI_THREADS];
+    __shared__ int32_t s_id[PRI_THREADS];
+    if (blockIdx.x != 0) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int P = a.population, count = a.count;
+    const uint32_t* __restrict__ tab = a.table;
+    // pass 1: qmax
+    uint32_t m = 0;
+    for (int k = tid; k < P; k += PRI_THREADS) { const uint32_t q = tab[k]; m = q > m ? q : m; }
+    s_red[tid] = m;
+    __syncthreads();
+    for (int w = PRI_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) { const uint32_t o = s_red[tid + w]; if (o > s_red[tid]) s_red[tid] = o; }
+        __syncthreads();
+    }
+    const uint32_t qmax = s_red[0] ? s_red[0] : SSD_PRIORITY_ONE;
+    __syncthreads();
+    // pass 2: chunk sums
+    const int chunk = (P + PRI_THREADS - 1) / PRI_THREADS;
+    const int k0 = tid * chunk < P ? tid * chunk : P, k1 = k0 + chunk < P ? k0 + chunk : P;
+    uint64_t sum = 0;
+    if ((chunk & 3) == 0 && (reinterpret_cast<uintptr_t>(tab) & 15) == 0) {       // k0 is a multiple of 4; so is k1, or it is P
+        int k = k0;
+        for (; k + 4 <= k1; k += 4) {
+            const uint4 v = *reinterpret_cast<const uint4*>(tab + k);
+            sum += (uint64_t)(v.x ? v.x : qmax) + (v.y ? v.y : qmax) + (v.z ? v.z : qmax) + (v.w ? v.w : qmax);
+        }
+        for (; k < k1; ++k) { const uint32_t q = tab[k]; sum += q ? q : qmax; }
+    } else {
+        for (int k = k0; k < k1; ++k) { const uint32_t q = tab[k]; sum += q ? q : qmax; }
+    }
+    // inclusive scan of the chunk sums
+    uint64_t inc = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t o = pri_shfl_up(inc, d);
+        if (lane >= d) inc += o;
+    }
+    if (lane == 63) s_wave[wave] = inc;
+    __syncthreads();
+    uint64_t before = 0;
+    for (int w = 0; w < wave; ++w) before += s_wave[w];
+    s_cum[tid] = inc + before;
+    __syncthreads();
+    const uint64_t total = s_cum[PRI_THREADS - 1];
+    // the draws
+    const uint32_t s0 = (uint32_t)a.seed, s1 = (uint32_t)(a.seed >> 32);
+    int id = 0;
+    uint32_t qe = 0xFFFFFFFFu;
+    if (tid < count) {
+        const uint64_t lo = total * (uint64_t)tid / (uint64_t)count, hi = total * (uint64_t)(tid + 1) / (uint64_t)count;   // total < 2^44, tid + 1 <= 2^10
+        const uint64_t width = hi - lo, d = sample_draw(s0, s1, a.call, (uint32_t)tid);
+        const uint64_t x = lo + d * (width >> 32) + ((d * (width & 0xFFFFFFFFull)) >> 32);          // floor(d width / 2^32), exactly
+        int c_lo = 0, c_hi = PRI_THREADS - 1;                                                      // s_cum[1023] = total > x
+        while (c_lo < c_hi) {
+            const int mid = (c_lo + c_hi) >> 1;
+            if (s_cum[mid] > x) c_hi = mid; else c_lo = mid + 1;
+        }
+        uint64_t acc = c_lo ? s_cum[c_lo - 1] : 0;
+        const int w0 = c_lo * chunk, w1 = w0 + chunk < P ? w0 + chunk : P;                           // s_cum[c_lo] > acc: the chunk is not empty
+        id = w1 - 1;
+        qe = qmax;
+        for (int k = w0; k < w1; ++k) {
+            const uint32_t q = tab[k], v = q ? q : qmax;
+            acc += v;
+            if (acc > x) { id = k; qe = v; break; }
+        }
+        a.ids[tid] = (int64_t)id;
+        a.t0[tid] = (int64_t)(((uint64_t)sample_draw(s0, s1, a.call, (uint32_t)(2 * count + tid)) * (uint32_t)a.n_starts) >> 32);
+    }
+    // the smallest sampled qeff carries the largest weight
+    s_id[tid] = id;
+    s_red[tid] = qe;
+    __syncthreads();
+    for (int w = PRI_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) { const uint32_t o = s_red[tid + w]; if (o < s_red[tid]) s_red[tid] = o; }
+        __syncthreads();
+    }
+    const uint32_t qmin = s_red[0];
+    __syncthreads();
+    float wgt = 2.f;
+    if (tid < count) {
+        wgt = (float)pow((double)qe / (double)qmin, -(double)a.beta);
+        a.weights[tid] = wgt;
+    }
+    s_w[tid] = wgt;
+    s_red[tid] = (tid > 0 && tid < count && id != s_id[tid - 1]) ? 1u : 0u;
+    __syncthreads();
+    for (int w = PRI_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) { s_w[tid] = fminf(s_w[tid], s_w[tid + w]); s_red[tid] += s_red[tid + w]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        a.log[0] = (float)((double)total / (double)P / (double)SSD_PRIORITY_ONE);
+        a.log[1] = (float)((double)qmax / (double)SSD_PRIORITY_ONE);
+        a.log[2] = s_w[0];
+        a.log[3] = (float)(1u + s_red[0]);
+    }
+}
+void launch_priority_sample(const ssd_priority_sample_args* a, hipStream_t stream) {
+    hipLaunchKernelGGL(k_priority_sample, dim3(1), dim3(PRI_THREADS), 0, stream, *a);
+}
+
+// k_priority_rows: sample e = blockIdx.x.  Its T n rows of partials -> q_new[e]; then its blocks of dq_env / dq_inc times weights[e].
+// pri_scale: the block [p, p + len) of floats, any 4-byte alignment: scalar elements up to the first 16-byte boundary, float4 in
+// between, scalar elements behind the last whole float4.
+__device__ __forceinline__ void pri_scale(float* __restrict__ p, size_t len, float w, int tid) {
+    size_t head = ((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) >> 2;
+    head = head < len ? head : len;
+    const size_t body = (len - head) >> 2, tail0 = head + (body << 2);
+    if ((size_t)tid < head) p[tid] *= w;
+    float4* __restrict__ p4 = reinterpret_cast<float4*>(p + head);
+    for (size_t k = tid; k < body; k += 256) {
+        float4 v = p4[k];
+        v.x *= w; v.y *= w; v.z *= w; v.w *= w;
+        p4[k] = v;
+    }
+    if (tail0 + (size_t)tid < len) p[tail0 + tid] *= w;
+}
+__global__ __launch_bounds__(256) void k_priority_rows(ssd_priority_update_args a) {
+    __shared__ float s_sum[256], s_cnt[256], s_max[256];
+    const int e = blockIdx.x, tid = threadIdx.x;
+    const int T1 = a.t_slots, n = a.n_agents, R = (T1 - 1) * n;
+    const float* __restrict__ rows = a.partials + (size_t)e * R * SSD_TD_LOSS_PARTIALS;
+    float sum = 0.f, cnt = 0.f, mx = 0.f;
+    for (int r = tid; r < R; r += 256) {
+        const float4 v = *reinterpret_cast<const float4*>(rows + (size_t)r * SSD_TD_LOSS_PARTIALS);     // columns 0 .. 3 (rows are 64 bytes)
+        const float d = sqrtf(v.z + v.w);
+        sum += d; cnt += v.x; mx = fmaxf(mx, d);
+    }
+    s_sum[tid] = sum; s_cnt[tid] = cnt; s_max[tid] = mx;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) { s_sum[tid] += s_sum[tid + w]; s_cnt[tid] += s_cnt[tid + w]; s_max[tid] = fmaxf(s_max[tid], s_max[tid + w]); }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const float p = a.eta * s_max[0] + (1.f - a.eta) * s_sum[0] / fmaxf(1.f, s_cnt[0]) + a.eps;
+        float q = powf(p, a.alpha) * (float)SSD_PRIORITY_ONE;
+        q = q == q ? q : (float)SSD_PRIORITY_MAX;
+        a.q_new[e] = (uint32_t)rintf(fminf(fmaxf(q, 1.f), (float)SSD_PRIORITY_MAX));
+    }
+    const float w = a.weights[e];
+    const size_t le = (size_t)T1 * n * a.n_actions, li = (size_t)T1 * n * n * 3;
+    pri_scale(a.dq_env + (size_t)e * le, le, w, tid);
+    pri_scale(a.dq_inc + (size_t)e * li, li, w, tid);
+}
+// k_priority_apply: one workgroup; thread e owns sample e (batch <= 1024).  One writer per table slot: the largest value, the
+// smallest index among equals.
+__global__ __launch_bounds__(PRI_THREADS) void k_priority_apply(ssd_priority_update_args a) {
+    __shared__ int64_t s_id[PRI_THREADS];
+    __shared__ uint32_t s_q[PRI_THREADS];
+    if (blockIdx.x != 0) return;
+    const int e = threadIdx.x, B = a.batch;
+    int64_t id = -1;
+    uint32_t q = 0;
+    if (e < B) { id = a.ids[e]; q = a.q_new[e]; }
+    s_id[e] = id; s_q[e] = q;
+    __syncthreads();
+    if (e >= B || id < 0 || id >= (int64_t)a.table_len) return;
+    bool wins = true;
+    for (int o = 0; o < B; ++o) {
+        const uint32_t qo = s_q[o];
+        if (s_id[o] == id && (qo > q || (qo == q && o < e))) wins = false;
+    }
+    if (wins) a.table[id] = q;
+}
+void launch_priority_update(const ssd_priority_update_args* a, hipStream_t stream) {
+    hipLaunchKernelGGL(k_priority_rows, dim3(a->batch), dim3(256), 0, stream, *a);
+    hipLaunchKernelGGL(k_priority_apply, dim3(1), dim3(PRI_THREADS), 0, stream, *a);
+}
+
 void launch_copy_blocks(const ssd_block_copy* blocks, int count, hipStream_t stream) {
     CopyTable t;
     int most = 1;

@@ -101,6 +101,8 @@ class HomophilyLearner:
         lam = float(getattr(args, "td_lambda", 0.0) or 0.0)
         if not 0.0 <= lam <= 1.0:                      # (NaN fails both comparisons)
             raise ValueError("td_lambda must lie in [0, 1], got %r" % (getattr(args, "td_lambda", None),))
+        # prioritised replay (ours; run.setup validates the keys): how a trained sample's new priority is formed (ops.priority_update)
+        self.per = (float(getattr(args, "per_alpha", 0.6)), float(getattr(args, "per_eta", 0.9)), float(getattr(args, "per_eps", 1e-3)))
         self.params = list(mac.parameters())
         self.params_env = mac.parameters_env()
         self.params_inc = mac.parameters_inc()
@@ -282,7 +284,16 @@ class HomophilyLearner:
     def _forward_backward_fused(self, batch, dens):
         a, n = self.args, self.n_agents
         q_env, q_inc, tq_env, tq_inc = self.unroll_pair(batch)
-        dq_env, dq_inc, sums = ops.td_sim_loss_grads(q_env, q_inc, tq_env, tq_inc, dens, batch, a)
+        priority = getattr(batch, "priority", None)
+        if priority is None:
+            dq_env, dq_inc, sums = ops.td_sim_loss_grads(q_env, q_inc, tq_env, tq_inc, dens, batch, a)
+        else:
+            # prioritised replay: the samples' new priorities from the rows the loss kernel just wrote, the importance weights on
+            # the gradient seeds, the table written -- in this step, before the next rollout reuses a slot (two launches)
+            table, ids, weights = priority
+            dq_env, dq_inc, sums, partials = ops.td_sim_loss_grads(q_env, q_inc, tq_env, tq_inc, dens, batch, a, with_partials=True)
+            self.last_q_new = ops.priority_update(partials, ids, weights, dq_env, dq_inc, th.empty(batch.batch_size, dtype=th.int32, device=dq_env.device),
+                                                  table, *self.per)
         self._backward([q_env, q_inc], seeds=[dq_env, dq_inc])
         return _FusedLogs(sums, dens, float(batch.batch_size * (batch.max_seq_length - 1) * n), n)
 
@@ -348,6 +359,15 @@ class HomophilyLearner:
         td_inc = (chosen_inc * self.inc_mask).sum(dim=-1) - targets_inc.detach()
         value_loss_env = ((td_env * mask) ** 2).sum() / dens[0]
         value_loss_inc = ((td_inc * mask) ** 2).sum() / dens[0]
+        # prioritised replay: per-sample importance weights inside the three sums of the optimised loss (the logged losses stay
+        # unweighted); the new priorities come from the same rows the fused path reads (d = sqrt of the two squared masked errors)
+        priority = getattr(batch, "priority", None)
+        w = None
+        if priority is not None:
+            w = priority[2].to(td_env.device).float()[:batch.batch_size]
+            w3 = w.reshape(-1, 1, 1)
+            weighted_env = (w3 * (td_env * mask) ** 2).sum() / dens[0]
+            weighted_inc = (w3 * (td_inc * mask) ** 2).sum() / dens[0]
 
         # similarity loss (:208-217)
         p_inc = th.softmax(q_inc, dim=-1)[:, :-1]                              # [bs, t-1, n(i), n(j), 3]
@@ -356,7 +376,20 @@ class HomophilyLearner:
         p_ikj = th.gather(p_inc.unsqueeze(3).expand(-1, -1, -1, n, -1, -1), dim=-1, index=idx.unsqueeze(-1)).squeeze(-1)
         sim_loss = (th.clamp_min(-th.log(p_ikj), a.sim_threshold) * sim_mask).sum() / (1 + dens[1])
 
-        self._backward(value_loss_inc + value_loss_env + sim_loss * a.sim_loss_weight)
+        if w is None:
+            self._backward(value_loss_inc + value_loss_env + sim_loss * a.sim_loss_weight)
+        else:
+            weighted_sim = (w.reshape(-1, 1, 1, 1, 1) * th.clamp_min(-th.log(p_ikj), a.sim_threshold) * sim_mask).sum() / (1 + dens[1])
+            self._backward(weighted_inc + weighted_env + weighted_sim * a.sim_loss_weight)
+            with th.no_grad():
+                B, T = td_env.shape[0], td_env.shape[1]
+                part = th.zeros(B * T * n, ops.abi.TD_LOSS_PARTIALS, dtype=th.float32, device=td_env.device)
+                part[:, 0], part[:, 2], part[:, 3] = mask.reshape(-1), ((td_env * mask) ** 2).reshape(-1), ((td_inc * mask) ** 2).reshape(-1)
+                self.last_td_rows = part
+                table, ids = priority[0], priority[1]
+                if not table.is_cuda and not ids.is_cuda:      # a host table: the restated write-back (a device table belongs to the fused path)
+                    self.last_q_new = ops.priority_update(part, ids, th.ones(B), th.zeros(B, T + 1, n, 1), th.zeros(B, T + 1, n, n, 3),
+                                                          th.empty(B, dtype=th.int32), table, *self.per)
 
         with th.no_grad():
             q_inc_taken = th.gather(q_inc[:, :-1], dim=-1, index=actions_inc).squeeze(-1)
@@ -460,6 +493,10 @@ class HomophilyLearner:
                                               data=SimpleNamespace(transition_data=self._static_data, episode_data={}),
                                               device=batch.device)
             self._static_batch.reward_norm = getattr(batch, "reward_norm", None)      # a window batch's normaliser is baked into the graph
+            # prioritised replay: table, ids and weights are baked into the graph by address (ReplayBuffer.sample_prioritized keeps them)
+            self._static_batch.priority = getattr(batch, "priority", None)
+            self._static_batch.priority_log = getattr(batch, "priority_log", None)
+            self._static_priority = self._priority_ptrs(batch)
             self._static_dens = th.zeros(2, device=batch.device)
             th.cuda.synchronize()
             # the step is captured on a stream of this learner's own: per-(device, stream) kernel scratch (the row-chunked affine
@@ -478,6 +515,10 @@ class HomophilyLearner:
         if (batch.batch_size, batch.max_seq_length, ops.reward_norm(batch)) != (st.batch_size, st.max_seq_length, ops.reward_norm(st)):
             raise ValueError("the train step was captured for %d x %d slots (reward normaliser %g), got a batch of %d x %d (%g)" % (
                 st.batch_size, st.max_seq_length, ops.reward_norm(st), batch.batch_size, batch.max_seq_length, ops.reward_norm(batch)))
+        got = self._priority_ptrs(batch)
+        if got != self._static_priority:             # (the addresses at capture: the static batch itself may be the batch handed in)
+            raise ValueError("the train step was captured %s priority tensors; this batch's (table, ids, weights) are %s" % (
+                "with its own" if self._static_priority else "without", "other tensors" if got else "absent"))
         for k, v in batch.data.transition_data.items():
             dst = self._static_data[k]
             if v.data_ptr() != dst.data_ptr() or v.shape != dst.shape:      # not sampled straight into the static batch (sample_out)
@@ -506,6 +547,10 @@ class HomophilyLearner:
         self._graph[1].replay()
         return self._static_logs
 
+    @staticmethod
+    def _priority_ptrs(batch):
+        return tuple(t.data_ptr() for t in (getattr(batch, "priority", None) or ()))
+
     def sample_out(self):
         """The static batch of the captured train step once it exists (else None): ReplayBuffer.sample(batch_size, out=...) gathers
         the sampled episodes straight into it and train() then copies nothing.  Under train_window it has the window's shape
@@ -523,6 +568,10 @@ class HomophilyLearner:
         clock = self.log_clock() if self.log_clock is not None else t_env
         if clock - self.log_stats_t >= self.args.learner_log_interval:
             means = (("clean_num_mean", batch["clean_num"][:, :-1].mean()), ("apple_den_mean", batch["apple_den"][:, :-1].mean()))
+            plog = getattr(batch, "priority_log", None)
+            if plog is not None:                                             # prioritised replay: the sample launch's four values
+                means += (("per_priority_mean", plog[0]), ("per_priority_max", plog[1]), ("per_weight_min", plog[2]),
+                          ("per_unique_frac", plog[3] / batch.batch_size))
             if self.distributed and isinstance(logs, _FusedLogs):
                 logs = logs.synced()
             if isinstance(logs, _FusedLogs):

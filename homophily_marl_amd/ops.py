@@ -265,12 +265,13 @@ def td_sim_loss(q_env, q_inc, tq_env, tq_inc, dens, batch, a):
     return _TdSimLoss.apply(q_env, q_inc, tq_env, tq_inc, dens, batch, a)
 
 
-def td_sim_loss_grads(q_env, q_inc, tq_env, tq_inc, dens, batch, a):
+def td_sim_loss_grads(q_env, q_inc, tq_env, tq_inc, dens, batch, a, with_partials=False):
     """(dL/dq_env, dL/dq_inc, column sums of the per-row partials) of the same loss from the same launch, WITHOUT an autograd node:
     the learner seeds the backward pass of the two Q tensors with the gradients directly (th.autograd.grad(..., grad_outputs=...)) --
     the loss scalar is a logged quantity only (_FusedLogs forms it when it is read), so the six scalar launches that assembled it and
     the two multiplications by d loss / d loss = 1 of the autograd form are gone.  Columns 13..15 of the partials are never read
-    (13 / 14 are written only with td_lambda > 0: the rows' lambda-returns)."""
+    (13 / 14 are written only with td_lambda > 0: the rows' lambda-returns).  with_partials: the per-row partials as a fourth result
+    (prioritised replay forms the samples' new priorities from columns 0, 2, 3: priority_update)."""
     lib = abi.load_library()
     B, T, n = batch.batch_size, batch.max_seq_length - 1, q_env.shape[2]
     q_env, q_inc, tq_env, tq_inc = q_env.detach().contiguous(), q_inc.detach().contiguous(), tq_env.contiguous(), tq_inc.contiguous()
@@ -281,6 +282,8 @@ def td_sim_loss_grads(q_env, q_inc, tq_env, tq_inc, dens, batch, a):
     dens = dens.contiguous().float()
     t.dens, t.dq_env, t.dq_inc = dens.data_ptr(), dq_env.data_ptr(), dq_inc.data_ptr()
     abi.check(lib, lib.ssd_td_sim_loss(C.byref(t), 1, _stream(q_env)))
+    if with_partials:
+        return dq_env, dq_inc, column_sums(partials), partials
     return dq_env, dq_inc, column_sums(partials)
 
 
@@ -636,6 +639,93 @@ def gather_windows(pairs, ids, t0, src_slots, win_slots, burn_in, filled_index):
     abi.check(lib, lib.ssd_gather_windows(tab, len(pairs), ids.contiguous().data_ptr(), t0.contiguous().data_ptr(), n, src_slots, win_slots,
                                           burn_in, _stream(ids)))
     return True
+
+
+def priority_sample(seed, call, table, population, count, n_starts, beta, ids_out, t0_out, weights_out, log_out):
+    """Prioritised replay's draw (include/ssd_hip.h: ssd_priority_sample): `count` stratified proportional draws with replacement from
+    the fixed-point priorities table[0 .. population) (int32 storage of the u32 values; 0 = never trained on, drawn at the table's
+    maximum), one window start each, and the importance weights (population qeff / total)^(-beta) divided by their maximum.
+    ids_out, t0_out: int64 [count]; weights_out: f32 [count]; log_out: f32 [4] = mean and max of qeff / PRIORITY_ONE, the smallest
+    weight, the number of distinct ids.  Device tensors: ONE launch.  Host tensors: the same arithmetic restated -- Python integers
+    for the draw, float64 then f32 for the weights.  Returns (ids_out, t0_out, weights_out, log_out)."""
+    outs = (ids_out, t0_out, weights_out, log_out)
+    if not (table.dtype == th.int32 and ids_out.dtype == th.long and t0_out.dtype == th.long and weights_out.dtype == th.float32 and log_out.dtype == th.float32):
+        raise _unfit("priority_sample", "table", table, "int32 table, int64 ids / t0 and f32 weights / log expected")
+    if not (1 <= population <= min(table.numel(), abi.PRIORITY_POP_MAX) and 1 <= count <= abi.SAMPLE_IDS_MAX and n_starts >= 1 and 0.0 <= beta <= 1.0):
+        raise ValueError("ops.priority_sample: population %r outside 1 .. min(len(table), PRIORITY_POP_MAX), count %r outside 1 .. SAMPLE_IDS_MAX, "
+                         "n_starts %r < 1 or beta %r outside [0, 1]" % (population, count, n_starts, beta))
+    if min(ids_out.numel(), t0_out.numel(), weights_out.numel()) < count or log_out.numel() < 4 or any(t.device != table.device or not t.is_contiguous() for t in outs + (table,)):
+        raise _unfit("priority_sample", "ids_out", ids_out, "contiguous outputs of count elements (log: 4) on the table's device expected")
+    if table.is_cuda:
+        lib = abi.load_library()
+        t = abi.SsdPrioritySampleArgs()
+        t.seed, t.call, t.population, t.count, t.n_starts, t.beta = seed & (2 ** 64 - 1), call & 0xFFFFFFFF, population, count, n_starts, float(beta)
+        t.table, t.ids, t.t0, t.weights, t.log = table.data_ptr(), ids_out.data_ptr(), t0_out.data_ptr(), weights_out.data_ptr(), log_out.data_ptr()
+        abi.check(lib, lib.ssd_priority_sample(C.byref(t), _stream(table)))
+        return outs
+    import bisect
+    import itertools
+    q = [int(v) for v in table[:population].tolist()]
+    qmax = max(q) or abi.PRIORITY_ONE
+    qeff = [v or qmax for v in q]
+    cum = list(itertools.accumulate(qeff))
+    total, call = cum[-1], call & 0xFFFFFFFF
+    ids = []
+    for e in range(count):
+        lo, hi = total * e // count, total * (e + 1) // count
+        x = lo + ((_sample_draw(seed, call, e) * (hi - lo)) >> 32)
+        ids.append(bisect.bisect_right(cum, x))                      # the smallest k with cum[k] > x
+    ids_out[:count] = th.tensor(ids, dtype=th.long)
+    t0_out[:count] = th.tensor([(_sample_draw(seed, call, 2 * count + e) * n_starts) >> 32 for e in range(count)], dtype=th.long)
+    w = th.tensor([population * qeff[k] / total for k in ids], dtype=th.float64) ** (-float(beta))
+    w = (w / w.max()).float()
+    weights_out[:count] = w
+    log_out[:4] = th.tensor([total / population / abi.PRIORITY_ONE, max(qeff) / abi.PRIORITY_ONE, float(w.min()), float(len(set(ids)))], dtype=th.float32)
+    return outs
+
+
+def priority_update(partials, ids, weights, dq_env, dq_inc, q_new, table, alpha, eta, eps):
+    """Prioritised replay's train-step half (include/ssd_hip.h: ssd_priority_update), after the loss launch that wrote `partials`
+    [B T n, TD_LOSS_PARTIALS] and the gradient seeds dq_env [B, T + 1, n, A] / dq_inc [B, T + 1, n, n, 3]:
+      q_new[e] = clamp(round(p^alpha PRIORITY_ONE), 1, PRIORITY_MAX),  p = eta max d + (1 - eta) sum d / max(1, sum col0) + eps over the
+      sample's rows, d = sqrt(col2 + col3);  dq_env[e], dq_inc[e] *= weights[e] in place;  table[ids[e]] = the largest q_new among the
+      samples of that id (an id outside the table is skipped).
+    Device tensors: two launches.  Host tensors: the same arithmetic in float64 (the scaling is the one f32 multiply).  Returns q_new."""
+    B, T1, n, A = dq_env.shape
+    if not (partials.dtype == th.float32 and weights.dtype == th.float32 and dq_env.dtype == th.float32 and dq_inc.dtype == th.float32
+            and ids.dtype == th.long and q_new.dtype == th.int32 and table.dtype == th.int32):
+        raise _unfit("priority_update", "partials", partials, "f32 partials / weights / dq, int64 ids, int32 q_new / table expected")
+    if not (tuple(dq_inc.shape) == (B, T1, n, n, 3) and tuple(partials.shape) == (B * (T1 - 1) * n, abi.TD_LOSS_PARTIALS) and T1 >= 2
+            and 1 <= B <= abi.SAMPLE_IDS_MAX and min(ids.numel(), weights.numel(), q_new.numel()) >= B and 1 <= table.numel() <= abi.PRIORITY_POP_MAX):
+        raise _unfit("priority_update", "dq_inc", dq_inc, "shapes that do not belong to one batch of 1 .. SAMPLE_IDS_MAX samples")
+    if not (0.0 <= alpha <= 1.0 and 0.0 <= eta <= 1.0 and eps > 0.0):
+        raise ValueError("ops.priority_update: alpha %r or eta %r outside [0, 1], or eps %r <= 0" % (alpha, eta, eps))
+    every = (partials, ids, weights, dq_env, dq_inc, q_new, table)
+    if any(t.device != table.device or not t.is_contiguous() for t in every):
+        raise _unfit("priority_update", "table", table, "contiguous tensors on one device expected")
+    if table.is_cuda:
+        lib = abi.load_library()
+        t = abi.SsdPriorityUpdateArgs()
+        t.batch, t.t_slots, t.n_agents, t.n_actions, t.table_len = B, T1, n, A, table.numel()
+        t.alpha, t.eta, t.eps = float(alpha), float(eta), float(eps)
+        t.partials, t.ids, t.weights, t.dq_env, t.dq_inc = partials.data_ptr(), ids.data_ptr(), weights.data_ptr(), dq_env.data_ptr(), dq_inc.data_ptr()
+        t.q_new, t.table = q_new.data_ptr(), table.data_ptr()
+        abi.check(lib, lib.ssd_priority_update(C.byref(t), _stream(table)))
+        return q_new
+    rows = partials.double().reshape(B, (T1 - 1) * n, -1)
+    d = (rows[..., 2] + rows[..., 3]).sqrt()
+    p = eta * d.max(dim=1)[0] + (1.0 - eta) * d.sum(dim=1) / rows[..., 0].sum(dim=1).clamp_min(1.0) + eps
+    q = th.nan_to_num((p ** alpha * abi.PRIORITY_ONE).round(), nan=float(abi.PRIORITY_MAX)).clamp(1, abi.PRIORITY_MAX).to(th.int32)
+    q_new[:B] = q
+    dq_env.mul_(weights[:B].reshape(B, 1, 1, 1))
+    dq_inc.mul_(weights[:B].reshape(B, 1, 1, 1, 1))
+    best = {}
+    for e, k in enumerate(ids[:B].tolist()):
+        if 0 <= k < table.numel():
+            best[k] = max(best.get(k, 0), int(q[e]))
+    for k, v in best.items():
+        table[k] = v
+    return q_new
 
 
 class _CatGroups(th.autograd.Function):

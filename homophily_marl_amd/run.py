@@ -78,6 +78,48 @@ def _check_train_window(args, episode_limit, runner):
     return norm
 
 
+def _check_prioritized(args, buffer, runner):
+    """The config keys of prioritised replay (absent = off), validated and written back with their defaults; returns whether it is on.
+    prioritized_replay: proportional draws from a device-side priority table, importance weights on the gradient seeds, new
+    priorities written in the train step (ssd_priority_sample / ssd_priority_update).  per_alpha: the priority exponent; per_beta:
+    the importance-weight exponent at the first train step, annealed linearly to 1 over per_beta_anneal_steps train steps (0:
+    constant); per_eta: the weight of a sample's largest TD error against its mean; per_eps: added to the aggregate error."""
+    on = args.prioritized_replay = bool(getattr(args, "prioritized_replay", False))
+    alpha = args.per_alpha = float(getattr(args, "per_alpha", 0.6))
+    beta = args.per_beta = float(getattr(args, "per_beta", 0.4))
+    eta = args.per_eta = float(getattr(args, "per_eta", 0.9))
+    eps = args.per_eps = float(getattr(args, "per_eps", 1e-3))
+    steps = args.per_beta_anneal_steps = int(getattr(args, "per_beta_anneal_steps", 0) or 0)
+    for name, v in (("per_alpha", alpha), ("per_beta", beta), ("per_eta", eta)):
+        if not 0.0 <= v <= 1.0:                        # (NaN fails both comparisons)
+            raise ValueError("%s must lie in [0, 1], got %r" % (name, v))
+    if not eps > 0.0:
+        raise ValueError("per_eps must be positive, got %r" % (eps,))
+    if steps < 0:
+        raise ValueError("per_beta_anneal_steps must not be negative, got %r" % (steps,))
+    if not on:
+        return False
+    from . import abi
+    if not getattr(runner, "fixed_length_episodes", False) or th.device(buffer.device).type != "cuda":
+        raise ValueError("prioritized_replay needs a device-resident replay buffer filled by a vectorised runner (buffer_cpu_only: False); "
+                         "runner %r, buffer on %s" % (args.runner, buffer.device))
+    if not getattr(args, "fused_loss", True):
+        raise ValueError("prioritized_replay needs the fused loss (fused_loss: True): the priorities come from its per-row partials")
+    if args.batch_size > abi.SAMPLE_IDS_MAX:
+        raise ValueError("prioritized_replay: batch_size %d over SSD_SAMPLE_IDS_MAX = %d" % (args.batch_size, abi.SAMPLE_IDS_MAX))
+    buffer.enable_priorities()
+    return True
+
+
+def per_beta(args, train_steps):
+    """the importance-weight exponent of train step number train_steps (0-based): per_beta, annealed linearly to 1 over
+    per_beta_anneal_steps train steps (0: constant)"""
+    steps = getattr(args, "per_beta_anneal_steps", 0)
+    if steps <= 0:
+        return args.per_beta
+    return args.per_beta + (1.0 - args.per_beta) * min(1.0, train_steps / steps)
+
+
 def setup(config, logger=None):
     """Build runner / buffer / mac / learner exactly in the order of run.py:84-135."""
     args = SimpleNamespace(**config)
@@ -105,6 +147,7 @@ def setup(config, logger=None):
     buffer = ReplayBuffer(scheme, groups, args.buffer_size, env_info["episode_limit"] + 1, preprocess=preprocess,
                           device="cpu" if args.buffer_cpu_only else args.device)
     buffer.window_norm = _check_train_window(args, env_info["episode_limit"], runner)
+    _check_prioritized(args, buffer, runner)
     mac = mac_REGISTRY[args.mac](buffer.scheme, groups, args)
     runner.setup(scheme=scheme, groups=groups, preprocess=preprocess, mac=mac)
     learner = le_REGISTRY[args.learner](mac, buffer.scheme, logger, args)
@@ -147,7 +190,9 @@ def train_iteration(ctx, episode):
     if ctx.buffer.can_sample(a.batch_size):
         for _ in range(a.train_steps_per_rollout):
             out = ctx.learner.sample_out() if hasattr(ctx.learner, "sample_out") else None
-            if window > 0:                 # windows of a runner that fills every slot (setup checked): nothing to trim
+            if getattr(a, "prioritized_replay", False):     # whole episodes or windows, drawn in proportion to the priority table
+                sample = ctx.buffer.sample_prioritized(a.batch_size, window, a.train_burn_in if window else 0, beta=per_beta(a, ctx.train_steps), out=out)
+            elif window > 0:               # windows of a runner that fills every slot (setup checked): nothing to trim
                 sample = ctx.buffer.sample_windows(a.batch_size, window, a.train_burn_in, out=out)
             else:
                 sample = ctx.buffer.sample(a.batch_size, out=out)

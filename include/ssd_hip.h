@@ -392,6 +392,85 @@ typedef struct ssd_window_field {
 int (ssd_gather_windows)(const ssd_window_field* fields, int32_t count, const int64_t* ids, const int64_t* t0, int32_t n_ids,
                          int32_t src_slots, int32_t win_slots, int32_t burn_in, void* stream);
 
+/* Prioritised replay (config key prioritized_replay, default off; per_alpha / per_beta / per_beta_anneal_steps / per_eta / per_eps):
+ * proportional draws, importance weights and new priorities on the device.  The reference has no counterpart (its
+ * ReplayBuffer.sample is np.random.choice).  Both names are declared in parentheses like ssd_behaviour_stats; their ctypes mirror is
+ * abi.PRIORITY_SIGNATURES and their symbol, struct-size and refusal checks are tests/test_priority_host.py.
+ *
+ * Priority table: one u32 per buffer slot, fixed point: SSD_PRIORITY_ONE is 1.0, stored values lie in [1, SSD_PRIORITY_MAX], 0 means
+ * "never trained on".  Integers, so that every sum is an integer sum: the order of summation cannot show and a draw is the same on
+ * every device (the argument of ssd_behaviour_stats).
+ *   qmax    = the largest table[k], k < population, or SSD_PRIORITY_ONE if all of them are 0
+ *   qeff[k] = table[k] ? table[k] : qmax          (a new episode is sampled at the current maximum; no state between calls)
+ *   total   = sum_k qeff[k]                       (u64; population <= SSD_PRIORITY_POP_MAX = 2^20, so total < 2^44)
+ *
+ * ssd_priority_sample: ONE launch, one workgroup.  Stratified, with replacement; draw(i) is the generator of ssd_sample_windows for
+ * (seed, call).  For e < count:
+ *   lo = floor(total * e / count);   hi = floor(total * (e + 1) / count)          (hi > lo wherever total >= count)
+ *   x  = lo + floor(draw(e) * (hi - lo) / 2^32)                                   (exact integers; the product is split, it passes 64 bits)
+ *   ids[e] = the smallest k with cum[k] > x,  cum[k] = qeff[0] + .. + qeff[k]
+ *   t0[e]  = floor(draw(2 * count + e) * n_starts / 2^32)                         (as ssd_sample_windows; n_starts = 1: t0 = 0)
+ *   w_raw[e] = (population * qeff[ids[e]] / total)^(-beta);   weights[e] = w_raw[e] / max_e' w_raw[e']
+ * count may exceed population (one episode can own several strata: duplicate ids are legal); where total < count a stratum can be
+ * empty (hi == lo) and x = lo.  x rises with e, so the ids come out in non-decreasing order.  The weights are evaluated in f64 as
+ * (qeff[ids[e]] / qmin)^(-beta), qmin the smallest sampled qeff -- the same number, the common factor population / total cancelled --
+ * and rounded to f32: the largest weight is exactly 1, and with beta = 0 every weight is.
+ * log f32 [4] = mean of qeff / SSD_PRIORITY_ONE over the population, max of the same, the smallest weight, the number of distinct ids.
+ * The kernel: pass 1 the maximum; pass 2 one contiguous chunk of ceil(population / 1024) entries per thread summed in u64; a
+ * workgroup prefix scan of the 1024 chunk sums (a wave scan by shuffles, the sixteen wave totals through LDS, chained in index
+ * order); thread e binary-searches the chunk sums and walks one chunk.  The table is read through L2 (three times at most); no
+ * atomics, no scratch.  table: DEVICE u32 [>= population]; ids, t0: DEVICE int64 [count]; weights: DEVICE f32 [count].
+ * Refused (SSD_ERR_INVALID): NULL args or a NULL member pointer; population outside 1 .. SSD_PRIORITY_POP_MAX; count outside
+ * 1 .. SSD_SAMPLE_IDS_MAX; n_starts < 1; beta outside [0, 1] or NaN; a table that is not 4-byte aligned. */
+#define SSD_PRIORITY_ONE 65536u
+#define SSD_PRIORITY_MAX 16777216u
+#define SSD_PRIORITY_POP_MAX 1048576
+typedef struct ssd_priority_sample_args {
+    uint64_t seed;
+    uint32_t call;
+    int32_t population, count, n_starts;
+    float beta;
+    const uint32_t* table;
+    int64_t *ids, *t0;
+    float* weights;
+    float* log;                  /* [4] */
+} ssd_priority_sample_args;
+int (ssd_priority_sample)(const ssd_priority_sample_args* args, void* stream);
+
+/* ssd_priority_update: after ssd_td_sim_loss (mode 1; either kernel) of a batch of `batch` samples over t_slots = T + 1 slots:
+ * the new priorities of the trained samples from the loss kernel's `partials`, the importance weights applied to the gradient
+ * seeds, the table written.  Two launches on the stream; no workgroup reads what another workgroup of the same launch wrote.
+ * k_priority_rows (one workgroup of 256 threads per sample e) over the sample's T * n rows of partials (col0 = mask,
+ * col2 = (td_env mask)^2, col3 = (td_inc mask)^2):
+ *   d_row = sqrt(col2 + col3)
+ *   p     = eta * max_rows d_row + (1 - eta) * (sum_rows d_row) / max(1, sum_rows col0) + eps
+ *   q_new[e] = clamp(round_to_nearest(p^alpha * SSD_PRIORITY_ONE), 1, SSD_PRIORITY_MAX)          (a NaN counts as SSD_PRIORITY_MAX)
+ * in f32.  Rows without loss (the unfilled tail, burn-in rows, rows after termination) have mask 0 and both squares 0: they add
+ * nothing; a sample with no loss row gets p = eps.  The float max does not depend on the order; the sums are deterministic: thread t
+ * adds its rows t, t + 256, t + 512 .. in rising order, and the 256 thread sums are added by the fixed tree of the optimiser's
+ * partial sums (stride 128, 64 .. 1: element t += element t + stride).
+ * The same workgroup then multiplies every element of the sample's block of dq_env [batch, t_slots, n, A] and of dq_inc
+ * [batch, t_slots, n, n, 3] by weights[e] in place -- one f32 multiply per element, 16-byte accesses between scalar edges.  The train
+ * step then minimises sum_e weights[e] L_e, L_e the sample's share of the loss over the unchanged global denominators.
+ * k_priority_apply (one workgroup): table[ids[e]] = max over the e' with ids[e'] == ids[e] of q_new[e']: thread e writes iff no e'
+ * carries the same id with a larger value, or the same value and a smaller index (ids and values in LDS, `batch` compares per
+ * thread): one writer per slot, whatever the launch order.  An id outside [0, table_len) is skipped.
+ * Refused (SSD_ERR_INVALID): NULL args or a NULL member pointer; batch outside 1 .. SSD_SAMPLE_IDS_MAX; t_slots < 2; n_agents,
+ * n_actions or table_len < 1; table_len over SSD_PRIORITY_POP_MAX; alpha or eta outside [0, 1] or NaN; eps <= 0 or NaN; batch *
+ * t_slots * n_agents over SSD_ROWS32_MAX; partials not 16-byte aligned (its rows are read as 16-byte columns 0 .. 3), dq_env / dq_inc
+ * not 4-byte aligned. */
+typedef struct ssd_priority_update_args {
+    int32_t batch, t_slots, n_agents, n_actions, table_len;
+    float alpha, eta, eps;
+    const float* partials;       /* [batch * (t_slots - 1) * n_agents, SSD_TD_LOSS_PARTIALS] */
+    const int64_t* ids;          /* [batch] */
+    const float* weights;        /* [batch] */
+    float *dq_env, *dq_inc;      /* scaled in place */
+    uint32_t* q_new;             /* [batch] staging */
+    uint32_t* table;             /* [table_len] */
+} ssd_priority_update_args;
+int (ssd_priority_update)(const ssd_priority_update_args* args, void* stream);
+
 /* ssd_clip_adam_step: the optimiser tail of HomophilyLearner.cal_loss_and_step (homophily_learner.py:223-226) --
  *   clip_grad_norm_(params_inc, clip); clip_grad_norm_(params_env, clip); optimiser_inc.step(); optimiser_env.step()
  * with the conv encoder a member of BOTH parameter groups (homophily_agent.py:127-146: its gradient is scaled by both clips, the second

@@ -1,0 +1,413 @@
+"""GPU suite of prioritised replay: ssd_priority_sample against the restatement of tests/priority_util.py (ids and starts exact,
+weights and log values against float64, guard words around every output), its determinism, ssd_priority_update in the poisoned arena
+of tests/arena_util.py (new priorities against float64, the gradient seeds scaled bit for bit, the write-back with duplicates and
+out-of-range ids), the priorities from the rows the loss kernels really wrote, the training loop eager and captured, and the key off
+against the keys' absence bit for bit."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch as th
+
+from homophily_marl_amd import abi, ops
+from tests import priority_util as P
+from tests.arena_util import Arena
+
+pytestmark = pytest.mark.gpu
+
+SEED = P.SEED
+GUARD = 8
+
+
+def _guarded(count, dtype, fill):
+    """a device tensor of `count` elements with GUARD sentinel elements on either side: (whole buffer, the view handed to the launch)"""
+    buf = th.full((count + 2 * GUARD,), fill, dtype=dtype, device="cuda")
+    return buf, buf[GUARD:GUARD + count]
+
+
+def _device_sample(seed, call, table, population, count, n_starts, beta):
+    """one launch; returns host copies (ids, t0, weights, log) after checking the guard words"""
+    bufs = [_guarded(count, th.long, -7), _guarded(count, th.long, -7), _guarded(count, th.float32, -7.0), _guarded(4, th.float32, -7.0)]
+    ops.priority_sample(seed, call, table, population, count, n_starts, beta, *[v for _, v in bufs])
+    out = []
+    for (buf, view), n in zip(bufs, (count, count, count, 4)):
+        host = buf.cpu()
+        assert (host[:GUARD] == -7).all() and (host[GUARD + n:] == -7).all()                 # nothing before, nothing past the output
+        out.append(host[GUARD:GUARD + n])
+    return out
+
+
+# ---- 1. the device draw ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("population", [1, 2, 63, 64, 65, 1023, 1024, 1025, 8192, 16385, 1 << 20])
+def test_device_draws_are_the_restatement(population):
+    """every table of the issue's list x counts 1, 2, 16, 64, 65, 1024 (count > population included) x (n_starts 1, beta 0.4) and
+    (n_starts 76, beta 1): ids and starts exact, weights within 1e-5 of float64 with the largest exactly 1, the four log values"""
+    for name, host_table in P.tables(population).items():
+        table = th.as_tensor(host_table).cuda()
+        if name == "max" and population >= 257:
+            assert P.effective(host_table, population)[2] > 1 << 32          # the total passes 32 bits (2^44 at 2^20 entries)
+        for count in (1, 2, 16, 64, 65, 1024):
+            for seed, call, n_starts, beta in ((SEED, count, 1, 0.4), (2 ** 64 - 1, 2 ** 32 - 1, 76, 1.0)):
+                ids, t0, w, log = _device_sample(seed, call, table, population, count, n_starts, beta)
+                ref = P.sample(seed, call, host_table, population, count, n_starts, beta)
+                where = (name, count, n_starts)
+                assert ids.tolist() == ref["ids"], where
+                assert t0.tolist() == ref["t0"] and (n_starts > 1 or not t0.any()), where
+                err = np.abs(w.numpy().astype(np.float64) - ref["weights"]) / ref["weights"]
+                assert err.max() <= 1e-5 and float(w.max()) == 1.0, (where, float(err.max()))
+                assert np.allclose(log.numpy()[:2], ref["log"][:2], rtol=1e-6, atol=0), (where, log, ref["log"])
+                assert abs(float(log[2]) - ref["log"][2]) <= 1e-5 * ref["log"][2] and float(log[2]) == float(w.min()), (where, log, ref["log"])
+                assert float(log[3]) == ref["log"][3] == len(set(ref["ids"])), (where, log, ref["log"])
+        if name in ("dominant_mid", "random_30pct_zero"):
+            ids, t0, w, log = _device_sample(SEED, 1, table, population, 64, 1, 0.0)
+            assert w.tolist() == [1.0] * 64 and float(log[2]) == 1.0, name    # beta 0: every weight exactly 1
+
+
+def test_same_call_same_bytes_another_call_other_ids():
+    host_table = P.tables(8192)["random_30pct_zero"]
+    table = th.as_tensor(host_table).cuda()
+    a = _device_sample(SEED, 5, table, 8192, 64, 76, 0.4)
+    b = _device_sample(SEED, 5, table, 8192, 64, 76, 0.4)
+    c = _device_sample(SEED, 6, table, 8192, 64, 76, 0.4)
+    assert all(x.numpy().tobytes() == y.numpy().tobytes() for x, y in zip(a, b))
+    assert a[0].tolist() != c[0].tolist() and a[1].tolist() != c[1].tolist()
+
+
+# ---- 2. the update in the arena --------------------------------------------------------------------------------------------------------------
+TABLE_LEN = 40
+
+
+def _hand_partials(rng, B, T, n, scale=1.0):
+    """[B * T * n, 16]: column 0 in {0, 1} with a masked tail, masked leading (burn-in) rows and -- where B allows -- a whole sample
+    masked out; columns 2 / 3 random non-negative under the mask; every other column large (never read)"""
+    part = (1e30 * rng.random((B, T, n, 16))).astype(np.float32)
+    mask = np.ones((B, T, n), np.float32)
+    for e in range(B):
+        lead, tail = (e % 3) * (T // 4), ((e + 1) % 3) * (T // 5)
+        mask[e, :lead] = 0
+        mask[e, T - tail:] = 0
+    if B > 1:
+        mask[1] = 0                                                          # no loss row at all: p = eps
+    part[..., 0] = mask
+    part[..., 2] = scale * rng.random((B, T, n)).astype(np.float32) * mask
+    part[..., 3] = 4 * scale * rng.random((B, T, n)).astype(np.float32) * mask
+    if B >= 16:
+        part[9] = part[8]                                                    # two samples with the same rows: equal q_new
+    return part.reshape(B * T * n, 16)
+
+
+def _ids_for(B):
+    if B == 1:
+        return [7]
+    if B == 2:
+        return [3, 3]
+    # a triple and a pair with different values, a pair with equal values (8, 9), an id at table_len, a negative one, the two ends
+    return [3, 5, 3, 12, 12, 3, 0, TABLE_LEN - 1, 20, 20, TABLE_LEN, -1, 17, 18, 19, 21]
+
+
+def _arena_update(B, T, n, A, part, ids, alpha, eta, eps, seed):
+    rng = np.random.default_rng(seed)
+    ar = Arena()
+    w = rng.uniform(0.01, 1.0, B).astype(np.float32)
+    w[rng.integers(B)] = 1.0
+    dqe = rng.standard_normal((B, T + 1, n, A)).astype(np.float32)
+    dqi = rng.standard_normal((B, T + 1, n, n, 3)).astype(np.float32)
+    table0 = (rng.integers(1, 1 << 24, TABLE_LEN)).astype(np.int32)
+    r = dict(part=ar.place("partials", part, align=16), ids=ar.place("ids", np.asarray(ids, np.int64), align=8, fill=0),
+             w=ar.place("weights", w), dqe=ar.place("dq_env", dqe, offset_in_16=4, inout=True), dqi=ar.place("dq_inc", dqi, offset_in_16=8, inout=True),
+             q=ar.reserve("q_new", (B,), np.int32), table=ar.place("table", table0, fill=-5, inout=True))
+    t = abi.SsdPriorityUpdateArgs()
+    t.batch, t.t_slots, t.n_agents, t.n_actions, t.table_len, t.alpha, t.eta, t.eps = B, T + 1, n, A, TABLE_LEN, alpha, eta, eps
+    t.partials, t.ids, t.weights, t.dq_env, t.dq_inc, t.q_new, t.table = (r[k].ptr for k in ("part", "ids", "w", "dqe", "dqi", "q", "table"))
+    lib = abi.load_library()
+    abi.check(lib, lib.ssd_priority_update(C.byref(t), None))
+    ar.check()                                                               # bands, slack and inputs untouched; no poison in an output
+    return r, w, dqe, dqi, table0
+
+
+@pytest.mark.parametrize("T", [1, 2, 100])
+@pytest.mark.parametrize("B", [1, 2, 16])
+def test_update_in_the_arena(B, T):
+    """n in {2, 5, 10} x A in {8, 9}; alpha 0.6, eta 0.9, eps 1e-3 -- and eta 0 / alpha 1 on the odd shapes"""
+    for n in (2, 5, 10):
+        for A in (8, 9):
+            alpha, eta, eps = (0.6, 0.9, 1e-3) if A == 8 else (1.0, 0.0, 0.25)
+            rng = np.random.default_rng(1000 * B + 10 * T + n)
+            part, ids = _hand_partials(rng, B, T, n), _ids_for(B)
+            r, w, dqe, dqi, table0 = _arena_update(B, T, n, A, part, ids, alpha, eta, eps, seed=B + T + n + A)
+            where = (B, T, n, A)
+            # the gradient seeds: one f32 multiply per element, bit for bit
+            assert r["dqe"].array().tobytes() == (dqe * w[:, None, None, None]).tobytes(), where
+            assert r["dqi"].array().tobytes() == (dqi * w[:, None, None, None, None]).tobytes(), where
+            # the new priorities against float64
+            exact, want = P.q_new(part, B, alpha, eta, eps)
+            q = r["q"].array().astype(np.int64)
+            print(where, "largest |q_new - float64| %.3f at q %.0f" % (np.abs(q - exact).max(), exact[np.abs(q - exact).argmax()]))
+            assert P.within_q(q, exact) and q.min() >= 1 and q.max() <= P.QMAX, (where, q, exact)
+            if B > 1:
+                assert q[1] == np.rint(eps ** alpha * P.ONE)                  # the sample without a loss row: p = eps
+            if B >= 16:
+                assert q[8] == q[9] and q[0] != q[2]
+            # the write-back: the largest value per id, untouched elsewhere, ids outside the table skipped
+            table = r["table"].array().astype(np.int64)
+            assert table.tolist() == P.write_back(table0, ids, q).tolist(), where
+            named = {k for k in ids if 0 <= k < TABLE_LEN}
+            assert all(table[k] == table0[k] for k in range(TABLE_LEN) if k not in named)
+            if B >= 16:
+                assert table[3] == max(q[0], q[2], q[5]) and table[20] == q[8]
+
+
+@pytest.mark.parametrize("alpha,eps,scale,want", [(1.0, 1e-6, 0.0, 1), (0.05, 1e-30, 0.0, None), (1.0, 1e-3, 1e12, P.QMAX), (0.6, 1e-3, 1e30, P.QMAX)])
+def test_update_clamps_at_both_ends(alpha, eps, scale, want):
+    """eps alone (every row masked): p^alpha ONE below 1 clamps to 1, and with a tiny alpha log p it is the float64 value; errors of
+    1e6 and 1e15 clamp to SSD_PRIORITY_MAX"""
+    B, T, n, A = 2, 7, 3, 8
+    rng = np.random.default_rng(2)
+    part = _hand_partials(rng, B, T, n, scale=scale)
+    if scale == 0.0:
+        part[:, 0] = 0
+    r, w, dqe, dqi, table0 = _arena_update(B, T, n, A, part, [4, 9], alpha, 0.9, eps, seed=3)
+    exact, ref = P.q_new(part, B, alpha, 0.9, eps)
+    q = r["q"].array().astype(np.int64)
+    assert P.within_q(q, exact), (q, exact)
+    if want is not None:
+        assert q[0] == want and ref[0] == want, (q, ref)
+    assert r["table"].array()[4] == q[0] and r["table"].array()[9] == q[1]
+
+
+# ---- 3. from the rows the loss kernels wrote ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("lam", [0.0, 0.8])
+def test_priorities_from_the_real_loss_kernels(lam):
+    """the learner fixture (B = 4) on the device: q_new formed by ssd_priority_update from the partials ssd_td_sim_loss wrote (one-step
+    and TD(lambda) kernel) against float64 over the tensor-op learner's per-row TD errors on the same device batch and weights"""
+    from tests.learner_util import build, load_fixture
+    from tests.test_learner_options import perturb_target
+    th.backends.cuda.matmul.allow_tf32 = False
+    z, meta = load_fixture("learner_cleanup5.npz")
+    args, batch, mac, fused = build(z, meta, device="cuda:0", overrides=dict(td_lambda=lam))
+    _, _, mac2, plain = build(z, meta, device="cuda:0", overrides=dict(td_lambda=lam, fused_loss=False))
+    for lr in (fused, plain):
+        perturb_target(lr)
+    assert fused._fused(batch) and not plain._fused(batch)
+    table = th.zeros(8, dtype=th.int32, device="cuda")
+    ids, w = th.tensor([5, 1, 5, 2], device="cuda"), th.tensor([1.0, 0.5, 0.25, 0.7], device="cuda")
+    batch.priority = (table, ids, w)
+    fused.forward_backward(batch)
+    q = fused.last_q_new.cpu().numpy().astype(np.int64)
+    plain.forward_backward(batch)
+    rows = plain.last_td_rows.cpu().numpy()
+    assert rows[:, 0].sum() > 0 and rows[:, 2].max() > 0
+    exact, want = P.q_new(rows, 4, *fused.per)
+    print("td_lambda %g: q_new %s, float64 %s" % (lam, q.tolist(), np.round(exact, 2).tolist()))
+    assert P.within_q(q, exact), (q, exact)
+    assert table.cpu().tolist() == P.write_back(np.zeros(8, np.int64), ids.cpu().tolist(), q).tolist()
+    del batch.priority
+
+
+# ---- 4. the loop: eager and captured -----------------------------------------------------------------------------------------------------------
+N_ENV, T_EP, BATCH, ITERS = 8, 12, 4, 6          # (the buffer holds 4 rollouts: 32 episodes)
+
+
+def _loop_ctx(drop=(), n_env=N_ENV, **over):
+    """Cleanup-3, hip_graph runner, episode_limit 12, batch_size 4, buffer of four rollouts.  A rollout of 8 envs is 8 x 13 x 3 x 49 bytes
+    of class codes, not a multiple of 16, and the env kernel writes observations at 16-byte aligned addresses only: at 8 envs the
+    runner keeps its own storage and the insert copies (replay_in_place off); at 16 envs the rollouts land in the buffer's slots."""
+    from homophily_marl_amd.run import load_config, setup
+    th.manual_seed(0)
+    np.random.seed(11)
+    cfg = load_config("cleanup", overrides=dict(dict(
+        runner="hip_graph", batch_size_run=n_env, batch_size=BATCH, buffer_size=4 * n_env, replay_in_place=n_env % 16 == 0,
+        buffer_cpu_only=False, store_state=False, obs_storage="code",
+        env_args=dict(num_agents=3, map="default3", episode_limit=T_EP, seed=3), use_cuda=True, save_model=False, runner_stats=False,
+        learner_log_interval=10 ** 12, strict_device_ops=True, train_graph=False, train_steps_per_rollout=2), **over))
+    for k in drop:
+        del cfg[k]
+    return setup(cfg)
+
+
+def _run_priority_loop(window, beta, train_graph, check_gradients, n_env=N_ENV):
+    """ITERS iterations of run.train_iteration with the key on; every train step is checked against the restatement (see the tests);
+    returns (final table, final parameters, ids of every step)"""
+    from homophily_marl_amd.run import train_iteration
+    keys = dict(prioritized_replay=True, per_beta=beta, train_graph=train_graph)
+    if window:
+        keys.update(train_window=window, train_burn_in=2)
+    ctx = _loop_ctx(n_env=n_env, **keys)
+    try:
+        buf, learner = ctx.buffer, ctx.learner
+        table = buf.priority_table
+        assert table is not None and table.dtype == th.int32 and table.numel() == 4 * n_env and not table.any()
+        in_place = []
+        inner_insert = buf.insert_episode_batch
+        buf.insert_episode_batch = lambda b: (in_place.append(getattr(b, "_reserved", None) is not None), inner_insert(b))[1]
+        n_starts = T_EP + 1 - window if window else 1
+        steps, grads = [], []
+        inner_train, inner_clip = learner.train, learner.clip_and_step
+
+        def clip_and_step():
+            grads.append(learner._flat_grad.clone())                         # the step's gradient before the clips scale it
+            inner_clip()
+        if check_gradients:
+            learner.clip_and_step = clip_and_step
+
+        def train(sample, t_env, episode):
+            k = len(steps)
+            tab, ids_t, w_t = sample.priority
+            before = table.cpu().numpy().astype(np.int64)
+            ids, w = ids_t.cpu().tolist(), w_t.cpu().numpy()
+            assert tab is table and sample.batch_size == BATCH and sample.max_seq_length == (window + 1 if window else T_EP + 1)
+            # (4) the draw is the restatement's draw from the table as it stands (after step k - 1 and the insert's resets)
+            ref = P.sample(buf._sample_seed, buf._sample_calls - 1, before, buf.episodes_in_buffer, BATCH, n_starts, beta)
+            assert ids == ref["ids"] and np.abs(w - ref["weights"]).max() <= 1e-5 and float(w.max()) == 1.0, (k, ids, ref["ids"])
+            if window:
+                assert buf.last_window_t0.cpu().tolist() == ref["t0"]
+            if k and k % 2:
+                assert np.array_equal(before, steps[-1]["after"]), k         # the second step of a rollout: the chain is exact
+            elif k:
+                # (6) the insert reset exactly the rollout's slots; everything else is as the last step left it
+                lo = ((k // 2) * n_env) % (4 * n_env)
+                want = steps[-1]["after"].copy()
+                want[lo:lo + n_env] = 0
+                assert np.array_equal(before, want), (k, lo)
+            if beta == 0.0:
+                assert w.tolist() == [1.0] * BATCH
+            eager = learner._graph is None and not (train_graph and learner._graph_calls >= 2)
+            ref_grad = None
+            if check_gradients and eager:
+                ops.set_strict(False)
+                try:
+                    if beta == 0.0:                                          # (1) the same batch without the tuple
+                        del sample.priority
+                        learner.forward_backward(sample)
+                        sample.priority = (tab, ids_t, w_t)
+                    else:                                                    # (2) the weighted tensor-op learner on the same batch
+                        learner.args.fused_loss = False
+                        assert not learner._fused(sample)
+                        learner.forward_backward(sample)
+                        learner.args.fused_loss = True
+                    ref_grad = learner._flat_grad.clone()
+                finally:
+                    ops.set_strict(True)
+                assert np.array_equal(table.cpu().numpy(), before)          # neither reference wrote the device table
+            n_grads = len(grads)
+            inner_train(sample, t_env, episode)
+            th.cuda.synchronize()
+            if ref_grad is not None:
+                assert len(grads) == n_grads + 1
+                g, top = grads[-1], float(ref_grad.abs().max())
+                assert top > 0
+                if beta == 0.0:
+                    assert th.equal(g, ref_grad), (k, float((g - ref_grad).abs().max()))
+                else:
+                    err = float((g - ref_grad).abs().max())
+                    print("step %d: fused weighted gradient against the tensor-op learner: %.3e (|g| max %.3e)" % (k, err, top))
+                    assert err <= 1e-5 * max(1.0, top), (k, err, top)
+            # (3) the table after the step is the restated write-back of the step's ids
+            q = learner.last_q_new.cpu().numpy().astype(np.int64)
+            after = table.cpu().numpy().astype(np.int64)
+            assert q.min() >= 1 and np.array_equal(after, P.write_back(before, ids, q)), (k, ids, q)
+            steps.append(dict(ids=ids, after=after, zero_drawn=int((before[ids] == 0).sum())))
+        learner.train = train
+        ep = 0
+        for _ in range(ITERS):
+            ep = train_iteration(ctx, ep)
+        th.cuda.synchronize()
+        assert len(steps) == 2 * ITERS and buf._sample_calls == 2 * ITERS
+        assert (learner._graph is not None) == train_graph and in_place == [n_env % 16 == 0] * ITERS
+        assert any(s["zero_drawn"] for s in steps[2:])                       # fresh episodes were drawn (at the table's maximum)
+        assert all(bool(th.isfinite(p).all()) for p in ctx.mac.parameters())
+        return table.cpu().numpy().astype(np.int64), [p.detach().cpu().clone() for p in ctx.mac.parameters()], [s["ids"] for s in steps]
+    finally:
+        ops.set_strict(False)
+        ctx.runner.close_env()
+
+
+@pytest.mark.parametrize("window", [0, 5])
+def test_beta_zero_is_the_unweighted_gradient_bit_for_bit(window):
+    """(1), (3), (4), (6): with per_beta 0 every weight is 1 and the flat gradient of every train step equals the gradient of the same
+    learner fed the same batch without the priority tuple, bit for bit"""
+    _run_priority_loop(window, 0.0, train_graph=False, check_gradients=True)
+
+
+@pytest.mark.parametrize("window", [0, 5])
+def test_weighted_fused_gradient_matches_the_weighted_tensor_op_learner(window):
+    """(2), (3), (4), (6): per_beta 0.7, every train step's fused gradient within 1e-5 of the tensor-op learner's on the same batch"""
+    _run_priority_loop(window, 0.7, train_graph=False, check_gradients=True)
+
+
+@pytest.mark.parametrize("window", [0, 5])
+def test_captured_replays_are_the_eager_run(window):
+    """(5): the same seed with the train step captured (eager twice, captured at the third call, replayed after; (3), (4), (6) hold at
+    every step of both runs): the sampled ids of every step are equal, the parameters agree within the bar of SSD_GRAPH_CHECK
+    (1e-4 max(1, |ref|)) and the tables within 1 + 1e-4 q"""
+    table_e, par_e, ids_e = _run_priority_loop(window, 0.7, train_graph=False, check_gradients=False)
+    table_g, par_g, ids_g = _run_priority_loop(window, 0.7, train_graph=True, check_gradients=False)
+    assert ids_e == ids_g
+    assert (np.abs(table_e - table_g) <= 1 + 1e-4 * table_e).all(), (table_e, table_g)
+    for a, b in zip(par_e, par_g):
+        assert float((a - b).abs().max()) <= 1e-4 * max(1.0, float(a.abs().max()))
+
+
+def test_rollouts_written_in_place_reset_their_slots():
+    """(3), (4), (6) at 16 envs, where the runner writes its episodes into the buffer's reserved slots and the insert only advances
+    the ring: windows, per_beta 0.7, the captured step"""
+    _run_priority_loop(5, 0.7, train_graph=True, check_gradients=False, n_env=16)
+
+
+def test_a_captured_step_refuses_other_priority_tensors():
+    from homophily_marl_amd.run import train_iteration
+    ctx = _loop_ctx(prioritized_replay=True, train_graph=True)
+    try:
+        ep = 0
+        for _ in range(2):
+            ep = train_iteration(ctx, ep)
+        assert ctx.learner._graph is not None
+        out = ctx.learner.sample_out()
+        sample = ctx.buffer.sample_prioritized(BATCH, beta=0.4, out=out)
+        assert sample is out
+        table, ids, w = sample.priority
+        sample.priority = (table, ids, w.clone())
+        with pytest.raises(ValueError, match="priority"):
+            ctx.learner.train(sample, 0, 0)
+        del sample.priority
+        with pytest.raises(ValueError, match="priority"):
+            ctx.learner.train(sample, 0, 0)
+    finally:
+        ops.set_strict(False)
+        ctx.runner.close_env()
+
+
+# ---- 5. the key off ----------------------------------------------------------------------------------------------------------------------------
+def test_key_off_is_the_loop_without_the_keys():
+    """the keys absent against prioritized_replay: False: stored bytes, the sampled ids of every call and the parameters after four
+    iterations are equal bit for bit; no priority tensor exists; the rollout timestep's launches are the same"""
+    from homophily_marl_amd.run import train_iteration
+    per = ("prioritized_replay", "per_alpha", "per_beta", "per_beta_anneal_steps", "per_eta", "per_eps")
+    runs = []
+    for drop, over in ((per, {}), ((), dict(prioritized_replay=False))):
+        ctx = _loop_ctx(drop=drop, train_graph=True, **over)
+        try:
+            ids = []
+            inner = ctx.learner.train
+
+            def train(sample, t_env, episode, ctx=ctx, ids=ids, inner=inner):
+                assert getattr(sample, "priority", None) is None
+                ids.append(None if ctx.buffer._sample_ids is None else ctx.buffer._sample_ids.cpu().tolist())
+                inner(sample, t_env, episode)
+            ctx.learner.train = train
+            ep = 0
+            for _ in range(4):
+                ep = train_iteration(ctx, ep)
+            th.cuda.synchronize()
+            assert ctx.buffer.priority_table is None and ctx.buffer._priority_draws is None and not hasattr(ctx.learner, "last_q_new")
+            runs.append((ids, {k: v.cpu().clone() for k, v in ctx.buffer.data.transition_data.items()},
+                         [p.detach().cpu().clone() for p in ctx.mac.parameters()], ctx.buffer._sample_calls,
+                         [(name, key) for name, key, _ in ctx.runner.timestep_launches()]))
+        finally:
+            ops.set_strict(False)
+            ctx.runner.close_env()
+    (ids_a, data_a, par_a, calls_a, launches_a), (ids_b, data_b, par_b, calls_b, launches_b) = runs
+    assert len(ids_a) == 8 and ids_a == ids_b and calls_a == calls_b and launches_a == launches_b and any(i is not None for i in ids_a)
+    for k in data_a:
+        assert th.equal(data_a[k], data_b[k]), k
+    assert all(th.equal(a, b) for a, b in zip(par_a, par_b)) and len(par_a) > 0

@@ -33,6 +33,7 @@ ap.add_argument("--behaviour-stats", action="store_true",
                 help="config key behaviour_stats: print abi.behaviour_summary of the training rollouts (and of the greedy test rollout) at every report")
 ap.add_argument("--train-window", type=int, default=0, help="config key train_window: train on windows of L transitions (0: whole episodes)")
 ap.add_argument("--burn-in", type=int, default=0, help="config key train_burn_in: rows of a window without loss")
+ap.add_argument("--prioritized", action="store_true", help="config key prioritized_replay (per_alpha, per_beta, ... through --set)")
 ap.add_argument("--set", action="append", default=[], help="extra config override key=value (python literal)")
 a = ap.parse_args()
 c = CONFIGS[a.config]
@@ -45,6 +46,8 @@ if a.behaviour_stats:
     over["behaviour_stats"] = True
 if a.train_window:
     over.update(train_window=a.train_window, train_burn_in=a.burn_in)
+if a.prioritized:
+    over["prioritized_replay"] = True
 import ast
 for kv in a.set:
     k, v = kv.split("=", 1)
@@ -163,6 +166,10 @@ for it in range(a.iters):
                 vec = [x for k in abi.behaviour_layout(n, ctx.args.n_actions) for x in b[k].reshape(-1)]
                 s = abi.behaviour_summary(vec, n, ctx.args.n_actions)
                 print("   behaviour %s (%d episodes): " % (label, int(b["n_episodes"][0])) + "  ".join("%s %.4f" % kv for kv in s.items()), flush=True)
+        if a.prioritized and ctx.buffer._priority_draws is not None:      # the last sample launch's four log values
+            pl = ctx.buffer._priority_draws.log.tolist()
+            print("   per_priority_mean %.4f  per_priority_max %.4f  per_weight_min %.4f  per_unique_frac %.4f" % (
+                pl[0], pl[1], pl[2], pl[3] / ctx.args.batch_size), flush=True)
         acc, cnt = 0.0, 0
         assert bool(th.isfinite(p).all())
 assert ctx.runner.env.native.poll_error() == 0
