@@ -17,6 +17,9 @@ def _count(idx, size):
 
 
 class EpisodeBatch:
+    # the sampler extras' defaults live on the class as well: `del batch.priority` takes an extra off a batch and it reads None again
+    reward_norm = priority = priority_log = None
+
     def __init__(self, scheme, groups, batch_size, max_seq_length, data=None, preprocess=None, device="cpu"):
         self.scheme = dict(scheme)
         self.groups = groups
@@ -24,6 +27,9 @@ class EpisodeBatch:
         self.max_seq_length = max_seq_length
         self.preprocess = {} if preprocess is None else preprocess
         self.device = device
+        # what a sampler tells the learner about the sample (None: nothing): the length the rewards are divided by (gather_windows), the
+        # (table, ids, weights) of a prioritised draw and its four logged values (sample_prioritized).  A slice carries none of them.
+        self.reward_norm = self.priority = self.priority_log = None
         if data is not None:
             self.data = data
         else:
@@ -60,6 +66,11 @@ class EpisodeBatch:
 
     def extend(self, scheme, groups=None):
         self._allocate(scheme, self.groups if groups is None else groups, self.batch_size, self.max_seq_length, None)
+
+    def take_extras(self, other):
+        """carry other's sampler extras (a learner's static batch stands for the batch it was captured on)"""
+        self.reward_norm, self.priority, self.priority_log = other.reward_norm, other.priority, other.priority_log
+        return self
 
     def to(self, device):
         for store in (self.data.transition_data, self.data.episode_data):
@@ -165,14 +176,14 @@ class ReplayBuffer(EpisodeBatch):
         # number of the sample call); host buffers keep the reference's np.random.choice and consume nothing else
         self._sample_seed = None
         self._sample_calls = 0
-        self._sample_ids = None
+        # the draws' persistent tensors (_draw_tensors): ids / t0 int64 [batch_size]; weights f32 [batch_size] and log f32 [4] exist only
+        # once a prioritised draw was made
+        self._draws = SimpleNamespace(ids=None, t0=None, weights=None, log=None)
         # time windows (sample_windows): "episode" | "window", the length a window batch's rewards are divided by (gather_windows)
         self.window_norm = "episode"
-        self._window_draws = None
         self.last_window_ids = self.last_window_t0 = None
         # prioritised replay (enable_priorities): the fixed-point priority table, one entry per slot; None = the feature is off
         self.priority_table = None
-        self._priority_draws = None
 
     def reserve(self, n):
         """A view over the next n episode slots, for producers that write whole episodes in place (vectorised runners): hand
@@ -187,24 +198,19 @@ class ReplayBuffer(EpisodeBatch):
     def insert_episode_batch(self, ep_batch):
         n = ep_batch.batch_size
         res = getattr(ep_batch, "_reserved", None)
-        if res is not None and res[0] is self and res[1] == self.buffer_index:      # written in place (reserve)
-            self._reset_priorities(self.buffer_index, n)
-            self.buffer_index += n
-            self.episodes_in_buffer = max(self.episodes_in_buffer, self.buffer_index)
-            self.buffer_index %= self.buffer_size
-            return
-        if self.buffer_index + n <= self.buffer_size:
-            where = slice(self.buffer_index, self.buffer_index + n)
-            self.update(ep_batch.data.transition_data, where, slice(0, ep_batch.max_seq_length), mark_filled=False)
-            self.update(ep_batch.data.episode_data, where)
-            self._reset_priorities(self.buffer_index, n)
-            self.buffer_index += n
-            self.episodes_in_buffer = max(self.episodes_in_buffer, self.buffer_index)
-            self.buffer_index %= self.buffer_size
-        else:
+        if self.buffer_index + n > self.buffer_size:
             left = self.buffer_size - self.buffer_index
             self.insert_episode_batch(ep_batch[0:left, :])
             self.insert_episode_batch(ep_batch[left:, :])
+            return
+        if not (res is not None and res[0] is self and res[1] == self.buffer_index):      # (else: written in place, reserve)
+            where = slice(self.buffer_index, self.buffer_index + n)
+            self.update(ep_batch.data.transition_data, where, slice(0, ep_batch.max_seq_length), mark_filled=False)
+            self.update(ep_batch.data.episode_data, where)
+        self._reset_priorities(self.buffer_index, n)
+        self.buffer_index += n
+        self.episodes_in_buffer = max(self.episodes_in_buffer, self.buffer_index)
+        self.buffer_index %= self.buffer_size
 
     def can_sample(self, batch_size):
         return self.episodes_in_buffer >= batch_size
@@ -217,26 +223,48 @@ class ReplayBuffer(EpisodeBatch):
         assert self.can_sample(batch_size)
         if self.episodes_in_buffer == batch_size:
             return self[:batch_size]
-        on_device = th.device(self.device).type == "cuda"
-        if on_device and batch_size <= ops.abi.SAMPLE_IDS_MAX:
-            if self._sample_seed is None:
-                self._sample_seed = int(np.random.randint(0, 2 ** 31 - 1)) | (int(np.random.randint(0, 2 ** 31 - 1)) << 32)
-            if self._sample_ids is None or self._sample_ids.numel() != batch_size:
-                self._sample_ids = th.empty(batch_size, dtype=th.long, device=self.device)
-            ids = ops.sample_ids(self._sample_seed, self._sample_calls, self.episodes_in_buffer, batch_size, self._sample_ids)
+        if self._draws_on_device(batch_size):
+            d = self._draw_tensors(batch_size)
+            ids = ops.sample_ids(self._sample_seed, self._sample_calls, self.episodes_in_buffer, batch_size, d.ids)
             self._sample_calls += 1
         else:
             ep_ids = np.random.choice(self.episodes_in_buffer, batch_size, replace=False)   # episode_buffer.py:243
             ids = th.as_tensor(ep_ids, dtype=th.long, device=self.device)
-        if (out is not None and out.batch_size == batch_size and out.max_seq_length == self.max_seq_length and not self.data.episode_data
-                and all(out.data.transition_data[k].device == v.device for k, v in self.data.transition_data.items())):
-            pairs = [(v, out.data.transition_data[k]) for k, v in self.data.transition_data.items()]
-            if not (ids.is_cuda and ops.gather_rows(pairs, ids)):       # device buffers: one launch for all fields
-                ops._leaving_kernels("gather_rows", ids, "fields that do not qualify for ssd_gather_rows")
-                for v, dst in pairs:
-                    th.index_select(v, 0, ids, out=dst)
-            return out
-        return self[ids]
+        return self._gather_episodes(ids, out)
+
+    def _draws_on_device(self, batch_size):
+        """a device-resident buffer draws batch_size <= SAMPLE_IDS_MAX samples with the draw kernel (else: numpy's generator)"""
+        return th.device(self.device).type == "cuda" and batch_size <= ops.abi.SAMPLE_IDS_MAX
+
+    def _draw_tensors(self, batch_size, prioritized=False):
+        """The persistent tensors a draw of batch_size samples writes, and the seed the draw is keyed by: taken from numpy's generator by
+        the first draw that asks.  The tensors are replaced only when batch_size changes -- a captured train step bakes their addresses
+        in -- and weights / log exist only once a prioritised draw asked for them."""
+        if self._sample_seed is None:
+            self._sample_seed = int(np.random.randint(0, 2 ** 31 - 1)) | (int(np.random.randint(0, 2 ** 31 - 1)) << 32)
+        d = self._draws
+        if d.ids is None or d.ids.numel() != batch_size:
+            idx = th.empty(2, batch_size, dtype=th.long, device=self.device)
+            d = self._draws = SimpleNamespace(ids=idx[0], t0=idx[1], weights=None, log=None)
+        if prioritized and d.weights is None:
+            d.weights, d.log = th.empty(batch_size, dtype=th.float32, device=self.device), th.empty(4, dtype=th.float32, device=self.device)
+        return d
+
+    def _fits(self, out, batch_size, slots):
+        """out can receive batch_size samples of `slots` slots each: that shape, every field on the buffer's device, no episode data"""
+        return (out is not None and out.batch_size == batch_size and out.max_seq_length == slots and not self.data.episode_data
+                and all(out.data.transition_data[k].device == v.device for k, v in self.data.transition_data.items()))
+
+    def _gather_episodes(self, ids, out):
+        """the whole episodes ids: gathered into `out` where it fits (device buffers: one launch for all fields), else a fresh batch"""
+        if not self._fits(out, ids.numel(), self.max_seq_length):
+            return self[ids]
+        pairs = [(v, out.data.transition_data[k]) for k, v in self.data.transition_data.items()]
+        if not (ids.is_cuda and ops.gather_rows(pairs, ids)):
+            ops._leaving_kernels("gather_rows", ids, "fields that do not qualify for ssd_gather_rows")
+            for v, dst in pairs:
+                th.index_select(v, 0, ids, out=dst)
+        return out
 
     # ---- time windows (config keys train_window / train_burn_in / train_window_norm) -------------------------------------------
     def gather_windows(self, ids, t0, window, burn_in, out=None):
@@ -256,8 +284,7 @@ class ReplayBuffer(EpisodeBatch):
         ids, t0 = as_idx(ids), as_idx(t0)
         B = ids.numel()
         src = self.data.transition_data
-        if out is not None and not (out.batch_size == B and out.max_seq_length == W and not self.data.episode_data
-                                    and all(out.data.transition_data[k].device == v.device for k, v in src.items())):
+        if out is not None and not self._fits(out, B, W):
             raise ValueError("gather_windows: out is not a batch of %d windows of %d slots on the buffer's device" % (B, W))
         if out is None:
             nd = SimpleNamespace(transition_data={k: th.empty((B, W) + tuple(v.shape[2:]), dtype=v.dtype, device=v.device) for k, v in src.items()},
@@ -289,13 +316,9 @@ class ReplayBuffer(EpisodeBatch):
         n_starts = self.max_seq_length - window
         if n_starts < 1:
             raise ValueError("sample_windows: window %r outside 1 .. %d" % (window, self.max_seq_length - 1))
-        if th.device(self.device).type == "cuda" and batch_size <= ops.abi.SAMPLE_IDS_MAX:
-            if self._sample_seed is None:
-                self._sample_seed = int(np.random.randint(0, 2 ** 31 - 1)) | (int(np.random.randint(0, 2 ** 31 - 1)) << 32)
-            if self._window_draws is None or self._window_draws.shape[1] != batch_size:
-                self._window_draws = th.empty(2, batch_size, dtype=th.long, device=self.device)
-            ids, t0 = ops.sample_windows(self._sample_seed, self._sample_calls, self.episodes_in_buffer, batch_size, n_starts,
-                                         self._window_draws[0], self._window_draws[1])
+        if self._draws_on_device(batch_size):
+            d = self._draw_tensors(batch_size)
+            ids, t0 = ops.sample_windows(self._sample_seed, self._sample_calls, self.episodes_in_buffer, batch_size, n_starts, d.ids, d.t0)
             if self.episodes_in_buffer == batch_size:
                 ids.copy_(th.arange(batch_size, device=self.device))
         else:
@@ -338,29 +361,15 @@ class ReplayBuffer(EpisodeBatch):
         n_starts = self.max_seq_length - window if window else 1
         if n_starts < 1 or window < 0:
             raise ValueError("sample_prioritized: window %r outside 0 .. %d" % (window, self.max_seq_length - 1))
-        if self._sample_seed is None:
-            self._sample_seed = int(np.random.randint(0, 2 ** 31 - 1)) | (int(np.random.randint(0, 2 ** 31 - 1)) << 32)
-        d = self._priority_draws
-        if d is None or d.ids.numel() != batch_size:
-            idx = th.empty(2, batch_size, dtype=th.long, device=self.device)
-            d = self._priority_draws = SimpleNamespace(ids=idx[0], t0=idx[1], weights=th.empty(batch_size, dtype=th.float32, device=self.device),
-                                                       log=th.empty(4, dtype=th.float32, device=self.device))
+        d = self._draw_tensors(batch_size, prioritized=True)
         ops.priority_sample(self._sample_seed, self._sample_calls, self.priority_table, self.episodes_in_buffer, batch_size, n_starts, beta,
                             d.ids, d.t0, d.weights, d.log)
         self._sample_calls += 1
         if window:
             self.last_window_ids, self.last_window_t0 = d.ids, d.t0
             batch = self.gather_windows(d.ids, d.t0, window, burn_in, out=out)
-        elif (out is not None and out.batch_size == batch_size and out.max_seq_length == self.max_seq_length and not self.data.episode_data
-                and all(out.data.transition_data[k].device == v.device for k, v in self.data.transition_data.items())):
-            pairs = [(v, out.data.transition_data[k]) for k, v in self.data.transition_data.items()]
-            if not (d.ids.is_cuda and ops.gather_rows(pairs, d.ids)):
-                ops._leaving_kernels("gather_rows", d.ids, "fields that do not qualify for ssd_gather_rows")
-                for v, dst in pairs:
-                    th.index_select(v, 0, d.ids, out=dst)
-            batch = out
         else:
-            batch = self[d.ids]
+            batch = self._gather_episodes(d.ids, out)
         batch.priority, batch.priority_log = (self.priority_table, d.ids, d.weights), d.log
         return batch
 

@@ -496,7 +496,7 @@ int ssd_gather_rows(const ssd_row_gather* fields, int32_t count, const int64_t* 
 
 int ssd_sample_ids(uint64_t seed, uint32_t call, int32_t population, int32_t count, int64_t* ids, void* stream) {
     if (!ids || count < 1 || count > SSD_SAMPLE_IDS_MAX || population < count) return fail(SSD_ERR_INVALID, "ssd_sample_ids: 1 <= count <= min(population, SSD_SAMPLE_IDS_MAX)");
-    launch_sample_ids(seed, call, population, count, ids, (hipStream_t)stream);
+    launch_sample_draw(seed, call, population, count, 1, ids, nullptr, (hipStream_t)stream);
     return launched();
 }
 
@@ -529,8 +529,8 @@ int ssd_sample_windows(uint64_t seed, uint32_t call, int32_t population, int32_t
     if (!ids || !t0) return fail(SSD_ERR_INVALID, "ssd_sample_windows: null pointer");
     if (count < 1 || count > SSD_SAMPLE_IDS_MAX || population < count) return fail(SSD_ERR_INVALID, "ssd_sample_windows: 1 <= count <= min(population, SSD_SAMPLE_IDS_MAX)");
     if (n_starts < 1) return fail(SSD_ERR_INVALID, "ssd_sample_windows: n_starts >= 1");
-    launch_sample_windows(seed, call, population, count, n_starts, ids, t0, (hipStream_t)stream);
-    return SSD_OK;
+    launch_sample_draw(seed, call, population, count, n_starts, ids, t0, (hipStream_t)stream);
+    return launched();
 }
 
 int ssd_gather_windows(const ssd_window_field* fields, int32_t count, const int64_t* ids, const int64_t* t0, int32_t n_ids, int32_t src_slots,
@@ -553,7 +553,7 @@ int ssd_gather_windows(const ssd_window_field* fields, int32_t count, const int6
         }
     }
     launch_gather_windows(fields, count, ids, t0, n_ids, src_slots, win_slots, burn_in, (hipStream_t)stream);
-    return SSD_OK;
+    return launched();
 }
 
 static bool unit_interval(float x) { return x >= 0.f && x <= 1.f; }          // (false for a NaN)

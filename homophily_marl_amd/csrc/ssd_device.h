@@ -161,7 +161,6 @@ void launch_copy_blocks(const ssd_block_copy* blocks, int count, hipStream_t str
 void launch_clip_adam(const ssd_clip_adam_args* a, hipStream_t stream);
 void launch_dueling_q(const float* a, const float* v, float* q, const float* dq, float* da, float* dv, int n, int T, int B, int inner, int K, hipStream_t stream,
                       int ld = 0, int merged = 0, float* gs = nullptr);
-void launch_sample_ids(uint64_t seed, uint32_t call, int population, int count, int64_t* out, hipStream_t stream);
 void launch_gather_rows(const ssd_row_gather* fields, int count, const int64_t* ids, int n_ids, hipStream_t stream);
 void launch_td_sim_loss(const ssd_td_loss_args* a, int mode, hipStream_t stream);
 void launch_encoder(const float* obs, int rows, int V, const float* cw, const float* cb, const float* lw, const float* lb, float* out,
@@ -196,7 +195,7 @@ void set_learner_precision(int p);
 void launch_fill_blocks(const ssd_block_fill* blocks, int count, hipStream_t stream);
 void launch_runner_stats(const float* coll, const float* eq, const float* ret, int n_env, int n_ret, double* acc, hipStream_t stream);
 void launch_behaviour_stats(const ssd_behaviour_args* a, hipStream_t stream);
-void launch_sample_windows(uint64_t seed, uint32_t call, int population, int count, int n_starts, int64_t* ids, int64_t* t0, hipStream_t stream);
+void launch_sample_draw(uint64_t seed, uint32_t call, int population, int count, int n_starts, int64_t* ids, int64_t* t0, hipStream_t stream);   // t0 null: ids alone
 void launch_gather_windows(const ssd_window_field* fields, int count, const int64_t* ids, const int64_t* t0, int n_ids, int src_slots,
                            int win_slots, int burn_in, hipStream_t stream);
 void launch_priority_sample(const ssd_priority_sample_args* a, hipStream_t stream);

@@ -776,10 +776,17 @@ void launch_gather_rows(const ssd_row_gather* fields, int count, const int64_t* 
     hipLaunchKernelGGL(k_gather_rows, dim3(gx, count, n_ids), dim3(256), 0, stream, t, ids);
 }
 
-// k_sample_ids: `count` distinct episode ids out of [0, population), uniformly, from a counter generator keyed by (seed, call) --
-// ReplayBuffer.sample's np.random.choice(replace = False) (episode_buffer.py:240-244) without a host draw or an H2D copy.  Floyd's
-// subset sampling (a uniform count-subset with count draws, no population-sized permutation), then a Fisher-Yates pass over the
-// count picks.  One thread: count is a batch size (16 in the shipped configuration; the ABI bounds it at SSD_SAMPLE_IDS_MAX).
+// k_sample_draw<S>: the one replay draw kernel (ssd_sample_ids: t0 null; ssd_sample_windows: t0 given).  ids: `count` distinct episode
+// ids out of [0, population), uniformly, from a counter generator keyed by (seed, call) -- ReplayBuffer.sample's
+// np.random.choice(replace = False) (episode_buffer.py:240-244) without a host draw or an H2D copy.  Floyd's subset sampling (a uniform
+// count-subset with count draws, no population-sized permutation), then a Fisher-Yates pass over the count picks.  t0, where asked
+// for: one window start per id from the draws the ids do not use, t0[e] = floor(draw(2 count + e) n_starts / 2^32) (include/ssd_hip.h);
+// t0 is a kernel argument, so the branch on it is uniform, and with a null t0 no start is formed or written.
+// One wave.  Every draw depends on its index alone, so the lanes form all of them first: the Floyd candidates t_i and the Fisher-Yates
+// partners k_i go to LDS, the starts straight out.  What stays serial is the chain over the picks, and that runs in registers: pick
+// s * 64 + l lives in p[s] of lane l (S = ceil(count / 64) slots, -1 while unset), "already picked" is S compares per lane and a
+// ballot, a swap two readlanes and two predicated moves; the next step's t / k is fetched from LDS a step ahead.  (One thread walking
+// the picks in LDS is no faster at 16 ids and takes 41 us at 64 ids and 118 us at 128: the compares are quadratic in count.)
 __device__ __forceinline__ uint32_t sample_draw(uint32_t s0, uint32_t s1, uint32_t call, uint32_t i) {
     uint32_t x = s0 ^ (call * 0x9E3779B9u);
     x ^= x >> 17; x *= 0xed5ad4bbu; x ^= x >> 11; x *= 0xac4c1b51u; x ^= x >> 15; x *= 0x31848babu; x ^= x >> 14;
@@ -787,47 +794,16 @@ __device__ __forceinline__ uint32_t sample_draw(uint32_t s0, uint32_t s1, uint32
     x ^= x >> 17; x *= 0xed5ad4bbu; x ^= x >> 11; x *= 0xac4c1b51u; x ^= x >> 15; x *= 0x31848babu; x ^= x >> 14;
     return x;
 }
-__global__ __launch_bounds__(64) void k_sample_ids(uint32_t s0, uint32_t s1, uint32_t call, int population, int count, int64_t* __restrict__ out) {
-    // the picks live in LDS while they are compared and swapped (through `out` every pick waited for the stores before it: 15 us for 16 ids)
-    __shared__ int32_t pick[SSD_SAMPLE_IDS_MAX];
-    if (blockIdx.x != 0) return;
-    if (threadIdx.x == 0) {
-        for (int i = 0; i < count; ++i) {
-            const int j = population - count + i;
-            const int t = (int)(((uint64_t)sample_draw(s0, s1, call, (uint32_t)i) * (uint32_t)(j + 1)) >> 32);
-            bool taken = false;
-            for (int k = 0; k < i; ++k) taken |= pick[k] == t;
-            pick[i] = taken ? j : t;
-        }
-        for (int i = count - 1; i > 0; --i) {
-            const int k = (int)(((uint64_t)sample_draw(s0, s1, call, (uint32_t)(count + i)) * (uint32_t)(i + 1)) >> 32);
-            const int32_t a = pick[i]; pick[i] = pick[k]; pick[k] = a;
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < count; i += 64) out[i] = (int64_t)pick[i];
-}
-void launch_sample_ids(uint64_t seed, uint32_t call, int population, int count, int64_t* out, hipStream_t stream) {
-    hipLaunchKernelGGL(k_sample_ids, dim3(1), dim3(64), 0, stream, (uint32_t)seed, (uint32_t)(seed >> 32), call, population, count, out);
-}
-
-// k_sample_windows: the ids of k_sample_ids (the same draws, the same Floyd and Fisher-Yates steps) and one window start per id from the
-// draws the ids do not use: t0[e] = floor(draw(2 count + e) n_starts / 2^32) (include/ssd_hip.h).  One wave.  Every draw depends on
-// its index alone, so the lanes form all of them first: the Floyd candidates t_i and the Fisher-Yates partners k_i go to LDS, the
-// starts straight out.  What stays serial is the chain over the picks, and that runs in registers: pick s * 64 + l lives in p[s] of
-// lane l (S = ceil(count / 64) slots, -1 while unset), "already picked" is S compares per lane and a ballot, a swap two readlanes
-// and two predicated moves; the next step's t / k is fetched from LDS a step ahead.  (One thread walking the picks in LDS, as
-// k_sample_ids does at its 16 ids, took 41 us at 64 ids and 118 us at 128: the compares are quadratic in count.)
 template <int S>
-__global__ __launch_bounds__(64) void k_sample_windows(uint32_t s0, uint32_t s1, uint32_t call, int population, int count, int n_starts,
-                                                       int64_t* __restrict__ ids, int64_t* __restrict__ t0) {
+__global__ __launch_bounds__(64) void k_sample_draw(uint32_t s0, uint32_t s1, uint32_t call, int population, int count, int n_starts,
+                                                    int64_t* __restrict__ ids, int64_t* __restrict__ t0) {
     __shared__ int32_t tv[SSD_SAMPLE_IDS_MAX], kv[SSD_SAMPLE_IDS_MAX];
     if (blockIdx.x != 0) return;
     const int lane = threadIdx.x;
     for (int i = lane; i < count; i += 64) {
         tv[i] = (int)(((uint64_t)sample_draw(s0, s1, call, (uint32_t)i) * (uint32_t)(population - count + i + 1)) >> 32);
         kv[i] = (int)(((uint64_t)sample_draw(s0, s1, call, (uint32_t)(count + i)) * (uint32_t)(i + 1)) >> 32);      // (kv[0] is never used)
-        t0[i] = (int64_t)(((uint64_t)sample_draw(s0, s1, call, (uint32_t)(2 * count + i)) * (uint32_t)n_starts) >> 32);
+        if (t0) t0[i] = (int64_t)(((uint64_t)sample_draw(s0, s1, call, (uint32_t)(2 * count + i)) * (uint32_t)n_starts) >> 32);
     }
     __syncthreads();
     int32_t p[S];
@@ -867,12 +843,12 @@ __global__ __launch_bounds__(64) void k_sample_windows(uint32_t s0, uint32_t s1,
     for (int s = 0; s < S; ++s)
         if (s * 64 + lane < count) ids[s * 64 + lane] = (int64_t)p[s];
 }
-void launch_sample_windows(uint64_t seed, uint32_t call, int population, int count, int n_starts, int64_t* ids, int64_t* t0, hipStream_t stream) {
+void launch_sample_draw(uint64_t seed, uint32_t call, int population, int count, int n_starts, int64_t* ids, int64_t* t0, hipStream_t stream) {
     const uint32_t s0 = (uint32_t)seed, s1 = (uint32_t)(seed >> 32);
-    if (count <= 64) hipLaunchKernelGGL(k_sample_windows<1>, dim3(1), dim3(64), 0, stream, s0, s1, call, population, count, n_starts, ids, t0);
-    else if (count <= 128) hipLaunchKernelGGL(k_sample_windows<2>, dim3(1), dim3(64), 0, stream, s0, s1, call, population, count, n_starts, ids, t0);
-    else if (count <= 256) hipLaunchKernelGGL(k_sample_windows<4>, dim3(1), dim3(64), 0, stream, s0, s1, call, population, count, n_starts, ids, t0);
-    else hipLaunchKernelGGL(k_sample_windows<SSD_SAMPLE_IDS_MAX / 64>, dim3(1), dim3(64), 0, stream, s0, s1, call, population, count, n_starts, ids, t0);
+    if (count <= 64) hipLaunchKernelGGL(k_sample_draw<1>, dim3(1), dim3(64), 0, stream, s0, s1, call, population, count, n_starts, ids, t0);
+    else if (count <= 128) hipLaunchKernelGGL(k_sample_draw<2>, dim3(1), dim3(64), 0, stream, s0, s1, call, population, count, n_starts, ids, t0);
+    else if (count <= 256) hipLaunchKernelGGL(k_sample_draw<4>, dim3(1), dim3(64), 0, stream, s0, s1, call, population, count, n_starts, ids, t0);
+    else hipLaunchKernelGGL(k_sample_draw<SSD_SAMPLE_IDS_MAX / 64>, dim3(1), dim3(64), 0, stream, s0, s1, call, population, count, n_starts, ids, t0);
 }
 
 // k_gather_windows: windows [t0[e], t0[e] + win_slots) of rows ids[e] of up to SSD_COPY_BLOCKS_MAX fields into consecutive rows of

@@ -284,7 +284,7 @@ class HomophilyLearner:
     def _forward_backward_fused(self, batch, dens):
         a, n = self.args, self.n_agents
         q_env, q_inc, tq_env, tq_inc = self.unroll_pair(batch)
-        priority = getattr(batch, "priority", None)
+        priority = batch.priority
         if priority is None:
             dq_env, dq_inc, sums = ops.td_sim_loss_grads(q_env, q_inc, tq_env, tq_inc, dens, batch, a)
         else:
@@ -361,7 +361,7 @@ class HomophilyLearner:
         value_loss_inc = ((td_inc * mask) ** 2).sum() / dens[0]
         # prioritised replay: per-sample importance weights inside the three sums of the optimised loss (the logged losses stay
         # unweighted); the new priorities come from the same rows the fused path reads (d = sqrt of the two squared masked errors)
-        priority = getattr(batch, "priority", None)
+        priority = batch.priority
         w = None
         if priority is not None:
             w = priority[2].to(td_env.device).float()[:batch.batch_size]
@@ -478,39 +478,41 @@ class HomophilyLearner:
         return logs
 
     # ---- hipGraph path ---------------------------------------------------------------------------------------------
+    def _capture(self, batch):
+        """The static copy of `batch` and the step captured on it: forward_backward and clip_and_step as two graphs, with the gradient
+        all-reduce between them."""
+        self._static_data = {k: v.clone() for k, v in batch.data.transition_data.items()}
+        # a window batch's normaliser is baked into the graph, and so are a prioritised sample's table, ids and weights, by address
+        # (ReplayBuffer.sample_prioritized keeps them)
+        self._static_batch = EpisodeBatch(batch.scheme, batch.groups, batch.batch_size, batch.max_seq_length,
+                                          data=SimpleNamespace(transition_data=self._static_data, episode_data={}),
+                                          device=batch.device).take_extras(batch)
+        self._static_priority = self._priority_ptrs(batch)
+        self._static_dens = th.zeros(2, device=batch.device)
+        th.cuda.synchronize()
+        # the step is captured on a stream of this learner's own: per-(device, stream) kernel scratch (the row-chunked affine
+        # backward's partial tiles) baked into the graph then belongs to THIS graph and nothing else
+        self._capture_stream = th.cuda.Stream(device=batch.device)
+        ops.reserve_bmm_scratch(self._capture_stream)
+        # thread_local: with an initialised process group the RCCL watchdog thread keeps polling events while we capture
+        g1, g2 = th.cuda.CUDAGraph(), th.cuda.CUDAGraph()
+        with th.cuda.graph(g1, stream=self._capture_stream, capture_error_mode="thread_local"):
+            # data parallel: the denominators are all-reduced OUTSIDE the graph and handed in; else they are part of the graph
+            self._static_logs = self.forward_backward(self._static_batch, self._static_dens if self.distributed else None)
+        with th.cuda.graph(g2, pool=g1.pool(), stream=self._capture_stream, capture_error_mode="thread_local"):
+            self.clip_and_step()
+        self._graph = (g1, g2)
+
     def _graph_step(self, batch):
         """Replay of the captured step on a static copy of the sampled batch.  The first two calls run eagerly (warm-up
-        of allocator, hipBLASLt / MIOpen plans and Adam state), the third captures forward_backward and clip_and_step
-        as two graphs with the gradient all-reduce between them."""
+        of allocator, hipBLASLt / MIOpen plans and Adam state), the third captures the step (_capture)."""
         self._graph_calls += 1
         # Only the fused-loss step is captured: the tensor-op loss is full of ATen multi-block reductions, which are not safe in
         # a replayed hipGraph on this stack (ops.column_sums)
         if self._graph_calls <= 2 or not self._fused(batch):
             return self.cal_loss_and_step(batch)
         if self._graph is None:
-            self._static_data = {k: v.clone() for k, v in batch.data.transition_data.items()}
-            self._static_batch = EpisodeBatch(batch.scheme, batch.groups, batch.batch_size, batch.max_seq_length,
-                                              data=SimpleNamespace(transition_data=self._static_data, episode_data={}),
-                                              device=batch.device)
-            self._static_batch.reward_norm = getattr(batch, "reward_norm", None)      # a window batch's normaliser is baked into the graph
-            # prioritised replay: table, ids and weights are baked into the graph by address (ReplayBuffer.sample_prioritized keeps them)
-            self._static_batch.priority = getattr(batch, "priority", None)
-            self._static_batch.priority_log = getattr(batch, "priority_log", None)
-            self._static_priority = self._priority_ptrs(batch)
-            self._static_dens = th.zeros(2, device=batch.device)
-            th.cuda.synchronize()
-            # the step is captured on a stream of this learner's own: per-(device, stream) kernel scratch (the row-chunked affine
-            # backward's partial tiles) baked into the graph then belongs to THIS graph and nothing else
-            self._capture_stream = th.cuda.Stream(device=batch.device)
-            ops.reserve_bmm_scratch(self._capture_stream)
-            # thread_local: with an initialised process group the RCCL watchdog thread keeps polling events while we capture
-            g1, g2 = th.cuda.CUDAGraph(), th.cuda.CUDAGraph()
-            with th.cuda.graph(g1, stream=self._capture_stream, capture_error_mode="thread_local"):
-                # data parallel: the denominators are all-reduced OUTSIDE the graph and handed in; else they are part of the graph
-                self._static_logs = self.forward_backward(self._static_batch, self._static_dens if self.distributed else None)
-            with th.cuda.graph(g2, pool=g1.pool(), stream=self._capture_stream, capture_error_mode="thread_local"):
-                self.clip_and_step()
-            self._graph = (g1, g2)
+            self._capture(batch)
         st = self._static_batch
         if (batch.batch_size, batch.max_seq_length, ops.reward_norm(batch)) != (st.batch_size, st.max_seq_length, ops.reward_norm(st)):
             raise ValueError("the train step was captured for %d x %d slots (reward normaliser %g), got a batch of %d x %d (%g)" % (
@@ -549,7 +551,7 @@ class HomophilyLearner:
 
     @staticmethod
     def _priority_ptrs(batch):
-        return tuple(t.data_ptr() for t in (getattr(batch, "priority", None) or ()))
+        return tuple(t.data_ptr() for t in (batch.priority or ()))
 
     def sample_out(self):
         """The static batch of the captured train step once it exists (else None): ReplayBuffer.sample(batch_size, out=...) gathers
@@ -568,7 +570,7 @@ class HomophilyLearner:
         clock = self.log_clock() if self.log_clock is not None else t_env
         if clock - self.log_stats_t >= self.args.learner_log_interval:
             means = (("clean_num_mean", batch["clean_num"][:, :-1].mean()), ("apple_den_mean", batch["apple_den"][:, :-1].mean()))
-            plog = getattr(batch, "priority_log", None)
+            plog = batch.priority_log
             if plog is not None:                                             # prioritised replay: the sample launch's four values
                 means += (("per_priority_mean", plog[0]), ("per_priority_max", plog[1]), ("per_weight_min", plog[2]),
                           ("per_unique_frac", plog[3] / batch.batch_size))

@@ -1,8 +1,18 @@
-"""Torch-facing wrappers of the two learner-side HIP kernels (csrc/ssd_learner.hip) through the C ABI.
+"""The operator layer: every torch-facing operator of the learner, the controller and the replay buffer over the C ABI of
+libssd_hip.so (include/ssd_hip.h) -- loss and incentive transfer, agent inputs, affine layers, dueling heads, encoder, recurrence,
+replay draws and gathers, priorities, fills and statistics -- with the autograd Functions that give the kernels their backward.
 
-Device tensors always go through libssd_hip.so (load_library() raises if it is missing: no silent fallback on a GPU
-box).  For CPU tensors -- the CPU test-suite and the gloo rehearsal of the data-parallel path, where no HIP device
-exists -- the same arithmetic is evaluated with torch expressions; that branch is never taken by a GPU run.
+Guard rules, the same for every operator:
+  * device tensors go through the library (load_library() raises if it is missing: no silent fallback on a GPU box);
+  * every launch is guarded over device, dtype and the sizes its arguments are derived from.  A call its kernel is not instantiated
+    for takes the operator's tensor-op statement -- the same arithmetic in torch expressions -- after _leaving_kernels, or raises a
+    ValueError naming the argument (_unfit) where no statement can take it either;
+  * host tensors -- the CPU test-suite and the gloo rehearsal of the data-parallel path, where no HIP device exists -- always take the
+    tensor-op statement; a GPU run never does;
+  * a Function records the learner precision (LEARNER_PRECISION, _precision) at forward and runs its backward launches under it.
+
+Strict mode (config key strict_device_ops, SSD_STRICT_DEVICE_OPS=1, set_strict): _leaving_kernels raises for a device tensor, so a
+tensor-op branch on a GPU run is a failure, not a fallback.  bench.py, smoke() and the GPU suite run under it.
 """
 import ctypes as C
 
@@ -198,7 +208,7 @@ def incentive_transfer(actions_inc, rewards, effect_ratio, cost_ratio, incentive
 def reward_norm(batch):
     """The length the rewards are divided by (homophily_learner.py:112-115, `/ batch.max_seq_length`): the attribute a window batch
     carries (ReplayBuffer.gather_windows; config key train_window_norm), else the batch's own slot count."""
-    return float(getattr(batch, "reward_norm", None) or batch.max_seq_length)
+    return float(batch.reward_norm or batch.max_seq_length)
 
 
 def _td_loss_args(batch, a, n_actions, partials):
@@ -233,41 +243,10 @@ def loss_denominators(batch, a, n_actions):
     return column_sums(partials)[:2]
 
 
-class _TdSimLoss(th.autograd.Function):
-    """loss = (sum (td_env mask)^2 + sum (td_inc mask)^2) / dens[0] + sim_loss_weight * sum_sim / (1 + dens[1]) and its gradient w.r.t.
-    q_env / q_inc from one launch (csrc/ssd_learner.hip: k_td_sim_loss); returns (loss, column sums of the per-row partials)."""
-
-    @staticmethod
-    def forward(ctx, q_env, q_inc, tq_env, tq_inc, dens, batch, a):
-        lib = abi.load_library()
-        B, T, n = batch.batch_size, batch.max_seq_length - 1, q_env.shape[2]
-        q_env, q_inc, tq_env, tq_inc = q_env.contiguous(), q_inc.contiguous(), tq_env.contiguous(), tq_inc.contiguous()
-        partials = th.zeros(B * T * n, abi.TD_LOSS_PARTIALS, dtype=th.float32, device=q_env.device)
-        dq_env, dq_inc = th.empty_like(q_env), th.empty_like(q_inc)
-        t, keep = _td_loss_args(batch, a, q_env.shape[-1], partials)
-        t.q_env, t.q_inc, t.tq_env, t.tq_inc = q_env.data_ptr(), q_inc.data_ptr(), tq_env.data_ptr(), tq_inc.data_ptr()
-        dens = dens.contiguous().float()
-        t.dens, t.dq_env, t.dq_inc = dens.data_ptr(), dq_env.data_ptr(), dq_inc.data_ptr()
-        abi.check(lib, lib.ssd_td_sim_loss(C.byref(t), 1, _stream(q_env)))
-        sums = column_sums(partials)
-        loss = (sums[2] + sums[3]) / dens[0] + a.sim_loss_weight * sums[4] / (1 + dens[1])
-        ctx.save_for_backward(dq_env, dq_inc)
-        ctx.mark_non_differentiable(sums)
-        return loss, sums
-
-    @staticmethod
-    def backward(ctx, g_loss, g_sums):
-        dq_env, dq_inc = ctx.saved_tensors
-        return dq_env * g_loss, dq_inc * g_loss, None, None, None, None, None
-
-
-def td_sim_loss(q_env, q_inc, tq_env, tq_inc, dens, batch, a):
-    return _TdSimLoss.apply(q_env, q_inc, tq_env, tq_inc, dens, batch, a)
-
-
 def td_sim_loss_grads(q_env, q_inc, tq_env, tq_inc, dens, batch, a, with_partials=False):
-    """(dL/dq_env, dL/dq_inc, column sums of the per-row partials) of the same loss from the same launch, WITHOUT an autograd node:
-    the learner seeds the backward pass of the two Q tensors with the gradients directly (th.autograd.grad(..., grad_outputs=...)) --
+    """(dL/dq_env, dL/dq_inc, column sums of the per-row partials) of the loss
+        (sum (td_env mask)^2 + sum (td_inc mask)^2) / dens[0] + sim_loss_weight * sum_sim / (1 + dens[1])
+    from one launch (csrc/ssd_learner.hip: k_td_sim_loss / k_td_lambda_loss), WITHOUT an autograd node: the learner seeds the backward pass of the two Q tensors with the gradients directly (th.autograd.grad(..., grad_outputs=...)) --
     the loss scalar is a logged quantity only (_FusedLogs forms it when it is read), so the six scalar launches that assembled it and
     the two multiplications by d loss / d loss = 1 of the autograd form are gone.  Columns 13..15 of the partials are never read
     (13 / 14 are written only with td_lambda > 0: the rows' lambda-returns).  with_partials: the per-row partials as a fourth result

@@ -264,7 +264,9 @@ int ssd_gather_rows(const ssd_row_gather* fields, int32_t count, const int64_t* 
  * ReplayBuffer.sample's `np.random.choice(episodes_in_buffer, batch_size, replace=False)` (episode_buffer.py:240-244) without a host
  * draw or an H2D copy of the indices.  Counter generator keyed by (seed, call): the caller advances `call` per sample; the same
  * (seed, call, population, count) gives the same ids on every device (a restatement for host tensors: ops.sample_ids).  Floyd's
- * subset sampling + a Fisher-Yates pass over the picks; a bounded draw is floor(u32 * m / 2^32) (bias < m / 2^32).  ids: DEVICE int64. */
+ * subset sampling + a Fisher-Yates pass over the picks; a bounded draw is floor(u32 * m / 2^32) (bias < m / 2^32).  ids: DEVICE int64.
+ * One draw kernel serves this export and ssd_sample_windows (k_sample_draw, the former k_sample_windows; the single-thread
+ * k_sample_ids is gone): here it runs without a t0 and forms no starts. */
 #define SSD_SAMPLE_IDS_MAX 1024
 int ssd_sample_ids(uint64_t seed, uint32_t call, int32_t population, int32_t count, int64_t* ids, void* stream);
 
@@ -352,8 +354,8 @@ int (ssd_behaviour_stats)(const ssd_behaviour_args* args, void* stream);
  * ssd_behaviour_stats; their ctypes mirror is abi.WINDOW_SIGNATURES and their symbol, struct-size and refusal checks are
  * tests/test_train_window_host.py.
  *
- * ssd_sample_windows: ids[0 .. count) exactly as ssd_sample_ids gives them for the same (seed, call, population, count) -- turning
- * windows on does not change which episodes are sampled -- and t0[e] uniform on [0, n_starts):
+ * ssd_sample_windows: ids[0 .. count) exactly as ssd_sample_ids gives them for the same (seed, call, population, count) -- the same
+ * kernel writes them; turning windows on does not change which episodes are sampled -- and t0[e] uniform on [0, n_starts):
  *     t0[e] = floor(draw(2 * count + e) * n_starts / 2^32)
  * where draw(i) is the counter generator's 32-bit draw number i of (seed, call), all arithmetic in u32 (mix32p: "Exploration draws"
  * below), s0 / s1 the low / high 32 bits of seed:

@@ -1063,7 +1063,9 @@ def test_replay_indices_are_drawn_on_the_device():
     from homophily_marl_amd.components.episode_buffer import ReplayBuffer
     for seed, call, pop, cnt in [(0x1234567890ABCDEF, 0, 8192, 16), (7, 3, 4096, 16), (2 ** 63 + 5, 2 ** 31 + 1, 17, 16), (1, 1, 64, 64),
                                  (5, 9, 5000, 1024), (11, 0, 1, 1)]:
-        dev = ops.sample_ids(seed, call, pop, cnt, th.empty(cnt, dtype=th.long, device="cuda")).cpu()
+        dev = ops.sample_ids(seed, call, pop, cnt, th.full((cnt + 8,), -7, dtype=th.long, device="cuda")).cpu()
+        assert (dev[cnt:] == -7).all(), (seed, call, pop, cnt)           # nothing past count is written
+        dev = dev[:cnt]
         host = ops.sample_ids(seed, call, pop, cnt, th.empty(cnt, dtype=th.long))
         assert th.equal(dev, host), (seed, call, pop, cnt)
         assert len(set(dev.tolist())) == cnt and 0 <= int(dev.min()) and int(dev.max()) < pop

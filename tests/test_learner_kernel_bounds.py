@@ -437,7 +437,9 @@ def test_gather_rows_in_the_arena(count, n_ids):
 
 
 # ---- ssd_sample_ids / ssd_runner_stats -----------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("count,population", [(1, 1), (1, 7), (2, 2), (2, 4096), (abi.SAMPLE_IDS_MAX, abi.SAMPLE_IDS_MAX), (abi.SAMPLE_IDS_MAX, 5000)])
+# (with the register-slot edges of the wave kernel: 64 / 128 / 256 picks and one past each)
+@pytest.mark.parametrize("count,population", [(1, 1), (1, 7), (2, 2), (2, 4096), (16, 8192), (64, 64), (65, 70), (128, 128), (129, 4096), (256, 256), (257, 300),
+                                              (abi.SAMPLE_IDS_MAX, abi.SAMPLE_IDS_MAX), (abi.SAMPLE_IDS_MAX, 5000)])
 def test_sample_ids_in_the_arena(count, population):
     """the expected ids come from ops.sample_ids on a HOST tensor: that branch is a pure-Python restatement of the generator and of
     Floyd's sampling (no library call), i.e. a second implementation, not the kernel; distinctness and range are asserted on their own."""

@@ -392,14 +392,14 @@ def test_key_off_is_the_loop_without_the_keys():
 
             def train(sample, t_env, episode, ctx=ctx, ids=ids, inner=inner):
                 assert getattr(sample, "priority", None) is None
-                ids.append(None if ctx.buffer._sample_ids is None else ctx.buffer._sample_ids.cpu().tolist())
+                ids.append(None if ctx.buffer._draws.ids is None else ctx.buffer._draws.ids.cpu().tolist())
                 inner(sample, t_env, episode)
             ctx.learner.train = train
             ep = 0
             for _ in range(4):
                 ep = train_iteration(ctx, ep)
             th.cuda.synchronize()
-            assert ctx.buffer.priority_table is None and ctx.buffer._priority_draws is None and not hasattr(ctx.learner, "last_q_new")
+            assert ctx.buffer.priority_table is None and ctx.buffer._draws.weights is None and ctx.buffer._draws.log is None and not hasattr(ctx.learner, "last_q_new")
             runs.append((ids, {k: v.cpu().clone() for k, v in ctx.buffer.data.transition_data.items()},
                          [p.detach().cpu().clone() for p in ctx.mac.parameters()], ctx.buffer._sample_calls,
                          [(name, key) for name, key, _ in ctx.runner.timestep_launches()]))

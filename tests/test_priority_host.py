@@ -228,9 +228,7 @@ def _learner(overrides=None):
 
 def _step(learner, batch, weights=None):
     """(logs as floats, the flat gradient) of one forward_backward; weights: the batch carries a priority tuple with a host table"""
-    for k in ("priority", "priority_log"):
-        if hasattr(batch, k):
-            delattr(batch, k)
+    batch.priority = batch.priority_log = None
     if weights is not None:
         batch.priority = (th.zeros(8, dtype=th.int32), th.arange(batch.batch_size), th.as_tensor(weights, dtype=th.float32))
     logs = learner.forward_backward(batch)
@@ -281,7 +279,7 @@ def _buffer(size=8):
 def test_no_table_without_the_key_and_inserts_zero_exactly_the_advanced_slots():
     buf, batch = _buffer(10)
     buf.insert_episode_batch(batch)
-    assert buf.priority_table is None and buf._priority_draws is None
+    assert buf.priority_table is None and buf._draws.weights is None and buf._draws.log is None
     with pytest.raises(ValueError, match="enable_priorities"):
         buf.sample_prioritized(2)
     table = buf.enable_priorities()

@@ -1,5 +1,6 @@
 """ReplayBuffer (reference src/components/episode_buffer.py:207-250) incl. the in-place producer protocol (reserve)."""
 import numpy as np
+import pytest
 import torch as th
 
 from homophily_marl_amd.components.episode_buffer import EpisodeBatch, ReplayBuffer
@@ -104,3 +105,52 @@ def test_sample_ids_restatement_draws_distinct_uniform_ids():
         first[ids[0]] += 1
     assert abs(hits / 4000 - 0.2).max() < 0.03          # inclusion probability 8 / 40 for every id (sd 0.0063)
     assert abs(first / 4000 - 1 / 40).max() < 0.012     # and every id equally likely in a given position (sd 0.0025)
+
+
+def _two_field_buffer():
+    """8 episodes x 6 slots, two fields, every stored value distinct"""
+    scheme = {"obs": {"vshape": (3,), "group": "agents"}, "reward": {"vshape": (2,)}}
+    buf = ReplayBuffer(scheme, {"agents": 2}, 8, 6)
+    ep = EpisodeBatch(scheme, {"agents": 2}, 8, 6)
+    ep.update({"obs": th.arange(8 * 6 * 2 * 3, dtype=th.float32).view(8, 6, 2, 3), "reward": -th.arange(8 * 6 * 2, dtype=th.float32).view(8, 6, 2)},
+              slice(None), slice(0, 6))
+    buf.insert_episode_batch(ep)
+    return buf, (lambda batch_size: EpisodeBatch(scheme, {"agents": 2}, batch_size, 6))
+
+
+@pytest.mark.parametrize("out_size", [4, 3, None], ids=["fitting_out", "out_of_another_batch_size", "no_out"])
+@pytest.mark.parametrize("sampler", ["sample", "sample_prioritized"])
+def test_whole_episode_samplers_share_one_gather(sampler, out_size):
+    """sample and sample_prioritized(window=0) gather alike: into a fitting `out`, which comes back itself, else into a fresh batch;
+    the rows are storage[ids] either way"""
+    buf, make = _two_field_buffer()
+    out = None if out_size is None else make(out_size)
+    if sampler == "sample":
+        np.random.seed(11)
+        ids = th.as_tensor(np.random.choice(8, 4, replace=False))
+        np.random.seed(11)
+        got = buf.sample(4, out=out)
+        assert got.priority is None and got.priority_log is None
+    else:
+        buf.enable_priorities().copy_(th.tensor([0, 3, 0, 9, 1, 0, 70000, 5]))
+        got = buf.sample_prioritized(4, window=0, out=out)
+        table, ids, weights = got.priority
+        assert table is buf.priority_table and ids is buf._draws.ids and weights is buf._draws.weights and got.priority_log is buf._draws.log
+    assert (got is out) == (out_size == 4) and (got.batch_size, got.max_seq_length) == (4, 6) and got.reward_norm is None
+    for k, v in buf.data.transition_data.items():
+        assert th.equal(got[k], v[ids]), k
+
+
+def test_extras_are_carried_by_name_and_dropped_by_a_slice():
+    buf, make = _two_field_buffer()
+    buf.enable_priorities().fill_(7)
+    src = buf.sample_prioritized(4, window=3, burn_in=1)
+    assert src.reward_norm == 6.0 and len(src.priority) == 3 and src.priority_log is not None
+    copy = make(4).take_extras(src)
+    assert copy.reward_norm == src.reward_norm and copy.priority is src.priority and copy.priority_log is src.priority_log
+    part = src[:, :2]
+    assert part.reward_norm is None and part.priority is None and part.priority_log is None
+    fresh = make(4)
+    assert fresh.reward_norm is None and fresh.priority is None and fresh.priority_log is None
+    del copy.priority                                                        # taking an extra off: it reads None again
+    assert copy.priority is None and copy.priority_log is src.priority_log

@@ -22,7 +22,7 @@ SEED = 0x1234567890ABCDEF
 
 
 # ---- 7. the device draws -----------------------------------------------------------------------------------------------------------------
-# beyond the shapes of the host test: every register-slot count of k_sample_windows (count up to 64, 128, 256, SSD_SAMPLE_IDS_MAX) and its edges
+# beyond the shapes of the host test: every register-slot count of k_sample_draw (count up to 64, 128, 256, SSD_SAMPLE_IDS_MAX) and its edges
 MORE_SHAPES = [(64, 64, 1), (65, 65, 2), (300, 128, 89), (129, 129, 3), (2000, 200, 5), (256, 256, 7), (257, 257, 2), (5000, 1024, 3), (1, 1, 4)]
 
 
@@ -326,7 +326,7 @@ def test_window_zero_is_the_loop_without_the_keys():
 
             def train(sample, t_env, episode, ctx=ctx, ids=ids, inner=inner):
                 assert sample.max_seq_length == T_EP + 1 and ctx.buffer.last_window_ids is None
-                ids.append(None if ctx.buffer._sample_ids is None else ctx.buffer._sample_ids.cpu().tolist())
+                ids.append(None if ctx.buffer._draws.ids is None else ctx.buffer._draws.ids.cpu().tolist())
                 inner(sample, t_env, episode)
             ctx.learner.train = train
             ep = 0

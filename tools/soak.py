@@ -166,8 +166,8 @@ for it in range(a.iters):
                 vec = [x for k in abi.behaviour_layout(n, ctx.args.n_actions) for x in b[k].reshape(-1)]
                 s = abi.behaviour_summary(vec, n, ctx.args.n_actions)
                 print("   behaviour %s (%d episodes): " % (label, int(b["n_episodes"][0])) + "  ".join("%s %.4f" % kv for kv in s.items()), flush=True)
-        if a.prioritized and ctx.buffer._priority_draws is not None:      # the last sample launch's four log values
-            pl = ctx.buffer._priority_draws.log.tolist()
+        if a.prioritized and ctx.buffer._draws.log is not None:      # the last sample launch's four log values
+            pl = ctx.buffer._draws.log.tolist()
             print("   per_priority_mean %.4f  per_priority_max %.4f  per_weight_min %.4f  per_unique_frac %.4f" % (
                 pl[0], pl[1], pl[2], pl[3] / ctx.args.batch_size), flush=True)
         acc, cnt = 0.0, 0
