@@ -407,6 +407,22 @@ PRIORITY_SIGNATURES = {
 }
 
 
+class SsdStoreHiddenArgs(C.Structure):
+    """include/ssd_hip.h: ssd_store_hidden_args."""
+    _fields_ = [("t_index", C.c_void_p), ("n_env", C.c_int32), ("n_agents", C.c_int32), ("t_slots", C.c_int32), ("reserved", C.c_int32),
+                ("h_env", C.c_void_p), ("h_inc", C.c_void_p), ("src_agent_stride", C.c_int64), ("src_env_stride", C.c_int64), ("dst", C.c_void_p)]
+
+
+# the three exports of training windows from the rollout's stored recurrent state (train_stored_state), in a table of their own like
+# ssd_behaviour_stats (their checks: tests/test_stored_state_host.py)
+STORED_STATE_SIGNATURES = {
+    "ssd_store_hidden": (C.c_int, [C.POINTER(SsdStoreHiddenArgs), C.c_void_p]),
+    "ssd_gru_seq_fwd_h0": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 3
+                           + [C.c_int32] * 3 + [C.c_void_p]),
+    "ssd_gru_seq_bwd_h0": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p]),
+}
+
+
 def behaviour_len(n, A):
     """SSD_BEHAVIOUR_LEN"""
     return 12 * n + n * A + 3 * n * n + 3
@@ -500,6 +516,7 @@ def load_library():
         bind(lib, BEHAVIOUR_SIGNATURES)
         bind(lib, WINDOW_SIGNATURES)
         bind(lib, PRIORITY_SIGNATURES)
+        bind(lib, STORED_STATE_SIGNATURES)
         ver = lib.ssd_abi_version()
         if ver != ABI_VERSION:
             raise ImportError("libssd_hip.so ABI version %d != %d" % (ver, ABI_VERSION))

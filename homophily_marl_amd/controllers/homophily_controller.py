@@ -176,8 +176,18 @@ class HomophilyMAC(nn.Module):
         the input assembly and all non-recurrent layers evaluated once over all T."""
         shared = self.unroll_shared(batch)
         parts, wh, bh = self.unroll_pre(batch, shared)
-        he, hi = ops.gru_sequence_parts(parts, batch.max_seq_length, batch.batch_size, wh, bh)
+        he, hi = ops.gru_sequence_parts(parts, batch.max_seq_length, batch.batch_size, wh, bh, h0=self.stored_h0(batch))
         return self.agent.unroll_post(he, hi, shared["other"])
+
+    def stored_h0(self, batch):
+        """train_stored_state: the state the recurrences of `batch` start from, as ops.gru_sequence_parts takes it -- one view
+        [n, B, H] per projection part (env head, inc head) of batch["hidden"][:, 0] where it lies (no copy): the rollout's state AFTER
+        the controller consumed the batch's first slot, so row 0 is loaded, not computed.  None with the key off: from zeros."""
+        if not getattr(self.args, "train_stored_state", False):
+            return None
+        H = self.args.rnn_hidden_dim
+        h = batch["hidden"][:, 0].detach()                                             # [B, n, 2H]
+        return [h[..., :H].transpose(0, 1), h[..., H:].transpose(0, 1)]
 
     def unroll_shared(self, batch):
         """Everything of an unroll that does not depend on the weights (the learner evaluates the live and the target net on the

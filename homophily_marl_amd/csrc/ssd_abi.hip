@@ -643,6 +643,19 @@ int ssd_store_step_launch(const ssd_store_step* a, void* stream) {
     return launched();
 }
 
+int ssd_store_hidden(const ssd_store_hidden_args* a, void* stream) {
+    if (!a) return fail(SSD_ERR_INVALID, "ssd_store_hidden: null args");
+    if (!a->t_index || !a->h_env || !a->h_inc || !a->dst) return fail(SSD_ERR_INVALID, "ssd_store_hidden: null member pointer");
+    if (a->n_env < 1 || a->n_agents < 1 || a->t_slots < 1) return fail(SSD_ERR_INVALID, "ssd_store_hidden: n_env, n_agents and t_slots must be at least 1");
+    if ((reinterpret_cast<uintptr_t>(a->dst) | reinterpret_cast<uintptr_t>(a->h_env) | reinterpret_cast<uintptr_t>(a->h_inc)) & 15)
+        return fail(SSD_ERR_INVALID, "ssd_store_hidden: h_env, h_inc and dst must be 16-byte aligned");
+    if (a->src_agent_stride < 0 || a->src_env_stride < 0 || (a->src_agent_stride & 3) || (a->src_env_stride & 3))
+        return fail(SSD_ERR_INVALID, "ssd_store_hidden: source strides must be non-negative multiples of 4 elements");
+    if ((int64_t)a->n_env * a->n_agents >= (int64_t)1 << 34) return fail(SSD_ERR_INVALID, "ssd_store_hidden: n_env * n_agents over 2^34");
+    launch_store_hidden(a, (hipStream_t)stream);
+    return launched();
+}
+
 int ssd_gru_gates(const float* gi, const float* gh, float* h, int32_t rows, int32_t hidden, void* stream) {
     if (!gi || !gh || !h || rows < 1 || hidden < 1) return fail(SSD_ERR_INVALID, "bad argument");
     launch_gru_gates(gi, gh, h, rows, hidden, (hipStream_t)stream);
@@ -719,6 +732,45 @@ int ssd_gru_seq_bwd_parts(const float* const* dhs_parts, const float* hs, const 
         if (!d_gi_parts[k] || !al16(d_gi_parts[k])) return fail(SSD_ERR_INVALID, "d_gi parts of the sets with a gradient must be non-null and 16-byte aligned");
     if (!al16(hs) || !al16(rzn) || !al16(ghn) || !al16(dgh)) return fail(SSD_ERR_INVALID, "tensors must be 16-byte aligned");
     launch_gru_seq_bwd(dhs_parts, hs, rzn, ghn, wh_parts, n_wparts, d_gi_parts, n_parts, dgh, d_wh, d_bh_part, T, G, G_grad, B, (hipStream_t)stream);
+    return launched();
+}
+
+int ssd_gru_seq_fwd_h0(const float* const* gi_parts, int32_t n_parts, const float* const* wh_parts, const float* const* bh_parts, int32_t n_wparts,
+                       const float* const* h0_parts, int64_t h0_set_stride, int64_t h0_row_stride, float* hs, float* rzn, float* ghn, int32_t T, int32_t G,
+                       int32_t B, void* stream) {
+    const int np = n_parts < 1 ? 1 : n_parts;
+    if (!gi_parts || n_parts < 0 || n_parts > 4 || !wh_parts || !bh_parts || n_wparts < 1 || n_wparts > 4 || !h0_parts || !hs || T < 1 || G < 1 || G % np ||
+        G % n_wparts || B < 1 || (!rzn) != (!ghn))
+        return fail(SSD_ERR_INVALID, "ssd_gru_seq_fwd_h0: bad argument");
+    for (int k = 0; k < n_wparts; ++k)
+        if (!wh_parts[k] || !bh_parts[k] || !al16(wh_parts[k]) || !al16(bh_parts[k])) return fail(SSD_ERR_INVALID, "ssd_gru_seq_fwd_h0: weight parts must be non-null and 16-byte aligned");
+    if (B % 16) return fail(SSD_ERR_INVALID, "ssd_gru_seq_fwd_h0: B must be a multiple of 16 (pad the sequences and h0)");
+    for (int k = 0; k < np; ++k) {
+        if (!gi_parts[k] || !al16(gi_parts[k])) return fail(SSD_ERR_INVALID, "ssd_gru_seq_fwd_h0: gi parts must be non-null and 16-byte aligned");
+        if (!h0_parts[k] || !al16(h0_parts[k])) return fail(SSD_ERR_INVALID, "ssd_gru_seq_fwd_h0: h0 parts must be non-null and 16-byte aligned");
+    }
+    if (h0_set_stride < 0 || h0_row_stride < 0 || (h0_set_stride & 3) || (h0_row_stride & 3))
+        return fail(SSD_ERR_INVALID, "ssd_gru_seq_fwd_h0: h0 strides must be non-negative multiples of 4 elements");
+    if (!al16(hs) || !al16(rzn) || !al16(ghn)) return fail(SSD_ERR_INVALID, "ssd_gru_seq_fwd_h0: tensors must be 16-byte aligned");
+    launch_gru_seq_fwd(gi_parts, n_parts, wh_parts, bh_parts, n_wparts, hs, rzn, ghn, T, G, B, (hipStream_t)stream, h0_parts, (long)h0_set_stride,
+                       (long)h0_row_stride);
+    return launched();
+}
+int ssd_gru_seq_bwd_h0(const float* const* dhs_parts, const float* hs, const float* rzn, const float* ghn, const float* const* wh_parts, int32_t n_wparts,
+                       float* const* d_gi_parts, int32_t n_parts, float* dgh, float* d_wh, float* d_bh_part, int32_t T, int32_t G, int32_t G_grad, int32_t B,
+                       void* stream) {
+    const int np = n_parts < 1 ? 1 : n_parts;
+    if (!dhs_parts || !hs || !rzn || !ghn || !wh_parts || n_wparts < 1 || n_wparts > 4 || !d_gi_parts || n_parts < 0 || n_parts > 4 || !dgh || !d_wh ||
+        !d_bh_part || T < 1 || G < 1 || G % np || G % n_wparts || B < 1 || G_grad < 1 || G_grad > G || G_grad % (G / np))
+        return fail(SSD_ERR_INVALID, "ssd_gru_seq_bwd_h0: bad argument");
+    for (int k = 0; k * (G / np) < G_grad; ++k)
+        if (!dhs_parts[k] || !al16(dhs_parts[k]) || !d_gi_parts[k] || !al16(d_gi_parts[k]))
+            return fail(SSD_ERR_INVALID, "ssd_gru_seq_bwd_h0: dhs and d_gi parts of the sets with a gradient must be non-null and 16-byte aligned");
+    for (int k = 0; k < n_wparts; ++k)
+        if (!wh_parts[k] || !al16(wh_parts[k])) return fail(SSD_ERR_INVALID, "ssd_gru_seq_bwd_h0: weight parts must be non-null and 16-byte aligned");
+    if (B % 16) return fail(SSD_ERR_INVALID, "ssd_gru_seq_bwd_h0: B must be a multiple of 16 (pad the sequences)");
+    if (!al16(hs) || !al16(rzn) || !al16(ghn) || !al16(dgh)) return fail(SSD_ERR_INVALID, "ssd_gru_seq_bwd_h0: tensors must be 16-byte aligned");
+    launch_gru_seq_bwd(dhs_parts, hs, rzn, ghn, wh_parts, n_wparts, d_gi_parts, n_parts, dgh, d_wh, d_bh_part, T, G, G_grad, B, (hipStream_t)stream, true);
     return launched();
 }
 

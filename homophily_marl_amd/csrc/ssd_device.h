@@ -169,6 +169,7 @@ void launch_encoder(const float* obs, int rows, int V, const float* cw, const fl
 void launch_conv_leaky(const float* obs, int rows, int V, const float* cw, const float* cb, float* out, int n_agents, int agent_major,
                        float* store, long store_env_stride, const int64_t* store_t, hipStream_t s);
 void launch_store_step(const ssd_store_step* a, hipStream_t s);
+void launch_store_hidden(const ssd_store_hidden_args* a, hipStream_t s);
 void launch_gru_gates(const float* gi, const float* gh, float* h, int R, int H, hipStream_t s);
 void launch_gru_fwd_train(const float* gi, const float* gh, const float* h, float* h_new, float* rzn, int R, int H, hipStream_t s);
 void launch_gru_bwd(const float* dh, const float* rzn, const float* gh, const float* h, float* d_gi, float* d_gh, float* dh_prev, int R,
@@ -178,9 +179,11 @@ int launch_pack_encoder_lut(const float* cw, const float* cb, const float* lw, i
 int launch_pack_encoder(const float* cw, const float* cb, const float* lw, int V, int prec, void* conv_frags, void* lin_frags, hipStream_t s);
 void launch_pack_head(const ssd_policy_head_params* p, int prec, void* image, hipStream_t s);
 void launch_gru_seq_fwd(const float* const* gi_parts, int n_parts, const float* const* wh_parts, const float* const* bh_parts, int n_wparts, float* hs,
-                        float* rzn, float* ghn, int T, int G, int B, hipStream_t s);
+                        float* rzn, float* ghn, int T, int G, int B, hipStream_t s, const float* const* h0_parts = nullptr, long h0_set_stride = 0,
+                        long h0_row_stride = 0);
 void launch_gru_seq_bwd(const float* const* dhs_parts, const float* hs, const float* rzn, const float* ghn, const float* const* wh_parts, int n_wparts,
-                        float* const* d_gi_parts, int n_parts, float* dgh, float* d_wh, float* d_bh_part, int T, int G, int Gn, int B, hipStream_t s);
+                        float* const* d_gi_parts, int n_parts, float* dgh, float* d_wh, float* d_bh_part, int T, int G, int Gn, int B, hipStream_t s,
+                        bool h0 = false);
 int launch_policy_head(const ssd_policy_head* p, int inc, hipStream_t s);
 void policy_head_plan(int n_env, int n_agents, int mode, int* wg_per_agent, int* waves_out, int* tiles_per_wave);
 int launch_policy_inc_encode(const ssd_policy_head* ph, const ssd_policy_encode_args* pe, hipStream_t s);

@@ -6,6 +6,7 @@
 //   k_dueling_pick  q = v + a - mean(a) and the epsilon-greedy choice                    (homophily_agent.py:168-170,204-206;
 //                                                                                         action_selectors.py:44-68)
 //   k_store_step    the small per-step fields of the episode storage in one launch       (episode_runner.py:59-93)
+//   k_store_hidden  the recurrent state after slot t into the episode storage (train_stored_state; no counterpart in the reference)
 // In this per-layer composition the per-agent matrix products stay in hipBLASLt.  It is the second implementation of the
 // rollout-time controller (window sizes / palettes without a fused encoder, FastPolicy(fused=False)) and the cross-check of the
 // fused matrix-core kernels in ssd_policy_mfma.hip, which replace it on the hot path.
@@ -314,6 +315,26 @@ void launch_store_step(const ssd_store_step* a, hipStream_t s) {
     const long total = (long)k.N * (k.n * (8 + k.A + k.n) + 1);
     int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(k_store_step, dim3(blocks), dim3(256), 0, s, k);
+}
+// The recurrent state the heads of slot t left (h_env, h_inc: 64 floats per (env, agent) each) -> dst[env, *t_index, agent, 0..127].
+// One thread per 16 bytes: thread (env, agent, c) moves floats 4 c .. 4 c + 3 of the agent's 128 (c < 16: h_env, else h_inc); the 32
+// threads of an (env, agent) pair write 512 contiguous bytes.  A slot index outside [0, t_slots) files nothing.
+__global__ __launch_bounds__(256) void k_store_hidden(const ssd_store_hidden_args a) {
+    const int64_t t = *a.t_index;
+    if (t < 0 || t >= a.t_slots) return;
+    const int64_t total = (int64_t)a.n_env * a.n_agents * 32;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int c = (int)(idx & 31);
+    const int64_t pair = idx >> 5, env = pair / a.n_agents;
+    const int agent = (int)(pair - env * a.n_agents);
+    const float* src = (c < 16 ? a.h_env : a.h_inc) + (int64_t)agent * a.src_agent_stride + env * a.src_env_stride + 4 * (c & 15);
+    float* dst = a.dst + ((env * a.t_slots + t) * a.n_agents + agent) * 128 + 4 * c;
+    *reinterpret_cast<float4*>(dst) = *reinterpret_cast<const float4*>(src);
+}
+void launch_store_hidden(const ssd_store_hidden_args* a, hipStream_t s) {
+    const int64_t total = (int64_t)a->n_env * a->n_agents * 32;
+    hipLaunchKernelGGL(k_store_hidden, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, *a);
 }
 void launch_gru_gates(const float* gi, const float* gh, float* h, int R, int H, hipStream_t s) {
     const size_t total = (size_t)R * H, want = (total + 255) / 256; const int blocks = want > 4096 ? 4096 : (int)want;   // (any rows x hidden: the kernels stride)

@@ -162,7 +162,12 @@ class HomophilyLearner:
             gi_t, wh_t, bh_t = tgt.unroll_pre(batch, shared)
         # live env / inc, target env / inc: the four projection outputs AND the four recurrence weight images go to the sequence kernel
         # as they are (no concatenation), and the states come back as four tensors (no slicing: a slice's backward is a zero-fill + copy)
-        he, hi, he_t, hi_t = ops.gru_sequence_parts(list(gi) + list(gi_t), batch.max_seq_length, batch.batch_size, list(wh) + list(wh_t), list(bh) + list(bh_t))
+        # train_stored_state: the live and the target net both start from the state the rollout stored for the batch's first slot
+        h0 = mac.stored_h0(batch)
+        he, hi, he_t, hi_t = ops.gru_sequence_parts(list(gi) + list(gi_t), batch.max_seq_length, batch.batch_size, list(wh) + list(wh_t), list(bh) + list(bh_t),
+                                                    h0=None if h0 is None else h0 + h0)
+        if h0 is not None:
+            self.last_first_states = (he.detach()[:, 0], hi.detach()[:, 0])            # [n, B, H] each: what row 0 was evaluated on (the tests read it)
         q_env, q_inc = mac.agent.unroll_post(he, hi, shared["other"])
         with th.no_grad():
             tq_env, tq_inc = tgt.agent.unroll_post(he_t.detach(), hi_t.detach(), shared["other"])

@@ -620,6 +620,40 @@ def gather_windows(pairs, ids, t0, src_slots, win_slots, burn_in, filled_index):
     return True
 
 
+def store_hidden_args(t_index, h_env, h_inc, dst):
+    """The argument block of ssd_store_hidden (include/ssd_hip.h) for a rollout's static tensors: the recurrent states h_env / h_inc,
+    agent-major [n, N, 64] (FastPolicy) or [N, n, 1, 64] (the generic timestep), filed as dst[:, *t_index] of the episode field
+    "hidden" f32 [N, t_slots, n, 128] = [h_env | h_inc] -- the state AFTER the controller consumed slot t.  t_index: int64 device scalar.
+    The block holds raw addresses: the caller keeps the tensors alive (the runner's per-storage bundle)."""
+    if dst.dim() != 4 or dst.shape[3] != 128 or dst.dtype != th.float32 or not dst.is_cuda or not dst.is_contiguous():
+        raise _unfit("store_hidden", "dst", dst, "contiguous f32 [N, t_slots, n, 128] on the device expected")
+    N, slots, n = dst.shape[:3]
+    if t_index.dtype != th.long or t_index.numel() != 1 or t_index.device != dst.device:
+        raise _unfit("store_hidden", "t_index", t_index, "one int64 on the device of dst expected")
+    a = abi.SsdStoreHiddenArgs()
+    for name, h in (("h_env", h_env), ("h_inc", h_inc)):
+        if h.dtype != th.float32 or h.device != dst.device or h.shape[-1] != 64 or h.stride(-1) != 1:
+            raise _unfit("store_hidden", name, h, "f32 [n, N, 64] or [N, n, 1, 64] on the device of dst expected")
+        if h.dim() == 3 and tuple(h.shape[:2]) == (n, N):
+            strides = (h.stride(0), h.stride(1))
+        elif h.dim() == 4 and tuple(h.shape[:3]) == (N, n, 1):
+            strides = (h.stride(1), h.stride(0))
+        else:
+            raise _unfit("store_hidden", name, h, "f32 [n = %d, N = %d, 64] or [N, n, 1, 64] expected" % (n, N))
+        if name == "h_inc" and strides != (a.src_agent_stride, a.src_env_stride):
+            raise _unfit("store_hidden", name, h, "the layout of h_env expected")
+        a.src_agent_stride, a.src_env_stride = strides
+    a.t_index, a.n_env, a.n_agents, a.t_slots = t_index.data_ptr(), N, n, slots
+    a.h_env, a.h_inc, a.dst = h_env.data_ptr(), h_inc.data_ptr(), dst.data_ptr()
+    return a
+
+
+def store_hidden(args, device):
+    """one ssd_store_hidden launch of the block store_hidden_args built, on the current stream of `device`"""
+    lib = abi.load_library()
+    abi.check(lib, lib.ssd_store_hidden(C.byref(args), th.cuda.current_stream(device).cuda_stream))
+
+
 def priority_sample(seed, call, table, population, count, n_starts, beta, ids_out, t0_out, weights_out, log_out):
     """Prioritised replay's draw (include/ssd_hip.h: ssd_priority_sample): `count` stratified proportional draws with replacement from
     the fixed-point priorities table[0 .. population) (int32 storage of the u32 values; 0 = never trained on, drawn at the table's
@@ -1034,6 +1068,11 @@ class _GruSeq(th.autograd.Function):
 
     @staticmethod
     def forward(ctx, gi, wh, bh):
+        return _GruSeq._forward(ctx, gi, wh, bh, None)
+
+    @staticmethod
+    def _forward(ctx, gi, wh, bh, h0):
+        """h0 None: from zero (ssd_gru_seq_fwd); else [G, B, H], hs[:, 0] := h0 (ssd_gru_seq_fwd_h0, time-major form: n_parts 0)"""
         lib = abi.load_library()
         gi, wh, bh = gi.contiguous(), wh.contiguous(), bh.contiguous()
         T, G, B, H3 = gi.shape
@@ -1045,8 +1084,15 @@ class _GruSeq(th.autograd.Function):
         need = any(ctx.needs_input_grad)
         rzn = th.empty_like(gi) if need else None
         ghn = th.empty(T, G, Bp, H, dtype=gi.dtype, device=gi.device) if need else None
-        abi.check(lib, lib.ssd_gru_seq_fwd(gi.data_ptr(), wh.data_ptr(), bh.data_ptr(), hs.data_ptr(), None if rzn is None else rzn.data_ptr(),
-                                           None if ghn is None else ghn.data_ptr(), T, G, Bp, _stream(gi)))
+        if h0 is None:
+            abi.check(lib, lib.ssd_gru_seq_fwd(gi.data_ptr(), wh.data_ptr(), bh.data_ptr(), hs.data_ptr(), None if rzn is None else rzn.data_ptr(),
+                                               None if ghn is None else ghn.data_ptr(), T, G, Bp, _stream(gi)))
+        else:
+            h0 = h0.contiguous() if Bp == B else th.nn.functional.pad(h0, (0, 0, 0, Bp - B))      # the given state is padded with the batch
+            one = lambda t: (C.c_void_p * 1)(t.data_ptr())
+            abi.check(lib, lib.ssd_gru_seq_fwd_h0(one(gi), 0, one(wh), one(bh), 1, one(h0), Bp * H, H, hs.data_ptr(), None if rzn is None else rzn.data_ptr(),
+                                                  None if ghn is None else ghn.data_ptr(), T, G, Bp, _stream(gi)))
+        ctx.h0 = h0 is not None
         if need:
             ctx.save_for_backward(hs, rzn, ghn, wh)
             ctx.B = B
@@ -1070,11 +1116,29 @@ class _GruSeq(th.autograd.Function):
         dgh = th.empty(G, T, Bp, H3, dtype=rzn.dtype, device=rzn.device)      # workspace: dL/dgh_t, the operand of the W_h gradient
         d_wh = th.empty(G, H3 // 3, H3, dtype=rzn.dtype, device=rzn.device)
         d_bh = th.empty(G, tiles, H3, dtype=rzn.dtype, device=rzn.device)
-        abi.check(lib, lib.ssd_gru_seq_bwd(dhs.data_ptr(), hs.data_ptr(), rzn.data_ptr(), ghn.data_ptr(), wh.data_ptr(), d_gi.data_ptr(),
-                                           dgh.data_ptr(), d_wh.data_ptr(), d_bh.data_ptr(), T, G, Bp, _stream(rzn)))
+        if ctx.h0:
+            one = lambda t: (C.c_void_p * 1)(t.data_ptr())
+            abi.check(lib, lib.ssd_gru_seq_bwd_h0(one(dhs), hs.data_ptr(), rzn.data_ptr(), ghn.data_ptr(), one(wh), 1, one(d_gi), 0, dgh.data_ptr(),
+                                                  d_wh.data_ptr(), d_bh.data_ptr(), T, G, G, Bp, _stream(rzn)))
+        else:
+            abi.check(lib, lib.ssd_gru_seq_bwd(dhs.data_ptr(), hs.data_ptr(), rzn.data_ptr(), ghn.data_ptr(), wh.data_ptr(), d_gi.data_ptr(),
+                                               dgh.data_ptr(), d_wh.data_ptr(), d_bh.data_ptr(), T, G, Bp, _stream(rzn)))
         if Bp != B:
             d_gi = d_gi[:, :, :B].contiguous()
         return d_gi, d_wh, (column_sums(d_bh) if tiles > 1 else d_bh[:, 0]).unsqueeze(1)      # per-tile bias sums: k_column_sums (no ATen reduction)
+
+
+class _GruSeqH0(th.autograd.Function):
+    """_GruSeq from a given state h0 [G, B, H]: hs[:, 0] := h0, steps 1 .. T - 1 computed; h0 is data (no gradient)."""
+
+    @staticmethod
+    def forward(ctx, gi, wh, bh, h0):
+        return _GruSeq._forward(ctx, gi, wh, bh, h0)
+
+    @staticmethod
+    def backward(ctx, dhs):
+        with _precision(ctx.precision):
+            return _GruSeq._backward(ctx, dhs) + (None,)
 
 
 class _GruSeqParts(th.autograd.Function):
@@ -1085,6 +1149,12 @@ class _GruSeqParts(th.autograd.Function):
 
     @staticmethod
     def forward(ctx, T, B, n_w, *tensors):
+        return _GruSeqParts._forward(ctx, T, B, n_w, None, tensors)
+
+    @staticmethod
+    def _forward(ctx, T, B, n_w, h0, tensors):
+        """h0 None: from zero (ssd_gru_seq_fwd_parts); else (views [sets, B, H] per projection part, set stride, row stride): read in
+        place by ssd_gru_seq_fwd_h0"""
         lib = abi.load_library()
         whs, bhs = [t.contiguous() for t in tensors[:n_w]], [t.contiguous() for t in tensors[n_w:2 * n_w]]
         parts = [p.contiguous() for p in tensors[2 * n_w:]]
@@ -1098,8 +1168,16 @@ class _GruSeqParts(th.autograd.Function):
         ptrs = (C.c_void_p * len(parts))(*[p.data_ptr() for p in parts])
         wptrs = (C.c_void_p * n_w)(*[w.data_ptr() for w in whs])
         bptrs = (C.c_void_p * n_w)(*[b.data_ptr() for b in bhs])
-        abi.check(lib, lib.ssd_gru_seq_fwd_parts(ptrs, len(parts), wptrs, bptrs, n_w, hs.data_ptr(), None if rzn is None else rzn.data_ptr(),
-                                                 None if ghn is None else ghn.data_ptr(), T, G, B, _stream(hs)))
+        if h0 is None:
+            abi.check(lib, lib.ssd_gru_seq_fwd_parts(ptrs, len(parts), wptrs, bptrs, n_w, hs.data_ptr(), None if rzn is None else rzn.data_ptr(),
+                                                     None if ghn is None else ghn.data_ptr(), T, G, B, _stream(hs)))
+        else:
+            views, set_stride, row_stride = h0
+            hptrs = (C.c_void_p * len(parts))(*[v.data_ptr() for v in views])
+            abi.check(lib, lib.ssd_gru_seq_fwd_h0(ptrs, len(parts), wptrs, bptrs, n_w, hptrs, set_stride, row_stride, hs.data_ptr(),
+                                                  None if rzn is None else rzn.data_ptr(), None if ghn is None else ghn.data_ptr(), T, G, B, _stream(hs)))
+        ctx.h0 = h0 is not None
+        ctx.lead = 3 if h0 is None else 4         # non-tensor arguments in front of the tensors
         if need:
             ctx.save_for_backward(hs, rzn, ghn, *whs)
             ctx.shapes = [p.shape for p in parts]
@@ -1125,7 +1203,7 @@ class _GruSeqParts(th.autograd.Function):
         T, G, B, H3 = rzn.shape
         n_parts = len(ctx.shapes)
         spp = G // n_parts
-        need = ctx.needs_input_grad
+        need, lead = ctx.needs_input_grad, ctx.lead
         # the sets whose states carry a gradient form a prefix (the live net's parts come first); the kernel walks only those
         last = max([k for k, d in enumerate(dhs_parts) if d is not None], default=-1)
         if last < 0:
@@ -1141,8 +1219,9 @@ class _GruSeqParts(th.autograd.Function):
         ptrs = (C.c_void_p * n_parts)(*pad(d_parts))
         dptrs = (C.c_void_p * n_parts)(*pad(dhs))
         wptrs = (C.c_void_p * n_w)(*[w.data_ptr() for w in whs])
-        abi.check(lib, lib.ssd_gru_seq_bwd_parts(dptrs, hs.data_ptr(), rzn.data_ptr(), ghn.data_ptr(), wptrs, n_w, ptrs, n_parts,
-                                                 dgh.data_ptr(), d_wh.data_ptr(), d_bh.data_ptr(), T, G, Gn, B, _stream(rzn)))
+        launch = lib.ssd_gru_seq_bwd_h0 if ctx.h0 else lib.ssd_gru_seq_bwd_parts
+        abi.check(lib, launch(dptrs, hs.data_ptr(), rzn.data_ptr(), ghn.data_ptr(), wptrs, n_w, ptrs, n_parts,
+                              dgh.data_ptr(), d_wh.data_ptr(), d_bh.data_ptr(), T, G, Gn, B, _stream(rzn)))
         d_bh_all = (column_sums(d_bh) if tiles > 1 else d_bh[:, 0]).unsqueeze(1)                    # [Gn, 1, 3H]
         spw = G // n_w
 
@@ -1158,18 +1237,63 @@ class _GruSeqParts(th.autograd.Function):
             out = full.new_zeros((spw,) + tuple(full.shape[1:]))
             out[:Gn - lo] = full[lo:Gn]
             return out
-        g_wh = tuple(of_part(d_wh, k) if need[3 + k] else None for k in range(n_w))
-        g_bh = tuple(of_part(d_bh_all, k) if need[3 + n_w + k] else None for k in range(n_w))
-        g_parts = tuple(d_parts[k] if (k <= last and need[3 + 2 * n_w + k]) else None for k in range(n_parts))
-        return (None, None, None) + g_wh + g_bh + g_parts
+        g_wh = tuple(of_part(d_wh, k) if need[lead + k] else None for k in range(n_w))
+        g_bh = tuple(of_part(d_bh_all, k) if need[lead + n_w + k] else None for k in range(n_w))
+        g_parts = tuple(d_parts[k] if (k <= last and need[lead + 2 * n_w + k]) else None for k in range(n_parts))
+        return (None,) * lead + g_wh + g_bh + g_parts
 
 
-def gru_sequence_parts(parts, T, B, wh, bh):
+class _GruSeqPartsH0(th.autograd.Function):
+    """_GruSeqParts from a given state: h0 = (views [sets, B, H] per projection part, set stride, row stride in elements), read in place
+    (the learner: batch["hidden"][:, 0] of the static batch, no copy launch); hs[:, 0] := h0, no gradient into it."""
+
+    @staticmethod
+    def forward(ctx, T, B, n_w, h0, *tensors):
+        return _GruSeqParts._forward(ctx, T, B, n_w, h0, tensors)
+
+    @staticmethod
+    def backward(ctx, *dhs_parts):
+        with _precision(ctx.precision):
+            return _GruSeqParts._backward(ctx, *dhs_parts)
+
+
+def _gru_h0_views(op, h0, like, n_parts, spp, B, H):
+    """The given initial state of `op` as one view [spp, B, H] per projection part: h0 is ONE tensor [n_parts * spp, B, H] or a list
+    of n_parts tensors / strided views [spp, B, H].  It is data: a state that asks for a gradient is refused."""
+    views = [h0[k * spp:(k + 1) * spp] for k in range(n_parts)] if isinstance(h0, th.Tensor) else list(h0)
+    if isinstance(h0, th.Tensor) and (h0.dim() != 3 or tuple(h0.shape) != (n_parts * spp, B, H)):
+        raise _unfit(op, "h0", h0, "[G = %d, B = %d, H = %d] or one view [sets, B, H] per projection part expected" % (n_parts * spp, B, H))
+    if len(views) != n_parts:
+        raise ValueError("ops.%s: h0 comes as %d parts for %d projection parts" % (op, len(views), n_parts))
+    for k, v in enumerate(views):
+        if not isinstance(v, th.Tensor) or tuple(v.shape) != (spp, B, H) or v.device != like.device:
+            raise _unfit(op, "h0[%d]" % k, v, "[sets = %d, B = %d, H = %d] on the device of the projections expected" % (spp, B, H))
+        if v.requires_grad:
+            raise ValueError("ops.%s: h0 requires a gradient; the given state is data (the recurrence sends no gradient into it): detach it" % op)
+    return views
+
+
+def _gru_h0_in_place(views):
+    """(set stride, row stride) if the sequence kernel can read these views where they lie, else None"""
+    v0 = views[0]
+    ss, rs = (v0.stride(0) if v0.shape[0] > 1 else 0), (v0.stride(1) if v0.shape[1] > 1 else 0)
+    for v in views:
+        if (v.dtype != th.float32 or v.stride(2) != 1 or (v.shape[0] > 1 and v.stride(0) != ss) or (v.shape[1] > 1 and v.stride(1) != rs)
+                or v.data_ptr() % 16):
+            return None
+    if ss < 0 or rs < 0 or ss % 4 or rs % 4:
+        return None
+    return ss, rs
+
+
+def gru_sequence_parts(parts, T, B, wh, bh, h0=None):
     """gru_sequence for projections held as equally sized set-major parts [sets, T * B, 3H] (rows t * B + b); wh [G, H, 3H], bh [G, 1, 3H]
     over all sets in part order -- each either ONE tensor or a list of 1..4 equally sized parts over the sets (no concatenation).
     Returns the states as a LIST with one tensor [sets, T, B, H] per projection part.  A weight part whose sets' states carry no
     gradient gets none (the learner puts the target net's parts last); one that only partly lies among the sets with a gradient gets
-    its full size, zeros for the rest."""
+    its full size, zeros for the rest.
+    h0 (None: from zero): the state the sequences start from, ONE tensor [G, B, H] or one (strided) view [sets, B, H] per projection
+    part; then hs[:, 0] = h0, steps 1 .. T - 1 are computed and the projections of step 0 are not read.  h0 is data."""
     H3 = parts[0].shape[-1]
     whs, bhs = (list(wh) if isinstance(wh, (list, tuple)) else [wh]), (list(bh) if isinstance(bh, (list, tuple)) else [bh])
     G = sum(p.shape[0] for p in parts)
@@ -1178,16 +1302,28 @@ def gru_sequence_parts(parts, T, B, wh, bh):
         if p.dim() != 3 or p.shape[1] != T * B or p.shape[2] != H3 or p.device != parts[0].device:
             raise _unfit("gru_sequence_parts", "parts[%d]" % k, p, "[sets, T * B = %d, 3H = %d] on one device expected" % (T * B, H3))
     _gru_weights_fit("gru_sequence_parts", parts[0], whs, bhs, G, H)
+    if h0 is not None:
+        if any(p.shape != parts[0].shape for p in parts):
+            raise _unfit("gru_sequence_parts", "parts", parts[0], "equally sized parts expected with h0")
+        h0 = _gru_h0_views("gru_sequence_parts", h0, parts[0], len(parts), parts[0].shape[0], B, H)
     if (parts[0].is_cuda and H3 == 192 and B % 16 == 0 and 1 <= len(parts) <= 4 and all(p.shape == parts[0].shape for p in parts)
             and _f32_on(*parts, *whs, *bhs) and 1 <= len(whs) <= 4 and all(w.shape == whs[0].shape for w in whs)
             and all(b.shape == bhs[0].shape for b in bhs) and whs[0].shape[0] * len(whs) == G):
-        return list(_GruSeqParts.apply(T, B, len(whs), *whs, *bhs, *parts))
+        if h0 is None:
+            return list(_GruSeqParts.apply(T, B, len(whs), *whs, *bhs, *parts))
+        if _f32_on(*h0):
+            strides = _gru_h0_in_place(h0)
+            if strides is None:         # a layout the kernel does not index (odd strides, misaligned): one contiguous copy
+                full = th.stack([v.contiguous() for v in h0], dim=0).reshape(G, B, H)
+                h0 = [full[k * parts[0].shape[0]:(k + 1) * parts[0].shape[0]] for k in range(len(parts))]
+                strides = (B * H, H)
+            return list(_GruSeqPartsH0.apply(T, B, len(whs), (h0, strides[0], strides[1]), *whs, *bhs, *parts))
     wh, bh = (whs[0] if len(whs) == 1 else th.cat(whs, dim=0)), (bhs[0] if len(bhs) == 1 else th.cat(bhs, dim=0))
     if H3 != 192 or parts[0].dtype != th.float32:
         _leaving_kernels("gru_sequence_parts", parts[0], "hidden size %d / dtype" % (H3 // 3))
     # ragged batches (B % 16) and other part counts: the time-major launch (it pads the batch itself); still the HIP recurrence
     gi = th.cat([p.reshape(p.shape[0], T, B, H3) for p in parts], dim=0).transpose(0, 1).contiguous()      # [T, G, B, 3H]
-    hs = gru_sequence(gi, wh, bh)
+    hs = gru_sequence(gi, wh, bh) if h0 is None else gru_sequence(gi, wh, bh, th.cat(list(h0), dim=0))
     spp = parts[0].shape[0]
     return [hs[k * spp:(k + 1) * spp] for k in range(len(parts))]
 
@@ -1205,18 +1341,21 @@ def _gru_weights_fit(op, like, whs, bhs, G, H):
             raise _unfit(op, name, ts[0], "%d sets in all expected, got %d" % (G, sum(t.shape[0] for t in ts)))
 
 
-def gru_sequence(gi, wh, bh):
-    """hs [G, T, B, H]: the GRU states h_1..h_T for the input-side projections gi [T, G, B, 3H] from a zero initial state."""
+def gru_sequence(gi, wh, bh, h0=None):
+    """hs [G, T, B, H]: the GRU states h_1..h_T for the input-side projections gi [T, G, B, 3H] from a zero initial state.
+    h0 [G, B, H] (data, no gradient): hs[:, 0] = h0 and steps 1 .. T - 1 are computed from it; gi[0] is not read."""
     if gi.dim() != 4 or gi.shape[3] % 3:
         raise _unfit("gru_sequence", "gi", gi, "[T, G, B, 3H] expected")
     T, G, B, H3 = gi.shape
     _gru_weights_fit("gru_sequence", gi, [wh], [bh], G, H3 // 3)
-    if gi.is_cuda and H3 == 192 and _f32_on(gi, wh, bh):
-        return _GruSeq.apply(gi, wh, bh)
+    if h0 is not None:
+        h0 = _gru_h0_views("gru_sequence", h0, gi, 1, G, B, H3 // 3)[0]
+    if gi.is_cuda and H3 == 192 and _f32_on(gi, wh, bh) and (h0 is None or _f32_on(h0)):
+        return _GruSeq.apply(gi, wh, bh) if h0 is None else _GruSeqH0.apply(gi, wh, bh, h0)
     _leaving_kernels("gru_sequence", gi, "hidden size %d (the sequence kernels are instantiated for 64) / dtypes %s, %s, %s" % (H3 // 3, gi.dtype, wh.dtype, bh.dtype))
-    h = gi.new_zeros(G, B, H3 // 3)
-    hs = []
-    for t in range(T):
+    h = gi.new_zeros(G, B, H3 // 3) if h0 is None else h0.to(gi.dtype)
+    hs = [] if h0 is None else [h]                  # the given state IS the state after step 0
+    for t in range(len(hs), T):
         h = gru_gates(gi[t], _baddbmm(bh, h, wh), h)
         hs.append(h)
     return th.stack(hs, dim=1)

@@ -54,6 +54,9 @@ def build_scheme(args, env_info):
         del scheme["state"]        # nothing downstream reads it; 22 MB/step at 4096 envs
     if "homophily" in args.name:
         scheme["actions_inc"] = {"vshape": (args.n_agents, 1), "group": "agents", "dtype": th.long}
+    if getattr(args, "train_stored_state", False):
+        # the rollout's recurrent state AFTER the controller consumed the slot, [h_env | h_inc] per agent (ssd_store_hidden)
+        scheme["hidden"] = {"vshape": (2 * args.rnn_hidden_dim,), "group": "agents", "dtype": th.float32}
     groups = {"agents": args.n_agents}
     preprocess = {"actions": ("actions_onehot", [OneHot(out_dim=args.n_actions)])}
     return scheme, groups, preprocess
@@ -76,6 +79,26 @@ def _check_train_window(args, episode_limit, runner):
     if L > 0 and not getattr(runner, "fixed_length_episodes", False):
         raise ValueError("train_window > 0 needs a runner that fills every slot of an episode (the vectorised runners); runner %r does not" % (args.runner,))
     return norm
+
+
+def _check_stored_state(args):
+    """train_stored_state (absent = off), validated: sampled windows start their recurrence from the state the rollout stored for
+    their first slot (R2D2's stored state) instead of zeros.  The episode scheme gains the field "hidden"; slot t holds the state
+    AFTER the controller consumed slot t, so a window's row 0 is loaded, not computed, and carries loss.  train_burn_in stays legal
+    (the stored state is as stale as the episode is old; burn-in refreshes it) and 0 is a sensible value."""
+    on = args.train_stored_state = bool(getattr(args, "train_stored_state", False))
+    if not on:
+        return False
+    if int(getattr(args, "train_window", 0) or 0) <= 0:
+        raise ValueError("train_stored_state needs train_window > 0: whole episodes start at slot 0, where the state is zero anyway")
+    if args.runner != "hip_graph":
+        raise ValueError("train_stored_state needs runner hip_graph (the runner that files the recurrent state with the episode); runner %r does not" % (args.runner,))
+    if args.buffer_cpu_only or not args.use_cuda:
+        raise ValueError("train_stored_state needs a device-resident replay buffer (buffer_cpu_only: False, use_cuda: True): "
+                         "the state is filed by a device launch and read in place by the learner's recurrence")
+    if int(args.rnn_hidden_dim) != 64:
+        raise ValueError("train_stored_state needs rnn_hidden_dim 64 (the snapshot and the sequence kernels are instantiated for it), got %r" % (args.rnn_hidden_dim,))
+    return True
 
 
 def _check_prioritized(args, buffer, runner):
@@ -137,6 +160,7 @@ def setup(config, logger=None):
         from . import ops
         ops.set_strict(True)
     logger = logger or Logger()
+    _check_stored_state(args)
     runner = r_REGISTRY[args.runner](args=args, logger=logger)
     env_info = runner.get_env_info()
     args.n_agents, args.n_actions = env_info["n_agents"], env_info["n_actions"]

@@ -19,6 +19,9 @@ mechanics that make a timestep capturable and replayable for every t:
     t reads prev_rec[t & 1] and writes the other buffer, the inc head inside the third launch reads prev_rec[t & 1]; the exploration
     draws are those of the four-launch timestep.
     Other configurations (obs_others_last_action without that key, fast_policy=False) take the generic torch timestep, captured the same way;
+  * train_stored_state (default off): the episode field "hidden" receives the recurrent state AFTER the controller consumed slot t
+    (the state the heads of slot t produced Q_t from), [h_env | h_inc] per agent: one ssd_store_hidden launch ends every timestep,
+    the slot-T pass included, reading the device-side slot index the heads of slot t filed under;
   * epsilon is a device scalar; exploration uses the package's counter generator (no multinomial, no host sync).
 Which of these a runner takes is decided once, on the host: plan_rollout (fast_policy.py) for the controller, plan_runner below for
 the storage format, the graph length and the config keys.
@@ -140,6 +143,7 @@ class HipGraphRunner(HipVecRunner):
             self.actions_i32 = th.zeros(N, n, dtype=th.int32, device=dev)
             self.t_store = th.zeros(1, dtype=th.long, device=dev)     # the encoder's copy of t_dev, read by the store-step launch
         self.rng_copy = th.zeros(1, dtype=th.long, device=dev)          # pipelined: the env head's copy of rng_ctr for the inc head
+        self.stored_state = bool(getattr(a, "train_stored_state", False))
         self._par = 0
         self._ready = True
 
@@ -155,7 +159,13 @@ class HipGraphRunner(HipVecRunner):
             st["filled"].fill_(1)                                       # fixed-length episodes: every slot is filled
             st["avail_actions"].copy_(self.env.avail_actions_batch.unsqueeze(1).expand(-1, self.episode_limit + 1, -1, -1))
             b = SimpleNamespace(graph=None, cur=self._dense_cur, ss=None, ss_last=None, file_env=None, file_inc=None, file_inc_last=None,
-                                begin_graph=None, finish_graph=None)
+                                begin_graph=None, finish_graph=None, hidden=None)
+            if self.stored_state:
+                # the slot index the heads of slot t filed under, which the launch only reads: the encoder's / env head's copy where
+                # one is written (direct_obs), else the master before it is advanced
+                fast = self.fast is not None
+                b.hidden = ops.store_hidden_args(self.t_store if (fast and self.direct_obs) else self.t_dev,
+                                                 self.fast.h_env if fast else self.h_env, self.fast.h_inc if fast else self.h_inc, st["hidden"])
             if self.fast is not None:
                 if self.direct_obs:
                     b.cur = self.env.native.storage_obs_buffers(st["obs"], self.obs_fmt, want_code=self._want_code)
@@ -247,9 +257,13 @@ class HipGraphRunner(HipVecRunner):
             else:
                 fast.act_inc(actions, pos_t, orient_t, reward, clean, den, self.eps, inc_step, file=file, buf=buf, par=par)
 
+        def store_hidden():     # train_stored_state: the state after slot t, behind the inc head that produced it
+            ops.store_hidden(bundle.hidden, self.env.device)
+
         return ([] if pipe else [("ssd::k_encode", "encode", encode)]) + [("ssd::k_head<env>", "head_env", env_head)] + \
             ([("ssd::k_env<MODE_STEP_OBS>", "env", env_step)] if store_env_step or not pipe else []) + \
-            [("ssd::k_inc_encode", "inc_encode", inc_head) if inc_encode else ("ssd::k_head<inc>", "head_inc", inc_head)]
+            [("ssd::k_inc_encode", "inc_encode", inc_head) if inc_encode else ("ssd::k_head<inc>", "head_inc", inc_head)] + \
+            ([("ssd::k_store_hidden", "store_hidden", store_hidden)] if self.stored_state else [])
 
     def timestep_launches(self):
         """(kernel name, key, closure) of the launches of one rollout timestep on the live buffers -- what the rollout hipGraph was
@@ -330,6 +344,8 @@ class HipGraphRunner(HipVecRunner):
         q_inc, h_inc, _ = mac.agent.forward_inc(inputs, self.h_inc, onehot, pos_t / mac.pos_scale, orient_t, reward.unsqueeze(-1),
                                                 clean.unsqueeze(-1), den.unsqueeze(-1))
         self.h_inc.copy_(h_inc)
+        if self.stored_state:       # both states of slot t are in place; t_dev is advanced below
+            ops.store_hidden(self._bundle.hidden, self.env.device)
         actions_inc = self._pick(q_inc, None, None, a.n_inc_actions) * self.inc_mask              # [N, n, n]
         st["actions_inc"].index_copy_(1, td, actions_inc.reshape(actions_inc.shape[0], 1, actions_inc.shape[1], -1, 1))
         if store_env_step:

@@ -607,6 +607,27 @@ typedef struct ssd_store_step {
     int64_t* counter_inc;
 } ssd_store_step;
 int ssd_store_step_launch(const ssd_store_step* args, void* stream);
+
+/* ssd_store_hidden (config key train_stored_state, default off): the rollout's recurrent state filed with the episode, one launch per
+ * timestep after the inc head of slot t (R2D2's stored state).  The state filed in slot t is the state AFTER the controller consumed
+ * slot t -- the one the heads of slot t produced Q_t from.  dst f32 [n_env, t_slots, n_agents, 128] = [h_env 64 | h_inc 64] per agent;
+ * only slot *t_index is written, and nothing at all when *t_index lies outside [0, t_slots).  The sources are read as
+ * h[agent * src_agent_stride + env * src_env_stride + 0..63] (elements): FastPolicy's agent-major [n, N, 64] is (N * 64, 64), the
+ * generic timestep's [N, n, 1, 64] is (64, n * 64).  k_store_hidden: one thread per 16 bytes, 64-bit offsets, no atomics; the launch
+ * writes no scalar.  Declared in parentheses like ssd_behaviour_stats; the ctypes mirror is abi.STORED_STATE_SIGNATURES, the symbol,
+ * struct-size and refusal checks are tests/test_stored_state_host.py.
+ * Refused (SSD_ERR_INVALID): NULL args or a NULL member pointer; n_env, n_agents or t_slots below 1; h_env, h_inc or dst not 16-byte
+ * aligned; a negative source stride or one that is not a multiple of 4 elements. */
+typedef struct ssd_store_hidden_args {
+    const int64_t* t_index;     /* device scalar */
+    int32_t n_env, n_agents, t_slots;
+    int32_t reserved;           /* 0 */
+    const float *h_env, *h_inc;
+    int64_t src_agent_stride, src_env_stride;        /* elements */
+    float* dst;
+} ssd_store_hidden_args;
+int (ssd_store_hidden)(const ssd_store_hidden_args* args, void* stream);
+
 int ssd_gru_gates(const float* gi, const float* gh, float* h, int32_t rows, int32_t hidden, void* stream);
 /* ssd_gru_gates / _fwd / _bwd: any rows >= 1 and any hidden >= 1 (elementwise kernels that stride over rows x hidden with a grid of at
  * most 4096 workgroups; 64-bit offsets) -- the bounds suite runs hidden 1, 3, 64, 65. */
@@ -645,6 +666,29 @@ int ssd_gru_seq_bwd_parts(const float* const* dhs_parts, const float* hs, const 
  * states carry a gradient -- the live net's, the target net's follow): dhs_parts[k] f32 [G / n_parts, T, B, 64] are the gradients of the
  * states per gi part (parts past G_grad are not read), d_gi_parts past G_grad are not written, dgh [G_grad, T, B, 192],
  * d_wh [G_grad, 64, 192], d_bh_part [G_grad, tiles, 192]; hs / rzn / ghn keep the forward's shapes over all G sets. */
+
+/* The recurrence from a GIVEN state (train_stored_state: a sampled window starts from the state the rollout stored; the reference has no
+ * counterpart, its learner unrolls whole episodes from zeros).  Step 0 is not computed, it is loaded: hs[:, 0] := h0, steps 1 .. T - 1
+ * run as in ssd_gru_seq_fwd_parts; gi of step 0 is never read; rzn / ghn of step 0 receive zeros.  The given state is data: the
+ * backward writes zeros to d_gi of step 0 (and to dgh of step 0), adds nothing of step 0 to d_bh_part and sends no gradient into h0;
+ * d_wh = sum_{t >= 1} h_{t-1}^T dL/dgh_t is the product of ssd_gru_seq_bwd_parts with hs[:, 0] = h0 (T = 1: zeros).
+ * n_parts 1..4: set-major gi parts as in ssd_gru_seq_fwd_parts; n_parts 0: gi_parts[0] is ONE time-major tensor [T, G, B, 192] (the
+ * form of ssd_gru_seq_fwd: ragged batches, the host pads h0 with the batch).  h0_parts: max(1, n_parts) pointers, one per gi part;
+ * the state of set g (part k = g / spp, spp = G / max(1, n_parts)) and row b is the 64 floats at
+ *   h0_parts[k] + (g - k * spp) * h0_set_stride + b * h0_row_stride        (elements)
+ * so a contiguous [G, B, 64] is one pointer per part with strides (B * 64, 64), and the learner hands over batch["hidden"][:, 0] of
+ * a [B, W, n, 128] field in place: pointers p, p + 64, p, p + 64 (live env / inc, target env / inc), set stride 128, row stride
+ * W * n * 128.  Every row b < B is read (B a multiple of 16).  Kernels k_gru_seq_fwd_h0 / k_gru_seq_bwd_h0: the text of the
+ * zero-state kernels compiled a second time (csrc/ssd_gru_seq_kernels.h); the compute waves issue no stores, the steps hold no row
+ * predicate.  Both names are declared in parentheses; ctypes mirror abi.STORED_STATE_SIGNATURES.
+ * Refused (SSD_ERR_INVALID) like the _parts forms, and: a NULL or not 16-byte aligned h0 part; a negative h0 stride or one that is
+ * not a multiple of 4 elements. */
+int (ssd_gru_seq_fwd_h0)(const float* const* gi_parts, int32_t n_parts, const float* const* wh_parts, const float* const* bh_parts, int32_t n_wparts,
+                         const float* const* h0_parts, int64_t h0_set_stride, int64_t h0_row_stride, float* hs, float* rzn, float* ghn, int32_t T,
+                         int32_t G, int32_t B, void* stream);
+int (ssd_gru_seq_bwd_h0)(const float* const* dhs_parts, const float* hs, const float* rzn, const float* ghn, const float* const* wh_parts,
+                         int32_t n_wparts, float* const* d_gi_parts, int32_t n_parts, float* dgh, float* d_wh, float* d_bh_part, int32_t T, int32_t G,
+                         int32_t G_grad, int32_t B, void* stream);
 
 /* ---- the learner's per-agent affine layers (csrc/ssd_bmm.hip) ---------------------------------------------------------------
  * th.baddbmm(b, x, w) over the agent axis (homophily_agent.py:154-208: fc1, GRU input projections, dueling heads) and its backward,

@@ -33,6 +33,7 @@ ap.add_argument("--behaviour-stats", action="store_true",
                 help="config key behaviour_stats: print abi.behaviour_summary of the training rollouts (and of the greedy test rollout) at every report")
 ap.add_argument("--train-window", type=int, default=0, help="config key train_window: train on windows of L transitions (0: whole episodes)")
 ap.add_argument("--burn-in", type=int, default=0, help="config key train_burn_in: rows of a window without loss")
+ap.add_argument("--stored-state", action="store_true", help="config key train_stored_state: windows start from the rollout's stored recurrent state")
 ap.add_argument("--prioritized", action="store_true", help="config key prioritized_replay (per_alpha, per_beta, ... through --set)")
 ap.add_argument("--set", action="append", default=[], help="extra config override key=value (python literal)")
 a = ap.parse_args()
@@ -46,6 +47,8 @@ if a.behaviour_stats:
     over["behaviour_stats"] = True
 if a.train_window:
     over.update(train_window=a.train_window, train_burn_in=a.burn_in)
+if a.stored_state:
+    over.update(train_stored_state=True)
 if a.prioritized:
     over["prioritized_replay"] = True
 import ast

@@ -4,6 +4,7 @@ launch stream.  One JSON line.
 
     python tools/train_window_cost.py --batch 16                              whole episodes (today's path)
     python tools/train_window_cost.py --batch 64 --window 25 --burn-in 10     windows
+    python tools/train_window_cost.py --batch 64 --window 15 --stored-state   windows from the rollout's stored recurrent state
     python tools/train_window_cost.py --batch 64 --window 25 --gather-only    ssd_gather_windows alone (captured back to back)
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/train_window_cost.py ...      the kernels' own times
 
@@ -29,20 +30,21 @@ ap.add_argument("--n-env", type=int, default=512)
 ap.add_argument("--calls", type=int, default=40)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--gather-only", action="store_true")
+ap.add_argument("--stored-state", action="store_true", help="config key train_stored_state")
 a = ap.parse_args()
 
 over = dict(runner="hip_graph", train_graph=1, batch_size_run=a.n_env, batch_size=a.batch, buffer_size=a.n_env, buffer_cpu_only=False,
             store_state=False, obs_storage="code", env_args=dict(num_agents=5, map="default5", episode_limit=100, seed=1), use_cuda=True,
             save_model=False, runner_stats=False, learner_log_interval=10 ** 12)
 if a.window:
-    over.update(train_window=a.window, train_burn_in=a.burn_in)
+    over.update(train_window=a.window, train_burn_in=a.burn_in, train_stored_state=a.stored_state)
 th.manual_seed(0)
 ctx = setup(load_config("cleanup", overrides=over))
 buf, learner = ctx.buffer, ctx.learner
 buf.insert_episode_batch(ctx.runner.run(False))
 summary = lambda xs: dict(median=statistics.median(xs), min=min(xs), max=max(xs))
 ev = lambda: th.cuda.Event(enable_timing=True)
-out = dict(batch=a.batch, window=a.window, burn_in=a.burn_in, slots=(a.window or 100) + 1, rounds=a.rounds, calls_per_round=a.calls)
+out = dict(batch=a.batch, window=a.window, burn_in=a.burn_in, stored_state=a.stored_state, slots=(a.window or 100) + 1, rounds=a.rounds, calls_per_round=a.calls)
 
 if a.gather_only:
     buf.sample_windows(a.batch, a.window, a.burn_in)
