@@ -1,11 +1,15 @@
 """Property test: C restatement (oracle/ssd_oracle.c) == imported reference, step by step.
 
 TEST INFRASTRUCTURE; runs only in the build container (needs /root/reference).  Usage:
-    python oracle/check_vs_reference.py [--steps 12000] [--seed 0]
+    python oracle/check_vs_reference.py [--steps 12000] [--seed 0] [--warm]
 Every step compares grid, positions, orientations, reward, clean_num, apple_den, terminated, the number of uniforms
 consumed, and (every --obs-every steps) the full get_obs() / get_state() tensors.  Agents are periodically
 teleported into a tight cluster (Agent.set_pos on the reference, ssd_cpu_import_state on the oracle) so the
 move-conflict code of map_env.py:553-661 is exercised far more often than a random walk would.
+With --warm every episode starts from a swept grid instead of the reset state (RefEnv.set_state(grid=...) on the reference,
+import_state(grid=...) on the oracle; tests/env_state_util.py builds it): a uniformly drawn waste count 0..n_waste with a random
+fraction of the apple sites filled on Cleanup, a uniformly drawn apple count 0..n_apple on Harvest -- the counts a walk from reset
+never visits, among them waste count 0, the only one on the `waste_density <= thresholdRestoration` branch (cleanup.py:198).
 Both RNG contracts are covered: mode=tape (unmodified reference RNG, recorded) and mode=counter (reference RNG
 functions replaced by the Philox counter generator).
 """
@@ -53,7 +57,15 @@ def cluster_positions(rng, grid, n, spread):
     return np.array(out, np.int16)
 
 
-def run_config(cfg, steps, seed, mode, extra_args, obs_every, episode_limit=50):
+def warm_grid(layout, rng):
+    """one row of the sweep, drawn uniformly: every count of waste cells (Cleanup) / apples (Harvest) is equally likely"""
+    from tests import env_state_util as U
+    if layout.env == "cleanup":
+        return U.waste_sweep(layout.n_waste + 1, layout, rng)[rng.integers(layout.n_waste + 1)]
+    return U.harvest_sweep(layout.n_apple + 1, layout, rng)[rng.integers(layout.n_apple + 1)]
+
+
+def run_config(cfg, steps, seed, mode, extra_args, obs_every, episode_limit=50, warm=False):
     rng = np.random.default_rng(seed)
     np.random.seed(seed)
     import random
@@ -67,6 +79,10 @@ def run_config(cfg, steps, seed, mode, extra_args, obs_every, episode_limit=50):
     n = cfg["num_agents"]
     maxu, nw = orc.info.max_uniforms, orc.info.n_waste_sites
     assert orc.info.n_apple_sites == ref.n_apple and nw == ref.n_waste
+    if warm:
+        from tests import env_state_util as U
+        layout = U.shipped(cfg["env"], cfg["map"])
+        assert (layout.n_apple, layout.n_waste) == (ref.n_apple, ref.n_waste)
     full_actions = extra_args is not None and not extra_args.get("disable_rotation_action", True)
     avail = list(range(orc.n_actions)) if full_actions else [a for a in range(orc.n_actions) if a not in (5, 6, 7)]
 
@@ -105,6 +121,12 @@ def run_config(cfg, steps, seed, mode, extra_args, obs_every, episode_limit=50):
         assert o["n_draws"][0] == ta["n_uniforms"], ("reset draws", o["n_draws"][0], ta["n_uniforms"])
         compare("reset", t_done)
         compare_obs(t_done)
+        if warm:
+            g = warm_grid(layout, rng)
+            ref.set_state(grid=g.reshape(layout.H, layout.W))
+            orc.import_state(grid=g[None])
+            compare("warm", t_done)
+            compare_obs(t_done)
         term = False
         ep_t = 0
         while not term:
@@ -140,6 +162,7 @@ def main():
     ap.add_argument("--steps", type=int, default=2000, help="steps per (config, mode, option set)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--obs-every", type=int, default=7)
+    ap.add_argument("--warm", action="store_true", help="start every episode from a swept grid instead of the reset state")
     ap.add_argument("--configs", default="", help="comma-separated indices into CONFIGS (default: all)")
     a = ap.parse_args()
     option_sets = [
@@ -154,11 +177,11 @@ def main():
     for cfg in [CONFIGS[int(i)] for i in a.configs.split(",")] if a.configs else CONFIGS:
         for mode in ("tape", "counter"):
             for oi, ea in enumerate(option_sets):
-                nsteps = run_config(cfg, a.steps, a.seed + oi, mode, ea, a.obs_every)
+                nsteps = run_config(cfg, a.steps, a.seed + oi, mode, ea, a.obs_every, warm=a.warm)
                 total += nsteps
                 print("ok  %-8s %-10s n=%-2d mode=%-7s opts=%d  %d steps  (%.0fs)" %
                       (cfg["env"], cfg["map"], cfg["num_agents"], mode, oi, nsteps, time.time() - t0), flush=True)
-    print("ALL OK: %d steps compared, 0 mismatches" % total)
+    print("ALL OK%s: %d steps compared, 0 mismatches" % (" (warm starts)" if a.warm else "", total))
 
 
 if __name__ == "__main__":

@@ -7,6 +7,8 @@ traj_<name>.npz  one env, a list of calls c = 0..C-1 (kind 0 = reset, 1 = step):
     meta                json: env, map, num_agents, view_size, episode_limit, extra_args
     kind[C] u8, actions[C,n] i32
     pre_pos[C,n,2] i16, pre_orient[C,n] u8      agent state fed to the call (after an optional teleport)
+    pre_grid[C,H,W] u8                          (warm trajectories only) the grid fed to the call: every episode starts from a
+                                                grid set on the reference after its reset, not from the reset state
     move_order[C,n] u8, uniforms[C,U] f64, n_uniforms[C] i32, waste_order[C,Wn] u8, shuffled[C] u8, spawn_rot[C,n] u8
     grid[C,H,W] u8, pos[C,n,2] i16, orient[C,n] u8                     state after the call
     reward[C,n] f64, clean_num[C,n] f64, apple_den[C] f64, terminated[C] u8, collective_return[C] f64, equality[C] f64
@@ -25,9 +27,25 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from oracle import ref_harness as RH  # noqa: E402
 from oracle.check_vs_reference import cluster_positions  # noqa: E402
+from tests import env_state_util as U  # noqa: E402
 
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
 ALL = dict(disable_rotation_action=False, disable_fire_action=False)
+
+
+
+def warm(waste, apples):
+    """Start grid of an episode: the fraction `waste` of the waste sites holds waste (the others are cleaned), and a number of
+    apples drawn from apples = (lo, hi) lies on random apple sites (lo in the first episode)."""
+    def make(L, rng, ep):
+        g = L.base.copy()
+        g[L.waste] = U.RIVER
+        g[L.waste[rng.permutation(L.n_waste)[:int(round(waste * L.n_waste))]]] = U.WASTE
+        g[L.apple] = U.EMPTY
+        g[L.apple[rng.permutation(L.n_apple)[:int(rng.integers(apples[0], apples[1] + 1)) if ep else apples[0]]]] = U.APPLE
+        return g.reshape(L.H, L.W)
+    return make
+
 
 TRAJ = [
     # name, cfg, episodes, episode_limit, extra_args, seed, teleport prob
@@ -60,10 +78,17 @@ TRAJ = [
      dict(ALL, obs_color="full", random_spawn_rotation=None), 65, 0.15),
     ("cleanup8_v16", dict(env="cleanup", map="default10", num_agents=8, view_size=16), 2, 30, ALL, 66, 0.2),
     ("cleanup1_v0", dict(env="cleanup", map="default5", num_agents=1, view_size=0), 2, 40, None, 67, 0.1),
+    # warm starts: the waste counts (and the sparse orchards) a walk from reset never visits -- half the waste cleaned with apples
+    # present, no waste at all (count 0: the only one on the `waste_density <= thresholdRestoration` branch), an empty map, and a
+    # Harvest orchard of 0 to 10 apples
+    ("cleanup5_warm", dict(env="cleanup", map="default5", num_agents=5, view_size=7), 3, 16, ALL, 71, 0.1, warm(0.5, (20, 60))),
+    ("cleanup10_clean", dict(env="cleanup", map="default10", num_agents=10, view_size=7), 3, 16, ALL, 72, 0.1, warm(0.0, (0, 100))),
+    ("cleanup3_empty", dict(env="cleanup", map="default3", num_agents=3, view_size=7), 3, 16, ALL, 73, 0.1, warm(0.0, (0, 0))),
+    ("harvest5_sparse", dict(env="harvest", map="default10", num_agents=5, view_size=7), 4, 12, ALL, 74, 0.1, warm(0.0, (0, 10))),
 ]
 
 
-def gen_traj(name, cfg, episodes, limit, ea, seed, p_tele):
+def gen_traj(name, cfg, episodes, limit, ea, seed, p_tele, warm_start=None):
     np.random.seed(seed); random.seed(seed)
     rng = np.random.default_rng(seed)
     ref = RH.RefEnv(cfg["env"], cfg["map"], cfg["num_agents"], cfg["view_size"], limit, ea)
@@ -75,11 +100,14 @@ def gen_traj(name, cfg, episodes, limit, ea, seed, p_tele):
     rows = []
     obs_rows = []
 
-    def add(kind, acts, pre_pos, pre_orient, rec, reward, info, term):
+    layout = U.shipped(cfg["env"], cfg["map"]) if warm_start else None
+
+    def add(kind, acts, pre_pos, pre_orient, rec, reward, info, term, pre_grid=None):
         ta = RH.tape_arrays(rec, n, maxu, nw, ref.spawn_len)
         rsp = bool(ea and ea.get("random_spawn_point"))
         rows.append(dict(
             **({"spawn_order": ta["spawn_order"]} if rsp else {}),
+            **({"pre_grid": np.zeros((ref.H, ref.W), np.uint8) if pre_grid is None else pre_grid} if warm_start else {}),
             kind=kind, actions=acts, pre_pos=pre_pos, pre_orient=pre_orient,
             move_order=ta["move_order"], uniforms=ta["uniforms"], n_uniforms=ta["n_uniforms"],
             waste_order=ta["waste_order"], shuffled=int(ta["shuffled"]), spawn_rot=ta["spawn_rot"],
@@ -105,6 +133,8 @@ def gen_traj(name, cfg, episodes, limit, ea, seed, p_tele):
         rec = ref.reset()
         add(0, np.zeros(n, np.int32), pre_pos, pre_ori, rec, None, None, False)
         add_obs()
+        if warm_start:
+            ref.set_state(grid=warm_start(layout, rng, ep))
         term = False
         t = 0
         while not term:
@@ -112,10 +142,10 @@ def gen_traj(name, cfg, episodes, limit, ea, seed, p_tele):
                 p = cluster_positions(rng, ref.grid(), n, int(rng.integers(1, 3)))
                 ori = rng.integers(0, 4, n).astype(np.uint8) if full else ref.orient()
                 ref.set_state(pos=p, orient=ori)
-            pre_pos, pre_ori = ref.pos(), ref.orient()
+            pre_pos, pre_ori, pre_grid = ref.pos(), ref.orient(), ref.grid()
             acts = np.array([rng.choice(avail) for _ in range(n)], np.int32)
             reward, term, info, rec = ref.step(acts)
-            add(1, acts, pre_pos, pre_ori, rec, reward, info, term)
+            add(1, acts, pre_pos, pre_ori, rec, reward, info, term, pre_grid)
             t += 1
             if t % 17 == 3 or term:
                 add_obs()
@@ -129,10 +159,14 @@ def gen_traj(name, cfg, episodes, limit, ea, seed, p_tele):
     out["agent_pos"] = np.stack([r["agent_pos"] for r in obs_rows])
     out["agent_orient"] = np.stack([r["agent_orient"] for r in obs_rows])
     meta = dict(cfg, episode_limit=limit, extra_args=ea, n_actions=int(n_actions), n_apple=ref.n_apple, n_waste=ref.n_waste,
-                generator="oracle/gen_golden.py", seed=seed)
+                generator="oracle/gen_golden.py", seed=seed, **({"warm_start": True} if warm_start else {}))
     out["meta"] = np.frombuffer(json.dumps(meta).encode(), np.uint8)
     path = os.path.join(OUT, "traj_%s.npz" % name)
     np.savez_compressed(path, **out)
+    if warm_start:
+        step = out["kind"] == 1
+        print("  waste count fed to the steps:", sorted(set((out["pre_grid"][step] == U.WASTE).sum((1, 2)).tolist())),
+              "apples:", sorted(set((out["pre_grid"][step] == U.APPLE).sum((1, 2)).tolist())))
     ev = dict(calls=len(rows), eaten=int((out["reward"] > 0).sum()), cleaned=int(out["clean_num"].sum()),
               shuffles=int(out["shuffled"].sum()), kb=os.path.getsize(path) // 1024)
     print("wrote", path, ev, flush=True)

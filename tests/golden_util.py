@@ -42,7 +42,8 @@ def replay(make_env, make_tape, path, n_env=1):
         if z["kind"][c] == 0:
             o = env.reset(tape)
         else:
-            env.import_state(pos=rep(z["pre_pos"][c]), orient=rep(z["pre_orient"][c]))
+            grid = dict(grid=rep(z["pre_grid"][c].reshape(-1))) if "pre_grid" in z else {}      # warm trajectories (gen_golden.py)
+            env.import_state(pos=rep(z["pre_pos"][c]), orient=rep(z["pre_orient"][c]), **grid)
             o = env.step(rep(z["actions"][c]), tape)
         st = env.export_state()
         for e in range(n_env):
