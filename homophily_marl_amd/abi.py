@@ -423,6 +423,22 @@ STORED_STATE_SIGNATURES = {
 }
 
 
+class SsdRolloutPriorityArgs(C.Structure):
+    """include/ssd_hip.h: ssd_rollout_priority_args."""
+    _fields_ = [("t_index", C.c_void_p), ("n_env", C.c_int32), ("n_agents", C.c_int32), ("n_actions", C.c_int32), ("t_slots", C.c_int32),
+                ("avail_bits", C.c_uint32), ("reserved", C.c_int32), ("q_env", C.c_void_p), ("q_inc", C.c_void_p),
+                ("q_env_agent_stride", C.c_int64), ("q_env_env_stride", C.c_int64), ("q_inc_agent_stride", C.c_int64), ("q_inc_env_stride", C.c_int64),
+                ("actions", C.c_void_p), ("actions_inc", C.c_void_p), ("reward", C.c_void_p), ("terminated", C.c_void_p), ("filled", C.c_void_p),
+                ("gamma_env", C.c_float), ("gamma_inc", C.c_float), ("reward_scale", C.c_float), ("incentive_ratio", C.c_float),
+                ("incentive_cost", C.c_float), ("incentive", C.c_float), ("seq_len", C.c_float), ("alpha", C.c_float), ("eta", C.c_float),
+                ("eps", C.c_float), ("carry", C.c_void_p), ("acc", C.c_void_p), ("q_init", C.c_void_p)]
+
+
+# the export of prioritised replay's initial priorities (per_initial_priority: "rollout"), in a table of its own like
+# ssd_behaviour_stats (its checks: tests/test_rollout_priority_host.py)
+ROLLOUT_PRIORITY_SIGNATURES = {"ssd_rollout_priority": (C.c_int, [C.POINTER(SsdRolloutPriorityArgs), C.c_void_p])}
+
+
 def behaviour_len(n, A):
     """SSD_BEHAVIOUR_LEN"""
     return 12 * n + n * A + 3 * n * n + 3
@@ -517,6 +533,7 @@ def load_library():
         bind(lib, WINDOW_SIGNATURES)
         bind(lib, PRIORITY_SIGNATURES)
         bind(lib, STORED_STATE_SIGNATURES)
+        bind(lib, ROLLOUT_PRIORITY_SIGNATURES)
         ver = lib.ssd_abi_version()
         if ver != ABI_VERSION:
             raise ImportError("libssd_hip.so ABI version %d != %d" % (ver, ABI_VERSION))

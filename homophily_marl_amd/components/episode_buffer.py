@@ -195,19 +195,31 @@ class ReplayBuffer(EpisodeBatch):
         view._reserved = (self, self.buffer_index)
         return view
 
-    def insert_episode_batch(self, ep_batch):
+    def insert_episode_batch(self, ep_batch, priorities=None):
+        """priorities (prioritised replay, per_initial_priority "rollout"): a device int32 tensor of ep_batch.batch_size fixed-point
+        priorities the episodes enter the table with (one ops.copy_blocks launch per contiguous run of slots; split with the batch
+        on wrap-around).  None: the slots are zeroed -- drawn at the table's maximum until trained on."""
         n = ep_batch.batch_size
         res = getattr(ep_batch, "_reserved", None)
+        if priorities is not None:
+            if self.priority_table is None:
+                raise ValueError("insert_episode_batch: priorities given, but enable_priorities() was not called")
+            if priorities.dtype != th.int32 or priorities.dim() != 1 or priorities.numel() != n or priorities.device != self.priority_table.device:
+                raise ValueError("insert_episode_batch: priorities %s %s on %s: int32 [%d] on %s expected"
+                                 % (tuple(priorities.shape), priorities.dtype, priorities.device, n, self.priority_table.device))
         if self.buffer_index + n > self.buffer_size:
             left = self.buffer_size - self.buffer_index
-            self.insert_episode_batch(ep_batch[0:left, :])
-            self.insert_episode_batch(ep_batch[left:, :])
+            self.insert_episode_batch(ep_batch[0:left, :], None if priorities is None else priorities[:left])
+            self.insert_episode_batch(ep_batch[left:, :], None if priorities is None else priorities[left:])
             return
         if not (res is not None and res[0] is self and res[1] == self.buffer_index):      # (else: written in place, reserve)
             where = slice(self.buffer_index, self.buffer_index + n)
             self.update(ep_batch.data.transition_data, where, slice(0, ep_batch.max_seq_length), mark_filled=False)
             self.update(ep_batch.data.episode_data, where)
-        self._reset_priorities(self.buffer_index, n)
+        if priorities is None:
+            self._reset_priorities(self.buffer_index, n)
+        else:
+            self._write_priorities(self.buffer_index, priorities)
         self.buffer_index += n
         self.episodes_in_buffer = max(self.episodes_in_buffer, self.buffer_index)
         self.buffer_index %= self.buffer_size
@@ -290,7 +302,7 @@ class ReplayBuffer(EpisodeBatch):
             nd = SimpleNamespace(transition_data={k: th.empty((B, W) + tuple(v.shape[2:]), dtype=v.dtype, device=v.device) for k, v in src.items()},
                                  episode_data={k: v[ids] for k, v in self.data.episode_data.items()})
             out = EpisodeBatch(self.scheme, self.groups, B, W, data=nd, device=self.device)
-        out.reward_norm = float(self.max_seq_length if self.window_norm == "episode" else W)
+        out.reward_norm = ops.window_reward_norm(self.window_norm, self.max_seq_length, window)
         keys = list(src)
         pairs = [(src[k], out.data.transition_data[k]) for k in keys]
         if ids.is_cuda and ops.gather_windows(pairs, ids, t0, self.max_seq_length, W, burn_in, keys.index("filled")):
@@ -344,6 +356,14 @@ class ReplayBuffer(EpisodeBatch):
         """the n slots from `start` hold new episodes: their priorities go back to 0 (one ssd_fill_blocks launch on the device)"""
         if self.priority_table is not None and n > 0:
             ops.fill_blocks([(self.priority_table[start:start + n], 0)])
+
+    def _write_priorities(self, start, priorities):
+        """the slots from `start` hold new episodes that bring their priorities along (one ssd_copy_blocks launch on the device)"""
+        dst = self.priority_table[start:start + priorities.numel()]
+        if dst.is_cuda:
+            ops.copy_blocks([(priorities.contiguous(), dst)])
+        else:
+            dst.copy_(priorities)
 
     def sample_prioritized(self, batch_size, window=0, burn_in=0, beta=0.4, out=None):
         """batch_size samples drawn in proportion to the priority table (stratified, with replacement: duplicate ids are legal; no

@@ -585,6 +585,28 @@ int ssd_priority_update(const ssd_priority_update_args* a, void* stream) {
     return launched();
 }
 
+int ssd_rollout_priority(const ssd_rollout_priority_args* a, void* stream) {
+    if (!a) return fail(SSD_ERR_INVALID, "ssd_rollout_priority: null args");
+    if (!a->t_index || !a->q_env || !a->q_inc || !a->actions || !a->actions_inc || !a->reward || !a->terminated || !a->carry || !a->acc || !a->q_init)
+        return fail(SSD_ERR_INVALID, "ssd_rollout_priority: null member pointer");
+    if (a->n_env < 1 || a->n_env > (1 << 24) || a->t_slots < 2) return fail(SSD_ERR_INVALID, "ssd_rollout_priority: n_env outside 1 .. 2^24, or t_slots < 2");
+    if (a->n_agents < 2 || a->n_agents > SSD_MAX_AGENTS) return fail(SSD_ERR_INVALID, "ssd_rollout_priority: n_agents outside 2 .. SSD_MAX_AGENTS");
+    if (a->n_actions < 1 || a->n_actions > 16) return fail(SSD_ERR_INVALID, "ssd_rollout_priority: n_actions outside 1 .. 16");
+    if (!(a->avail_bits & ((1u << a->n_actions) - 1u))) return fail(SSD_ERR_INVALID, "ssd_rollout_priority: avail_bits names no action below n_actions");
+    if (!unit_interval(a->alpha) || !unit_interval(a->eta)) return fail(SSD_ERR_INVALID, "ssd_rollout_priority: alpha or eta outside [0, 1]");
+    if (!(a->eps > 0.f)) return fail(SSD_ERR_INVALID, "ssd_rollout_priority: eps <= 0");
+    if (!(a->seq_len > 0.f) || !(a->reward_scale > 0.f)) return fail(SSD_ERR_INVALID, "ssd_rollout_priority: seq_len or reward_scale <= 0");
+    if (a->q_env_agent_stride < 0 || a->q_env_env_stride < 0 || a->q_inc_agent_stride < 0 || a->q_inc_env_stride < 0)
+        return fail(SSD_ERR_INVALID, "ssd_rollout_priority: negative stride");
+    if ((reinterpret_cast<uintptr_t>(a->q_env) | reinterpret_cast<uintptr_t>(a->q_inc) | reinterpret_cast<uintptr_t>(a->reward) | reinterpret_cast<uintptr_t>(a->carry)
+         | reinterpret_cast<uintptr_t>(a->acc) | reinterpret_cast<uintptr_t>(a->q_init)) & 3)
+        return fail(SSD_ERR_INVALID, "ssd_rollout_priority: q_env, q_inc, reward, carry, acc and q_init must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(a->t_index) | reinterpret_cast<uintptr_t>(a->actions) | reinterpret_cast<uintptr_t>(a->actions_inc) | reinterpret_cast<uintptr_t>(a->filled)) & 7)
+        return fail(SSD_ERR_INVALID, "ssd_rollout_priority: t_index, actions, actions_inc and filled must be 8-byte aligned");
+    launch_rollout_priority(a, (hipStream_t)stream);
+    return launched();
+}
+
 int ssd_behaviour_stats(const ssd_behaviour_args* a, void* stream) {
     if (!a) return fail(SSD_ERR_INVALID, "ssd_behaviour_stats: null args");
     if (!a->actions || !a->actions_inc || !a->reward || !a->clean_num || !a->workspace || !a->acc)

@@ -203,6 +203,7 @@ void launch_gather_windows(const ssd_window_field* fields, int count, const int6
                            int win_slots, int burn_in, hipStream_t stream);
 void launch_priority_sample(const ssd_priority_sample_args* a, hipStream_t stream);
 void launch_priority_update(const ssd_priority_update_args* a, hipStream_t stream);
+void launch_rollout_priority(const ssd_rollout_priority_args* a, hipStream_t stream);
 int launch_bias_bmm_fwd(const float* x, const float* w, const float* b, float* y, int n, int R, int I, int O, hipStream_t s, int leaky = 0);
 int launch_bias_bmm_bwd(const float* g, const float* x, const float* w, float* dx, float* dw, float* db, const float* slope_of, int n, int R,
                         int I, int O, hipStream_t s, long x_set = 0, long g_set = 0, const float* act_y = nullptr, const float* x2 = nullptr, int I1 = 0,

@@ -1136,6 +1136,93 @@ void launch_priority_update(const ssd_priority_update_args* a, hipStream_t strea
     hipLaunchKernelGGL(k_priority_apply, dim3(1), dim3(PRI_THREADS), 0, stream, *a);
 }
 
+// k_rollout_priority (ssd_rollout_priority; the contract is in include/ssd_hip.h): the priority an episode enters the table with, from
+// the rollout's own one-step TD errors, one launch per timestep slot behind the inc head.  16 lanes per env, four envs per wave, lane
+// g & 15 = agent (n <= 10); a thread owns its (env, agent) pair's carry and acc.  At slot t it forms row t - 1 with the expressions
+// and operation order of k_td_sim_loss<1> (plain branch, q = tq) and of k_priority_rows; at t = T the env's agents are reduced by
+// __shfl reads of registers (every lane of the wave takes part, idle ones with zeros) and lane 0 of the env writes q_init.  Every
+// lane walks its own row of A floats with scalar-width loads; in FastPolicy's agent-major layout the lanes of one env lie N A floats
+// apart, so a wave touches about n segments of 4 A floats (the four envs' rows of one agent are neighbours) -- not a coalesced read.
+// The launch reads ~0.5 KB per env and sits at the launch floor, so the access pattern was left at that.
+__global__ __launch_bounds__(256) void k_rollout_priority(const ssd_rollout_priority_args a) {
+    const int64_t t = *a.t_index;
+    const int T1 = a.t_slots, T = T1 - 1, n = a.n_agents, A = a.n_actions;
+    if (t < 0 || t > T) return;                                                 // (uniform over the launch)
+    const int lane = threadIdx.x & 63, i = lane & 15, base = lane & 48;
+    const int64_t env = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+    const bool active = env < a.n_env && i < n;
+    float mx = 0.f, sum = 0.f, cnt = 0.f;
+    if (active) {
+        const float* __restrict__ qe = a.q_env + (int64_t)i * a.q_env_agent_stride + env * a.q_env_env_stride;
+        const float* __restrict__ qi = a.q_inc + (int64_t)i * a.q_inc_agent_stride + env * a.q_inc_env_stride;
+        float* __restrict__ carry = a.carry + (env * n + i) * 2;
+        float* __restrict__ acc = a.acc + (env * n + i) * 3;
+        if (t > 0) {
+            mx = acc[0]; sum = acc[1]; cnt = acc[2];
+            const int64_t bt = env * T1 + (t - 1);                              // (env, slot t - 1)
+            const float mask = (a.filled ? (float)a.filled[bt] : 1.f) * (t - 1 ? 1.f - (float)a.terminated[bt - 1] : 1.f);
+            const int64_t* __restrict__ ainc = a.actions_inc + bt * n * n;      // [giver][receiver]
+            int give = 0, rp = 0, rn = 0;
+            for (int j = 0; j < n; ++j) {
+                if (j == i) continue;
+                give += ainc[(int64_t)i * n + j] != 0;
+                const int64_t x = ainc[(int64_t)j * n + i];
+                rp += x == 1; rn += x == 2;
+            }
+            const float r = a.reward[bt * n + i] / a.reward_scale;
+            const float rv = (float)(rp - rn);
+            const float r_env = (r + rv * a.incentive_ratio * a.incentive) / a.seq_len;
+            const float r_inc = (r - (float)give * a.incentive_cost * a.incentive) / a.seq_len;
+            const float live = 1.f - (float)a.terminated[bt];
+            float v_env = -INFINITY;
+            for (int k = 0; k < A; ++k) {
+                const float q = (a.avail_bits >> k) & 1u ? qe[k] : kNeg;
+                if (q > v_env) v_env = q;
+            }
+            float v_inc = 0.f;
+            for (int j = 0; j < n; ++j) {
+                if (j == i) continue;
+                const float* s = qi + j * 3;
+                v_inc += s[1] > s[0] ? (s[2] > s[1] ? s[2] : s[1]) : (s[2] > s[0] ? s[2] : s[0]);
+            }
+            const float td_env = carry[0] - (r_env + a.gamma_env * live * v_env);
+            const float td_inc = carry[1] - (r_inc + a.gamma_inc * live * v_inc);
+            const float d = sqrtf((td_env * mask) * (td_env * mask) + (td_inc * mask) * (td_inc * mask));
+            mx = fmaxf(mx, d); sum += d; cnt += mask;
+        }
+        acc[0] = mx; acc[1] = sum; acc[2] = cnt;
+        if (t < T) {
+            const int64_t row = (env * T1 + t) * n + i;                         // (env, slot t, agent i)
+            int64_t a_t = a.actions[row];
+            a_t = a_t < 0 ? 0 : a_t >= A ? A - 1 : a_t;
+            const int64_t* __restrict__ mine = a.actions_inc + row * n;
+            float chosen = 0.f;
+            for (int j = 0; j < n; ++j) {
+                if (j == i) continue;
+                int64_t c = mine[j];
+                c = c < 0 ? 0 : c > 2 ? 2 : c;
+                chosen += qi[j * 3 + c];
+            }
+            carry[0] = qe[a_t]; carry[1] = chosen;
+        }
+    }
+    if (t < T) return;
+    // t == T: the env's agents, lanes base .. base + n - 1 of this wave
+    float m = mx;
+    for (int w = 8; w > 0; w >>= 1) m = fmaxf(m, __shfl_xor(m, w));             // lanes n .. 15 hold 0 <= every d
+    float s = 0.f, c = 0.f;
+    for (int j = 0; j < n; ++j) { s += __shfl(sum, base + j); c += __shfl(cnt, base + j); }
+    if (active && i == 0) {
+        const float p = a.eta * m + (1.f - a.eta) * s / fmaxf(1.f, c) + a.eps;
+        float q = powf(p, a.alpha) * (float)SSD_PRIORITY_ONE;
+        q = q == q ? q : (float)SSD_PRIORITY_MAX;
+        a.q_init[env] = (uint32_t)rintf(fminf(fmaxf(q, 1.f), (float)SSD_PRIORITY_MAX));
+    }
+}
+void launch_rollout_priority(const ssd_rollout_priority_args* a, hipStream_t stream) {
+    hipLaunchKernelGGL(k_rollout_priority, dim3((unsigned)((a->n_env + 15) / 16)), dim3(256), 0, stream, *a);
+}
+
 void launch_copy_blocks(const ssd_block_copy* blocks, int count, hipStream_t stream) {
     CopyTable t;
     int most = 1;

@@ -211,6 +211,20 @@ def reward_norm(batch):
     return float(batch.reward_norm or batch.max_seq_length)
 
 
+def window_reward_norm(norm, slots, window):
+    """The length a batch's rewards are divided by under train_window_norm `norm`: the episode's slot count ("episode", or whole
+    episodes), else window + 1 -- one statement for the buffer's window batches and the rollout's initial priorities."""
+    return float(slots if norm == "episode" or not window else window + 1)
+
+
+def td_constants(a, seq_len):
+    """The scalars of the TD targets by the names the argument blocks carry them under, from the config `a` and the reward norm: what
+    the loss launch (_td_loss_args) and the rollout's initial priorities (rollout_priority_args) both take, so the two cannot drift."""
+    return dict(gamma_env=float(a.gamma_env), gamma_inc=float(a.gamma_inc), reward_scale=float(a.reward_scale),
+                incentive_ratio=float(a.incentive_ratio), incentive_cost=float(a.incentive_cost), incentive=float(a.incentive),
+                seq_len=float(seq_len))
+
+
 def _td_loss_args(batch, a, n_actions, partials):
     """ssd_td_loss_args over the batch's tensors (contiguous copies where a view is not); returns (args, keep-alive list)."""
     c = lambda x: x.contiguous()
@@ -221,9 +235,9 @@ def _td_loss_args(batch, a, n_actions, partials):
     assert keep["avail"].dtype == th.int32 and keep["terminated"].dtype == th.uint8 and keep["filled"].dtype == th.int64
     t = abi.SsdTdLossArgs()
     t.batch, t.t_slots, t.n_agents, t.n_actions, t.sim_horizon, t.double_q = B, T1, n, n_actions, int(a.sim_horizon), int(bool(a.double_q))
-    t.gamma_env, t.gamma_inc, t.reward_scale = float(a.gamma_env), float(a.gamma_inc), float(a.reward_scale)
-    t.incentive_ratio, t.incentive_cost, t.incentive = float(a.incentive_ratio), float(a.incentive_cost), float(a.incentive)
-    t.seq_len, t.sim_threshold, t.sim_loss_weight = reward_norm(batch), float(a.sim_threshold), float(a.sim_loss_weight)
+    for k, v in td_constants(a, reward_norm(batch)).items():
+        setattr(t, k, v)
+    t.sim_threshold, t.sim_loss_weight = float(a.sim_threshold), float(a.sim_loss_weight)
     t.consider_others_inc = int(bool(a.consider_others_inc))
     t.td_lambda = float(getattr(a, "td_lambda", 0.0) or 0.0)
     for k, v in keep.items():
@@ -652,6 +666,73 @@ def store_hidden(args, device):
     """one ssd_store_hidden launch of the block store_hidden_args built, on the current stream of `device`"""
     lib = abi.load_library()
     abi.check(lib, lib.ssd_store_hidden(C.byref(args), th.cuda.current_stream(device).cuda_stream))
+
+
+def rollout_priority_args(t_index, q_env, q_inc, agent_major, avail_bits, store, constants, alpha, eta, eps):
+    """The argument block of ssd_rollout_priority (include/ssd_hip.h) for a rollout's static tensors, and the state it owns.
+    q_env / q_inc: the heads' Q-values of the current slot; agent_major says which layout they have -- True: f32 [n, N, A] /
+    [n, N, n, 3] (FastPolicy's q_out), False: env-major [N, n, A] / [N, n, n, 3] (the generic timestep).  The caller states the layout:
+    with N == n the shapes cannot tell.  store: the transition data of the episode storage being written (actions,
+    actions_inc, reward [N, T + 1, n], terminated, filled); constants: td_constants(...); t_index: int64 device scalar.
+    Returns (args, keep): keep holds carry f32 [N, n, 2], acc f32 [N, n, 3] and q_init int32 [N] plus every tensor the block points
+    to -- the block holds raw addresses, the caller keeps `keep` alive (the runner's per-storage bundle)."""
+    reward = store["reward"]
+    if reward.dim() != 3 or reward.dtype != th.float32 or not reward.is_cuda or not reward.is_contiguous():
+        raise _unfit("rollout_priority", "reward", reward, "contiguous f32 [N, t_slots, n] on the device expected (ind_reward)")
+    N, slots, n = reward.shape
+    dev = reward.device
+    if t_index.dtype != th.long or t_index.numel() != 1 or t_index.device != dev:
+        raise _unfit("rollout_priority", "t_index", t_index, "one int64 on the device of the storage expected")
+    fields = (("actions", th.long, N * slots * n), ("actions_inc", th.long, N * slots * n * n), ("terminated", th.uint8, N * slots),
+              ("filled", th.long, N * slots))
+    for name, dtype, count in fields:
+        f = store[name]
+        if f.dtype != dtype or f.device != dev or not f.is_contiguous() or f.numel() != count or f.shape[:2] != (N, slots):
+            raise _unfit("rollout_priority", name, f, "contiguous %s of %d elements [N = %d, t_slots = %d, ...] on the device of reward expected" % (dtype, count, N, slots))
+    a = abi.SsdRolloutPriorityArgs()
+    for name, q, inner in (("q_env", q_env, None), ("q_inc", q_inc, (n, 3))):
+        if q.dtype != th.float32 or q.device != dev or q.stride(-1) != 1:
+            raise _unfit("rollout_priority", name, q, "f32 agent-major [n, N, ...] or env-major [N, n, ...] on the device of the storage expected")
+        tail = tuple(q.shape[2:])
+        if (inner is None and len(tail) != 1) or (inner is not None and (tail != inner or not q[0, 0].is_contiguous())):
+            raise _unfit("rollout_priority", name, q, "rows [A] (q_env) or contiguous [n, 3] (q_inc) per (env, agent) expected")
+        if tuple(q.shape[:2]) != ((n, N) if agent_major else (N, n)):
+            raise _unfit("rollout_priority", name, q, "%s expected" % ("agent-major [n = %d, N = %d, ...]" % (n, N) if agent_major else
+                                                                      "env-major [N = %d, n = %d, ...]" % (N, n)))
+        strides = (q.stride(0), q.stride(1)) if agent_major else (q.stride(1), q.stride(0))       # (agent, env), elements
+        if name == "q_env":
+            a.q_env_agent_stride, a.q_env_env_stride = strides
+        else:
+            a.q_inc_agent_stride, a.q_inc_env_stride = strides
+    A = q_env.shape[2]
+    keep = dict(t_index=t_index, q_env=q_env, q_inc=q_inc, carry=th.zeros(N, n, 2, device=dev), acc=th.zeros(N, n, 3, device=dev),
+                q_init=th.zeros(N, dtype=th.int32, device=dev), **{name: store[name] for name, _, _ in fields}, reward=reward)
+    a.t_index, a.n_env, a.n_agents, a.n_actions, a.t_slots, a.avail_bits = t_index.data_ptr(), N, n, A, slots, int(avail_bits) & 0xFFFFFFFF
+    for k, v in constants.items():
+        setattr(a, k, v)
+    a.alpha, a.eta, a.eps = float(alpha), float(eta), float(eps)
+    for k in ("q_env", "q_inc", "actions", "actions_inc", "reward", "terminated", "filled", "carry", "acc", "q_init"):
+        setattr(a, k, keep[k].data_ptr())
+    return a, keep
+
+
+def rollout_priority(args, device):
+    """one ssd_rollout_priority launch of the block rollout_priority_args built, on the current stream of `device`"""
+    lib = abi.load_library()
+    abi.check(lib, lib.ssd_rollout_priority(C.byref(args), th.cuda.current_stream(device).cuda_stream))
+
+
+def copy_blocks(pairs):
+    """dst <- src for every (src, dst) pair of contiguous device tensors of 4-byte elements and equal size, as ONE launch
+    (ssd_copy_blocks; at most COPY_BLOCKS_MAX pairs of under 2^31 elements)."""
+    if not pairs or len(pairs) > abi.COPY_BLOCKS_MAX:
+        raise ValueError("ops.copy_blocks: %d pairs outside 1 .. COPY_BLOCKS_MAX = %d" % (len(pairs), abi.COPY_BLOCKS_MAX))
+    for src, dst in pairs:
+        if not (src.is_cuda and dst.device == src.device and src.is_contiguous() and dst.is_contiguous() and src.dtype == dst.dtype
+                and src.element_size() == 4 and 0 < src.numel() == dst.numel() < 2 ** 31):
+            raise _unfit("copy_blocks", "src", src, "contiguous device tensors of 4-byte elements, equal dtype and size expected (dst %s %s on %s)"
+                         % (tuple(dst.shape), dst.dtype, dst.device))
+    _copy_blocks([(s.data_ptr(), d.data_ptr(), 1, s.numel(), s.numel(), s.numel()) for s, d in pairs], pairs[0][0])
 
 
 def priority_sample(seed, call, table, population, count, n_starts, beta, ids_out, t0_out, weights_out, log_out):

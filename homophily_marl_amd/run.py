@@ -106,13 +106,20 @@ def _check_prioritized(args, buffer, runner):
     prioritized_replay: proportional draws from a device-side priority table, importance weights on the gradient seeds, new
     priorities written in the train step (ssd_priority_sample / ssd_priority_update).  per_alpha: the priority exponent; per_beta:
     the importance-weight exponent at the first train step, annealed linearly to 1 over per_beta_anneal_steps train steps (0:
-    constant); per_eta: the weight of a sample's largest TD error against its mean; per_eps: added to the aggregate error."""
+    constant); per_eta: the weight of a sample's largest TD error against its mean; per_eps: added to the aggregate error.
+    per_initial_priority: what a new episode enters the table with -- "max" (default): 0, drawn at the table's current maximum until a
+    train step has seen it; "rollout": the priority of its own one-step TD errors under the acting network, formed by the rollout
+    (ssd_rollout_priority; always the plain one-step form, also under td_lambda / consider_others_inc -- a starting estimate the first
+    train step on the episode overwrites)."""
     on = args.prioritized_replay = bool(getattr(args, "prioritized_replay", False))
     alpha = args.per_alpha = float(getattr(args, "per_alpha", 0.6))
     beta = args.per_beta = float(getattr(args, "per_beta", 0.4))
     eta = args.per_eta = float(getattr(args, "per_eta", 0.9))
     eps = args.per_eps = float(getattr(args, "per_eps", 1e-3))
     steps = args.per_beta_anneal_steps = int(getattr(args, "per_beta_anneal_steps", 0) or 0)
+    initial = args.per_initial_priority = getattr(args, "per_initial_priority", "max")
+    if initial not in ("max", "rollout"):
+        raise ValueError('per_initial_priority must be "max" or "rollout", got %r' % (initial,))
     for name, v in (("per_alpha", alpha), ("per_beta", beta), ("per_eta", eta)):
         if not 0.0 <= v <= 1.0:                        # (NaN fails both comparisons)
             raise ValueError("%s must lie in [0, 1], got %r" % (name, v))
@@ -120,6 +127,15 @@ def _check_prioritized(args, buffer, runner):
         raise ValueError("per_eps must be positive, got %r" % (eps,))
     if steps < 0:
         raise ValueError("per_beta_anneal_steps must not be negative, got %r" % (steps,))
+    if initial == "rollout":
+        if not on:
+            raise ValueError('per_initial_priority "rollout" needs prioritized_replay: True (there is no priority table without it)')
+        if args.runner != "hip_graph":
+            raise ValueError('per_initial_priority "rollout" needs runner hip_graph (the runner that forms the priorities during the rollout); '
+                             "runner %r does not" % (args.runner,))
+        if th.device(buffer.device).type != "cuda":
+            raise ValueError('per_initial_priority "rollout" needs a device-resident replay buffer (buffer_cpu_only: False, use_cuda: True): '
+                             "the priorities are written into the table by a device launch; buffer on %s" % (buffer.device,))
     if not on:
         return False
     from . import abi
@@ -210,7 +226,12 @@ def train_iteration(ctx, episode):
     mark("start")
     batch = ctx.runner.run(test_mode=False)
     mark("rollout")
-    ctx.buffer.insert_episode_batch(batch)
+    initial = getattr(ctx.runner, "initial_priorities", None)
+    priorities = initial() if initial is not None else None
+    if priorities is None:
+        ctx.buffer.insert_episode_batch(batch)
+    else:                                   # per_initial_priority "rollout": the episodes enter the table with the rollout's own priorities
+        ctx.buffer.insert_episode_batch(batch, priorities=priorities)
     if ctx.buffer.can_sample(a.batch_size):
         for _ in range(a.train_steps_per_rollout):
             out = ctx.learner.sample_out() if hasattr(ctx.learner, "sample_out") else None

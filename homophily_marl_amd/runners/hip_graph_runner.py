@@ -22,6 +22,10 @@ mechanics that make a timestep capturable and replayable for every t:
   * train_stored_state (default off): the episode field "hidden" receives the recurrent state AFTER the controller consumed slot t
     (the state the heads of slot t produced Q_t from), [h_env | h_inc] per agent: one ssd_store_hidden launch ends every timestep,
     the slot-T pass included, reading the device-side slot index the heads of slot t filed under;
+  * per_initial_priority "rollout" (prioritised replay; default "max"): both heads write their Q-values into static buffers (q_out) and one
+    ssd_rollout_priority launch ends every timestep (behind ssd_store_hidden where both are on), the slot-T pass included: it forms the
+    one-step TD errors of slot t - 1 online and, at slot T, the fixed-point priority every episode enters the table with
+    (initial_priorities()).  Test episodes take the same launches on their own storage's state; nothing reads their result;
   * epsilon is a device scalar; exploration uses the package's counter generator (no multinomial, no host sync).
 Which of these a runner takes is decided once, on the host: plan_rollout (fast_policy.py) for the controller, plan_runner below for
 the storage format, the graph length and the config keys.
@@ -144,6 +148,17 @@ class HipGraphRunner(HipVecRunner):
             self.t_store = th.zeros(1, dtype=th.long, device=dev)     # the encoder's copy of t_dev, read by the store-step launch
         self.rng_copy = th.zeros(1, dtype=th.long, device=dev)          # pipelined: the env head's copy of rng_ctr for the inc head
         self.stored_state = bool(getattr(a, "train_stored_state", False))
+        # per_initial_priority "rollout": the heads' Q-values of the current slot (FastPolicy's q_out is agent-major, the generic
+        # timestep's copy env-major) and the constants of the one-step TD error, from where the loss launch takes them
+        self.initial_priority = getattr(a, "per_initial_priority", "max") == "rollout"
+        self.q_env = self.q_inc = None
+        if self.initial_priority:
+            A = a.n_actions
+            self.q_env = th.zeros((n, N, A) if rp.fast else (N, n, A), device=dev)
+            self.q_inc = th.zeros((n, N, n, 3) if rp.fast else (N, n, n, 3), device=dev)
+            self._avail_bits = sum(1 << k for k, v in enumerate(avail.reshape(-1).tolist()) if v)
+            norm = ops.window_reward_norm(getattr(a, "train_window_norm", "episode"), T + 1, int(getattr(a, "train_window", 0) or 0))
+            self._td_constants = ops.td_constants(a, norm)
         self._par = 0
         self._ready = True
 
@@ -159,13 +174,16 @@ class HipGraphRunner(HipVecRunner):
             st["filled"].fill_(1)                                       # fixed-length episodes: every slot is filled
             st["avail_actions"].copy_(self.env.avail_actions_batch.unsqueeze(1).expand(-1, self.episode_limit + 1, -1, -1))
             b = SimpleNamespace(graph=None, cur=self._dense_cur, ss=None, ss_last=None, file_env=None, file_inc=None, file_inc_last=None,
-                                begin_graph=None, finish_graph=None, hidden=None)
+                                begin_graph=None, finish_graph=None, hidden=None, priority=None, priority_state=None)
+            # the slot index the heads of slot t filed under, which the two launches below only read: the encoder's / env head's copy
+            # where one is written (direct_obs), else the master before it is advanced
+            fast = self.fast is not None
+            t_filed = self.t_store if (fast and self.direct_obs) else self.t_dev
             if self.stored_state:
-                # the slot index the heads of slot t filed under, which the launch only reads: the encoder's / env head's copy where
-                # one is written (direct_obs), else the master before it is advanced
-                fast = self.fast is not None
-                b.hidden = ops.store_hidden_args(self.t_store if (fast and self.direct_obs) else self.t_dev,
-                                                 self.fast.h_env if fast else self.h_env, self.fast.h_inc if fast else self.h_inc, st["hidden"])
+                b.hidden = ops.store_hidden_args(t_filed, self.fast.h_env if fast else self.h_env, self.fast.h_inc if fast else self.h_inc, st["hidden"])
+            if self.initial_priority:
+                b.priority, b.priority_state = ops.rollout_priority_args(t_filed, self.q_env, self.q_inc, fast, self._avail_bits, st, self._td_constants,
+                                                                         self.args.per_alpha, self.args.per_eta, self.args.per_eps)
             if self.fast is not None:
                 if self.direct_obs:
                     b.cur = self.env.native.storage_obs_buffers(st["obs"], self.obs_fmt, want_code=self._want_code)
@@ -235,7 +253,7 @@ class HipGraphRunner(HipVecRunner):
         def env_head():
             extra = dict(orient=orient, actions_i32=self.actions_i32, pos_copy=pos_t, orient_copy=orient_t) if fused else {}
             fast.head_env(self.prev_actions, self.prev_reward, self.prev_inc, pos, self.eps, self.rng_ctr, file=bundle.file_env,
-                          buf=buf, par=par, **extra)
+                          buf=buf, par=par, q_out=self.q_env, **extra)
 
         def env_step():
             if not fused:
@@ -253,9 +271,9 @@ class HipGraphRunner(HipVecRunner):
             file = bundle.file_inc if store_env_step else bundle.file_inc_last
             if inc_encode:
                 fast.act_inc_encode(actions, pos_t, orient_t, reward, clean, den, self.eps, inc_step, codes, slot_t=self.t_store, slot_add=1,
-                                    buf=buf, file=file, par=par)
+                                    buf=buf, file=file, par=par, q_out=self.q_inc)
             else:
-                fast.act_inc(actions, pos_t, orient_t, reward, clean, den, self.eps, inc_step, file=file, buf=buf, par=par)
+                fast.act_inc(actions, pos_t, orient_t, reward, clean, den, self.eps, inc_step, file=file, buf=buf, par=par, q_out=self.q_inc)
 
         def store_hidden():     # train_stored_state: the state after slot t, behind the inc head that produced it
             ops.store_hidden(bundle.hidden, self.env.device)
@@ -263,7 +281,20 @@ class HipGraphRunner(HipVecRunner):
         return ([] if pipe else [("ssd::k_encode", "encode", encode)]) + [("ssd::k_head<env>", "head_env", env_head)] + \
             ([("ssd::k_env<MODE_STEP_OBS>", "env", env_step)] if store_env_step or not pipe else []) + \
             [("ssd::k_inc_encode", "inc_encode", inc_head) if inc_encode else ("ssd::k_head<inc>", "head_inc", inc_head)] + \
-            ([("ssd::k_store_hidden", "store_hidden", store_hidden)] if self.stored_state else [])
+            ([("ssd::k_store_hidden", "store_hidden", store_hidden)] if self.stored_state else []) + \
+            ([("ssd::k_rollout_priority", "rollout_priority", self._rollout_priority)] if self.initial_priority and self.fold_store else [])
+
+    def _rollout_priority(self):
+        """per_initial_priority "rollout": row t - 1 of the one-step TD errors from this slot's Q-values, behind the launches that
+        filed slot t's actions and before the slot index is advanced"""
+        ops.rollout_priority(self._bundle.priority, self.env.device)
+
+    def initial_priorities(self):
+        """int32 [N]: the fixed-point priorities of the episodes the last TRAINING rollout produced (ssd_rollout_priority), for
+        ReplayBuffer.insert_episode_batch; None with per_initial_priority "max" (or after a test episode): the slots are zeroed"""
+        if not self._ready or not self.initial_priority or getattr(self, "_test_mode", True):
+            return None
+        return self._bundle.priority_state["q_init"]
 
     def timestep_launches(self):
         """(kernel name, key, closure) of the launches of one rollout timestep on the live buffers -- what the rollout hipGraph was
@@ -284,6 +315,8 @@ class HipGraphRunner(HipVecRunner):
         # ONE launch: the nine small fields of slot t, the controller's "previous step" inputs, the episode return and the
         # time / exploration counters (incremented after every block has read t)
         abi.check(self.fast.lib, self.fast.lib.ssd_store_step_launch(C.byref(ss), th.cuda.current_stream(self.env.device).cuda_stream))
+        if self.initial_priority:       # the store step filed slot t's actions; the counters are advanced below / by the next encoder
+            self._rollout_priority()
         if not self.direct_obs:     # without the encoder's t copy the counters are advanced by two small torch kernels
             self.rng_ctr += 1
             if store_env_step:
@@ -348,6 +381,10 @@ class HipGraphRunner(HipVecRunner):
             ops.store_hidden(self._bundle.hidden, self.env.device)
         actions_inc = self._pick(q_inc, None, None, a.n_inc_actions) * self.inc_mask              # [N, n, n]
         st["actions_inc"].index_copy_(1, td, actions_inc.reshape(actions_inc.shape[0], 1, actions_inc.shape[1], -1, 1))
+        if self.initial_priority:       # slot t is filed; t_dev is advanced below
+            self.q_env.copy_(q_env.reshape(self.q_env.shape))
+            self.q_inc.copy_(q_inc.reshape(self.q_inc.shape))
+            self._rollout_priority()
         if store_env_step:
             self.prev_actions.copy_(actions)
             self.prev_reward.copy_(reward)

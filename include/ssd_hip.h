@@ -473,6 +473,68 @@ typedef struct ssd_priority_update_args {
 } ssd_priority_update_args;
 int (ssd_priority_update)(const ssd_priority_update_args* args, void* stream);
 
+/* ssd_rollout_priority (config key per_initial_priority: "rollout"; default "max" = the zero entry above): the priority an episode
+ * enters the table with, formed by the rollout from the TD errors of what it just produced (Ape-X / R2D2), ONE launch per timestep
+ * slot behind the inc head of slot t = *t_index (the slot scalar ssd_store_hidden reads).  Online: no Q-value is kept per slot.
+ * Declared in parentheses like ssd_store_hidden; the ctypes mirror is abi.ROLLOUT_PRIORITY_SIGNATURES, the symbol, struct-size and
+ * refusal checks are tests/test_rollout_priority_host.py.
+ *
+ * The value is ssd_priority_update's formula and f32 operation sequence over the episode's T * n rows (t, agent i), T = t_slots - 1:
+ *   d      = sqrt((td_env mask)^2 + (td_inc mask)^2)
+ *   p      = eta * max d + (1 - eta) * (sum d) / max(1, sum mask) + eps
+ *   q_init = clamp(round_to_nearest(p^alpha * SSD_PRIORITY_ONE), 1, SSD_PRIORITY_MAX)                (a NaN counts as SSD_PRIORITY_MAX)
+ * where td is the ONE-STEP TD error of k_td_sim_loss<1> (its plain branch: no consider_others_inc, no td_lambda, whatever the learner
+ * runs with) evaluated with the acting network as live AND target net.  For row t of env b, agent i, from slot t of the storage:
+ *   give, rp, rn = incentives i gave / received (+) / received (-);   r = reward[b, t, i] / reward_scale
+ *   r_env = (r + (rp - rn) incentive_ratio incentive) / seq_len;      r_inc = (r - give incentive_cost incentive) / seq_len
+ *   mask  = filled[b, t] (t ? 1 - terminated[b, t - 1] : 1);          live = 1 - terminated[b, t]
+ *   td_env = Q_env,t[i, a_t] - (r_env + gamma_env live max_{k available} Q_env,t+1[i, k])
+ *   td_inc = sum_{j != i} Q_inc,t[i, j, a_inc,t[i, j]] - (r_inc + gamma_inc live sum_{j != i} max_c Q_inc,t+1[i, j, c])
+ * Q_t is what the heads computed at slot t (exploration does not enter it); live = target, so double_q selects the same value.  The
+ * value is a starting estimate: the first train step on the episode overwrites it (ssd_priority_update).
+ * The mask is the learner's: it looks one slot back only and row 0 is never masked by `terminated`.  An env that terminates AT slot 0
+ * therefore keeps row 0 (with live = 0) and does NOT get p = eps; the rows behind a termination add nothing because a runner leaves
+ * them unfilled.  p = eps belongs to an env without a filled slot.
+ *
+ * The launch at slot t, per (env, agent) -- 16 lanes per env, four envs per wave, one thread per agent:
+ *   t == 0        acc = (0, 0, 0)
+ *   1 <= t <= T   row t - 1 from carry (chosen_env, chosen_inc of slot t - 1), slot t - 1 of the storage and this slot's Q:
+ *                 acc.max = fmaxf(acc.max, d); acc.sum += d; acc.cnt += mask     (so every agent's sums run in rising t)
+ *   t < T         carry = (Q_env,t[i, actions[b, t, i]], sum_{j != i} Q_inc,t[i, j, actions_inc[b, t, i, j]]) (j rising), the actions the
+ *                 heads just filed in slot t (an index outside its range is clamped into it)
+ *   t == T        additionally the env's agents are reduced inside their wave by cross-lane reads of registers (the max is order-free; sum d
+ *                 and sum mask are added agent 0, 1 .. n - 1 in that order) and q_init[env] is written
+ *   otherwise     nothing is written
+ * No thread reads what another thread of the same launch wrote: carry / acc belong to their (env, agent); the other agents'
+ * actions_inc of slot t - 1 were filed by earlier launches.  Plain loads and vector stores, no atomics, no scratch, no LDS; 64-bit
+ * offsets into the storage.
+ * q_env f32 is read as q_env[agent * q_env_agent_stride + env * q_env_env_stride + k], q_inc likewise as [.. + j * 3 + c] (elements):
+ * FastPolicy's agent-major q_out [n, N, A] / [n, N, n, 3] is (N A, A) / (N n 3, n 3); the generic timestep's env-major [N, n, A] /
+ * [N, n, n, 3] is (A, n A) / (n 3, n n 3).  avail_bits: bit k = env action k available.  Storage fields of the episode being written:
+ * actions i64 [N, T + 1, n], actions_inc i64 [N, T + 1, n, n] (giver, receiver), reward f32 [N, T + 1, n], terminated u8 [N, T + 1],
+ * filled i64 [N, T + 1] (nullable: all ones).  Caller-owned state: carry f32 [N, n, 2], acc f32 [N, n, 3] (max d, sum d, sum mask),
+ * q_init u32 [N].
+ * Refused (SSD_ERR_INVALID, nothing launched): NULL args or a NULL member pointer other than filled; n_env < 1 or over 2^24; t_slots < 2;
+ * n_agents outside 2 .. SSD_MAX_AGENTS; n_actions outside 1 .. 16; none of the low n_actions bits of avail_bits set; alpha or eta outside
+ * [0, 1] or NaN; eps, seq_len or reward_scale <= 0 or NaN; a negative stride; q_env, q_inc, reward, carry, acc or q_init not 4-byte
+ * aligned, t_index, actions, actions_inc or filled not 8-byte aligned. */
+typedef struct ssd_rollout_priority_args {
+    const int64_t* t_index;      /* device scalar */
+    int32_t n_env, n_agents, n_actions, t_slots;
+    uint32_t avail_bits;
+    int32_t reserved;            /* 0 */
+    const float *q_env, *q_inc;
+    int64_t q_env_agent_stride, q_env_env_stride, q_inc_agent_stride, q_inc_env_stride;      /* elements */
+    const int64_t *actions, *actions_inc;
+    const float* reward;
+    const uint8_t* terminated;
+    const int64_t* filled;       /* nullable */
+    float gamma_env, gamma_inc, reward_scale, incentive_ratio, incentive_cost, incentive, seq_len, alpha, eta, eps;
+    float *carry, *acc;
+    uint32_t* q_init;            /* [n_env] */
+} ssd_rollout_priority_args;
+int (ssd_rollout_priority)(const ssd_rollout_priority_args* args, void* stream);
+
 /* ssd_clip_adam_step: the optimiser tail of HomophilyLearner.cal_loss_and_step (homophily_learner.py:223-226) --
  *   clip_grad_norm_(params_inc, clip); clip_grad_norm_(params_env, clip); optimiser_inc.step(); optimiser_env.step()
  * with the conv encoder a member of BOTH parameter groups (homophily_agent.py:127-146: its gradient is scaled by both clips, the second

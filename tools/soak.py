@@ -35,6 +35,7 @@ ap.add_argument("--train-window", type=int, default=0, help="config key train_wi
 ap.add_argument("--burn-in", type=int, default=0, help="config key train_burn_in: rows of a window without loss")
 ap.add_argument("--stored-state", action="store_true", help="config key train_stored_state: windows start from the rollout's stored recurrent state")
 ap.add_argument("--prioritized", action="store_true", help="config key prioritized_replay (per_alpha, per_beta, ... through --set)")
+ap.add_argument("--initial-priority", choices=("max", "rollout"), default="max", help="config key per_initial_priority (with --prioritized)")
 ap.add_argument("--set", action="append", default=[], help="extra config override key=value (python literal)")
 a = ap.parse_args()
 c = CONFIGS[a.config]
@@ -51,6 +52,7 @@ if a.stored_state:
     over.update(train_stored_state=True)
 if a.prioritized:
     over["prioritized_replay"] = True
+    over["per_initial_priority"] = a.initial_priority
 import ast
 for kv in a.set:
     k, v = kv.split("=", 1)
