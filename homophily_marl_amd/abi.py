@@ -2,10 +2,15 @@
 
 The native library is REQUIRED: there is no CPU fallback on the product path.  `load_library()` raises if
 `libssd_hip.so` is missing or does not export every symbol the header declares.
+
+Top to bottom: constants, struct classes, the export table, the size / layout helpers, the loader.  A new export is one line of
+HIP_SIGNATURES under its header section; a new struct is a class named after its typedef (ssd_td_loss_args -> SsdTdLossArgs).
+tests/test_abi_symbols.py holds the table to the header's declarations and every struct to the header's layout.
 """
 import ctypes as C
 import os
 
+# ---- constants ---------------------------------------------------------------------------------------------------------------
 ABI_VERSION = 10
 MAX_AGENTS = 10
 MAX_CELLS = 1024
@@ -25,8 +30,32 @@ INPUT_EXPLICIT = 0x80000000   # marks a given flag word: the empty set is INPUT_
 STREAM_UNIFORM, STREAM_MOVE, STREAM_WASTE, STREAM_SPAWN_ROT = 0, 1, 2, 3
 
 SSD_OK, SSD_ERR_INVALID, SSD_ERR_DEVICE, SSD_ERR_NOMEM, SSD_ERR_UNSUPPORTED = 0, -1, -2, -3, -4
+ERRBIT_F16_RANGE = 32
+ERR_BAD_RENDER = 64
+
+COPY_BLOCKS_MAX = 32
+FILL_BLOCKS_MAX = 16
+ADAM_MAX_JOBS = 64
+SAMPLE_IDS_MAX = 1024
+COLSUM_CHUNK = 64
+TD_LOSS_PARTIALS = 16
+POLICY_HEAD_FRAGS, POLICY_HEAD_TAIL_FLOATS = 58, 464 + 64
+POLICY_TAIL_PIECES = 3
+
+ENCODE_EDGE_MIN, ENCODE_EDGE_MAX, ENCODE_BANDS_MAX = 3, 63, 6
+ENCODE_LAYOUT_TOEPLITZ, ENCODE_LAYOUT_LUT = 0, 1
+ENCODE_LUT_TABLE_BYTES = 3 * 64 * 6 * 4
+
+BEHAVIOUR_MAX_GROUPS = 256
+BEHAVIOUR_WAVES = 16         # envs a workgroup of k_behaviour_partials walks at a time (a wave each)
+BEHAVIOUR_ROLES = ("idle", "cleaner", "harvester", "mixed")
+
+PRIORITY_ONE = 65536
+PRIORITY_MAX = 1 << 24
+PRIORITY_POP_MAX = 1 << 20
 
 
+# ---- struct classes (include/ssd_hip.h, in its order) ------------------------------------------------------------------------
 class SsdConfig(C.Structure):
     _fields_ = [
         ("env_kind", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
@@ -76,34 +105,77 @@ class SsdInfo(C.Structure):
     ]
 
 
-# name -> (restype, argtypes); the single source the symbol test and both loaders use.
-def _sigs(prefix, with_stream):
-    vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
-    st = [vp] if with_stream else []
-    P = C.POINTER
-    return {
-        prefix + "abi_version": (C.c_int, []),
-        prefix + "last_error": (C.c_char_p, []),
-        prefix + "create": (C.c_int, [P(SsdConfig), P(vp)]),
-        prefix + "destroy": (C.c_int, [vp]),
-        prefix + "reset": (C.c_int, [vp, vp, P(SsdTape), P(SsdStepOut)] + st),
-        prefix + "step": (C.c_int, [vp, vp, P(SsdTape), P(SsdStepOut)] + st),
-        prefix + "observe": (C.c_int, [vp, P(SsdObsOut)] + st),
-        prefix + "export_state": (C.c_int, [vp, P(SsdState)] + st),
-        prefix + "import_state": (C.c_int, [vp, P(SsdState)] + st),
-        prefix + "get_info": (C.c_int, [vp, P(SsdInfo)]),
-        prefix + "build_inputs": (C.c_int, [i32, i32, i32, i32, vp, vp, vp, vp, f32, vp, i32, i32] + st),
-        prefix + "incentive_transfer": (C.c_int, [i32, i32, i32, vp, vp, f32, f32, f32, f32,
-                                                  vp, vp, vp, vp, vp, vp] + st),
-    }
+class SsdRowGather(C.Structure):
+    """one field of ssd_gather_rows"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int64)]
 
 
-HIP_SIGNATURES = _sigs("ssd_", True)
-HIP_SIGNATURES["ssd_step_observe"] = (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SsdTape), C.POINTER(SsdStepOut),
-                                                C.POINTER(SsdObsOut), C.c_void_p])
-HIP_SIGNATURES["ssd_encoder"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
-                                          C.c_void_p])
+class SsdBlockCopy(C.Structure):
+    """one strided 2-D f32 block copy of ssd_copy_blocks"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("src_stride", C.c_int32),
+                ("dst_stride", C.c_int32)]
+
+
+class SsdBlockFill(C.Structure):
+    """one 32-bit pattern fill of ssd_fill_blocks"""
+    _fields_ = [("dst", C.c_void_p), ("bytes", C.c_int64), ("value", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SsdBehaviourArgs(C.Structure):
+    _fields_ = [("n_env", C.c_int32), ("t_slots", C.c_int32), ("n_agents", C.c_int32), ("n_actions", C.c_int32),
+                ("actions", C.c_void_p), ("actions_inc", C.c_void_p), ("reward", C.c_void_p), ("clean_num", C.c_void_p),
+                ("workspace", C.c_void_p), ("acc", C.c_void_p)]
+
+
+class SsdWindowField(C.Structure):
+    """one field of ssd_gather_windows"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("slot_bytes", C.c_int64), ("filled", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SsdPrioritySampleArgs(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("call", C.c_uint32), ("population", C.c_int32), ("count", C.c_int32), ("n_starts", C.c_int32),
+                ("beta", C.c_float), ("table", C.c_void_p), ("ids", C.c_void_p), ("t0", C.c_void_p), ("weights", C.c_void_p), ("log", C.c_void_p)]
+
+
+class SsdPriorityUpdateArgs(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("t_slots", C.c_int32), ("n_agents", C.c_int32), ("n_actions", C.c_int32), ("table_len", C.c_int32),
+                ("alpha", C.c_float), ("eta", C.c_float), ("eps", C.c_float),
+                ("partials", C.c_void_p), ("ids", C.c_void_p), ("weights", C.c_void_p), ("dq_env", C.c_void_p), ("dq_inc", C.c_void_p),
+                ("q_new", C.c_void_p), ("table", C.c_void_p)]
+
+
+class SsdRolloutPriorityArgs(C.Structure):
+    _fields_ = [("t_index", C.c_void_p), ("n_env", C.c_int32), ("n_agents", C.c_int32), ("n_actions", C.c_int32), ("t_slots", C.c_int32),
+                ("avail_bits", C.c_uint32), ("reserved", C.c_int32), ("q_env", C.c_void_p), ("q_inc", C.c_void_p),
+                ("q_env_agent_stride", C.c_int64), ("q_env_env_stride", C.c_int64), ("q_inc_agent_stride", C.c_int64), ("q_inc_env_stride", C.c_int64),
+                ("actions", C.c_void_p), ("actions_inc", C.c_void_p), ("reward", C.c_void_p), ("terminated", C.c_void_p), ("filled", C.c_void_p),
+                ("gamma_env", C.c_float), ("gamma_inc", C.c_float), ("reward_scale", C.c_float), ("incentive_ratio", C.c_float),
+                ("incentive_cost", C.c_float), ("incentive", C.c_float), ("seq_len", C.c_float), ("alpha", C.c_float), ("eta", C.c_float),
+                ("eps", C.c_float), ("carry", C.c_void_p), ("acc", C.c_void_p), ("q_init", C.c_void_p)]
+
+
+class SsdAdamJob(C.Structure):
+    """one parameter tensor of ssd_clip_adam_step"""
+    _fields_ = [("param", C.c_void_p), ("offset", C.c_int64), ("numel", C.c_int32), ("segment", C.c_int32),
+                ("exp_avg", C.c_void_p * 2), ("exp_avg_sq", C.c_void_p * 2), ("step", C.c_void_p * 2)]
+
+
+class SsdClipAdamArgs(C.Structure):
+    _fields_ = [("flat_grad", C.c_void_p), ("total", C.c_int64), ("jobs", C.c_void_p),
+                ("n_jobs", C.c_int32), ("partials", C.c_void_p), ("lr_inc", C.c_float), ("lr_env", C.c_float), ("beta1", C.c_float),
+                ("beta2", C.c_float), ("eps", C.c_float), ("clip", C.c_float)]
+
+
+class SsdTdLossArgs(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("t_slots", C.c_int32), ("n_agents", C.c_int32), ("n_actions", C.c_int32), ("sim_horizon", C.c_int32),
+                ("double_q", C.c_int32),
+                ("gamma_env", C.c_float), ("gamma_inc", C.c_float), ("reward_scale", C.c_float), ("incentive_ratio", C.c_float),
+                ("incentive_cost", C.c_float), ("incentive", C.c_float), ("seq_len", C.c_float), ("sim_threshold", C.c_float),
+                ("sim_loss_weight", C.c_float), ("td_lambda", C.c_float),
+                ("q_env", C.c_void_p), ("q_inc", C.c_void_p), ("tq_env", C.c_void_p), ("tq_inc", C.c_void_p),
+                ("actions", C.c_void_p), ("actions_inc", C.c_void_p), ("avail", C.c_void_p), ("reward", C.c_void_p), ("clean_num", C.c_void_p),
+                ("terminated", C.c_void_p), ("filled", C.c_void_p), ("dens", C.c_void_p),
+                ("dq_env", C.c_void_p), ("dq_inc", C.c_void_p), ("partials", C.c_void_p), ("consider_others_inc", C.c_int32)]
 
 
 class SsdStoreStep(C.Structure):
@@ -117,44 +189,13 @@ class SsdStoreStep(C.Structure):
                 ("next_t_out", C.c_void_p), ("counter_inc", C.c_void_p)]
 
 
-COPY_BLOCKS_MAX = 32
-ADAM_MAX_JOBS = 64
-
-
-class SsdRowGather(C.Structure):
-    """ssd_row_gather (include/ssd_hip.h): one field of ssd_gather_rows."""
-    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int64)]
-
-
-class SsdAdamJob(C.Structure):
-    """ssd_adam_job (include/ssd_hip.h): one parameter tensor of ssd_clip_adam_step."""
-    _fields_ = [("param", C.c_void_p), ("offset", C.c_int64), ("numel", C.c_int32), ("segment", C.c_int32),
-                ("exp_avg", C.c_void_p * 2), ("exp_avg_sq", C.c_void_p * 2), ("step", C.c_void_p * 2)]
-
-
-class SsdClipAdamArgs(C.Structure):
-    """ssd_clip_adam_args (include/ssd_hip.h)."""
-    _fields_ = [("flat_grad", C.c_void_p), ("total", C.c_int64), ("jobs", C.c_void_p),
-                ("n_jobs", C.c_int32), ("partials", C.c_void_p), ("lr_inc", C.c_float), ("lr_env", C.c_float), ("beta1", C.c_float),
-                ("beta2", C.c_float), ("eps", C.c_float), ("clip", C.c_float)]
-
-
-class SsdBlockCopy(C.Structure):
-    """ssd_block_copy (include/ssd_hip.h): one strided 2-D f32 block copy of ssd_copy_blocks."""
-    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("src_stride", C.c_int32),
-                ("dst_stride", C.c_int32)]
-
-
-class SsdBlockFill(C.Structure):
-    """ssd_block_fill (include/ssd_hip.h): one 32-bit pattern fill of ssd_fill_blocks."""
-    _fields_ = [("dst", C.c_void_p), ("bytes", C.c_int64), ("value", C.c_uint32), ("reserved", C.c_uint32)]
-
-
-FILL_BLOCKS_MAX = 16
+class SsdStoreHiddenArgs(C.Structure):
+    _fields_ = [("t_index", C.c_void_p), ("n_env", C.c_int32), ("n_agents", C.c_int32), ("t_slots", C.c_int32), ("reserved", C.c_int32),
+                ("h_env", C.c_void_p), ("h_inc", C.c_void_p), ("src_agent_stride", C.c_int64), ("src_env_stride", C.c_int64), ("dst", C.c_void_p)]
 
 
 class SsdPolicyHead(C.Structure):
-    """include/ssd_hip.h: ssd_policy_head (fused controller step, one launch per head)."""
+    """fused controller step, one launch per head"""
     _fields_ = [("n_env", C.c_int32), ("n_agents", C.c_int32), ("n_actions", C.c_int32), ("input_shape", C.c_int32),
                 ("pos_scale", C.c_float), ("seed", C.c_uint32),
                 ("inputs", C.c_void_p), ("h", C.c_void_p), ("weights", C.c_void_p), ("avail", C.c_void_p), ("epsilon", C.c_void_p),
@@ -177,7 +218,7 @@ class SsdPolicyHead(C.Structure):
 
 
 class SsdPolicyHeadParams(C.Structure):
-    """include/ssd_hip.h: ssd_policy_head_params (the reference-shaped f32 parameters of one head)."""
+    """the reference-shaped f32 parameters of one head"""
     _fields_ = [("fc1_w", C.c_void_p), ("fc1_b", C.c_void_p), ("w_i", C.c_void_p * 3), ("w_h", C.c_void_p * 3), ("b_i", C.c_void_p * 3),
                 ("b_h", C.c_void_p * 3), ("fc2_w", C.c_void_p), ("fc2_b", C.c_void_p), ("fc2_v_w", C.c_void_p), ("fc2_v_b", C.c_void_p),
                 ("n_agents", C.c_int32), ("fc1_in", C.c_int32), ("fc2_in", C.c_int32), ("fc2_out", C.c_int32),
@@ -185,7 +226,6 @@ class SsdPolicyHeadParams(C.Structure):
 
 
 class SsdPolicyEncodeArgs(C.Structure):
-    """include/ssd_hip.h: ssd_policy_encode_args."""
     _fields_ = [("codes", C.c_void_p), ("code_bytes", C.c_int64), ("env_stride", C.c_int64), ("slot_stride", C.c_int64),
                 ("agent_stride", C.c_int64), ("slot_t", C.c_void_p),
                 ("rows", C.c_int32), ("view_edge", C.c_int32), ("n_agents", C.c_int32), ("agent_major", C.c_int32), ("precision", C.c_int32),
@@ -194,26 +234,109 @@ class SsdPolicyEncodeArgs(C.Structure):
                 ("alphabet", C.c_int32), ("act", C.c_void_p), ("slot_add", C.c_int32), ("layout", C.c_int32)]
 
 
-class SsdTdLossArgs(C.Structure):
-    """include/ssd_hip.h: ssd_td_loss_args."""
-    _fields_ = [("batch", C.c_int32), ("t_slots", C.c_int32), ("n_agents", C.c_int32), ("n_actions", C.c_int32), ("sim_horizon", C.c_int32),
-                ("double_q", C.c_int32),
-                ("gamma_env", C.c_float), ("gamma_inc", C.c_float), ("reward_scale", C.c_float), ("incentive_ratio", C.c_float),
-                ("incentive_cost", C.c_float), ("incentive", C.c_float), ("seq_len", C.c_float), ("sim_threshold", C.c_float),
-                ("sim_loss_weight", C.c_float), ("td_lambda", C.c_float),
-                ("q_env", C.c_void_p), ("q_inc", C.c_void_p), ("tq_env", C.c_void_p), ("tq_inc", C.c_void_p),
-                ("actions", C.c_void_p), ("actions_inc", C.c_void_p), ("avail", C.c_void_p), ("reward", C.c_void_p), ("clean_num", C.c_void_p),
-                ("terminated", C.c_void_p), ("filled", C.c_void_p), ("dens", C.c_void_p),
-                ("dq_env", C.c_void_p), ("dq_inc", C.c_void_p), ("partials", C.c_void_p), ("consider_others_inc", C.c_int32)]
+# ---- the export table: name -> (restype, argtypes) ---------------------------------------------------------------------------
+# the exports that the CPU checker (prefix ssd_cpu_, no stream argument) shares with the library
+def _sigs(prefix, with_stream):
+    vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
+    st = [vp] if with_stream else []
+    P = C.POINTER
+    return {
+        prefix + "abi_version": (C.c_int, []),
+        prefix + "last_error": (C.c_char_p, []),
+        prefix + "create": (C.c_int, [P(SsdConfig), P(vp)]),
+        prefix + "destroy": (C.c_int, [vp]),
+        prefix + "reset": (C.c_int, [vp, vp, P(SsdTape), P(SsdStepOut)] + st),
+        prefix + "step": (C.c_int, [vp, vp, P(SsdTape), P(SsdStepOut)] + st),
+        prefix + "observe": (C.c_int, [vp, P(SsdObsOut)] + st),
+        prefix + "export_state": (C.c_int, [vp, P(SsdState)] + st),
+        prefix + "import_state": (C.c_int, [vp, P(SsdState)] + st),
+        prefix + "get_info": (C.c_int, [vp, P(SsdInfo)]),
+        prefix + "build_inputs": (C.c_int, [i32, i32, i32, i32, vp, vp, vp, vp, f32, vp, i32, i32] + st),
+        prefix + "incentive_transfer": (C.c_int, [i32, i32, i32, vp, vp, f32, f32, f32, f32,
+                                                  vp, vp, vp, vp, vp, vp] + st),
+    }
 
 
-TD_LOSS_PARTIALS = 16
-POLICY_HEAD_FRAGS, POLICY_HEAD_TAIL_FLOATS = 58, 464 + 64
+CPU_SIGNATURES = _sigs("ssd_cpu_", False)
+
+vp, i32, i64, u32, u64, f32, P = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.POINTER
+# every export of libssd_hip.so, grouped like include/ssd_hip.h; every one returns int
+HIP_SIGNATURES = {name: (C.c_int, args) for name, args in {
+    # environment: fused step, error word, render mode (device-only: no CPU counterpart)
+    "ssd_step_observe": [vp, vp, P(SsdTape), P(SsdStepOut), P(SsdObsOut), vp],
+    "ssd_poll_error": [vp, P(i32)],
+    "ssd_set_render": [vp, i32],
+    "ssd_render": [vp, vp, i32, vp, vp, i64, vp],
+    # learner pieces outside the GEMMs, replay gathers, fills and rollout statistics
+    "ssd_unroll_other": [vp] * 6 + [f32] + [i32] * 4 + [vp] * 3,
+    "ssd_column_sums": [vp, vp, i32, i32, i32, vp, vp],
+    "ssd_dueling_q_fwd": [vp] * 3 + [i32] * 5 + [vp],
+    "ssd_dueling_q_bwd": [vp] * 3 + [i32] * 5 + [vp],
+    "ssd_gather_rows": [vp, i32, vp, i32, vp],
+    "ssd_sample_ids": [u64, u32, i32, i32, vp, vp],
+    "ssd_copy_blocks": [vp, i32, vp],
+    "ssd_fill_blocks": [vp, i32, vp],
+    "ssd_runner_stats": [vp, vp, vp, i32, i32, vp, vp],
+    "ssd_behaviour_stats": [P(SsdBehaviourArgs), vp],
+    # sampled time windows
+    "ssd_sample_windows": [u64, u32, i32, i32, i32, vp, vp, vp],
+    "ssd_gather_windows": [vp, i32, vp, vp, i32, i32, i32, i32, vp],
+    # prioritised replay
+    "ssd_priority_sample": [P(SsdPrioritySampleArgs), vp],
+    "ssd_priority_update": [P(SsdPriorityUpdateArgs), vp],
+    "ssd_rollout_priority": [P(SsdRolloutPriorityArgs), vp],
+    # optimiser tail and fused loss
+    "ssd_clip_adam_step": [P(SsdClipAdamArgs), vp],
+    "ssd_td_sim_loss": [P(SsdTdLossArgs), i32, vp],
+    # rollout-time controller pieces that are not GEMMs
+    "ssd_encoder": [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, i64, vp, vp],
+    "ssd_conv_leaky": [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, i64, vp, vp],
+    "ssd_store_step_launch": [P(SsdStoreStep), vp],
+    "ssd_store_hidden": [P(SsdStoreHiddenArgs), vp],
+    "ssd_gru_gates": [vp, vp, vp, i32, i32, vp],
+    "ssd_gru_gates_fwd": [vp] * 5 + [i32, i32, vp],
+    "ssd_gru_gates_bwd": [vp] * 7 + [i32, i32, vp],
+    "ssd_dueling_pick": [vp, i32, i32, vp, vp, vp, u32, i32, i32, i32, vp, vp, u32, vp],
+    # the learner's recurrence over all T timesteps
+    "ssd_gru_seq_fwd": [vp] * 6 + [i32] * 3 + [vp],
+    "ssd_gru_seq_bwd": [vp] * 9 + [i32] * 3 + [vp],
+    "ssd_gru_seq_fwd_parts": [vp, i32, vp, vp, i32] + [vp] * 3 + [i32] * 3 + [vp],
+    "ssd_gru_seq_bwd_parts": [vp] * 5 + [i32, vp, i32] + [vp] * 3 + [i32] * 4 + [vp],
+    "ssd_gru_seq_fwd_h0": [vp, i32, vp, vp, i32, vp, i64, i64] + [vp] * 3 + [i32] * 3 + [vp],
+    "ssd_gru_seq_bwd_h0": [vp] * 5 + [i32, vp, i32] + [vp] * 3 + [i32] * 4 + [vp],
+    # the learner's per-agent affine layers and dueling heads
+    "ssd_bias_bmm_fwd": [vp] * 4 + [i32] * 4 + [vp],
+    "ssd_bias_bmm_leaky_fwd": [vp] * 4 + [i32] * 4 + [vp],
+    "ssd_bias_bmm_leaky_bwd": [vp] * 8 + [i32] * 4 + [vp],
+    "ssd_bias_bmm_bwd": [vp] * 7 + [i32] * 4 + [vp],
+    "ssd_bias_bmm2_fwd": [vp] * 5 + [i32] * 7 + [vp],
+    "ssd_bias_bmm2_bwd_w": [vp] * 5 + [i32] * 7 + [vp],
+    "ssd_bias_bmm_bwd_x": [vp] * 3 + [i32] * 4 + [i64, vp],
+    "ssd_dueling_head_fwd": [vp] * 2 + [i32] * 5 + [vp],
+    "ssd_dueling_head_bwd": [vp] * 3 + [i32] * 5 + [vp],
+    "ssd_bmm_reserve_scratch": [vp],
+    "ssd_set_learner_precision": [i32],
+    "ssd_learner_precision": [],
+    "ssd_conv_wgrad_partial_rows": [i32],
+    "ssd_conv_wgrad_codes": [vp, vp, vp, i32, i32, vp],
+    # fused rollout-time controller step
+    "ssd_build_inputs_width": [i32, i32, u32],
+    "ssd_build_inputs_flags": [i32, i32, i32, i32, u32, vp, vp, vp, vp, f32, vp, i32, i32, vp],
+    "ssd_policy_head_env": [P(SsdPolicyHead), vp],
+    "ssd_policy_head_inc": [P(SsdPolicyHead), vp],
+    "ssd_policy_head_plan": [i32] * 3 + [P(i32)] * 3,
+    "ssd_policy_pack_head": [P(SsdPolicyHeadParams), i32, vp, vp],
+    "ssd_policy_encode": [P(SsdPolicyEncodeArgs), vp],
+    "ssd_policy_head_inc_encode": [P(SsdPolicyHead), P(SsdPolicyEncodeArgs), vp],
+    "ssd_policy_pack_encoder_lut": [vp, vp, vp, i32, i32, vp, vp, vp],
+    "ssd_policy_pack_encoder": [vp, vp, vp, i32, i32, vp, vp, vp],
+    "ssd_numeric_status": [P(i32)],
+}.items()}
+# library, lifecycle, step / observe, state, inputs and incentives: shared with the CPU checker
+HIP_SIGNATURES.update(_sigs("ssd_", True))
 
 
-POLICY_TAIL_PIECES = 3
-
-
+# ---- size / layout helpers ---------------------------------------------------------------------------------------------------
 def onehot_rows(n_agents, n_actions, flags):
     """include/ssd_hip.h SSD_ONEHOT_ROWS: rows per owner of the INPUT_GATHER_ONEHOT table (id row | last action | inc action | others)."""
     return 1 + 2 * n_actions + (n_agents * n_actions if flags & INPUT_OTHERS_LAST_ACTION else 0)
@@ -252,9 +375,6 @@ def policy_head_plan(n_env, n_agents, fused_with_encoder=False):
     return a.value, b.value, c.value
 
 
-ENCODE_EDGE_MIN, ENCODE_EDGE_MAX, ENCODE_BANDS_MAX = 3, 63, 6
-
-
 def encode_edge_supported(V):
     """Whether the class-LUT encoder (ssd_policy_encode, ssd_policy_pack_encoder_lut, ssd_conv_wgrad_codes) takes window edge V:
     every odd edge 3 .. 63 (view_size 1 .. 31)."""
@@ -271,10 +391,6 @@ def encode_band_rows(V):
 def encode_bands(V):
     """SSD_ENCODE_BANDS: bands the encoder cuts the output rows into (each writes a partial Linear sum when > 1)"""
     return (V - 2 + encode_band_rows(V) - 1) // encode_band_rows(V)
-
-
-ENCODE_LAYOUT_TOEPLITZ, ENCODE_LAYOUT_LUT = 0, 1
-ENCODE_LUT_TABLE_BYTES = 3 * 64 * 6 * 4
 
 
 def encode_lut_ksteps(V):
@@ -294,149 +410,6 @@ def encode_frag_bytes(V, precision, layout=ENCODE_LAYOUT_TOEPLITZ):
 
 def code_agent_stride(V):
     return (V * V + 15) & ~15
-
-
-HIP_SIGNATURES["ssd_policy_head_env"] = (C.c_int, [C.POINTER(SsdPolicyHead), C.c_void_p])
-HIP_SIGNATURES["ssd_policy_head_inc"] = (C.c_int, [C.POINTER(SsdPolicyHead), C.c_void_p])
-HIP_SIGNATURES["ssd_gru_seq_fwd"] = (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p])
-HIP_SIGNATURES["ssd_gru_seq_bwd"] = (C.c_int, [C.c_void_p] * 9 + [C.c_int32] * 3 + [C.c_void_p])
-HIP_SIGNATURES["ssd_build_inputs_width"] = (C.c_int, [C.c_int32, C.c_int32, C.c_uint32])
-HIP_SIGNATURES["ssd_build_inputs_flags"] = (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,
-                                                     C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p])
-HIP_SIGNATURES["ssd_clip_adam_step"] = (C.c_int, [C.POINTER(SsdClipAdamArgs), C.c_void_p])
-HIP_SIGNATURES["ssd_dueling_q_fwd"] = (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_void_p])
-HIP_SIGNATURES["ssd_dueling_q_bwd"] = (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_void_p])
-HIP_SIGNATURES["ssd_gather_rows"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p])
-HIP_SIGNATURES["ssd_sample_ids"] = (C.c_int, [C.c_uint64, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p])
-SAMPLE_IDS_MAX = 1024
-HIP_SIGNATURES["ssd_copy_blocks"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p])
-HIP_SIGNATURES["ssd_fill_blocks"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p])
-HIP_SIGNATURES["ssd_runner_stats"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p])
-HIP_SIGNATURES["ssd_gru_seq_fwd_parts"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p])
-HIP_SIGNATURES["ssd_gru_seq_bwd_parts"] = (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p])
-HIP_SIGNATURES["ssd_bias_bmm_fwd"] = (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p])
-HIP_SIGNATURES["ssd_bias_bmm_bwd"] = (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 4 + [C.c_void_p])
-HIP_SIGNATURES["ssd_bias_bmm_leaky_fwd"] = (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p])
-HIP_SIGNATURES["ssd_bias_bmm_leaky_bwd"] = (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 4 + [C.c_void_p])
-HIP_SIGNATURES["ssd_bias_bmm2_fwd"] = (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 7 + [C.c_void_p])
-HIP_SIGNATURES["ssd_bias_bmm2_bwd_w"] = (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 7 + [C.c_void_p])
-HIP_SIGNATURES["ssd_bias_bmm_bwd_x"] = (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_int64, C.c_void_p])
-HIP_SIGNATURES["ssd_dueling_head_fwd"] = (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 5 + [C.c_void_p])
-HIP_SIGNATURES["ssd_dueling_head_bwd"] = (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_void_p])
-HIP_SIGNATURES["ssd_unroll_other"] = (C.c_int, [C.c_void_p] * 6 + [C.c_float] + [C.c_int32] * 4 + [C.c_void_p] * 3)
-HIP_SIGNATURES["ssd_bmm_reserve_scratch"] = (C.c_int, [C.c_void_p])
-HIP_SIGNATURES["ssd_set_learner_precision"] = (C.c_int, [C.c_int32])
-HIP_SIGNATURES["ssd_learner_precision"] = (C.c_int, [])
-HIP_SIGNATURES["ssd_conv_wgrad_partial_rows"] = (C.c_int, [C.c_int32])
-HIP_SIGNATURES["ssd_conv_wgrad_codes"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p])
-HIP_SIGNATURES["ssd_policy_head_plan"] = (C.c_int, [C.c_int32] * 3 + [C.POINTER(C.c_int32)] * 3)
-HIP_SIGNATURES["ssd_policy_encode"] = (C.c_int, [C.POINTER(SsdPolicyEncodeArgs), C.c_void_p])
-HIP_SIGNATURES["ssd_policy_head_inc_encode"] = (C.c_int, [C.POINTER(SsdPolicyHead), C.POINTER(SsdPolicyEncodeArgs), C.c_void_p])
-HIP_SIGNATURES["ssd_policy_pack_encoder_lut"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p])
-HIP_SIGNATURES["ssd_policy_pack_encoder"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p])
-HIP_SIGNATURES["ssd_numeric_status"] = (C.c_int, [C.POINTER(C.c_int32)])
-ERRBIT_F16_RANGE = 32
-HIP_SIGNATURES["ssd_column_sums"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p])
-COLSUM_CHUNK = 64
-HIP_SIGNATURES["ssd_td_sim_loss"] = (C.c_int, [C.POINTER(SsdTdLossArgs), C.c_int32, C.c_void_p])
-HIP_SIGNATURES["ssd_policy_pack_head"] = (C.c_int, [C.POINTER(SsdPolicyHeadParams), C.c_int32, C.c_void_p, C.c_void_p])
-HIP_SIGNATURES["ssd_conv_leaky"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                             C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p])
-HIP_SIGNATURES["ssd_store_step_launch"] = (C.c_int, [C.POINTER(SsdStoreStep), C.c_void_p])
-HIP_SIGNATURES["ssd_gru_gates"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p])
-HIP_SIGNATURES["ssd_gru_gates_fwd"] = (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_void_p])
-HIP_SIGNATURES["ssd_gru_gates_bwd"] = (C.c_int, [C.c_void_p] * 7 + [C.c_int32, C.c_int32, C.c_void_p])
-HIP_SIGNATURES["ssd_dueling_pick"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32,
-                                               C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p])
-HIP_SIGNATURES["ssd_poll_error"] = (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)])
-# render mode (device-only: no CPU counterpart)
-HIP_SIGNATURES["ssd_set_render"] = (C.c_int, [C.c_void_p, C.c_int32])
-HIP_SIGNATURES["ssd_render"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
-ERR_BAD_RENDER = 64
-
-
-class SsdBehaviourArgs(C.Structure):
-    """include/ssd_hip.h: ssd_behaviour_args."""
-    _fields_ = [("n_env", C.c_int32), ("t_slots", C.c_int32), ("n_agents", C.c_int32), ("n_actions", C.c_int32),
-                ("actions", C.c_void_p), ("actions_inc", C.c_void_p), ("reward", C.c_void_p), ("clean_num", C.c_void_p),
-                ("workspace", C.c_void_p), ("acc", C.c_void_p)]
-
-
-BEHAVIOUR_MAX_GROUPS = 256
-BEHAVIOUR_WAVES = 16         # envs a workgroup of k_behaviour_partials walks at a time (a wave each)
-BEHAVIOUR_ROLES = ("idle", "cleaner", "harvester", "mixed")
-# ssd_behaviour_stats has a table of its own: HIP_SIGNATURES is pinned to the plainly declared names of the header and to the refusal
-# tables of tests/test_learner_abi_refusals.py; this export's checks of the same kind are tests/test_behaviour_host.py
-BEHAVIOUR_SIGNATURES = {"ssd_behaviour_stats": (C.c_int, [C.POINTER(SsdBehaviourArgs), C.c_void_p])}
-
-
-class SsdWindowField(C.Structure):
-    """ssd_window_field (include/ssd_hip.h): one field of ssd_gather_windows."""
-    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("slot_bytes", C.c_int64), ("filled", C.c_int32), ("reserved", C.c_int32)]
-
-
-# the two exports of training on sampled time windows, in a table of their own like ssd_behaviour_stats (their checks:
-# tests/test_train_window_host.py)
-WINDOW_SIGNATURES = {
-    "ssd_sample_windows": (C.c_int, [C.c_uint64, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "ssd_gather_windows": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-}
-
-
-class SsdPrioritySampleArgs(C.Structure):
-    """include/ssd_hip.h: ssd_priority_sample_args."""
-    _fields_ = [("seed", C.c_uint64), ("call", C.c_uint32), ("population", C.c_int32), ("count", C.c_int32), ("n_starts", C.c_int32),
-                ("beta", C.c_float), ("table", C.c_void_p), ("ids", C.c_void_p), ("t0", C.c_void_p), ("weights", C.c_void_p), ("log", C.c_void_p)]
-
-
-class SsdPriorityUpdateArgs(C.Structure):
-    """include/ssd_hip.h: ssd_priority_update_args."""
-    _fields_ = [("batch", C.c_int32), ("t_slots", C.c_int32), ("n_agents", C.c_int32), ("n_actions", C.c_int32), ("table_len", C.c_int32),
-                ("alpha", C.c_float), ("eta", C.c_float), ("eps", C.c_float),
-                ("partials", C.c_void_p), ("ids", C.c_void_p), ("weights", C.c_void_p), ("dq_env", C.c_void_p), ("dq_inc", C.c_void_p),
-                ("q_new", C.c_void_p), ("table", C.c_void_p)]
-
-
-PRIORITY_ONE = 65536
-PRIORITY_MAX = 1 << 24
-PRIORITY_POP_MAX = 1 << 20
-# the two exports of prioritised replay, in a table of their own like ssd_behaviour_stats (their checks: tests/test_priority_host.py)
-PRIORITY_SIGNATURES = {
-    "ssd_priority_sample": (C.c_int, [C.POINTER(SsdPrioritySampleArgs), C.c_void_p]),
-    "ssd_priority_update": (C.c_int, [C.POINTER(SsdPriorityUpdateArgs), C.c_void_p]),
-}
-
-
-class SsdStoreHiddenArgs(C.Structure):
-    """include/ssd_hip.h: ssd_store_hidden_args."""
-    _fields_ = [("t_index", C.c_void_p), ("n_env", C.c_int32), ("n_agents", C.c_int32), ("t_slots", C.c_int32), ("reserved", C.c_int32),
-                ("h_env", C.c_void_p), ("h_inc", C.c_void_p), ("src_agent_stride", C.c_int64), ("src_env_stride", C.c_int64), ("dst", C.c_void_p)]
-
-
-# the three exports of training windows from the rollout's stored recurrent state (train_stored_state), in a table of their own like
-# ssd_behaviour_stats (their checks: tests/test_stored_state_host.py)
-STORED_STATE_SIGNATURES = {
-    "ssd_store_hidden": (C.c_int, [C.POINTER(SsdStoreHiddenArgs), C.c_void_p]),
-    "ssd_gru_seq_fwd_h0": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 3
-                           + [C.c_int32] * 3 + [C.c_void_p]),
-    "ssd_gru_seq_bwd_h0": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p]),
-}
-
-
-class SsdRolloutPriorityArgs(C.Structure):
-    """include/ssd_hip.h: ssd_rollout_priority_args."""
-    _fields_ = [("t_index", C.c_void_p), ("n_env", C.c_int32), ("n_agents", C.c_int32), ("n_actions", C.c_int32), ("t_slots", C.c_int32),
-                ("avail_bits", C.c_uint32), ("reserved", C.c_int32), ("q_env", C.c_void_p), ("q_inc", C.c_void_p),
-                ("q_env_agent_stride", C.c_int64), ("q_env_env_stride", C.c_int64), ("q_inc_agent_stride", C.c_int64), ("q_inc_env_stride", C.c_int64),
-                ("actions", C.c_void_p), ("actions_inc", C.c_void_p), ("reward", C.c_void_p), ("terminated", C.c_void_p), ("filled", C.c_void_p),
-                ("gamma_env", C.c_float), ("gamma_inc", C.c_float), ("reward_scale", C.c_float), ("incentive_ratio", C.c_float),
-                ("incentive_cost", C.c_float), ("incentive", C.c_float), ("seq_len", C.c_float), ("alpha", C.c_float), ("eta", C.c_float),
-                ("eps", C.c_float), ("carry", C.c_void_p), ("acc", C.c_void_p), ("q_init", C.c_void_p)]
-
-
-# the export of prioritised replay's initial priorities (per_initial_priority: "rollout"), in a table of its own like
-# ssd_behaviour_stats (its checks: tests/test_rollout_priority_host.py)
-ROLLOUT_PRIORITY_SIGNATURES = {"ssd_rollout_priority": (C.c_int, [C.POINTER(SsdRolloutPriorityArgs), C.c_void_p])}
 
 
 def behaviour_len(n, A):
@@ -491,8 +464,7 @@ def behaviour_summary(vec, n, A):
     return out
 
 
-CPU_SIGNATURES = _sigs("ssd_cpu_", False)
-
+# ---- the loader --------------------------------------------------------------------------------------------------------------
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # SSD_HIP_LIB_PATH: diagnostics only (tools/stamps.py loads a -DSSD_STAMPS build of the same sources)
 HIP_LIB_PATH = os.environ.get("SSD_HIP_LIB_PATH", os.path.join(_PKG_DIR, "libssd_hip.so"))
@@ -529,11 +501,6 @@ def load_library():
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback." % HIP_LIB_PATH)
         lib = C.CDLL(HIP_LIB_PATH)
         bind(lib, HIP_SIGNATURES)
-        bind(lib, BEHAVIOUR_SIGNATURES)
-        bind(lib, WINDOW_SIGNATURES)
-        bind(lib, PRIORITY_SIGNATURES)
-        bind(lib, STORED_STATE_SIGNATURES)
-        bind(lib, ROLLOUT_PRIORITY_SIGNATURES)
         ver = lib.ssd_abi_version()
         if ver != ABI_VERSION:
             raise ImportError("libssd_hip.so ABI version %d != %d" % (ver, ABI_VERSION))

@@ -709,89 +709,88 @@ int ssd_dueling_pick(const float* av, int32_t rows, int32_t n_actions, const uin
 }
 
 static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// The argument checks of the six ssd_gru_seq_* exports, written once per direction.  `who`: the calling export, first in every
+// message.  min_parts: the smallest n_parts the export admits -- 1 for the _parts forms, 0 (one time-major tensor behind a
+// one-element table) for the _h0 forms and the time-major pair, which hands its single pointers over as such tables.  h0_parts
+// is looked at only with with_h0.  SSD_OK or SSD_ERR_INVALID.
+static int gru_seq_fwd_check(const char* who, int min_parts, bool with_h0, const float* const* gi_parts, int32_t n_parts, const float* const* wh_parts,
+                             const float* const* bh_parts, int32_t n_wparts, const float* const* h0_parts, int64_t h0_set_stride, int64_t h0_row_stride,
+                             const float* hs, const float* rzn, const float* ghn, int32_t T, int32_t G, int32_t B) {
+    const int np = n_parts < 1 ? 1 : n_parts;
+    if (!gi_parts || n_parts < min_parts || n_parts > 4 || !wh_parts || !bh_parts || n_wparts < 1 || n_wparts > 4 || (with_h0 && !h0_parts) || !hs || T < 1 ||
+        G < 1 || G % np || G % n_wparts || B < 1 || (!rzn) != (!ghn))
+        return fail(SSD_ERR_INVALID, "%s: bad argument", who);
+    for (int k = 0; k < n_wparts; ++k)
+        if (!wh_parts[k] || !bh_parts[k] || !al16(wh_parts[k]) || !al16(bh_parts[k])) return fail(SSD_ERR_INVALID, "%s: weight parts must be non-null and 16-byte aligned", who);
+    if (B % 16) return fail(SSD_ERR_INVALID, "%s: B must be a multiple of 16 (pad the sequences)", who);
+    for (int k = 0; k < np; ++k) {
+        if (!gi_parts[k] || !al16(gi_parts[k])) return fail(SSD_ERR_INVALID, "%s: gi parts must be non-null and 16-byte aligned", who);
+        if (with_h0 && (!h0_parts[k] || !al16(h0_parts[k]))) return fail(SSD_ERR_INVALID, "%s: h0 parts must be non-null and 16-byte aligned", who);
+    }
+    if (with_h0 && (h0_set_stride < 0 || h0_row_stride < 0 || (h0_set_stride & 3) || (h0_row_stride & 3)))
+        return fail(SSD_ERR_INVALID, "%s: h0 strides must be non-negative multiples of 4 elements", who);
+    if (!al16(hs) || !al16(rzn) || !al16(ghn)) return fail(SSD_ERR_INVALID, "%s: tensors must be 16-byte aligned", who);
+    return SSD_OK;
+}
+static int gru_seq_bwd_check(const char* who, int min_parts, const float* const* dhs_parts, const float* hs, const float* rzn, const float* ghn,
+                             const float* const* wh_parts, int32_t n_wparts, float* const* d_gi_parts, int32_t n_parts, const float* dgh, const float* d_wh,
+                             const float* d_bh_part, int32_t T, int32_t G, int32_t G_grad, int32_t B) {
+    const int np = n_parts < 1 ? 1 : n_parts;
+    if (!dhs_parts || !hs || !rzn || !ghn || !wh_parts || n_wparts < 1 || n_wparts > 4 || !d_gi_parts || n_parts < min_parts || n_parts > 4 || !dgh || !d_wh ||
+        !d_bh_part || T < 1 || G < 1 || G % np || G % n_wparts || B < 1 || G_grad < 1 || G_grad > G || G_grad % (G / np))
+        return fail(SSD_ERR_INVALID, "%s: bad argument", who);
+    for (int k = 0; k * (G / np) < G_grad; ++k)
+        if (!dhs_parts[k] || !al16(dhs_parts[k]) || !d_gi_parts[k] || !al16(d_gi_parts[k]))
+            return fail(SSD_ERR_INVALID, "%s: dhs and d_gi parts of the sets with a gradient must be non-null and 16-byte aligned", who);
+    for (int k = 0; k < n_wparts; ++k)
+        if (!wh_parts[k] || !al16(wh_parts[k])) return fail(SSD_ERR_INVALID, "%s: weight parts must be non-null and 16-byte aligned", who);
+    if (B % 16) return fail(SSD_ERR_INVALID, "%s: B must be a multiple of 16 (pad the sequences)", who);
+    if (!al16(hs) || !al16(rzn) || !al16(ghn) || !al16(dgh)) return fail(SSD_ERR_INVALID, "%s: tensors must be 16-byte aligned", who);
+    return SSD_OK;
+}
+
 int ssd_gru_seq_fwd(const float* gi, const float* wh, const float* bh, float* hs, float* rzn, float* ghn, int32_t T, int32_t G, int32_t B,
                     void* stream) {
-    if (!gi || !wh || !bh || !hs || T < 1 || G < 1 || B < 1 || (!rzn) != (!ghn)) return fail(SSD_ERR_INVALID, "bad argument");
-    if (B % 16) return fail(SSD_ERR_INVALID, "B must be a multiple of 16 (pad the sequences)");
-    if (!al16(gi) || !al16(wh) || !al16(bh) || !al16(hs) || !al16(rzn) || !al16(ghn)) return fail(SSD_ERR_INVALID, "tensors must be 16-byte aligned");
+    if (int rc = gru_seq_fwd_check("ssd_gru_seq_fwd", 0, false, &gi, 0, &wh, &bh, 1, nullptr, 0, 0, hs, rzn, ghn, T, G, B)) return rc;
     launch_gru_seq_fwd(&gi, 0, &wh, &bh, 1, hs, rzn, ghn, T, G, B, (hipStream_t)stream);
     return launched();
 }
 int ssd_gru_seq_fwd_parts(const float* const* gi_parts, int32_t n_parts, const float* const* wh_parts, const float* const* bh_parts, int32_t n_wparts,
                           float* hs, float* rzn, float* ghn, int32_t T, int32_t G, int32_t B, void* stream) {
-    if (!gi_parts || n_parts < 1 || n_parts > 4 || !wh_parts || !bh_parts || n_wparts < 1 || n_wparts > 4 || !hs || T < 1 || G < 1 || G % n_parts ||
-        G % n_wparts || B < 1 || (!rzn) != (!ghn))
-        return fail(SSD_ERR_INVALID, "bad argument");
-    for (int k = 0; k < n_wparts; ++k)
-        if (!wh_parts[k] || !bh_parts[k] || !al16(wh_parts[k]) || !al16(bh_parts[k])) return fail(SSD_ERR_INVALID, "weight parts must be non-null and 16-byte aligned");
-    if (B % 16) return fail(SSD_ERR_INVALID, "B must be a multiple of 16 (pad the sequences)");
-    for (int k = 0; k < n_parts; ++k)
-        if (!gi_parts[k] || !al16(gi_parts[k])) return fail(SSD_ERR_INVALID, "gi parts must be non-null and 16-byte aligned");
-    if (!al16(hs) || !al16(rzn) || !al16(ghn)) return fail(SSD_ERR_INVALID, "tensors must be 16-byte aligned");
+    if (int rc = gru_seq_fwd_check("ssd_gru_seq_fwd_parts", 1, false, gi_parts, n_parts, wh_parts, bh_parts, n_wparts, nullptr, 0, 0, hs, rzn, ghn, T, G, B)) return rc;
     launch_gru_seq_fwd(gi_parts, n_parts, wh_parts, bh_parts, n_wparts, hs, rzn, ghn, T, G, B, (hipStream_t)stream);
     return launched();
 }
+int ssd_gru_seq_fwd_h0(const float* const* gi_parts, int32_t n_parts, const float* const* wh_parts, const float* const* bh_parts, int32_t n_wparts,
+                       const float* const* h0_parts, int64_t h0_set_stride, int64_t h0_row_stride, float* hs, float* rzn, float* ghn, int32_t T, int32_t G,
+                       int32_t B, void* stream) {
+    if (int rc = gru_seq_fwd_check("ssd_gru_seq_fwd_h0", 0, true, gi_parts, n_parts, wh_parts, bh_parts, n_wparts, h0_parts, h0_set_stride, h0_row_stride, hs, rzn,
+                                   ghn, T, G, B))
+        return rc;
+    launch_gru_seq_fwd(gi_parts, n_parts, wh_parts, bh_parts, n_wparts, hs, rzn, ghn, T, G, B, (hipStream_t)stream, h0_parts, (long)h0_set_stride,
+                       (long)h0_row_stride);
+    return launched();
+}
+
 int ssd_gru_seq_bwd(const float* dhs, const float* hs, const float* rzn, const float* ghn, const float* wh, float* d_gi, float* dgh,
                     float* d_wh, float* d_bh_part, int32_t T, int32_t G, int32_t B, void* stream) {
-    if (!dhs || !hs || !rzn || !ghn || !wh || !d_gi || !dgh || !d_wh || !d_bh_part || T < 1 || G < 1 || B < 1) return fail(SSD_ERR_INVALID, "bad argument");
-    if (B % 16) return fail(SSD_ERR_INVALID, "B must be a multiple of 16 (pad the sequences)");
-    if (!al16(dhs) || !al16(hs) || !al16(rzn) || !al16(ghn) || !al16(wh) || !al16(d_gi) || !al16(dgh)) return fail(SSD_ERR_INVALID, "tensors must be 16-byte aligned");
+    if (int rc = gru_seq_bwd_check("ssd_gru_seq_bwd", 0, &dhs, hs, rzn, ghn, &wh, 1, &d_gi, 0, dgh, d_wh, d_bh_part, T, G, G, B)) return rc;
     launch_gru_seq_bwd(&dhs, hs, rzn, ghn, &wh, 1, &d_gi, 0, dgh, d_wh, d_bh_part, T, G, G, B, (hipStream_t)stream);
     return launched();
 }
 int ssd_gru_seq_bwd_parts(const float* const* dhs_parts, const float* hs, const float* rzn, const float* ghn, const float* const* wh_parts, int32_t n_wparts,
                           float* const* d_gi_parts, int32_t n_parts, float* dgh, float* d_wh, float* d_bh_part, int32_t T, int32_t G, int32_t G_grad, int32_t B,
                           void* stream) {
-    if (!dhs_parts || !hs || !rzn || !ghn || !wh_parts || n_wparts < 1 || n_wparts > 4 || !d_gi_parts || n_parts < 1 || n_parts > 4 || !dgh || !d_wh ||
-        !d_bh_part || T < 1 || G < 1 || G % n_parts || G % n_wparts || B < 1 || G_grad < 1 || G_grad > G || G_grad % (G / n_parts))
-        return fail(SSD_ERR_INVALID, "bad argument");
-    for (int k = 0; k * (G / n_parts) < G_grad; ++k)
-        if (!dhs_parts[k] || !al16(dhs_parts[k])) return fail(SSD_ERR_INVALID, "dhs parts of the sets with a gradient must be non-null and 16-byte aligned");
-    for (int k = 0; k < n_wparts; ++k)
-        if (!wh_parts[k] || !al16(wh_parts[k])) return fail(SSD_ERR_INVALID, "weight parts must be non-null and 16-byte aligned");
-    if (B % 16) return fail(SSD_ERR_INVALID, "B must be a multiple of 16 (pad the sequences)");
-    for (int k = 0; k * (G / n_parts) < G_grad; ++k)
-        if (!d_gi_parts[k] || !al16(d_gi_parts[k])) return fail(SSD_ERR_INVALID, "d_gi parts of the sets with a gradient must be non-null and 16-byte aligned");
-    if (!al16(hs) || !al16(rzn) || !al16(ghn) || !al16(dgh)) return fail(SSD_ERR_INVALID, "tensors must be 16-byte aligned");
+    if (int rc = gru_seq_bwd_check("ssd_gru_seq_bwd_parts", 1, dhs_parts, hs, rzn, ghn, wh_parts, n_wparts, d_gi_parts, n_parts, dgh, d_wh, d_bh_part, T, G, G_grad, B))
+        return rc;
     launch_gru_seq_bwd(dhs_parts, hs, rzn, ghn, wh_parts, n_wparts, d_gi_parts, n_parts, dgh, d_wh, d_bh_part, T, G, G_grad, B, (hipStream_t)stream);
-    return launched();
-}
-
-int ssd_gru_seq_fwd_h0(const float* const* gi_parts, int32_t n_parts, const float* const* wh_parts, const float* const* bh_parts, int32_t n_wparts,
-                       const float* const* h0_parts, int64_t h0_set_stride, int64_t h0_row_stride, float* hs, float* rzn, float* ghn, int32_t T, int32_t G,
-                       int32_t B, void* stream) {
-    const int np = n_parts < 1 ? 1 : n_parts;
-    if (!gi_parts || n_parts < 0 || n_parts > 4 || !wh_parts || !bh_parts || n_wparts < 1 || n_wparts > 4 || !h0_parts || !hs || T < 1 || G < 1 || G % np ||
-        G % n_wparts || B < 1 || (!rzn) != (!ghn))
-        return fail(SSD_ERR_INVALID, "ssd_gru_seq_fwd_h0: bad argument");
-    for (int k = 0; k < n_wparts; ++k)
-        if (!wh_parts[k] || !bh_parts[k] || !al16(wh_parts[k]) || !al16(bh_parts[k])) return fail(SSD_ERR_INVALID, "ssd_gru_seq_fwd_h0: weight parts must be non-null and 16-byte aligned");
-    if (B % 16) return fail(SSD_ERR_INVALID, "ssd_gru_seq_fwd_h0: B must be a multiple of 16 (pad the sequences and h0)");
-    for (int k = 0; k < np; ++k) {
-        if (!gi_parts[k] || !al16(gi_parts[k])) return fail(SSD_ERR_INVALID, "ssd_gru_seq_fwd_h0: gi parts must be non-null and 16-byte aligned");
-        if (!h0_parts[k] || !al16(h0_parts[k])) return fail(SSD_ERR_INVALID, "ssd_gru_seq_fwd_h0: h0 parts must be non-null and 16-byte aligned");
-    }
-    if (h0_set_stride < 0 || h0_row_stride < 0 || (h0_set_stride & 3) || (h0_row_stride & 3))
-        return fail(SSD_ERR_INVALID, "ssd_gru_seq_fwd_h0: h0 strides must be non-negative multiples of 4 elements");
-    if (!al16(hs) || !al16(rzn) || !al16(ghn)) return fail(SSD_ERR_INVALID, "ssd_gru_seq_fwd_h0: tensors must be 16-byte aligned");
-    launch_gru_seq_fwd(gi_parts, n_parts, wh_parts, bh_parts, n_wparts, hs, rzn, ghn, T, G, B, (hipStream_t)stream, h0_parts, (long)h0_set_stride,
-                       (long)h0_row_stride);
     return launched();
 }
 int ssd_gru_seq_bwd_h0(const float* const* dhs_parts, const float* hs, const float* rzn, const float* ghn, const float* const* wh_parts, int32_t n_wparts,
                        float* const* d_gi_parts, int32_t n_parts, float* dgh, float* d_wh, float* d_bh_part, int32_t T, int32_t G, int32_t G_grad, int32_t B,
                        void* stream) {
-    const int np = n_parts < 1 ? 1 : n_parts;
-    if (!dhs_parts || !hs || !rzn || !ghn || !wh_parts || n_wparts < 1 || n_wparts > 4 || !d_gi_parts || n_parts < 0 || n_parts > 4 || !dgh || !d_wh ||
-        !d_bh_part || T < 1 || G < 1 || G % np || G % n_wparts || B < 1 || G_grad < 1 || G_grad > G || G_grad % (G / np))
-        return fail(SSD_ERR_INVALID, "ssd_gru_seq_bwd_h0: bad argument");
-    for (int k = 0; k * (G / np) < G_grad; ++k)
-        if (!dhs_parts[k] || !al16(dhs_parts[k]) || !d_gi_parts[k] || !al16(d_gi_parts[k]))
-            return fail(SSD_ERR_INVALID, "ssd_gru_seq_bwd_h0: dhs and d_gi parts of the sets with a gradient must be non-null and 16-byte aligned");
-    for (int k = 0; k < n_wparts; ++k)
-        if (!wh_parts[k] || !al16(wh_parts[k])) return fail(SSD_ERR_INVALID, "ssd_gru_seq_bwd_h0: weight parts must be non-null and 16-byte aligned");
-    if (B % 16) return fail(SSD_ERR_INVALID, "ssd_gru_seq_bwd_h0: B must be a multiple of 16 (pad the sequences)");
-    if (!al16(hs) || !al16(rzn) || !al16(ghn) || !al16(dgh)) return fail(SSD_ERR_INVALID, "ssd_gru_seq_bwd_h0: tensors must be 16-byte aligned");
+    if (int rc = gru_seq_bwd_check("ssd_gru_seq_bwd_h0", 0, dhs_parts, hs, rzn, ghn, wh_parts, n_wparts, d_gi_parts, n_parts, dgh, d_wh, d_bh_part, T, G, G_grad, B))
+        return rc;
     launch_gru_seq_bwd(dhs_parts, hs, rzn, ghn, wh_parts, n_wparts, d_gi_parts, n_parts, dgh, d_wh, d_bh_part, T, G, G_grad, B, (hipStream_t)stream, true);
     return launched();
 }

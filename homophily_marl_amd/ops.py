@@ -1144,16 +1144,12 @@ class _GruGates(th.autograd.Function):
 
 
 class _GruSeq(th.autograd.Function):
-    """The whole recurrence h_t = GRU(gi_t, h_{t-1}) for t = 0..T-1 from h = 0 as one forward and one backward launch
-    (csrc/ssd_gru_seq.hip).  gi [T, G, B, 3H], wh [G, H, 3H], bh [G, 1, 3H] -> hs [G, T, B, H]."""
+    """The whole recurrence h_t = GRU(gi_t, h_{t-1}) for t = 0..T-1 as one forward and one backward launch (csrc/ssd_gru_seq.hip).
+    gi [T, G, B, 3H], wh [G, H, 3H], bh [G, 1, 3H] -> hs [G, T, B, H].  h0 None: from h = 0 (ssd_gru_seq_fwd); else a state
+    [G, B, H]: hs[:, 0] := h0, steps 1 .. T - 1 computed (ssd_gru_seq_fwd_h0, time-major form: n_parts 0); h0 is data (no gradient)."""
 
     @staticmethod
-    def forward(ctx, gi, wh, bh):
-        return _GruSeq._forward(ctx, gi, wh, bh, None)
-
-    @staticmethod
-    def _forward(ctx, gi, wh, bh, h0):
-        """h0 None: from zero (ssd_gru_seq_fwd); else [G, B, H], hs[:, 0] := h0 (ssd_gru_seq_fwd_h0, time-major form: n_parts 0)"""
+    def forward(ctx, gi, wh, bh, h0):
         lib = abi.load_library()
         gi, wh, bh = gi.contiguous(), wh.contiguous(), bh.contiguous()
         T, G, B, H3 = gi.shape
@@ -1206,36 +1202,21 @@ class _GruSeq(th.autograd.Function):
                                                dgh.data_ptr(), d_wh.data_ptr(), d_bh.data_ptr(), T, G, Bp, _stream(rzn)))
         if Bp != B:
             d_gi = d_gi[:, :, :B].contiguous()
-        return d_gi, d_wh, (column_sums(d_bh) if tiles > 1 else d_bh[:, 0]).unsqueeze(1)      # per-tile bias sums: k_column_sums (no ATen reduction)
-
-
-class _GruSeqH0(th.autograd.Function):
-    """_GruSeq from a given state h0 [G, B, H]: hs[:, 0] := h0, steps 1 .. T - 1 computed; h0 is data (no gradient)."""
-
-    @staticmethod
-    def forward(ctx, gi, wh, bh, h0):
-        return _GruSeq._forward(ctx, gi, wh, bh, h0)
-
-    @staticmethod
-    def backward(ctx, dhs):
-        with _precision(ctx.precision):
-            return _GruSeq._backward(ctx, dhs) + (None,)
+        return d_gi, d_wh, (column_sums(d_bh) if tiles > 1 else d_bh[:, 0]).unsqueeze(1), None      # per-tile bias sums: k_column_sums (no ATen reduction); h0 is data
 
 
 class _GruSeqParts(th.autograd.Function):
     """_GruSeq with the input-side projections given as separately allocated set-major parts [sets, T * B, 3H] (the per-agent affine
     layers' outputs as they are: ssd_gru_seq_fwd_parts / _bwd_parts) -- no concatenation / transpose copies, and the gradients come back
     per part, contiguous.  The recurrence weights come as n_w separately allocated parts too (wh [sets, H, 3H], bh [sets, 1, 3H]: the
-    live net's and the target net's images as they are).  B is a multiple of 16 here (gru_sequence_parts falls back otherwise)."""
+    live net's and the target net's images as they are).  B is a multiple of 16 here (gru_sequence_parts falls back otherwise).
+    h0 None: from zero (ssd_gru_seq_fwd_parts); else (views [sets, B, H] per projection part, set stride, row stride in elements), read
+    in place by ssd_gru_seq_fwd_h0 (the learner: batch["hidden"][:, 0] of the static batch, no copy launch); hs[:, 0] := h0, no gradient
+    into it."""
+    LEAD = 4          # non-tensor arguments in front of the tensors: T, B, n_w, h0
 
     @staticmethod
-    def forward(ctx, T, B, n_w, *tensors):
-        return _GruSeqParts._forward(ctx, T, B, n_w, None, tensors)
-
-    @staticmethod
-    def _forward(ctx, T, B, n_w, h0, tensors):
-        """h0 None: from zero (ssd_gru_seq_fwd_parts); else (views [sets, B, H] per projection part, set stride, row stride): read in
-        place by ssd_gru_seq_fwd_h0"""
+    def forward(ctx, T, B, n_w, h0, *tensors):
         lib = abi.load_library()
         whs, bhs = [t.contiguous() for t in tensors[:n_w]], [t.contiguous() for t in tensors[n_w:2 * n_w]]
         parts = [p.contiguous() for p in tensors[2 * n_w:]]
@@ -1258,7 +1239,6 @@ class _GruSeqParts(th.autograd.Function):
             abi.check(lib, lib.ssd_gru_seq_fwd_h0(ptrs, len(parts), wptrs, bptrs, n_w, hptrs, set_stride, row_stride, hs.data_ptr(),
                                                   None if rzn is None else rzn.data_ptr(), None if ghn is None else ghn.data_ptr(), T, G, B, _stream(hs)))
         ctx.h0 = h0 is not None
-        ctx.lead = 3 if h0 is None else 4         # non-tensor arguments in front of the tensors
         if need:
             ctx.save_for_backward(hs, rzn, ghn, *whs)
             ctx.shapes = [p.shape for p in parts]
@@ -1284,7 +1264,7 @@ class _GruSeqParts(th.autograd.Function):
         T, G, B, H3 = rzn.shape
         n_parts = len(ctx.shapes)
         spp = G // n_parts
-        need, lead = ctx.needs_input_grad, ctx.lead
+        need, lead = ctx.needs_input_grad, _GruSeqParts.LEAD
         # the sets whose states carry a gradient form a prefix (the live net's parts come first); the kernel walks only those
         last = max([k for k, d in enumerate(dhs_parts) if d is not None], default=-1)
         if last < 0:
@@ -1322,20 +1302,6 @@ class _GruSeqParts(th.autograd.Function):
         g_bh = tuple(of_part(d_bh_all, k) if need[lead + n_w + k] else None for k in range(n_w))
         g_parts = tuple(d_parts[k] if (k <= last and need[lead + 2 * n_w + k]) else None for k in range(n_parts))
         return (None,) * lead + g_wh + g_bh + g_parts
-
-
-class _GruSeqPartsH0(th.autograd.Function):
-    """_GruSeqParts from a given state: h0 = (views [sets, B, H] per projection part, set stride, row stride in elements), read in place
-    (the learner: batch["hidden"][:, 0] of the static batch, no copy launch); hs[:, 0] := h0, no gradient into it."""
-
-    @staticmethod
-    def forward(ctx, T, B, n_w, h0, *tensors):
-        return _GruSeqParts._forward(ctx, T, B, n_w, h0, tensors)
-
-    @staticmethod
-    def backward(ctx, *dhs_parts):
-        with _precision(ctx.precision):
-            return _GruSeqParts._backward(ctx, *dhs_parts)
 
 
 def _gru_h0_views(op, h0, like, n_parts, spp, B, H):
@@ -1391,14 +1357,14 @@ def gru_sequence_parts(parts, T, B, wh, bh, h0=None):
             and _f32_on(*parts, *whs, *bhs) and 1 <= len(whs) <= 4 and all(w.shape == whs[0].shape for w in whs)
             and all(b.shape == bhs[0].shape for b in bhs) and whs[0].shape[0] * len(whs) == G):
         if h0 is None:
-            return list(_GruSeqParts.apply(T, B, len(whs), *whs, *bhs, *parts))
+            return list(_GruSeqParts.apply(T, B, len(whs), None, *whs, *bhs, *parts))
         if _f32_on(*h0):
             strides = _gru_h0_in_place(h0)
             if strides is None:         # a layout the kernel does not index (odd strides, misaligned): one contiguous copy
                 full = th.stack([v.contiguous() for v in h0], dim=0).reshape(G, B, H)
                 h0 = [full[k * parts[0].shape[0]:(k + 1) * parts[0].shape[0]] for k in range(len(parts))]
                 strides = (B * H, H)
-            return list(_GruSeqPartsH0.apply(T, B, len(whs), (h0, strides[0], strides[1]), *whs, *bhs, *parts))
+            return list(_GruSeqParts.apply(T, B, len(whs), (h0, strides[0], strides[1]), *whs, *bhs, *parts))
     wh, bh = (whs[0] if len(whs) == 1 else th.cat(whs, dim=0)), (bhs[0] if len(bhs) == 1 else th.cat(bhs, dim=0))
     if H3 != 192 or parts[0].dtype != th.float32:
         _leaving_kernels("gru_sequence_parts", parts[0], "hidden size %d / dtype" % (H3 // 3))
@@ -1432,7 +1398,7 @@ def gru_sequence(gi, wh, bh, h0=None):
     if h0 is not None:
         h0 = _gru_h0_views("gru_sequence", h0, gi, 1, G, B, H3 // 3)[0]
     if gi.is_cuda and H3 == 192 and _f32_on(gi, wh, bh) and (h0 is None or _f32_on(h0)):
-        return _GruSeq.apply(gi, wh, bh) if h0 is None else _GruSeqH0.apply(gi, wh, bh, h0)
+        return _GruSeq.apply(gi, wh, bh, h0)
     _leaving_kernels("gru_sequence", gi, "hidden size %d (the sequence kernels are instantiated for 64) / dtypes %s, %s, %s" % (H3 // 3, gi.dtype, wh.dtype, bh.dtype))
     h = gi.new_zeros(G, B, H3 // 3) if h0 is None else h0.to(gi.dtype)
     hs = [] if h0 is None else [h]                  # the given state IS the state after step 0

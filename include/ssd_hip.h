@@ -333,9 +333,7 @@ int ssd_runner_stats(const float* collective_return, const float* equality, cons
  * Refused (SSD_ERR_INVALID): NULL args or a NULL member pointer; n_env < 1; t_slots < 2; n_agents outside 1 .. SSD_MAX_AGENTS;
  * n_actions outside 1 .. 16; t_slots * n_agents * n_agents above INT32_MAX (an element's index inside one env's block of
  * actions_inc is 32-bit; offsets across envs, the time sums and every counter are 64-bit, so n_env has no bound of its own).
- * The name is declared in parentheses (an ordinary declaration to a compiler): tests/test_abi_symbols.py and
- * tests/test_learner_abi_refusals.py together pin the plainly declared exports to the refusal tables of the latter; this export's
- * ctypes mirror is abi.BEHAVIOUR_SIGNATURES and its symbol, struct-size and refusal checks are tests/test_behaviour_host.py. */
+ * Refusal checks: tests/test_behaviour_host.py. */
 #define SSD_BEHAVIOUR_MAX_GROUPS 256
 #define SSD_BEHAVIOUR_WAVES 16
 #define SSD_BEHAVIOUR_LEN(n, A) (12 * (n) + (n) * (A) + 3 * (n) * (n) + 3)
@@ -347,11 +345,10 @@ typedef struct ssd_behaviour_args {
     int64_t* workspace;          /* [SSD_BEHAVIOUR_MAX_GROUPS, LEN] */
     double* acc;                 /* [LEN]  += this rollout */
 } ssd_behaviour_args;
-int (ssd_behaviour_stats)(const ssd_behaviour_args* args, void* stream);
+int ssd_behaviour_stats(const ssd_behaviour_args* args, void* stream);
 
 /* Training on sampled time windows (config keys train_window / train_burn_in): one window of win_slots = L + 1 consecutive slots
- * [t0, t0 + L] per sampled episode, drawn and gathered on the device.  Both names are declared in parentheses like
- * ssd_behaviour_stats; their ctypes mirror is abi.WINDOW_SIGNATURES and their symbol, struct-size and refusal checks are
+ * [t0, t0 + L] per sampled episode, drawn and gathered on the device.  Refusal checks:
  * tests/test_train_window_host.py.
  *
  * ssd_sample_windows: ids[0 .. count) exactly as ssd_sample_ids gives them for the same (seed, call, population, count) -- the same
@@ -366,8 +363,8 @@ int (ssd_behaviour_stats)(const ssd_behaviour_args* args, void* stream);
  * so the id draws use i < 2 * count and the starts the indices from 2 * count on.  ONE launch; ids, t0: DEVICE int64
  * [count].  A restatement for host tensors: ops.sample_windows.  Refused (SSD_ERR_INVALID): a NULL pointer, n_starts < 1, and what
  * ssd_sample_ids refuses (count outside 1 .. min(population, SSD_SAMPLE_IDS_MAX)). */
-int (ssd_sample_windows)(uint64_t seed, uint32_t call, int32_t population, int32_t count, int32_t n_starts, int64_t* ids, int64_t* t0,
-                         void* stream);
+int ssd_sample_windows(uint64_t seed, uint32_t call, int32_t population, int32_t count, int32_t n_starts, int64_t* ids, int64_t* t0,
+                       void* stream);
 
 /* ssd_gather_windows: for every field f < count (1..SSD_COPY_BLOCKS_MAX) and every e < n_ids, win_slots * slot_bytes_f contiguous
  * bytes from  src_f + (ids[e] * src_slots + t0[e]) * slot_bytes_f  to  dst_f + e * win_slots * slot_bytes_f, as ONE launch; ids and
@@ -391,13 +388,12 @@ typedef struct ssd_window_field {
     int32_t filled;        /* 1: the `filled` mask (see above); 0: a plain copy */
     int32_t reserved;
 } ssd_window_field;
-int (ssd_gather_windows)(const ssd_window_field* fields, int32_t count, const int64_t* ids, const int64_t* t0, int32_t n_ids,
-                         int32_t src_slots, int32_t win_slots, int32_t burn_in, void* stream);
+int ssd_gather_windows(const ssd_window_field* fields, int32_t count, const int64_t* ids, const int64_t* t0, int32_t n_ids,
+                       int32_t src_slots, int32_t win_slots, int32_t burn_in, void* stream);
 
 /* Prioritised replay (config key prioritized_replay, default off; per_alpha / per_beta / per_beta_anneal_steps / per_eta / per_eps):
  * proportional draws, importance weights and new priorities on the device.  The reference has no counterpart (its
- * ReplayBuffer.sample is np.random.choice).  Both names are declared in parentheses like ssd_behaviour_stats; their ctypes mirror is
- * abi.PRIORITY_SIGNATURES and their symbol, struct-size and refusal checks are tests/test_priority_host.py.
+ * ReplayBuffer.sample is np.random.choice).  Refusal checks: tests/test_priority_host.py.
  *
  * Priority table: one u32 per buffer slot, fixed point: SSD_PRIORITY_ONE is 1.0, stored values lie in [1, SSD_PRIORITY_MAX], 0 means
  * "never trained on".  Integers, so that every sum is an integer sum: the order of summation cannot show and a draw is the same on
@@ -437,7 +433,7 @@ typedef struct ssd_priority_sample_args {
     float* weights;
     float* log;                  /* [4] */
 } ssd_priority_sample_args;
-int (ssd_priority_sample)(const ssd_priority_sample_args* args, void* stream);
+int ssd_priority_sample(const ssd_priority_sample_args* args, void* stream);
 
 /* ssd_priority_update: after ssd_td_sim_loss (mode 1; either kernel) of a batch of `batch` samples over t_slots = T + 1 slots:
  * the new priorities of the trained samples from the loss kernel's `partials`, the importance weights applied to the gradient
@@ -471,13 +467,12 @@ typedef struct ssd_priority_update_args {
     uint32_t* q_new;             /* [batch] staging */
     uint32_t* table;             /* [table_len] */
 } ssd_priority_update_args;
-int (ssd_priority_update)(const ssd_priority_update_args* args, void* stream);
+int ssd_priority_update(const ssd_priority_update_args* args, void* stream);
 
 /* ssd_rollout_priority (config key per_initial_priority: "rollout"; default "max" = the zero entry above): the priority an episode
  * enters the table with, formed by the rollout from the TD errors of what it just produced (Ape-X / R2D2), ONE launch per timestep
  * slot behind the inc head of slot t = *t_index (the slot scalar ssd_store_hidden reads).  Online: no Q-value is kept per slot.
- * Declared in parentheses like ssd_store_hidden; the ctypes mirror is abi.ROLLOUT_PRIORITY_SIGNATURES, the symbol, struct-size and
- * refusal checks are tests/test_rollout_priority_host.py.
+ * Refusal checks: tests/test_rollout_priority_host.py.
  *
  * The value is ssd_priority_update's formula and f32 operation sequence over the episode's T * n rows (t, agent i), T = t_slots - 1:
  *   d      = sqrt((td_env mask)^2 + (td_inc mask)^2)
@@ -533,7 +528,7 @@ typedef struct ssd_rollout_priority_args {
     float *carry, *acc;
     uint32_t* q_init;            /* [n_env] */
 } ssd_rollout_priority_args;
-int (ssd_rollout_priority)(const ssd_rollout_priority_args* args, void* stream);
+int ssd_rollout_priority(const ssd_rollout_priority_args* args, void* stream);
 
 /* ssd_clip_adam_step: the optimiser tail of HomophilyLearner.cal_loss_and_step (homophily_learner.py:223-226) --
  *   clip_grad_norm_(params_inc, clip); clip_grad_norm_(params_env, clip); optimiser_inc.step(); optimiser_env.step()
@@ -676,8 +671,7 @@ int ssd_store_step_launch(const ssd_store_step* args, void* stream);
  * only slot *t_index is written, and nothing at all when *t_index lies outside [0, t_slots).  The sources are read as
  * h[agent * src_agent_stride + env * src_env_stride + 0..63] (elements): FastPolicy's agent-major [n, N, 64] is (N * 64, 64), the
  * generic timestep's [N, n, 1, 64] is (64, n * 64).  k_store_hidden: one thread per 16 bytes, 64-bit offsets, no atomics; the launch
- * writes no scalar.  Declared in parentheses like ssd_behaviour_stats; the ctypes mirror is abi.STORED_STATE_SIGNATURES, the symbol,
- * struct-size and refusal checks are tests/test_stored_state_host.py.
+ * writes no scalar.  Refusal checks: tests/test_stored_state_host.py.
  * Refused (SSD_ERR_INVALID): NULL args or a NULL member pointer; n_env, n_agents or t_slots below 1; h_env, h_inc or dst not 16-byte
  * aligned; a negative source stride or one that is not a multiple of 4 elements. */
 typedef struct ssd_store_hidden_args {
@@ -688,7 +682,7 @@ typedef struct ssd_store_hidden_args {
     int64_t src_agent_stride, src_env_stride;        /* elements */
     float* dst;
 } ssd_store_hidden_args;
-int (ssd_store_hidden)(const ssd_store_hidden_args* args, void* stream);
+int ssd_store_hidden(const ssd_store_hidden_args* args, void* stream);
 
 int ssd_gru_gates(const float* gi, const float* gh, float* h, int32_t rows, int32_t hidden, void* stream);
 /* ssd_gru_gates / _fwd / _bwd: any rows >= 1 and any hidden >= 1 (elementwise kernels that stride over rows x hidden with a grid of at
@@ -742,15 +736,15 @@ int ssd_gru_seq_bwd_parts(const float* const* dhs_parts, const float* hs, const 
  * a [B, W, n, 128] field in place: pointers p, p + 64, p, p + 64 (live env / inc, target env / inc), set stride 128, row stride
  * W * n * 128.  Every row b < B is read (B a multiple of 16).  Kernels k_gru_seq_fwd_h0 / k_gru_seq_bwd_h0: the text of the
  * zero-state kernels compiled a second time (csrc/ssd_gru_seq_kernels.h); the compute waves issue no stores, the steps hold no row
- * predicate.  Both names are declared in parentheses; ctypes mirror abi.STORED_STATE_SIGNATURES.
+ * predicate.
  * Refused (SSD_ERR_INVALID) like the _parts forms, and: a NULL or not 16-byte aligned h0 part; a negative h0 stride or one that is
  * not a multiple of 4 elements. */
-int (ssd_gru_seq_fwd_h0)(const float* const* gi_parts, int32_t n_parts, const float* const* wh_parts, const float* const* bh_parts, int32_t n_wparts,
-                         const float* const* h0_parts, int64_t h0_set_stride, int64_t h0_row_stride, float* hs, float* rzn, float* ghn, int32_t T,
-                         int32_t G, int32_t B, void* stream);
-int (ssd_gru_seq_bwd_h0)(const float* const* dhs_parts, const float* hs, const float* rzn, const float* ghn, const float* const* wh_parts,
-                         int32_t n_wparts, float* const* d_gi_parts, int32_t n_parts, float* dgh, float* d_wh, float* d_bh_part, int32_t T, int32_t G,
-                         int32_t G_grad, int32_t B, void* stream);
+int ssd_gru_seq_fwd_h0(const float* const* gi_parts, int32_t n_parts, const float* const* wh_parts, const float* const* bh_parts, int32_t n_wparts,
+                       const float* const* h0_parts, int64_t h0_set_stride, int64_t h0_row_stride, float* hs, float* rzn, float* ghn, int32_t T,
+                       int32_t G, int32_t B, void* stream);
+int ssd_gru_seq_bwd_h0(const float* const* dhs_parts, const float* hs, const float* rzn, const float* ghn, const float* const* wh_parts,
+                       int32_t n_wparts, float* const* d_gi_parts, int32_t n_parts, float* dgh, float* d_wh, float* d_bh_part, int32_t T, int32_t G,
+                       int32_t G_grad, int32_t B, void* stream);
 
 /* ---- the learner's per-agent affine layers (csrc/ssd_bmm.hip) ---------------------------------------------------------------
  * th.baddbmm(b, x, w) over the agent axis (homophily_agent.py:154-208: fc1, GRU input projections, dueling heads) and its backward,

@@ -1,4 +1,5 @@
-"""CPU suite: the C-ABI shared library loads and exports every symbol include/ssd_hip.h declares (no compute calls)."""
+"""CPU suite: the C-ABI shared library loads and exports every symbol include/ssd_hip.h declares, bound as abi.HIP_SIGNATURES says, and
+every struct of abi lays out as the header's (no compute calls)."""
 import ctypes
 import os
 import re
@@ -26,20 +27,41 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), name
     lib.ssd_abi_version.restype = ctypes.c_int
     assert lib.ssd_abi_version() == abi.ABI_VERSION
+    bound = abi.load_library()
+    for name, (res, argtypes) in abi.HIP_SIGNATURES.items():
+        assert getattr(bound, name).argtypes == argtypes and getattr(bound, name).restype is res, name
 
 
-def test_struct_sizes_match_the_header(tmp_path):
-    """sizeof() of every ABI struct as seen by a C compiler == the ctypes mirror."""
+def _c_name(cls):
+    """SsdTdLossArgs -> ssd_td_loss_args"""
+    return re.sub(r"(?<!^)(?=[A-Z])", "_", cls.__name__).lower()
+
+
+def test_struct_layouts_match_the_header(tmp_path):
+    """Every ctypes.Structure of abi is a typedef of the header under its snake-case name and the other way round (the ssd_status enum
+    aside), with the header's field names in the header's order; sizeof() and the offsetof() of every field as seen by a C compiler ==
+    the ctypes mirror.  ONE program prints them all."""
     import subprocess
+    structs = {_c_name(v): v for v in vars(abi).values()
+               if isinstance(v, type) and issubclass(v, ctypes.Structure) and v.__module__ == abi.__name__}
+    src = open(os.path.join(ROOT, "include", "ssd_hip.h")).read()
+    assert sorted(structs) == sorted(set(re.findall(r"^\}\s*(ssd_\w+)\s*;", src, flags=re.M)) - {"ssd_status"})
+    bodies = {name: body for body, name in re.findall(r"typedef\s+struct\s+\w*\s*\{([^{}]*)\}\s*(ssd_\w+)\s*;", re.sub(r"/\*.*?\*/", "", src, flags=re.S))}
+    for name, cls in structs.items():       # "int32_t a, b[4]; const float *c, *d;" -> a, b, c, d
+        declared = [re.sub(r"\[.*?\]", "", d).split()[-1].lstrip("*") for decl in bodies[name].split(";") if decl.strip() for d in decl.split(",")]
+        assert declared == [f[0] for f in cls._fields_], name
+    probes = [(c, cls, None) for c, cls in structs.items()] + [(c, cls, f[0]) for c, cls in structs.items() for f in cls._fields_]
     c = tmp_path / "s.c"
-    c.write_text('#include <stdio.h>\n#include "ssd_hip.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(ssd_config),'
-                 'sizeof(ssd_tape), sizeof(ssd_step_out), sizeof(ssd_obs_out), sizeof(ssd_state), sizeof(ssd_info),'
-                 'sizeof(ssd_store_step), sizeof(ssd_policy_head), sizeof(ssd_policy_encode_args), sizeof(ssd_block_copy), sizeof(ssd_adam_job), sizeof(ssd_clip_adam_args), sizeof(ssd_row_gather));return 0;}')
+    c.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ssd_hip.h"\nint main(){\n'
+                 + "".join('printf("%%zu\\n", %s);\n' % ("sizeof(%s)" % n if f is None else "offsetof(%s, %s)" % (n, f)) for n, _, f in probes)
+                 + "return 0;}\n")
     exe = tmp_path / "s"
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
-    sizes = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert sizes == [ctypes.sizeof(t) for t in (abi.SsdConfig, abi.SsdTape, abi.SsdStepOut, abi.SsdObsOut, abi.SsdState, abi.SsdInfo,
-                                                    abi.SsdStoreStep, abi.SsdPolicyHead, abi.SsdPolicyEncodeArgs, abi.SsdBlockCopy, abi.SsdAdamJob, abi.SsdClipAdamArgs, abi.SsdRowGather)]
+    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    want = [ctypes.sizeof(cls) if f is None else getattr(cls, f).offset for _, cls, f in probes]
+    print("%d structs, %d values" % (len(structs), len(want)))
+    assert len(got) == len(want)
+    assert got == want, [(n, f, g, w) for (n, _, f), g, w in zip(probes, got, want) if g != w]
 
 
 def test_oracle_is_not_reachable_from_the_product_package():

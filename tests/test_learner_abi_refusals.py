@@ -3,8 +3,10 @@ runs before any launch, as tests/test_encoder_any_view.py::test_encoder_entry_po
 
 For every learner export a baseline of valid arguments (dummy, never dereferenced device pointers) and a table of single departures
 from it, each with the status the header promises.  ONLY invalid calls are made: the baseline itself is never called, nothing here may
-reach a launch.  The export list is checked against abi.HIP_SIGNATURES, so a new export without a row fails."""
+reach a launch.  The export list is checked against abi.HIP_SIGNATURES, so a new export without a row in one of the three categories
+(a refusal table here, NOT_LEARNER, ELSEWHERE) fails."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -22,6 +24,15 @@ NOT_LEARNER = {
     "ssd_build_inputs_width", "ssd_bmm_reserve_scratch", "ssd_learner_precision", "ssd_policy_head_plan", "ssd_policy_head_inc_encode",
     "ssd_policy_pack_encoder_lut", "ssd_policy_pack_encoder", "ssd_numeric_status", "ssd_policy_pack_head", "ssd_conv_leaky",
     "ssd_store_step_launch", "ssd_dueling_pick", "ssd_poll_error", "ssd_set_render", "ssd_render",
+}
+
+# exports whose refusal tables live in their feature's host test: export -> test module (under tests/)
+ELSEWHERE = {
+    "ssd_behaviour_stats": "test_behaviour_host",
+    "ssd_sample_windows": "test_train_window_host", "ssd_gather_windows": "test_train_window_host",
+    "ssd_priority_sample": "test_priority_host", "ssd_priority_update": "test_priority_host",
+    "ssd_rollout_priority": "test_rollout_priority_host",
+    "ssd_store_hidden": "test_stored_state_host", "ssd_gru_seq_fwd_h0": "test_stored_state_host", "ssd_gru_seq_bwd_h0": "test_stored_state_host",
 }
 
 CASES = []          # (export, label, callable(lib) -> status, expected status)
@@ -226,11 +237,17 @@ LEARNER = sorted({c[0] for c in CASES} | {"ssd_conv_wgrad_partial_rows"})
 
 
 def test_every_export_is_categorised():
-    """abi.HIP_SIGNATURES = the learner exports with a refusal table here + the named others: a new export must be put in one of them."""
+    """abi.HIP_SIGNATURES = the learner exports with a refusal table here + the named others + the exports whose tables a feature's
+    host test holds: a new export must be put in exactly one of the three."""
     names = set(abi.HIP_SIGNATURES)
-    assert not (set(LEARNER) & NOT_LEARNER)
-    assert names - NOT_LEARNER == set(LEARNER), sorted(names - NOT_LEARNER - set(LEARNER)) + sorted(set(LEARNER) - names)
-    assert NOT_LEARNER <= names, sorted(NOT_LEARNER - names)
+    assert not (set(LEARNER) & NOT_LEARNER) and not (set(ELSEWHERE) & NOT_LEARNER) and not (set(ELSEWHERE) & set(LEARNER))
+    other = NOT_LEARNER | set(ELSEWHERE)
+    assert names - other == set(LEARNER), sorted(names - other - set(LEARNER)) + sorted(set(LEARNER) - names)
+    assert other <= names, sorted(other - names)
+    for name, module in ELSEWHERE.items():
+        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), module + ".py")
+        assert os.path.isfile(path), (name, module)
+        assert '"%s"' % name in open(path).read(), (name, module)
 
 
 @pytest.mark.parametrize("case", CASES, ids=["%s-%s" % (c[0], c[1].replace(" ", "_")) for c in CASES])

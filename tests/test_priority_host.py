@@ -1,6 +1,6 @@
 """CPU suite of prioritised replay (config key prioritized_replay; ssd_priority_sample / ssd_priority_update;
 ReplayBuffer.enable_priorities / sample_prioritized): ops' host restatement of the draw against tests/priority_util.py (written from
-the header), the proportionality of the draw, the exports' symbols, struct sizes and refusals, the tensor-op learner with per-sample
+the header), the proportionality of the draw, the exports' constants as compiled and refusals, the tensor-op learner with per-sample
 weights, the buffer's resets on insert, the config refusals, and the key off as today's path."""
 import ctypes as C
 import os
@@ -88,38 +88,26 @@ def test_an_all_zero_table_is_drawn_uniformly():
     _frequencies_within_five_sigma(np.zeros(64, np.int32), "all zero")
 
 
-# ---- 3. exports: symbols, struct sizes, refusals -------------------------------------------------------------------------------------------
+# ---- 3. exports: constants as compiled, refusals --------------------------------------------------------------------------------------------
 def test_exports_are_declared_exported_and_mirrored():
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ssd_hip.h")).read(), flags=re.S)
-    assert re.search(r"\bint\s*\(\s*ssd_priority_sample\s*\)\s*\(\s*const\s+ssd_priority_sample_args\s*\*", src)
-    assert re.search(r"\bint\s*\(\s*ssd_priority_update\s*\)\s*\(\s*const\s+ssd_priority_update_args\s*\*", src)
-    assert set(abi.PRIORITY_SIGNATURES) == {"ssd_priority_sample", "ssd_priority_update"}
-    assert not set(abi.PRIORITY_SIGNATURES) & (set(abi.HIP_SIGNATURES) | set(abi.BEHAVIOUR_SIGNATURES) | set(abi.WINDOW_SIGNATURES))
-    lib = abi.load_library()
-    for name, (res, argtypes) in abi.PRIORITY_SIGNATURES.items():
-        assert getattr(lib, name).argtypes == argtypes and getattr(lib, name).restype is res
-    assert lib.ssd_abi_version() == abi.ABI_VERSION == 10                    # two exports more, no version change
+    """declaration, export and argtypes of every name of the table: tests/test_abi_symbols.py"""
+    assert {"ssd_priority_sample", "ssd_priority_update"} <= set(abi.HIP_SIGNATURES)
+    assert abi.load_library().ssd_abi_version() == abi.ABI_VERSION == 10     # two exports more, no version change
 
 
 def test_struct_sizes_and_constants_as_compiled(tmp_path):
-    S, U = abi.SsdPrioritySampleArgs, abi.SsdPriorityUpdateArgs
-    s_fields, u_fields = [f[0] for f in S._fields_], [f[0] for f in U._fields_]
+    """the constants and the two declarations as a C compiler sees them (sizeof / offsetof: tests/test_abi_symbols.py)"""
     c = tmp_path / "p.c"
     c.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ssd_hip.h"\nint main(){\n'
-                 'printf("%zu %zu %u %u %d %d\\n", sizeof(ssd_priority_sample_args), sizeof(ssd_priority_update_args), SSD_PRIORITY_ONE, SSD_PRIORITY_MAX,'
-                 ' SSD_PRIORITY_POP_MAX, SSD_SAMPLE_IDS_MAX);\n'
-                 + "".join('printf("%%zu\\n", offsetof(ssd_priority_sample_args, %s));\n' % f for f in s_fields)
-                 + "".join('printf("%%zu\\n", offsetof(ssd_priority_update_args, %s));\n' % f for f in u_fields)
-                 + 'int (*f)(const ssd_priority_sample_args*, void*) = ssd_priority_sample;\n'
+                 'printf("%u %u %d %d\\n", SSD_PRIORITY_ONE, SSD_PRIORITY_MAX, SSD_PRIORITY_POP_MAX, SSD_SAMPLE_IDS_MAX);\n'
+                 'int (*f)(const ssd_priority_sample_args*, void*) = ssd_priority_sample;\n'
                    'int (*g)(const ssd_priority_update_args*, void*) = ssd_priority_update;\nreturn f == 0 || g == 0;}')
     subprocess.check_call(["gcc", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(c), "-o", str(tmp_path / "p.o")])   # the declarations are usable
     c.write_text(re.sub(r"int \(\*f\).*return f == 0 \|\| g == 0;", "return 0;", c.read_text(), flags=re.S))
     exe = tmp_path / "p"
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
     got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got[:6] == [C.sizeof(S), C.sizeof(U), abi.PRIORITY_ONE, abi.PRIORITY_MAX, abi.PRIORITY_POP_MAX, abi.SAMPLE_IDS_MAX]
-    assert got[2:6] == [65536, 1 << 24, 1 << 20, 1024]
-    assert got[6:] == [getattr(S, f).offset for f in s_fields] + [getattr(U, f).offset for f in u_fields]
+    assert got == [abi.PRIORITY_ONE, abi.PRIORITY_MAX, abi.PRIORITY_POP_MAX, abi.SAMPLE_IDS_MAX] == [65536, 1 << 24, 1 << 20, 1024]
 
 
 PTR = 1 << 20                    # a dummy device pointer: non-null, 16-byte aligned, never touched (the checks run before any launch)

@@ -1,10 +1,9 @@
 """CPU suite of prioritised replay's initial priorities (config key per_initial_priority: "rollout"; ssd_rollout_priority): the
-export's symbol, ctypes table and struct size against the header, every refusal of the export, the setup refusals of the key, the
+export's declaration as compiled, every refusal of the export, the setup refusals of the key, the
 insert with priorities (wrap-around split, None = zeroing) on a host buffer, the operator's refusals, and the numpy restatement
 (tests/rollout_priority_util.py) pinned to the CPU tensor-op learner independently of the kernel."""
 import ctypes as C
 import os
-import re
 import subprocess
 from types import SimpleNamespace
 
@@ -23,31 +22,16 @@ NAME = "ssd_rollout_priority"
 
 # ---- 1. the export ------------------------------------------------------------------------------------------------------------------------
 def test_export_is_declared_exported_and_mirrored():
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ssd_hip.h")).read(), flags=re.S)
-    assert re.search(r"\bint\s*\(\s*ssd_rollout_priority\s*\)\s*\(\s*const\s+ssd_rollout_priority_args\s*\*", src)
-    assert set(abi.ROLLOUT_PRIORITY_SIGNATURES) == {NAME}
-    assert NAME not in (set(abi.HIP_SIGNATURES) | set(abi.BEHAVIOUR_SIGNATURES) | set(abi.WINDOW_SIGNATURES) | set(abi.PRIORITY_SIGNATURES)
-                        | set(abi.STORED_STATE_SIGNATURES))
-    lib = abi.load_library()
-    res, argtypes = abi.ROLLOUT_PRIORITY_SIGNATURES[NAME]
-    assert getattr(lib, NAME).argtypes == argtypes and getattr(lib, NAME).restype is res
-    assert lib.ssd_abi_version() == abi.ABI_VERSION                           # one export more, no version change
+    """declaration, export and argtypes of every name of the table: tests/test_abi_symbols.py"""
+    assert NAME in abi.HIP_SIGNATURES
+    assert abi.load_library().ssd_abi_version() == abi.ABI_VERSION            # one export more, no version change
 
 
 def test_struct_size_and_declaration_as_compiled(tmp_path):
-    S = abi.SsdRolloutPriorityArgs
-    fields = [f[0] for f in S._fields_]
+    """the declaration is usable from C (sizeof / offsetof: tests/test_abi_symbols.py)"""
     c = tmp_path / "s.c"
-    body = ('#include <stdio.h>\n#include <stddef.h>\n#include "ssd_hip.h"\nint main(){\n'
-            'printf("%zu\\n", sizeof(ssd_rollout_priority_args));\n'
-            + "".join('printf("%%zu\\n", offsetof(ssd_rollout_priority_args, %s));\n' % f for f in fields))
-    c.write_text(body + 'int (*f)(const ssd_rollout_priority_args*, void*) = ssd_rollout_priority;\nreturn f == 0;}')
-    subprocess.check_call(["gcc", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(c), "-o", str(tmp_path / "s.o")])   # the declaration is usable
-    c.write_text(body + "return 0;}")
-    exe = tmp_path / "s"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got[0] == C.sizeof(S) and got[1:] == [getattr(S, f).offset for f in fields]
+    c.write_text('#include "ssd_hip.h"\nint main(){\nint (*f)(const ssd_rollout_priority_args*, void*) = ssd_rollout_priority;\nreturn f == 0;}')
+    subprocess.check_call(["gcc", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(c), "-o", str(tmp_path / "s.o")])
 
 
 P = 1 << 20                      # a dummy device pointer: non-null, 16-byte aligned, never touched (the checks run before any launch)

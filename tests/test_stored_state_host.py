@@ -2,10 +2,9 @@
 ssd_gru_seq_fwd_h0 / _bwd_h0): the chain identity of the tensor-op recurrence (a window evaluated from the stored state is the same
 slice of the whole unroll) with its gradients against autograd of a plain unroll, the CPU learner on gathered windows against the slice
 of its whole-episode Q-values -- with the key off the same windows must MISS the slice, so the identity cannot pass vacuously --, the
-exports' symbols, ctypes tables and struct sizes against the header, the setup and operator refusals, and the key off as today's scheme."""
+exports' declarations as compiled and refusals, the setup and operator refusals, and the key off as today's scheme."""
 import ctypes as C
 import os
-import re
 import subprocess
 from types import SimpleNamespace
 
@@ -110,39 +109,24 @@ NAMES = {"ssd_store_hidden", "ssd_gru_seq_fwd_h0", "ssd_gru_seq_bwd_h0"}
 
 
 def test_exports_are_declared_exported_and_mirrored():
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ssd_hip.h")).read(), flags=re.S)
-    assert re.search(r"\bint\s*\(\s*ssd_store_hidden\s*\)\s*\(\s*const\s+ssd_store_hidden_args\s*\*", src)
-    for name in ("ssd_gru_seq_fwd_h0", "ssd_gru_seq_bwd_h0"):
-        assert re.search(r"\bint\s*\(\s*%s\s*\)\s*\(\s*const\s+float\s*\*\s*const\s*\*" % name, src)
-    assert "#define SSD_ABI_VERSION 10" in src
-    assert set(abi.STORED_STATE_SIGNATURES) == NAMES
-    assert not NAMES & (set(abi.HIP_SIGNATURES) | set(abi.BEHAVIOUR_SIGNATURES) | set(abi.WINDOW_SIGNATURES) | set(abi.PRIORITY_SIGNATURES))
-    lib = abi.load_library()
-    for name, (res, argtypes) in abi.STORED_STATE_SIGNATURES.items():
-        assert getattr(lib, name).argtypes == argtypes and getattr(lib, name).restype is res
-    assert lib.ssd_abi_version() == abi.ABI_VERSION == 10                    # three exports more, no version change
+    """declaration, export and argtypes of every name of the table: tests/test_abi_symbols.py"""
+    assert "#define SSD_ABI_VERSION 10" in open(os.path.join(ROOT, "include", "ssd_hip.h")).read()
+    assert NAMES <= set(abi.HIP_SIGNATURES)
+    assert abi.load_library().ssd_abi_version() == abi.ABI_VERSION == 10     # three exports more, no version change
 
 
 def test_struct_size_and_declarations_as_compiled(tmp_path):
-    S = abi.SsdStoreHiddenArgs
-    fields = [f[0] for f in S._fields_]
+    """the three declarations are usable from C (sizeof / offsetof: tests/test_abi_symbols.py)"""
     c = tmp_path / "s.c"
-    c.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ssd_hip.h"\nint main(){\n'
-                 'printf("%zu\\n", sizeof(ssd_store_hidden_args));\n'
-                 + "".join('printf("%%zu\\n", offsetof(ssd_store_hidden_args, %s));\n' % f for f in fields)
-                 + 'int (*f)(const ssd_store_hidden_args*, void*) = ssd_store_hidden;\n'
+    c.write_text('#include "ssd_hip.h"\nint main(){\n'
+                 'int (*f)(const ssd_store_hidden_args*, void*) = ssd_store_hidden;\n'
                    'int (*g)(const float* const*, int32_t, const float* const*, const float* const*, int32_t, const float* const*, int64_t, int64_t, float*,'
                    ' float*, float*, int32_t, int32_t, int32_t, void*) = ssd_gru_seq_fwd_h0;\n'
                    'int (*h)(const float* const*, const float*, const float*, const float*, const float* const*, int32_t, float* const*, int32_t, float*,'
                    ' float*, float*, int32_t, int32_t, int32_t, int32_t, void*) = ssd_gru_seq_bwd_h0;\nreturn f == 0 || g == 0 || h == 0;}')
     subprocess.check_call(["gcc", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(c), "-o", str(tmp_path / "s.o")])   # the declarations are usable
-    c.write_text(re.sub(r"int \(\*f\).*return f == 0 \|\| g == 0 \|\| h == 0;", "return 0;", c.read_text(), flags=re.S))
-    exe = tmp_path / "s"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    assert got[0] == C.sizeof(S) and got[1:] == [getattr(S, f).offset for f in fields]
     # the argument counts of the two sequence exports as the header declares them
-    assert len(abi.STORED_STATE_SIGNATURES["ssd_gru_seq_fwd_h0"][1]) == 15 and len(abi.STORED_STATE_SIGNATURES["ssd_gru_seq_bwd_h0"][1]) == 16
+    assert len(abi.HIP_SIGNATURES["ssd_gru_seq_fwd_h0"][1]) == 15 and len(abi.HIP_SIGNATURES["ssd_gru_seq_bwd_h0"][1]) == 16
 
 
 P = 1 << 20                      # a dummy device pointer: non-null, 16-byte aligned, never touched (the checks run before any launch)

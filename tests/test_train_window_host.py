@@ -1,8 +1,8 @@
 """CPU suite of training on sampled time windows with burn-in (config keys train_window / train_burn_in / train_window_norm;
 ssd_sample_windows / ssd_gather_windows; ReplayBuffer.sample_windows / gather_windows): the draw contract against a restatement written
 from the header, the host gather against numpy slices, the tensor-op learner on windows against the numbers the reference recorded on
-time slices (tests/golden/learner_train_window.npz, tools/gen_train_window_golden.py), the "episode" normaliser, the exports' symbols,
-struct size and refusals, the config refusals, and train_window: 0 as today's path."""
+time slices (tests/golden/learner_train_window.npz, tools/gen_train_window_golden.py), the "episode" normaliser, the exports'
+declarations as compiled and refusals, the config refusals, and train_window: 0 as today's path."""
 import ctypes as C
 import os
 import re
@@ -210,17 +210,11 @@ def test_td_loss_args_carry_the_normaliser():
         assert (t.seq_len, t.t_slots, t.batch) == (want, 7, 4)
 
 
-# ---- 5. exports: symbol, struct size, refusals; config refusals ---------------------------------------------------------------------------------
+# ---- 5. exports: declarations as compiled, refusals; config refusals -----------------------------------------------------------------------------
 def test_exports_are_declared_exported_and_mirrored():
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ssd_hip.h")).read(), flags=re.S)
-    assert re.search(r"\bint\s*\(\s*ssd_sample_windows\s*\)\s*\(\s*uint64_t\s+seed", src)
-    assert re.search(r"\bint\s*\(\s*ssd_gather_windows\s*\)\s*\(\s*const\s+ssd_window_field\s*\*", src)
-    assert set(abi.WINDOW_SIGNATURES) == {"ssd_sample_windows", "ssd_gather_windows"}
-    assert not set(abi.WINDOW_SIGNATURES) & (set(abi.HIP_SIGNATURES) | set(abi.BEHAVIOUR_SIGNATURES))
-    lib = abi.load_library()
-    for name, (res, argtypes) in abi.WINDOW_SIGNATURES.items():
-        assert getattr(lib, name).argtypes == argtypes and getattr(lib, name).restype is res
-    assert lib.ssd_abi_version() == abi.ABI_VERSION == 10                    # two exports more, no version change
+    """declaration, export and argtypes of every name of the table: tests/test_abi_symbols.py"""
+    assert {"ssd_sample_windows", "ssd_gather_windows"} <= set(abi.HIP_SIGNATURES)
+    assert abi.load_library().ssd_abi_version() == abi.ABI_VERSION == 10     # two exports more, no version change
 
 
 def test_struct_size_and_declarations_as_compiled(tmp_path):
@@ -236,8 +230,7 @@ def test_struct_size_and_declarations_as_compiled(tmp_path):
     exe = tmp_path / "w"
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
     got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    F = abi.SsdWindowField
-    assert got == [C.sizeof(F), F.dst.offset, F.slot_bytes.offset, F.filled.offset, abi.COPY_BLOCKS_MAX, abi.SAMPLE_IDS_MAX] == [32, 8, 16, 24, 32, 1024]
+    assert got == [32, 8, 16, 24, abi.COPY_BLOCKS_MAX, abi.SAMPLE_IDS_MAX] == [32, 8, 16, 24, 32, 1024]      # the layout itself, as literals
 
 
 P = 1 << 20                      # a dummy device pointer: non-null, 16-byte aligned, never touched (the checks run before any launch)
