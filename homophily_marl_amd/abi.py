@@ -53,6 +53,7 @@ BEHAVIOUR_ROLES = ("idle", "cleaner", "harvester", "mixed")
 PRIORITY_ONE = 65536
 PRIORITY_MAX = 1 << 24
 PRIORITY_POP_MAX = 1 << 20
+PRIORITY_SEGMENTS_MAX = 256       # windows per episode of a per-window priority table (per_unit "window")
 
 
 # ---- struct classes (include/ssd_hip.h, in its order) ------------------------------------------------------------------------
@@ -134,7 +135,8 @@ class SsdWindowField(C.Structure):
 
 class SsdPrioritySampleArgs(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("call", C.c_uint32), ("population", C.c_int32), ("count", C.c_int32), ("n_starts", C.c_int32),
-                ("beta", C.c_float), ("table", C.c_void_p), ("ids", C.c_void_p), ("t0", C.c_void_p), ("weights", C.c_void_p), ("log", C.c_void_p)]
+                ("beta", C.c_float), ("table", C.c_void_p), ("ids", C.c_void_p), ("t0", C.c_void_p), ("weights", C.c_void_p), ("log", C.c_void_p),
+                ("n_segments", C.c_int32), ("seg_stride", C.c_int32), ("last_start", C.c_int32), ("entries", C.c_void_p)]
 
 
 class SsdPriorityUpdateArgs(C.Structure):
@@ -151,7 +153,8 @@ class SsdRolloutPriorityArgs(C.Structure):
                 ("actions", C.c_void_p), ("actions_inc", C.c_void_p), ("reward", C.c_void_p), ("terminated", C.c_void_p), ("filled", C.c_void_p),
                 ("gamma_env", C.c_float), ("gamma_inc", C.c_float), ("reward_scale", C.c_float), ("incentive_ratio", C.c_float),
                 ("incentive_cost", C.c_float), ("incentive", C.c_float), ("seq_len", C.c_float), ("alpha", C.c_float), ("eta", C.c_float),
-                ("eps", C.c_float), ("carry", C.c_void_p), ("acc", C.c_void_p), ("q_init", C.c_void_p)]
+                ("eps", C.c_float), ("carry", C.c_void_p), ("acc", C.c_void_p), ("q_init", C.c_void_p),
+                ("n_segments", C.c_int32), ("win_len", C.c_int32), ("seg_stride", C.c_int32), ("burn_in", C.c_int32)]
 
 
 class SsdAdamJob(C.Structure):

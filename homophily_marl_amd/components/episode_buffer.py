@@ -178,12 +178,16 @@ class ReplayBuffer(EpisodeBatch):
         self._sample_calls = 0
         # the draws' persistent tensors (_draw_tensors): ids / t0 int64 [batch_size]; weights f32 [batch_size] and log f32 [4] exist only
         # once a prioritised draw was made
-        self._draws = SimpleNamespace(ids=None, t0=None, weights=None, log=None)
+        self._draws = SimpleNamespace(ids=None, t0=None, entries=None, weights=None, log=None)
         # time windows (sample_windows): "episode" | "window", the length a window batch's rewards are divided by (gather_windows)
         self.window_norm = "episode"
         self.last_window_ids = self.last_window_t0 = None
         # prioritised replay (enable_priorities): the fixed-point priority table, one entry per slot; None = the feature is off
         self.priority_table = None
+        # a priority per training window (enable_priorities(segments=S, ...)): S entries per slot, entry (slot, k) at slot S + k, and
+        # the grid (S, s, last_start) of ops.window_grid the draws map entries with; None = one entry per slot
+        self.priority_segments = 1
+        self.priority_grid = self.priority_window = None
 
     def reserve(self, n):
         """A view over the next n episode slots, for producers that write whole episodes in place (vectorised runners): hand
@@ -197,16 +201,18 @@ class ReplayBuffer(EpisodeBatch):
 
     def insert_episode_batch(self, ep_batch, priorities=None):
         """priorities (prioritised replay, per_initial_priority "rollout"): a device int32 tensor of ep_batch.batch_size fixed-point
-        priorities the episodes enter the table with (one ops.copy_blocks launch per contiguous run of slots; split with the batch
-        on wrap-around).  None: the slots are zeroed -- drawn at the table's maximum until trained on."""
+        priorities the episodes enter the table with -- [n], or [n, S] with a priority per window (one ops.copy_blocks launch per
+        contiguous run of slots; split with the batch on wrap-around).  None: the slots' entries are zeroed -- drawn at the table's
+        maximum until trained on."""
         n = ep_batch.batch_size
         res = getattr(ep_batch, "_reserved", None)
         if priorities is not None:
             if self.priority_table is None:
                 raise ValueError("insert_episode_batch: priorities given, but enable_priorities() was not called")
-            if priorities.dtype != th.int32 or priorities.dim() != 1 or priorities.numel() != n or priorities.device != self.priority_table.device:
-                raise ValueError("insert_episode_batch: priorities %s %s on %s: int32 [%d] on %s expected"
-                                 % (tuple(priorities.shape), priorities.dtype, priorities.device, n, self.priority_table.device))
+            want = (n,) if self.priority_grid is None else (n, self.priority_segments)
+            if priorities.dtype != th.int32 or tuple(priorities.shape) != want or priorities.device != self.priority_table.device:
+                raise ValueError("insert_episode_batch: priorities %s %s on %s: int32 %s on %s expected"
+                                 % (tuple(priorities.shape), priorities.dtype, priorities.device, list(want), self.priority_table.device))
         if self.buffer_index + n > self.buffer_size:
             left = self.buffer_size - self.buffer_index
             self.insert_episode_batch(ep_batch[0:left, :], None if priorities is None else priorities[:left])
@@ -257,9 +263,11 @@ class ReplayBuffer(EpisodeBatch):
         d = self._draws
         if d.ids is None or d.ids.numel() != batch_size:
             idx = th.empty(2, batch_size, dtype=th.long, device=self.device)
-            d = self._draws = SimpleNamespace(ids=idx[0], t0=idx[1], weights=None, log=None)
+            d = self._draws = SimpleNamespace(ids=idx[0], t0=idx[1], entries=None, weights=None, log=None)
         if prioritized and d.weights is None:
             d.weights, d.log = th.empty(batch_size, dtype=th.float32, device=self.device), th.empty(4, dtype=th.float32, device=self.device)
+        if prioritized and self.priority_grid is not None and d.entries is None:      # (a priority per window: the drawn table entries)
+            d.entries = th.empty(batch_size, dtype=th.long, device=self.device)
         return d
 
     def _fits(self, out, batch_size, slots):
@@ -342,24 +350,41 @@ class ReplayBuffer(EpisodeBatch):
         return self.gather_windows(ids, t0, window, burn_in, out=out)
 
     # ---- prioritised replay (config keys prioritized_replay / per_*) --------------------------------------------------------------
-    def enable_priorities(self):
+    def enable_priorities(self, segments=1, stride=None, window=None):
         """Allocate the priority table: one fixed-point entry per slot (int32 storage of the u32 values of include/ssd_hip.h:
         PRIORITY_ONE = 1.0, 0 = never trained on) on the buffer's device.  From then on every insert zeroes the slots it advances over
-        and sample_prioritized can draw."""
-        if self.buffer_size > ops.abi.PRIORITY_POP_MAX:
-            raise ValueError("prioritized replay: buffer_size %d over PRIORITY_POP_MAX = %d" % (self.buffer_size, ops.abi.PRIORITY_POP_MAX))
+        and sample_prioritized can draw.
+        window = L with stride = s and segments = S: a priority per training window -- S entries per slot, entry (slot, k) at
+        slot S + k for the window starting at min(k s, T - L) (ops.window_grid(T, L, s) must give S); sample_prioritized(window=L) then
+        draws entries.  The layout is fixed by the first call."""
+        grid = None
+        if window is not None:
+            grid = ops.window_grid(self.max_seq_length - 1, window, stride or 0)
+            if grid[0] != segments or segments > ops.abi.PRIORITY_SEGMENTS_MAX:
+                raise ValueError("prioritized replay: segments %r is not the %d windows of length %r at stride %r in %d transitions, or over PRIORITY_SEGMENTS_MAX = %d"
+                                 % (segments, grid[0], window, grid[1], self.max_seq_length - 1, ops.abi.PRIORITY_SEGMENTS_MAX))
+        elif segments != 1:
+            raise ValueError("prioritized replay: segments %r without a window" % (segments,))
+        if self.buffer_size * segments > ops.abi.PRIORITY_POP_MAX:
+            raise ValueError("prioritized replay: buffer_size %d * %d entries over PRIORITY_POP_MAX = %d" % (self.buffer_size, segments, ops.abi.PRIORITY_POP_MAX))
         if self.priority_table is None:
-            self.priority_table = th.zeros(self.buffer_size, dtype=th.int32, device=self.device)
+            self.priority_segments, self.priority_grid, self.priority_window = segments, grid, window
+            self.priority_table = th.zeros(self.buffer_size * segments, dtype=th.int32, device=self.device)
+        elif (self.priority_segments, self.priority_grid) != (segments, grid):
+            raise ValueError("prioritized replay: the table exists with %d entries per slot (grid %r)" % (self.priority_segments, self.priority_grid))
         return self.priority_table
 
     def _reset_priorities(self, start, n):
-        """the n slots from `start` hold new episodes: their priorities go back to 0 (one ssd_fill_blocks launch on the device)"""
+        """the n slots from `start` hold new episodes: their entries go back to 0 (one ssd_fill_blocks launch on the device)"""
         if self.priority_table is not None and n > 0:
-            ops.fill_blocks([(self.priority_table[start:start + n], 0)])
+            S = self.priority_segments
+            ops.fill_blocks([(self.priority_table[start * S:(start + n) * S], 0)])
 
     def _write_priorities(self, start, priorities):
         """the slots from `start` hold new episodes that bring their priorities along (one ssd_copy_blocks launch on the device)"""
-        dst = self.priority_table[start:start + priorities.numel()]
+        S = self.priority_segments
+        dst = self.priority_table[start * S:start * S + priorities.numel()]
+        priorities = priorities.reshape(-1)
         if dst.is_cuda:
             ops.copy_blocks([(priorities.contiguous(), dst)])
         else:
@@ -372,7 +397,10 @@ class ReplayBuffer(EpisodeBatch):
         back with batch.priority = (table, ids, weights): the table, the drawn ids (int64) and the importance weights (f32,
         (population qeff / total)^(-beta) over their maximum), and batch.priority_log (f32 [4]: mean and max priority, smallest
         weight, distinct ids).  Ids, weights and log live in tensors that persist across calls: a captured train step sees stable
-        addresses.  The learner writes the new priorities back in its train step (ops.priority_update)."""
+        addresses.  The learner writes the new priorities back in its train step (ops.priority_update).
+        With a priority per window (enable_priorities(segments=S, ...)) the draw is over table entries: a drawn entry f is window
+        f % S of episode f // S -- no start is drawn, several strata in one episode are several windows of it -- and
+        batch.priority = (table, entries, weights): the learner's update writes table[entries[e]] without knowing the layout."""
         assert self.can_sample(batch_size)
         if self.priority_table is None:
             raise ValueError("sample_prioritized: enable_priorities() was not called")
@@ -381,16 +409,18 @@ class ReplayBuffer(EpisodeBatch):
         n_starts = self.max_seq_length - window if window else 1
         if n_starts < 1 or window < 0:
             raise ValueError("sample_prioritized: window %r outside 0 .. %d" % (window, self.max_seq_length - 1))
+        if self.priority_grid is not None and window != self.priority_window:
+            raise ValueError("sample_prioritized: the table holds priorities of windows of %r transitions, window %r asked" % (self.priority_window, window))
         d = self._draw_tensors(batch_size, prioritized=True)
-        ops.priority_sample(self._sample_seed, self._sample_calls, self.priority_table, self.episodes_in_buffer, batch_size, n_starts, beta,
-                            d.ids, d.t0, d.weights, d.log)
+        ops.priority_sample(self._sample_seed, self._sample_calls, self.priority_table, self.episodes_in_buffer * self.priority_segments, batch_size,
+                            n_starts, beta, d.ids, d.t0, d.weights, d.log, segments=self.priority_grid, entries_out=d.entries)
         self._sample_calls += 1
         if window:
             self.last_window_ids, self.last_window_t0 = d.ids, d.t0
             batch = self.gather_windows(d.ids, d.t0, window, burn_in, out=out)
         else:
             batch = self._gather_episodes(d.ids, out)
-        batch.priority, batch.priority_log = (self.priority_table, d.ids, d.weights), d.log
+        batch.priority, batch.priority_log = (self.priority_table, d.ids if self.priority_grid is None else d.entries, d.weights), d.log
         return batch
 
     def sample_latest(self, batch_size):

@@ -565,6 +565,13 @@ int ssd_priority_sample(const ssd_priority_sample_args* a, void* stream) {
     if (a->n_starts < 1) return fail(SSD_ERR_INVALID, "ssd_priority_sample: n_starts >= 1");
     if (!unit_interval(a->beta)) return fail(SSD_ERR_INVALID, "ssd_priority_sample: beta outside [0, 1]");
     if (reinterpret_cast<uintptr_t>(a->table) & 3) return fail(SSD_ERR_INVALID, "ssd_priority_sample: table is not 4-byte aligned");
+    if (a->n_segments < 0 || a->n_segments > SSD_PRIORITY_SEGMENTS_MAX) return fail(SSD_ERR_INVALID, "ssd_priority_sample: n_segments outside 0 .. SSD_PRIORITY_SEGMENTS_MAX");
+    if (a->n_segments) {                                                     // a priority per window: population counts entries
+        if (!a->entries) return fail(SSD_ERR_INVALID, "ssd_priority_sample: n_segments >= 1 with null entries");
+        if (a->seg_stride < 1 || a->last_start < 0) return fail(SSD_ERR_INVALID, "ssd_priority_sample: seg_stride < 1 or last_start < 0");
+        if ((int64_t)(a->n_segments - 1) * a->seg_stride < a->last_start) return fail(SSD_ERR_INVALID, "ssd_priority_sample: (n_segments - 1) * seg_stride does not reach last_start");
+        if (a->population % a->n_segments) return fail(SSD_ERR_INVALID, "ssd_priority_sample: population is not a multiple of n_segments");
+    }
     launch_priority_sample(a, (hipStream_t)stream);
     return launched();
 }
@@ -603,6 +610,15 @@ int ssd_rollout_priority(const ssd_rollout_priority_args* a, void* stream) {
         return fail(SSD_ERR_INVALID, "ssd_rollout_priority: q_env, q_inc, reward, carry, acc and q_init must be 4-byte aligned");
     if ((reinterpret_cast<uintptr_t>(a->t_index) | reinterpret_cast<uintptr_t>(a->actions) | reinterpret_cast<uintptr_t>(a->actions_inc) | reinterpret_cast<uintptr_t>(a->filled)) & 7)
         return fail(SSD_ERR_INVALID, "ssd_rollout_priority: t_index, actions, actions_inc and filled must be 8-byte aligned");
+    if (a->n_segments < 0 || a->n_segments > SSD_PRIORITY_SEGMENTS_MAX) return fail(SSD_ERR_INVALID, "ssd_rollout_priority: n_segments outside 0 .. SSD_PRIORITY_SEGMENTS_MAX");
+    if (a->n_segments) {                                                     // a priority per window of the stride grid
+        const int T = a->t_slots - 1, L = a->win_len, s = a->seg_stride;
+        if (L < 1 || L > T) return fail(SSD_ERR_INVALID, "ssd_rollout_priority: win_len outside 1 .. t_slots - 1");
+        if (s < 1 || s > L) return fail(SSD_ERR_INVALID, "ssd_rollout_priority: seg_stride outside 1 .. win_len");
+        if ((L + s - 1) / s > 8) return fail(SSD_ERR_INVALID, "ssd_rollout_priority: ceil(win_len / seg_stride) over 8");
+        if (a->burn_in < 0 || a->burn_in >= L) return fail(SSD_ERR_INVALID, "ssd_rollout_priority: burn_in outside 0 .. win_len - 1");
+        if (a->n_segments != (T - L + s - 1) / s + 1) return fail(SSD_ERR_INVALID, "ssd_rollout_priority: n_segments != ceil((T - win_len) / seg_stride) + 1");
+    }
     launch_rollout_priority(a, (hipStream_t)stream);
     return launched();
 }

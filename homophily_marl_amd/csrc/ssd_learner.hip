@@ -1063,8 +1063,118 @@ __global__ __launch_bounds__(PRI_THREADS) void k_priority_sample(ssd_priority_sa
         a.log[3] = (float)(1u + s_red[0]);
     }
 }
+// k_priority_sample_seq (n_segments >= 1): the table holds n_segments entries per slot; the same draw over entries, the drawn entry filed
+// and mapped to (slot, window start) where k_priority_sample draws a uniform start.  A copy, not a second instantiation of a shared
+// body: as a template the compiler commuted one add of k_priority_sample, and that kernel's instruction stream is kept as it was.
+// Whatever changes above changes here.
+__global__ __launch_bounds__(PRI_THREADS) void k_priority_sample_seq(ssd_priority_sample_args a) {
+    __shared__ uint64_t s_cum[PRI_THREADS];
+    __shared__ uint64_t s_wave[PRI_THREADS / 64];
+    __shared__ uint32_t s_red[PRI_THREADS];
+    __shared__ float s_w[PRI_THREADS];
+    __shared__ int32_t s_id[PRI_THREADS];
+    if (blockIdx.x != 0) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int P = a.population, count = a.count;
+    const uint32_t* __restrict__ tab = a.table;
+    // pass 1: qmax
+    uint32_t m = 0;
+    for (int k = tid; k < P; k += PRI_THREADS) { const uint32_t q = tab[k]; m = q > m ? q : m; }
+    s_red[tid] = m;
+    __syncthreads();
+    for (int w = PRI_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) { const uint32_t o = s_red[tid + w]; if (o > s_red[tid]) s_red[tid] = o; }
+        __syncthreads();
+    }
+    const uint32_t qmax = s_red[0] ? s_red[0] : SSD_PRIORITY_ONE;
+    __syncthreads();
+    // pass 2: chunk sums
+    const int chunk = (P + PRI_THREADS - 1) / PRI_THREADS;
+    const int k0 = tid * chunk < P ? tid * chunk : P, k1 = k0 + chunk < P ? k0 + chunk : P;
+    uint64_t sum = 0;
+    if ((chunk & 3) == 0 && (reinterpret_cast<uintptr_t>(tab) & 15) == 0) {       // k0 is a multiple of 4; so is k1, or it is P
+        int k = k0;
+        for (; k + 4 <= k1; k += 4) {
+            const uint4 v = *reinterpret_cast<const uint4*>(tab + k);
+            sum += (uint64_t)(v.x ? v.x : qmax) + (v.y ? v.y : qmax) + (v.z ? v.z : qmax) + (v.w ? v.w : qmax);
+        }
+        for (; k < k1; ++k) { const uint32_t q = tab[k]; sum += q ? q : qmax; }
+    } else {
+        for (int k = k0; k < k1; ++k) { const uint32_t q = tab[k]; sum += q ? q : qmax; }
+    }
+    // inclusive scan of the chunk sums
+    uint64_t inc = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t o = pri_shfl_up(inc, d);
+        if (lane >= d) inc += o;
+    }
+    if (lane == 63) s_wave[wave] = inc;
+    __syncthreads();
+    uint64_t before = 0;
+    for (int w = 0; w < wave; ++w) before += s_wave[w];
+    s_cum[tid] = inc + before;
+    __syncthreads();
+    const uint64_t total = s_cum[PRI_THREADS - 1];
+    // the draws
+    const uint32_t s0 = (uint32_t)a.seed, s1 = (uint32_t)(a.seed >> 32);
+    int id = 0;
+    uint32_t qe = 0xFFFFFFFFu;
+    if (tid < count) {
+        const uint64_t lo = total * (uint64_t)tid / (uint64_t)count, hi = total * (uint64_t)(tid + 1) / (uint64_t)count;   // total < 2^44, tid + 1 <= 2^10
+        const uint64_t width = hi - lo, d = sample_draw(s0, s1, a.call, (uint32_t)tid);
+        const uint64_t x = lo + d * (width >> 32) + ((d * (width & 0xFFFFFFFFull)) >> 32);          // floor(d width / 2^32), exactly
+        int c_lo = 0, c_hi = PRI_THREADS - 1;                                                      // s_cum[1023] = total > x
+        while (c_lo < c_hi) {
+            const int mid = (c_lo + c_hi) >> 1;
+            if (s_cum[mid] > x) c_hi = mid; else c_lo = mid + 1;
+        }
+        uint64_t acc = c_lo ? s_cum[c_lo - 1] : 0;
+        const int w0 = c_lo * chunk, w1 = w0 + chunk < P ? w0 + chunk : P;                           // s_cum[c_lo] > acc: the chunk is not empty
+        id = w1 - 1;
+        qe = qmax;
+        for (int k = w0; k < w1; ++k) {
+            const uint32_t q = tab[k], v = q ? q : qmax;
+            acc += v;
+            if (acc > x) { id = k; qe = v; break; }
+        }
+        const int64_t start = (int64_t)(id % a.n_segments) * a.seg_stride;
+        a.entries[tid] = (int64_t)id;
+        a.ids[tid] = (int64_t)(id / a.n_segments);
+        a.t0[tid] = start < a.last_start ? start : (int64_t)a.last_start;
+    }
+    // the smallest sampled qeff carries the largest weight
+    s_id[tid] = id;
+    s_red[tid] = qe;
+    __syncthreads();
+    for (int w = PRI_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) { const uint32_t o = s_red[tid + w]; if (o < s_red[tid]) s_red[tid] = o; }
+        __syncthreads();
+    }
+    const uint32_t qmin = s_red[0];
+    __syncthreads();
+    float wgt = 2.f;
+    if (tid < count) {
+        wgt = (float)pow((double)qe / (double)qmin, -(double)a.beta);
+        a.weights[tid] = wgt;
+    }
+    s_w[tid] = wgt;
+    s_red[tid] = (tid > 0 && tid < count && id != s_id[tid - 1]) ? 1u : 0u;
+    __syncthreads();
+    for (int w = PRI_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) { s_w[tid] = fminf(s_w[tid], s_w[tid + w]); s_red[tid] += s_red[tid + w]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        a.log[0] = (float)((double)total / (double)P / (double)SSD_PRIORITY_ONE);
+        a.log[1] = (float)((double)qmax / (double)SSD_PRIORITY_ONE);
+        a.log[2] = s_w[0];
+        a.log[3] = (float)(1u + s_red[0]);
+    }
+}
 void launch_priority_sample(const ssd_priority_sample_args* a, hipStream_t stream) {
-    hipLaunchKernelGGL(k_priority_sample, dim3(1), dim3(PRI_THREADS), 0, stream, *a);
+    if (a->n_segments) hipLaunchKernelGGL(k_priority_sample_seq, dim3(1), dim3(PRI_THREADS), 0, stream, *a);
+    else hipLaunchKernelGGL(k_priority_sample, dim3(1), dim3(PRI_THREADS), 0, stream, *a);
 }
 
 // k_priority_rows: sample e = blockIdx.x.  Its T n rows of partials -> q_new[e]; then its blocks of dq_env / dq_inc times weights[e].
@@ -1219,8 +1329,116 @@ __global__ __launch_bounds__(256) void k_rollout_priority(const ssd_rollout_prio
         a.q_init[env] = (uint32_t)rintf(fminf(fmaxf(q, 1.f), (float)SSD_PRIORITY_MAX));
     }
 }
+// The per-window kernel's pieces.  rollout_priority_row / rollout_priority_carry / rollout_priority_value restate k_rollout_priority's
+// row, carry and tail statement for statement (same expressions, same f32 operation order); k_rollout_priority itself keeps its text:
+// routed through these functions its block layout changed, and that kernel's instruction stream is kept as it was.  Whatever changes
+// above changes here.
+// rollout_priority_row: d and mask of row t - 1 (t >= 1) of (env, agent i) from carry, slot t - 1 of the storage and this slot's Q.
+__device__ __forceinline__ void rollout_priority_row(const ssd_rollout_priority_args& a, int64_t env, int i, int64_t t, const float* __restrict__ qe,
+                                                     const float* __restrict__ qi, const float* carry, float& d, float& mask) {
+    const int T1 = a.t_slots, n = a.n_agents, A = a.n_actions;
+    const int64_t bt = env * T1 + (t - 1);                                      // (env, slot t - 1)
+    mask = (a.filled ? (float)a.filled[bt] : 1.f) * (t - 1 ? 1.f - (float)a.terminated[bt - 1] : 1.f);
+    const int64_t* __restrict__ ainc = a.actions_inc + bt * n * n;              // [giver][receiver]
+    int give = 0, rp = 0, rn = 0;
+    for (int j = 0; j < n; ++j) {
+        if (j == i) continue;
+        give += ainc[(int64_t)i * n + j] != 0;
+        const int64_t x = ainc[(int64_t)j * n + i];
+        rp += x == 1; rn += x == 2;
+    }
+    const float r = a.reward[bt * n + i] / a.reward_scale;
+    const float rv = (float)(rp - rn);
+    const float r_env = (r + rv * a.incentive_ratio * a.incentive) / a.seq_len;
+    const float r_inc = (r - (float)give * a.incentive_cost * a.incentive) / a.seq_len;
+    const float live = 1.f - (float)a.terminated[bt];
+    float v_env = -INFINITY;
+    for (int k = 0; k < A; ++k) {
+        const float q = (a.avail_bits >> k) & 1u ? qe[k] : kNeg;
+        if (q > v_env) v_env = q;
+    }
+    float v_inc = 0.f;
+    for (int j = 0; j < n; ++j) {
+        if (j == i) continue;
+        const float* s = qi + j * 3;
+        v_inc += s[1] > s[0] ? (s[2] > s[1] ? s[2] : s[1]) : (s[2] > s[0] ? s[2] : s[0]);
+    }
+    const float td_env = carry[0] - (r_env + a.gamma_env * live * v_env);
+    const float td_inc = carry[1] - (r_inc + a.gamma_inc * live * v_inc);
+    d = sqrtf((td_env * mask) * (td_env * mask) + (td_inc * mask) * (td_inc * mask));
+}
+// rollout_priority_carry: the Q-values of the actions the heads just filed in slot t (t < T), for the row the next launch forms.
+__device__ __forceinline__ void rollout_priority_carry(const ssd_rollout_priority_args& a, int64_t env, int i, int64_t t, const float* __restrict__ qe,
+                                                       const float* __restrict__ qi, float* carry) {
+    const int n = a.n_agents, A = a.n_actions;
+    const int64_t row = (env * a.t_slots + t) * n + i;                          // (env, slot t, agent i)
+    int64_t a_t = a.actions[row];
+    a_t = a_t < 0 ? 0 : a_t >= A ? A - 1 : a_t;
+    const int64_t* __restrict__ mine = a.actions_inc + row * n;
+    float chosen = 0.f;
+    for (int j = 0; j < n; ++j) {
+        if (j == i) continue;
+        int64_t c = mine[j];
+        c = c < 0 ? 0 : c > 2 ? 2 : c;
+        chosen += qi[j * 3 + c];
+    }
+    carry[0] = qe[a_t]; carry[1] = chosen;
+}
+// rollout_priority_value: (max d, sum d, sum mask) of a set of rows -> the fixed-point priority (k_priority_rows' tail).
+__device__ __forceinline__ uint32_t rollout_priority_value(const ssd_rollout_priority_args& a, float m, float s, float c) {
+    const float p = a.eta * m + (1.f - a.eta) * s / fmaxf(1.f, c) + a.eps;
+    float q = powf(p, a.alpha) * (float)SSD_PRIORITY_ONE;
+    q = q == q ? q : (float)SSD_PRIORITY_MAX;
+    return (uint32_t)rintf(fminf(fmaxf(q, 1.f), (float)SSD_PRIORITY_MAX));
+}
+// k_rollout_priority_seq (n_segments = S >= 1): a priority per window of the stride grid.  The same lanes, rows and carry; acc is
+// [N, n, S, 3] and row t - 1 goes into the accumulators of the windows whose loss rows contain it -- k from the first window that
+// still reaches the row to the last that has started, each tested (the clamped last window is off the stride) -- and into no other.
+// At t == T every window's accumulators are read back by the thread that wrote them and reduced over the agents as above.
+__global__ __launch_bounds__(256) void k_rollout_priority_seq(const ssd_rollout_priority_args a) {
+    const int64_t t = *a.t_index;
+    const int T = a.t_slots - 1, n = a.n_agents, S = a.n_segments, L = a.win_len, st = a.seg_stride, last = T - L;
+    if (t < 0 || t > T) return;                                                 // (uniform over the launch)
+    const int lane = threadIdx.x & 63, i = lane & 15, base = lane & 48;
+    const int64_t env = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+    const bool active = env < a.n_env && i < n;
+    float* acc = a.acc + (env * n + i) * (int64_t)S * 3;                        // (dereferenced by active lanes only)
+    if (active) {
+        const float* __restrict__ qe = a.q_env + (int64_t)i * a.q_env_agent_stride + env * a.q_env_env_stride;
+        const float* __restrict__ qi = a.q_inc + (int64_t)i * a.q_inc_agent_stride + env * a.q_inc_env_stride;
+        float* carry = a.carry + (env * n + i) * 2;
+        if (t == 0) {
+            for (int k = 0; k < S * 3; ++k) acc[k] = 0.f;
+        } else {
+            float d, mask;
+            rollout_priority_row(a, env, i, t, qe, qi, carry, d, mask);
+            const int row = (int)t - 1;
+            const int k_lo = row < L ? 0 : (row - L) / st + 1;                  // the smallest k with k st + L > row
+            const int k_hi = row / st + 1 < S - 1 ? row / st + 1 : S - 1;       // no later window has started (the last one may be clamped back)
+            for (int k = k_lo; k <= k_hi; ++k) {
+                const int start = k * st < last ? k * st : last;
+                if (row < start + (start > 0 ? a.burn_in : 0) || row >= start + L) continue;
+                float* w = acc + k * 3;
+                w[0] = fmaxf(w[0], d); w[1] += d; w[2] += mask;
+            }
+        }
+        if (t < T) rollout_priority_carry(a, env, i, t, qe, qi, carry);
+    }
+    if (t < T) return;
+    for (int k = 0; k < S; ++k) {                                               // (uniform: every lane of the wave takes part)
+        float mx = 0.f, sum = 0.f, cnt = 0.f;
+        if (active) { mx = acc[k * 3]; sum = acc[k * 3 + 1]; cnt = acc[k * 3 + 2]; }
+        float m = mx;
+        for (int w = 8; w > 0; w >>= 1) m = fmaxf(m, __shfl_xor(m, w));
+        float s = 0.f, c = 0.f;
+        for (int j = 0; j < n; ++j) { s += __shfl(sum, base + j); c += __shfl(cnt, base + j); }
+        if (active && i == 0) a.q_init[env * S + k] = rollout_priority_value(a, m, s, c);
+    }
+}
 void launch_rollout_priority(const ssd_rollout_priority_args* a, hipStream_t stream) {
-    hipLaunchKernelGGL(k_rollout_priority, dim3((unsigned)((a->n_env + 15) / 16)), dim3(256), 0, stream, *a);
+    const dim3 grid((unsigned)((a->n_env + 15) / 16));
+    if (a->n_segments) hipLaunchKernelGGL(k_rollout_priority_seq, grid, dim3(256), 0, stream, *a);
+    else hipLaunchKernelGGL(k_rollout_priority, grid, dim3(256), 0, stream, *a);
 }
 
 void launch_copy_blocks(const ssd_block_copy* blocks, int count, hipStream_t stream) {

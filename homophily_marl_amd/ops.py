@@ -668,14 +668,16 @@ def store_hidden(args, device):
     abi.check(lib, lib.ssd_store_hidden(C.byref(args), th.cuda.current_stream(device).cuda_stream))
 
 
-def rollout_priority_args(t_index, q_env, q_inc, agent_major, avail_bits, store, constants, alpha, eta, eps):
+def rollout_priority_args(t_index, q_env, q_inc, agent_major, avail_bits, store, constants, alpha, eta, eps, windows=None):
     """The argument block of ssd_rollout_priority (include/ssd_hip.h) for a rollout's static tensors, and the state it owns.
     q_env / q_inc: the heads' Q-values of the current slot; agent_major says which layout they have -- True: f32 [n, N, A] /
     [n, N, n, 3] (FastPolicy's q_out), False: env-major [N, n, A] / [N, n, n, 3] (the generic timestep).  The caller states the layout:
     with N == n the shapes cannot tell.  store: the transition data of the episode storage being written (actions,
     actions_inc, reward [N, T + 1, n], terminated, filled); constants: td_constants(...); t_index: int64 device scalar.
     Returns (args, keep): keep holds carry f32 [N, n, 2], acc f32 [N, n, 3] and q_init int32 [N] plus every tensor the block points
-    to -- the block holds raw addresses, the caller keeps `keep` alive (the runner's per-storage bundle)."""
+    to -- the block holds raw addresses, the caller keeps `keep` alive (the runner's per-storage bundle).
+    windows = (S, L, s, K): a priority per training window of the grid window_grid(T, L, s) under burn-in K (k_rollout_priority_seq):
+    acc is f32 [N, n, S, 3] and q_init int32 [N, S]."""
     reward = store["reward"]
     if reward.dim() != 3 or reward.dtype != th.float32 or not reward.is_cuda or not reward.is_contiguous():
         raise _unfit("rollout_priority", "reward", reward, "contiguous f32 [N, t_slots, n] on the device expected (ind_reward)")
@@ -705,8 +707,15 @@ def rollout_priority_args(t_index, q_env, q_inc, agent_major, avail_bits, store,
         else:
             a.q_inc_agent_stride, a.q_inc_env_stride = strides
     A = q_env.shape[2]
-    keep = dict(t_index=t_index, q_env=q_env, q_inc=q_inc, carry=th.zeros(N, n, 2, device=dev), acc=th.zeros(N, n, 3, device=dev),
-                q_init=th.zeros(N, dtype=th.int32, device=dev), **{name: store[name] for name, _, _ in fields}, reward=reward)
+    if windows is not None:
+        S, L, stride, K = (int(v) for v in windows)
+        if not 1 <= L <= slots - 1 or (S, stride) != window_grid(slots - 1, L, stride or -1)[:2] or S > abi.PRIORITY_SEGMENTS_MAX or -(-L // stride) > 8 or not 0 <= K < L:
+            raise ValueError("ops.rollout_priority_args: windows %r is not (S, L, s, K) of a grid over %d transitions with S <= PRIORITY_SEGMENTS_MAX, "
+                             "ceil(L / s) <= 8 and 0 <= K < L" % (tuple(windows), slots - 1))
+        a.n_segments, a.win_len, a.seg_stride, a.burn_in = S, L, stride, K
+    acc_shape, q_shape = ((N, n, 3), (N,)) if windows is None else ((N, n, S, 3), (N, S))
+    keep = dict(t_index=t_index, q_env=q_env, q_inc=q_inc, carry=th.zeros(N, n, 2, device=dev), acc=th.zeros(acc_shape, device=dev),
+                q_init=th.zeros(q_shape, dtype=th.int32, device=dev), **{name: store[name] for name, _, _ in fields}, reward=reward)
     a.t_index, a.n_env, a.n_agents, a.n_actions, a.t_slots, a.avail_bits = t_index.data_ptr(), N, n, A, slots, int(avail_bits) & 0xFFFFFFFF
     for k, v in constants.items():
         setattr(a, k, v)
@@ -735,14 +744,42 @@ def copy_blocks(pairs):
     _copy_blocks([(s.data_ptr(), d.data_ptr(), 1, s.numel(), s.numel(), s.numel()) for s, d in pairs], pairs[0][0])
 
 
-def priority_sample(seed, call, table, population, count, n_starts, beta, ids_out, t0_out, weights_out, log_out):
+def window_grid(episode_limit, window, stride=0):
+    """The window grid of a priority per training window (per_unit "window"; include/ssd_hip.h: ssd_priority_sample): (S, s, last_start)
+    for episodes of T = episode_limit transitions and windows of L = `window`.  s = stride, or (L + 1) // 2 -- R2D2's half overlap -- for
+    0; S = ceil((T - L) / s) + 1 windows, window k starting at min(k s, T - L): the last one is clamped so that the episode's tail is
+    covered.  Raises ValueError outside 1 <= L <= T, 1 <= s <= L (a larger stride would leave gaps)."""
+    T, L = int(episode_limit), int(window)
+    s = int(stride) or (L + 1) // 2
+    if not 1 <= L <= T or not 1 <= s <= L:
+        raise ValueError("window_grid: window %r outside 1 .. %r, or stride %r outside 1 .. window" % (window, episode_limit, s))
+    return -(-(T - L) // s) + 1, s, T - L
+
+
+def window_starts(segments):
+    """[start_0 .. start_{S - 1}] of segments = (S, s, last_start)"""
+    S, s, last = segments
+    return [min(k * s, last) for k in range(S)]
+
+
+def priority_sample(seed, call, table, population, count, n_starts, beta, ids_out, t0_out, weights_out, log_out, segments=None, entries_out=None):
     """Prioritised replay's draw (include/ssd_hip.h: ssd_priority_sample): `count` stratified proportional draws with replacement from
     the fixed-point priorities table[0 .. population) (int32 storage of the u32 values; 0 = never trained on, drawn at the table's
     maximum), one window start each, and the importance weights (population qeff / total)^(-beta) divided by their maximum.
     ids_out, t0_out: int64 [count]; weights_out: f32 [count]; log_out: f32 [4] = mean and max of qeff / PRIORITY_ONE, the smallest
     weight, the number of distinct ids.  Device tensors: ONE launch.  Host tensors: the same arithmetic restated -- Python integers
-    for the draw, float64 then f32 for the weights.  Returns (ids_out, t0_out, weights_out, log_out)."""
+    for the draw, float64 then f32 for the weights.  Returns (ids_out, t0_out, weights_out, log_out).
+    segments = (S, s, last_start) (window_grid) with entries_out int64 [count]: a priority per window -- the table holds S entries per
+    slot, `population` counts entries, the same draw runs over entries (entries_out; log[3] counts distinct entries) and every entry f
+    gives ids = f // S, t0 = min((f % S) s, last_start); n_starts is not read and no start is drawn."""
     outs = (ids_out, t0_out, weights_out, log_out)
+    if segments is not None:
+        S, stride, last = (int(v) for v in segments)
+        if not (1 <= S <= abi.PRIORITY_SEGMENTS_MAX and stride >= 1 and last >= 0 and (S - 1) * stride >= last and population % S == 0):
+            raise ValueError("ops.priority_sample: segments %r: S outside 1 .. PRIORITY_SEGMENTS_MAX, stride < 1, last_start < 0, a grid that does not "
+                             "reach last_start, or population %r no multiple of S" % (tuple(segments), population))
+        if entries_out is None or entries_out.dtype != th.long or entries_out.numel() < count or entries_out.device != table.device or not entries_out.is_contiguous():
+            raise _unfit("priority_sample", "entries_out", entries_out if entries_out is not None else table, "contiguous int64 entries_out of count elements on the table's device expected with segments")
     if not (table.dtype == th.int32 and ids_out.dtype == th.long and t0_out.dtype == th.long and weights_out.dtype == th.float32 and log_out.dtype == th.float32):
         raise _unfit("priority_sample", "table", table, "int32 table, int64 ids / t0 and f32 weights / log expected")
     if not (1 <= population <= min(table.numel(), abi.PRIORITY_POP_MAX) and 1 <= count <= abi.SAMPLE_IDS_MAX and n_starts >= 1 and 0.0 <= beta <= 1.0):
@@ -755,6 +792,8 @@ def priority_sample(seed, call, table, population, count, n_starts, beta, ids_ou
         t = abi.SsdPrioritySampleArgs()
         t.seed, t.call, t.population, t.count, t.n_starts, t.beta = seed & (2 ** 64 - 1), call & 0xFFFFFFFF, population, count, n_starts, float(beta)
         t.table, t.ids, t.t0, t.weights, t.log = table.data_ptr(), ids_out.data_ptr(), t0_out.data_ptr(), weights_out.data_ptr(), log_out.data_ptr()
+        if segments is not None:
+            t.n_segments, t.seg_stride, t.last_start, t.entries = S, stride, last, entries_out.data_ptr()
         abi.check(lib, lib.ssd_priority_sample(C.byref(t), _stream(table)))
         return outs
     import bisect
@@ -769,8 +808,14 @@ def priority_sample(seed, call, table, population, count, n_starts, beta, ids_ou
         lo, hi = total * e // count, total * (e + 1) // count
         x = lo + ((_sample_draw(seed, call, e) * (hi - lo)) >> 32)
         ids.append(bisect.bisect_right(cum, x))                      # the smallest k with cum[k] > x
-    ids_out[:count] = th.tensor(ids, dtype=th.long)
-    t0_out[:count] = th.tensor([(_sample_draw(seed, call, 2 * count + e) * n_starts) >> 32 for e in range(count)], dtype=th.long)
+    if segments is not None:                                         # ids are entries: the slot and the window start of each
+        entries_out[:count] = th.tensor(ids, dtype=th.long)
+        ids_out[:count] = th.tensor([f // S for f in ids], dtype=th.long)
+        starts = window_starts((S, stride, last))
+        t0_out[:count] = th.tensor([starts[f % S] for f in ids], dtype=th.long)
+    else:
+        ids_out[:count] = th.tensor(ids, dtype=th.long)
+        t0_out[:count] = th.tensor([(_sample_draw(seed, call, 2 * count + e) * n_starts) >> 32 for e in range(count)], dtype=th.long)
     w = th.tensor([population * qeff[k] / total for k in ids], dtype=th.float64) ** (-float(beta))
     w = (w / w.max()).float()
     weights_out[:count] = w

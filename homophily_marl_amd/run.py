@@ -110,7 +110,15 @@ def _check_prioritized(args, buffer, runner):
     per_initial_priority: what a new episode enters the table with -- "max" (default): 0, drawn at the table's current maximum until a
     train step has seen it; "rollout": the priority of its own one-step TD errors under the acting network, formed by the rollout
     (ssd_rollout_priority; always the plain one-step form, also under td_lambda / consider_others_inc -- a starting estimate the first
-    train step on the episode overwrites)."""
+    train step on the episode overwrites).
+    per_unit: what a table entry stands for -- "episode" (default): one priority per stored episode, a window's start drawn uniformly
+    inside it; "window" (needs prioritized_replay and train_window L > 0): one priority per training window on a stride grid.  An
+    episode of T transitions has S = ceil((T - L) / s) + 1 windows, window k starting at min(k s, T - L) (the last one clamped onto the
+    episode's tail), s = per_window_stride, 0 = (L + 1) // 2 (R2D2's half overlap; written back resolved).  The table holds
+    buffer_size * S entries, the draw is over entries -- several windows of one episode can sit in one train step, and the priority a
+    train step measures on a window is spent on that window -- and with per_initial_priority "rollout" every window enters with the
+    priority of its own loss rows.  Refused: s outside 1 .. L (gaps), ceil(L / s) over 8 (the windows one row feeds), S over
+    PRIORITY_SEGMENTS_MAX, buffer_size * S over PRIORITY_POP_MAX."""
     on = args.prioritized_replay = bool(getattr(args, "prioritized_replay", False))
     alpha = args.per_alpha = float(getattr(args, "per_alpha", 0.6))
     beta = args.per_beta = float(getattr(args, "per_beta", 0.4))
@@ -136,9 +144,31 @@ def _check_prioritized(args, buffer, runner):
         if th.device(buffer.device).type != "cuda":
             raise ValueError('per_initial_priority "rollout" needs a device-resident replay buffer (buffer_cpu_only: False, use_cuda: True): '
                              "the priorities are written into the table by a device launch; buffer on %s" % (buffer.device,))
+    from . import abi, ops
+    unit = args.per_unit = getattr(args, "per_unit", "episode")
+    stride = args.per_window_stride = int(getattr(args, "per_window_stride", 0) or 0)
+    if unit not in ("episode", "window"):
+        raise ValueError('per_unit must be "episode" or "window", got %r' % (unit,))
+    segments = 1
+    if unit == "window":
+        L = int(getattr(args, "train_window", 0) or 0)
+        if not on:
+            raise ValueError('per_unit "window" needs prioritized_replay: True (there is no priority table without it)')
+        if L <= 0:
+            raise ValueError('per_unit "window" needs train_window > 0: whole episodes have no windows to prioritise')
+        stride = args.per_window_stride = stride or (L + 1) // 2
+        if not 1 <= stride <= L:
+            raise ValueError("per_window_stride %d outside 1 .. train_window = %d (a larger stride leaves rows no window trains on)" % (stride, L))
+        if -(-L // stride) > 8:
+            raise ValueError("per_window_stride %d: ceil(train_window / per_window_stride) = %d over 8 windows per row" % (stride, -(-L // stride)))
+        segments = ops.window_grid(buffer.max_seq_length - 1, L, stride)[0]
+        if segments > abi.PRIORITY_SEGMENTS_MAX:
+            raise ValueError("per_window_stride %d: %d windows per episode over SSD_PRIORITY_SEGMENTS_MAX = %d" % (stride, segments, abi.PRIORITY_SEGMENTS_MAX))
+        if buffer.buffer_size * segments > abi.PRIORITY_POP_MAX:
+            raise ValueError("per_unit \"window\": buffer_size %d * %d windows per episode (per_window_stride %d) over SSD_PRIORITY_POP_MAX = %d"
+                             % (buffer.buffer_size, segments, stride, abi.PRIORITY_POP_MAX))
     if not on:
         return False
-    from . import abi
     if not getattr(runner, "fixed_length_episodes", False) or th.device(buffer.device).type != "cuda":
         raise ValueError("prioritized_replay needs a device-resident replay buffer filled by a vectorised runner (buffer_cpu_only: False); "
                          "runner %r, buffer on %s" % (args.runner, buffer.device))
@@ -146,7 +176,10 @@ def _check_prioritized(args, buffer, runner):
         raise ValueError("prioritized_replay needs the fused loss (fused_loss: True): the priorities come from its per-row partials")
     if args.batch_size > abi.SAMPLE_IDS_MAX:
         raise ValueError("prioritized_replay: batch_size %d over SSD_SAMPLE_IDS_MAX = %d" % (args.batch_size, abi.SAMPLE_IDS_MAX))
-    buffer.enable_priorities()
+    if unit == "window":
+        buffer.enable_priorities(segments=segments, stride=stride, window=int(args.train_window))
+    else:
+        buffer.enable_priorities()
     return True
 
 

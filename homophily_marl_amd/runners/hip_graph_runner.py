@@ -152,6 +152,7 @@ class HipGraphRunner(HipVecRunner):
         # timestep's copy env-major) and the constants of the one-step TD error, from where the loss launch takes them
         self.initial_priority = getattr(a, "per_initial_priority", "max") == "rollout"
         self.q_env = self.q_inc = None
+        self.priority_windows = None
         if self.initial_priority:
             A = a.n_actions
             self.q_env = th.zeros((n, N, A) if rp.fast else (N, n, A), device=dev)
@@ -159,6 +160,10 @@ class HipGraphRunner(HipVecRunner):
             self._avail_bits = sum(1 << k for k, v in enumerate(avail.reshape(-1).tolist()) if v)
             norm = ops.window_reward_norm(getattr(a, "train_window_norm", "episode"), T + 1, int(getattr(a, "train_window", 0) or 0))
             self._td_constants = ops.td_constants(a, norm)
+            # per_unit "window": one priority per training window of the stride grid, (S, L, s, K) (run.setup resolved the stride)
+            if getattr(a, "per_unit", "episode") == "window":
+                L = int(a.train_window)
+                self.priority_windows = (ops.window_grid(T, L, int(a.per_window_stride))[0], L, int(a.per_window_stride), int(a.train_burn_in))
         self._par = 0
         self._ready = True
 
@@ -183,7 +188,8 @@ class HipGraphRunner(HipVecRunner):
                 b.hidden = ops.store_hidden_args(t_filed, self.fast.h_env if fast else self.h_env, self.fast.h_inc if fast else self.h_inc, st["hidden"])
             if self.initial_priority:
                 b.priority, b.priority_state = ops.rollout_priority_args(t_filed, self.q_env, self.q_inc, fast, self._avail_bits, st, self._td_constants,
-                                                                         self.args.per_alpha, self.args.per_eta, self.args.per_eps)
+                                                                         self.args.per_alpha, self.args.per_eta, self.args.per_eps,
+                                                                         windows=self.priority_windows)
             if self.fast is not None:
                 if self.direct_obs:
                     b.cur = self.env.native.storage_obs_buffers(st["obs"], self.obs_fmt, want_code=self._want_code)
@@ -282,7 +288,8 @@ class HipGraphRunner(HipVecRunner):
             ([("ssd::k_env<MODE_STEP_OBS>", "env", env_step)] if store_env_step or not pipe else []) + \
             [("ssd::k_inc_encode", "inc_encode", inc_head) if inc_encode else ("ssd::k_head<inc>", "head_inc", inc_head)] + \
             ([("ssd::k_store_hidden", "store_hidden", store_hidden)] if self.stored_state else []) + \
-            ([("ssd::k_rollout_priority", "rollout_priority", self._rollout_priority)] if self.initial_priority and self.fold_store else [])
+            ([("ssd::k_rollout_priority_seq" if self.priority_windows else "ssd::k_rollout_priority", "rollout_priority", self._rollout_priority)]
+             if self.initial_priority and self.fold_store else [])
 
     def _rollout_priority(self):
         """per_initial_priority "rollout": row t - 1 of the one-step TD errors from this slot's Q-values, behind the launches that
@@ -290,7 +297,8 @@ class HipGraphRunner(HipVecRunner):
         ops.rollout_priority(self._bundle.priority, self.env.device)
 
     def initial_priorities(self):
-        """int32 [N]: the fixed-point priorities of the episodes the last TRAINING rollout produced (ssd_rollout_priority), for
+        """int32 [N] (per_unit "window": [N, S], one per window of the grid): the fixed-point priorities of the episodes the last
+        TRAINING rollout produced (ssd_rollout_priority), for
         ReplayBuffer.insert_episode_batch; None with per_initial_priority "max" (or after a test episode): the slots are zeroed"""
         if not self._ready or not self.initial_priority or getattr(self, "_test_mode", True):
             return None

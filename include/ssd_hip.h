@@ -419,7 +419,21 @@ int ssd_gather_windows(const ssd_window_field* fields, int32_t count, const int6
  * order); thread e binary-searches the chunk sums and walks one chunk.  The table is read through L2 (three times at most); no
  * atomics, no scratch.  table: DEVICE u32 [>= population]; ids, t0: DEVICE int64 [count]; weights: DEVICE f32 [count].
  * Refused (SSD_ERR_INVALID): NULL args or a NULL member pointer; population outside 1 .. SSD_PRIORITY_POP_MAX; count outside
- * 1 .. SSD_SAMPLE_IDS_MAX; n_starts < 1; beta outside [0, 1] or NaN; a table that is not 4-byte aligned. */
+ * 1 .. SSD_SAMPLE_IDS_MAX; n_starts < 1; beta outside [0, 1] or NaN; a table that is not 4-byte aligned.
+ *
+ * A priority per training window (config key per_unit: "window"; n_segments >= 1): the table holds n_segments = S entries per buffer
+ * slot, entry (slot, k) at slot * S + k, one per window of the slot's episode on a stride grid: window k starts at
+ * start_k = min(k * seg_stride, last_start), last_start = T - L (the last window is clamped so that the episode's tail is covered).
+ * `population` counts ENTRIES (episodes * S).  The draw is the draw above on the flat table, unchanged -- qmax, qeff, total, strata,
+ * x, weights and log over entries, log[3] = the number of distinct entries -- written by a second kernel, k_priority_sample_seq (the
+ * same body instantiated a second time), which files the drawn entry and maps it:
+ *   entries[e] = the smallest f with cum[f] > x;   ids[e] = entries[e] / S;   t0[e] = min((entries[e] % S) * seg_stride, last_start)
+ * n_starts is not read and draw(2 * count + e) is not consumed.  Several strata landing in one episode are several windows of it (or
+ * one window several times).  entries: DEVICE int64 [count], what ssd_priority_update takes as ids with table_len = slots * S.
+ * n_segments == 0: the launch above, entries may be NULL.  Refused in addition: n_segments < 0 or over SSD_PRIORITY_SEGMENTS_MAX; with
+ * n_segments >= 1: NULL entries; seg_stride < 1; last_start < 0; (n_segments - 1) * seg_stride < last_start (the grid would not
+ * reach the last start); population not a multiple of n_segments. */
+#define SSD_PRIORITY_SEGMENTS_MAX 256
 #define SSD_PRIORITY_ONE 65536u
 #define SSD_PRIORITY_MAX 16777216u
 #define SSD_PRIORITY_POP_MAX 1048576
@@ -432,6 +446,8 @@ typedef struct ssd_priority_sample_args {
     int64_t *ids, *t0;
     float* weights;
     float* log;                  /* [4] */
+    int32_t n_segments, seg_stride, last_start;      /* 0: one entry per slot, the members behind are not read */
+    int64_t* entries;            /* [count], n_segments >= 1 */
 } ssd_priority_sample_args;
 int ssd_priority_sample(const ssd_priority_sample_args* args, void* stream);
 
@@ -512,7 +528,21 @@ int ssd_priority_update(const ssd_priority_update_args* args, void* stream);
  * Refused (SSD_ERR_INVALID, nothing launched): NULL args or a NULL member pointer other than filled; n_env < 1 or over 2^24; t_slots < 2;
  * n_agents outside 2 .. SSD_MAX_AGENTS; n_actions outside 1 .. 16; none of the low n_actions bits of avail_bits set; alpha or eta outside
  * [0, 1] or NaN; eps, seq_len or reward_scale <= 0 or NaN; a negative stride; q_env, q_inc, reward, carry, acc or q_init not 4-byte
- * aligned, t_index, actions, actions_inc or filled not 8-byte aligned. */
+ * aligned, t_index, actions, actions_inc or filled not 8-byte aligned.
+ *
+ * A priority per training window (per_unit: "window"; n_segments = S >= 1): a second kernel, k_rollout_priority_seq, same launch
+ * shape.  Window k of the grid (ssd_priority_sample) starts at start_k = min(k * seg_stride, T - win_len); its loss rows are
+ * start_k + K_k <= row < start_k + win_len, K_k = burn_in if start_k > 0 else 0 (the rule of ssd_gather_windows).  Every window enters
+ * the table with the value above over ITS loss rows, all agents: q_init u32 [N, S], acc f32 [N, n, S, 3].  d and mask of a row are
+ * the ones above (the same device function; seq_len is the episode's, whatever train_window_norm says); only the aggregation changes:
+ *   t == 0        the pair's S accumulators = (0, 0, 0)
+ *   1 <= t <= T   row t - 1 formed ONCE and added to the (max, sum, cnt) of every window whose loss rows contain it -- at most
+ *                 ceil(win_len / seg_stride) + 1 windows; no other accumulator is read or written; each window's sums run in rising t
+ *   t == T        additionally, for every k, the env's agents are reduced as above (max order-free, sums agent 0 .. n - 1) and
+ *                 q_init[env, k] is written (a thread re-reads accumulators it wrote itself, no other thread's)
+ * With S = 1 (win_len = T) q_init and acc are bit for bit those of n_segments = 0.  Refused in addition: n_segments < 0 or over
+ * SSD_PRIORITY_SEGMENTS_MAX; with n_segments >= 1: win_len outside 1 .. t_slots - 1; seg_stride outside 1 .. win_len;
+ * ceil(win_len / seg_stride) over 8; burn_in outside 0 .. win_len - 1; n_segments != ceil((T - win_len) / seg_stride) + 1. */
 typedef struct ssd_rollout_priority_args {
     const int64_t* t_index;      /* device scalar */
     int32_t n_env, n_agents, n_actions, t_slots;
@@ -526,7 +556,8 @@ typedef struct ssd_rollout_priority_args {
     const int64_t* filled;       /* nullable */
     float gamma_env, gamma_inc, reward_scale, incentive_ratio, incentive_cost, incentive, seq_len, alpha, eta, eps;
     float *carry, *acc;
-    uint32_t* q_init;            /* [n_env] */
+    uint32_t* q_init;            /* [n_env], or [n_env, n_segments] */
+    int32_t n_segments, win_len, seg_stride, burn_in;    /* 0: one priority per episode, the members behind are not read */
 } ssd_rollout_priority_args;
 int ssd_rollout_priority(const ssd_rollout_priority_args* args, void* stream);
 

@@ -36,6 +36,8 @@ ap.add_argument("--burn-in", type=int, default=0, help="config key train_burn_in
 ap.add_argument("--stored-state", action="store_true", help="config key train_stored_state: windows start from the rollout's stored recurrent state")
 ap.add_argument("--prioritized", action="store_true", help="config key prioritized_replay (per_alpha, per_beta, ... through --set)")
 ap.add_argument("--initial-priority", choices=("max", "rollout"), default="max", help="config key per_initial_priority (with --prioritized)")
+ap.add_argument("--per-unit", choices=("episode", "window"), default="episode", help="config key per_unit (with --prioritized and --train-window): a priority per episode or per training window")
+ap.add_argument("--per-window-stride", type=int, default=0, help="config key per_window_stride: the stride of the window grid (0: half overlap)")
 ap.add_argument("--set", action="append", default=[], help="extra config override key=value (python literal)")
 a = ap.parse_args()
 c = CONFIGS[a.config]
@@ -53,6 +55,8 @@ if a.stored_state:
 if a.prioritized:
     over["prioritized_replay"] = True
     over["per_initial_priority"] = a.initial_priority
+if a.per_unit == "window":             # (without --prioritized or --train-window, setup refuses it)
+    over.update(per_unit="window", per_window_stride=a.per_window_stride)
 import ast
 for kv in a.set:
     k, v = kv.split("=", 1)
