@@ -217,7 +217,7 @@ class SsdPolicyHead(C.Structure):
                 ("next_step_out", C.c_void_p), ("t_copy_out", C.c_void_p), ("step_copy_out", C.c_void_p),
                 ("recv_inc", C.c_void_p), ("recv_inc_out", C.c_void_p), ("avail_bits", C.c_uint32),
                 ("others_rows", C.c_void_p), ("prev_record", C.c_void_p), ("prev_record_out", C.c_void_p), ("onehot_rows", C.c_void_p),
-                ("pipeline_gather", C.c_int32)]
+                ("pipeline_gather", C.c_int32), ("epsilon_rows", C.c_void_p)]
 
 
 class SsdPolicyHeadParams(C.Structure):

@@ -987,6 +987,7 @@ int ssd_policy_pack_head(const ssd_policy_head_params* p, int32_t precision, voi
 static int check_head(const ssd_policy_head* a, int inc) {
     if (!a || !a->inputs || !a->h || !a->weights || !a->epsilon || !a->step || !a->out_actions) return fail(SSD_ERR_INVALID, "bad argument");
     if (a->n_env < 1 || a->n_agents < 1 || a->n_actions < 1) return fail(SSD_ERR_INVALID, "bad argument");
+    if (reinterpret_cast<uintptr_t>(a->epsilon_rows) & 3) return fail(SSD_ERR_INVALID, "ssd_policy_head: epsilon_rows (f32 [n_env]) must be 4-byte aligned");
     if (a->precision != 0 && a->precision != 1 && a->precision != 2) return fail(SSD_ERR_INVALID, "precision must be 1 (bf16) or 2 (f32-equivalent)");
     if (a->feat_part && (inc || a->feat_bands < 1 || !a->lin_b || (reinterpret_cast<uintptr_t>(a->feat_part) & 15)))
         return fail(SSD_ERR_INVALID, "feat_part (env head only) needs feat_bands >= 1, lin_b and 16-byte alignment");

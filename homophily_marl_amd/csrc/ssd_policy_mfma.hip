@@ -284,8 +284,11 @@ struct HeadK {
     const uint8_t* term;           // inc head: the env step's terminated flags
     const uint8_t* recv;           // env head, nullable: receiver-major incentive bytes [n, N, 16] (instead of prev_inc)
     uint32_t avail_bits;           // env head: bit 31 set = the availability mask itself (no loads from `avail`)
+    uint32_t eps_rows;             // nonzero: `eps` is ssd_policy_head.epsilon_rows, f32 [N] -- a rate per row, loaded at the pick sites
+                                   // (in the four bytes that were padding: sizeof(HeadK) and every other offset are what they were)
     PSTAMP_DECL
 };
+static_assert(offsetof(HeadK, eps_rows) == offsetof(HeadK, avail_bits) + 4 && offsetof(HeadK, eps_rows) % 8 == 4, "eps_rows fills HeadK's padding");
 struct HeadCold {
     // block A (64 bytes): what both epilogues write first, then the env head's results and by-products
     int64_t* out_actions; float* q_out; int32_t* out_actions_i32; int64_t* p_act; int64_t* d_actions; float* d_onehot; float *pos_copy, *orient_copy;
@@ -324,6 +327,21 @@ __device__ __forceinline__ T SSD_GLOBAL* cold_ptr(int cold_base, int field_offse
     uint64_t v;
     asm volatile("s_load_dwordx2 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(ka), "s"(cold_base + field_offset) : "memory");
     return (T SSD_GLOBAL*)v;
+}
+// one dword of the kernarg segment, fetched where it is used (a flag such as HeadK::eps_rows: nothing is held through the tile chain)
+__device__ __forceinline__ uint32_t cold_u32(int offset) {
+    auto ka = __builtin_amdgcn_kernarg_segment_ptr();
+    uint32_t v;
+    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(ka), "s"(offset) : "memory");
+    return v;
+}
+// The exploration rate of row bb: the launch's scalar, or -- a wave-uniform branch on HeadK::eps_rows -- the row's own value of the
+// table that then travels in HeadK::eps (ssd_policy_head.epsilon_rows).  Flag and pointer come from the kernarg segment here, at the
+// pick site; without a table no load is issued.
+template <int KOFF>
+__device__ __forceinline__ float row_eps(float eps, int bb) {
+    if (cold_u32(KOFF + (int)offsetof(HeadK, eps_rows))) return cold_ptr<const float>(KOFF, (int)offsetof(HeadK, eps))[bb];
+    return eps;
 }
 // Several cold pointers at once: ONE scalar-load burst and ONE wait instead of a load + wait per pointer (~150 cycles each on a wave
 // that is alone on its SIMD).  cold_blocks: block A [+ block B] [+ block C] of HeadCold.
@@ -1026,7 +1044,7 @@ __device__ __forceinline__ void head_body(const HeadK& a_entry, uint8_t* lds_raw
                 const float val = av[A];
                 const uint32_t rq = (uint32_t)(agent * N + bb);                                  // q_out row (agent-major)
                 const uint32_t rk = (a.env_id_base + (uint32_t)bb) * (uint32_t)n + (uint32_t)agent;   // exploration key: global env id
-                const int act = dueling_pick_bits<AT>(av, val, A, avail_bits, eps, step, a.seed, rk, q_out ? q_out + (size_t)rq * A : (decltype(q_out))nullptr);
+                const int act = dueling_pick_bits<AT>(av, val, A, avail_bits, row_eps<KOFF>(eps, bb), step, a.seed, rk, q_out ? q_out + (size_t)rq * A : (decltype(q_out))nullptr);
                 out_actions[(size_t)bb * n + agent] = act;
                 if (out_i32) out_i32[(size_t)bb * n + agent] = act;
                 if (p_act) p_act[(size_t)bb * n + agent] = act;
@@ -1088,7 +1106,7 @@ __device__ __forceinline__ void head_body(const HeadK& a_entry, uint8_t* lds_raw
                 pair_q(row, in.aj[k], in.f[k], av);
                 const uint32_t rq = (uint32_t)((agent * N + bb) * n + j);
                 const uint32_t rk = ((a.env_id_base + (uint32_t)bb) * (uint32_t)n + (uint32_t)agent) * (uint32_t)n + (uint32_t)j;
-                const int act = dueling_pick_bits<3>(av, av[3], 3, 0xFFFFFFFFu, eps, step, a.seed, rk, q_out ? q_out + (size_t)rq * 3 : (decltype(q_out))nullptr);
+                const int act = dueling_pick_bits<3>(av, av[3], 3, 0xFFFFFFFFu, row_eps<KOFF>(eps, bb), step, a.seed, rk, q_out ? q_out + (size_t)rq * 3 : (decltype(q_out))nullptr);
                 const size_t pair = ((size_t)bb * n + agent) * n + j;
                 out_actions[pair] = act;
                 if (p_inc) p_inc[pair] = act;
@@ -1227,7 +1245,8 @@ static int chip_cus() {
 static void head_args(const ssd_policy_head* p, HeadK& k, HeadCold& c) {
     k.N = p->n_env; k.n = p->n_agents; k.A = p->n_actions; k.inp = p->input_shape;
     k.pos_scale = p->pos_scale; k.seed = p->seed; k.env_id_base = p->env_id_base;
-    k.inputs = p->inputs; k.h = p->h; k.weights = static_cast<const uint8_t*>(p->weights); k.avail = p->avail; k.eps = p->epsilon; k.step = p->step;
+    k.inputs = p->inputs; k.h = p->h; k.weights = static_cast<const uint8_t*>(p->weights); k.avail = p->avail; k.step = p->step;
+    k.eps = p->epsilon_rows ? p->epsilon_rows : p->epsilon; k.eps_rows = p->epsilon_rows ? 1u : 0u;     // (see row_eps)
     k.prev_actions = p->prev_actions; k.prev_reward = p->prev_reward; k.prev_inc = p->prev_actions_inc; k.pos = p->pos; k.orient = p->orient;
     k.actions = p->actions; k.pos_pre = p->pos_pre; k.orient_pre = p->orient_pre; k.reward = p->reward; k.clean = p->clean_num;
     k.den = p->apple_den;

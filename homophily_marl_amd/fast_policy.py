@@ -230,8 +230,22 @@ class FastPolicy:
         hp.fc2_in, hp.fc2_out = g("fc2_%s_w" % head).shape[2], g("fc2_%s_w" % head).shape[3]
         return hp
 
-    def _head_args(self, inc, eps, step, q_out=None, buf=0, par=0):
+    def _check_eps_rows(self, eps_rows):
+        """eps_rows (ssd_policy_head.epsilon_rows): a rate per env of this policy, f32 [n_env], contiguous, on the policy's device"""
+        if not self.fused:
+            raise ValueError("eps_rows: a rate per env is read by the fused heads only (the per-layer path keeps the scalar eps)")
+        if not isinstance(eps_rows, th.Tensor) or eps_rows.dtype != th.float32:
+            raise TypeError("eps_rows must be a float32 tensor, got %s" % (getattr(eps_rows, "dtype", type(eps_rows)),))
+        if tuple(eps_rows.shape) != (self.N,) or not eps_rows.is_contiguous():
+            raise ValueError("eps_rows must be contiguous with shape [n_env] = [%d], got %s" % (self.N, tuple(eps_rows.shape)))
+        if eps_rows.device != self.dev:
+            raise ValueError("eps_rows must be on the policy's device %s, got %s" % (self.dev, eps_rows.device))
+        return eps_rows.data_ptr()
+
+    def _head_args(self, inc, eps, step, q_out=None, buf=0, par=0, eps_rows=None):
         a = abi.SsdPolicyHead()
+        if eps_rows is not None:
+            a.epsilon_rows = self._check_eps_rows(eps_rows)
         a.n_env, a.n_agents, a.n_actions, a.input_shape = self.N, self.n, self.A, self.inp
         a.pos_scale = float(self.mac.pos_scale)
         a.seed = (self.seed ^ 0x5bd1e995) if inc else self.seed
@@ -266,12 +280,14 @@ class FastPolicy:
     @th.no_grad()
     def act_env(self, obs, prev_actions, prev_reward, prev_inc, pos, eps, step, codes=None, slot_t=None, store_obs=None, store_t=None,
                 q_out=None, orient=None, actions_i32=None, pos_copy=None, orient_copy=None, t_copy=None, counter_inc=None, file=None,
-                mask_alphabet=None):
+                mask_alphabet=None, eps_rows=None):
         """encode() followed by head_env(); returns actions i64 [N, n] (static buffer).  See the two methods for the arguments."""
+        if eps_rows is not None:
+            self._check_eps_rows(eps_rows)         # (refused before the encoder is launched)
         self.encode(obs, codes=codes, slot_t=slot_t, store_obs=store_obs, store_t=store_t, t_copy=t_copy, counter_inc=counter_inc,
                     mask_alphabet=mask_alphabet)
         return self.head_env(prev_actions, prev_reward, prev_inc, pos, eps, step, q_out=q_out, orient=orient, actions_i32=actions_i32,
-                             pos_copy=pos_copy, orient_copy=orient_copy, file=file)
+                             pos_copy=pos_copy, orient_copy=orient_copy, file=file, eps_rows=eps_rows)
 
     @staticmethod
     def codes_from_obs(obs):
@@ -347,16 +363,20 @@ class FastPolicy:
 
     @th.no_grad()
     def head_env(self, prev_actions, prev_reward, prev_inc, pos, eps, step, q_out=None, orient=None, actions_i32=None, pos_copy=None,
-                 orient_copy=None, file=None, buf=0, par=None):
+                 orient_copy=None, file=None, buf=0, par=None, eps_rows=None):
         """input tail + fc1 + GRU + dueling + epsilon-greedy of the env head on the features encode() left in `inputs`.
+        eps_rows (optional, all three fused head launches): f32 [n_env] on the device, contiguous -- env b explores at eps_rows[b]
+        instead of the scalar eps (ssd_policy_head.epsilon_rows); the per-layer path refuses it.
         obs_others_last_action: `par` = the timestep's parity -- the head reads prev_rec[par] and writes its picks to prev_rec[par ^ 1]
         (the rollout); par = None: a stand-alone call, the record is first set from `prev_actions` (set_prev_actions) and parity 0 used."""
         p, lib, n, N, H = self.p, self.lib, self.n, self.N, self.H
         st = self._stream()
+        if eps_rows is not None:
+            self._check_eps_rows(eps_rows)
         if self.fused:
             if self.prev_rec is not None and par is None:
                 self.set_prev_actions(prev_actions, 0)
-            ha = self._head_args(False, eps, step, q_out, buf, par or 0)
+            ha = self._head_args(False, eps, step, q_out, buf, par or 0, eps_rows=eps_rows)
             ha.avail = self.avail.data_ptr()
             ha.avail_bits = self._avail_bits       # the mask itself (a constant of the env class): the kernel issues no loads for it
             ha.prev_actions, ha.prev_reward, ha.prev_actions_inc, ha.pos = (prev_actions.data_ptr(), prev_reward.data_ptr(),
@@ -387,8 +407,8 @@ class FastPolicy:
 
     # ---- incentive head ---------------------------------------------------------------------------------------------
     @th.no_grad()
-    def _inc_args(self, actions, pos, orient, reward, clean_num, apple_den, eps, step, q_out=None, file=None, buf=0, par=None):
-        ha = self._head_args(True, eps, step, q_out, buf, par or 0)
+    def _inc_args(self, actions, pos, orient, reward, clean_num, apple_den, eps, step, q_out=None, file=None, buf=0, par=None, eps_rows=None):
+        ha = self._head_args(True, eps, step, q_out, buf, par or 0, eps_rows=eps_rows)
         ha.actions, ha.pos_pre, ha.orient_pre = actions.data_ptr(), pos.data_ptr(), orient.data_ptr()
         ha.reward, ha.clean_num, ha.apple_den = reward.data_ptr(), clean_num.data_ptr(), apple_den.data_ptr()
         ha.out_actions = self.actions_inc.data_ptr()
@@ -398,13 +418,13 @@ class FastPolicy:
 
     @th.no_grad()
     def act_inc_encode(self, actions, pos, orient, reward, clean_num, apple_den, eps, step, codes, slot_t=None, slot_add=0, buf=0,
-                       q_out=None, file=None, mask_alphabet=None, par=None):
+                       q_out=None, file=None, mask_alphabet=None, par=None, eps_rows=None):
         """act_inc of timestep t on inputs_pair[buf] AND encode of timestep t + 1 into inputs_pair[buf ^ 1] (several bands: into
         the band sums) as ONE launch (ssd_policy_head_inc_encode; the gathered layouts: with ssd_policy_head.pipeline_gather set): the
         pipelined rollout's third launch of a timestep.  `codes` / slot_t / slot_add as in encode(): the observation the env step of t
         just produced (storage slot *slot_t + slot_add).  `par` as in act_inc (the gathered layouts read prev_rec[par])."""
         assert self.fused and self.inc_encode
-        ha = self._inc_args(actions, pos, orient, reward, clean_num, apple_den, eps, step, q_out=q_out, file=file, buf=buf, par=par)
+        ha = self._inc_args(actions, pos, orient, reward, clean_num, apple_den, eps, step, q_out=q_out, file=file, buf=buf, par=par, eps_rows=eps_rows)
         ea, codes = self._encode_args(None, codes, slot_t, mask_alphabet, buf=buf ^ 1, slot_add=slot_add)
         ha.pipeline_gather = int(self.others or self.gather)         # the gathered layouts ask for their own fused launch
         abi.check(self.lib, self.lib.ssd_policy_head_inc_encode(C.byref(ha), C.byref(ea), self._stream()))
@@ -412,14 +432,16 @@ class FastPolicy:
         return self.actions_inc
 
     @th.no_grad()
-    def act_inc(self, actions, pos, orient, reward, clean_num, apple_den, eps, step, q_out=None, file=None, buf=0, par=None):
+    def act_inc(self, actions, pos, orient, reward, clean_num, apple_den, eps, step, q_out=None, file=None, buf=0, par=None, eps_rows=None):
         """actions i64 [N, n] (the env actions just taken); pos / orient: the PRE-step pose [N, n, 2]; reward, clean_num,
         apple_den [N, n] of this step.  Returns actions_inc i64 [N, n, n] with a zero diagonal (static buffer).
         obs_others_last_action: reads prev_rec[par] (the same buffer the env head of this timestep read; None = 0)."""
         p, lib, n, N, H = self.p, self.lib, self.n, self.N, self.H
         st = self._stream()
+        if eps_rows is not None:
+            self._check_eps_rows(eps_rows)
         if self.fused:
-            ha = self._inc_args(actions, pos, orient, reward, clean_num, apple_den, eps, step, q_out=q_out, file=file, buf=buf, par=par)
+            ha = self._inc_args(actions, pos, orient, reward, clean_num, apple_den, eps, step, q_out=q_out, file=file, buf=buf, par=par, eps_rows=eps_rows)
             abi.check(lib, lib.ssd_policy_head_inc(C.byref(ha), st))
             return self.actions_inc
         assert buf == 0

@@ -183,6 +183,27 @@ def _check_prioritized(args, buffer, runner):
     return True
 
 
+def _check_epsilon_ladder(args, fused_heads=True):
+    """epsilon_ladder_alpha (absent = 0 = off: every env explores at the scheduled epsilon), validated and written back.  alpha > 0:
+    env g of the job's G envs (batch_size_run x ranks, g = env_id_base + local env) explores at epsilon(t) ** (1 + alpha g / (G - 1)) --
+    the Ape-X / R2D2 actor ladder: env 0 at the scheduled rate, env G - 1 at epsilon ** (1 + alpha).  The rates are rows of a device
+    table the fused rollout heads read (ssd_policy_head.epsilon_rows), so the key needs runner hip_graph on the fused heads
+    (`fused_heads`: what the runner planned; the generic torch timestep and the per-layer heads keep the scalar).  Runs without a
+    device; returns alpha."""
+    raw = getattr(args, "epsilon_ladder_alpha", 0.0)
+    alpha = float(0.0 if raw is None else raw)
+    if not alpha >= 0.0 or alpha == float("inf"):       # (NaN fails the comparison)
+        raise ValueError("epsilon_ladder_alpha must be a finite number >= 0, got %r" % (raw,))
+    args.epsilon_ladder_alpha = alpha
+    if alpha > 0.0:
+        if args.runner != "hip_graph":
+            raise ValueError("epsilon_ladder_alpha > 0 needs runner hip_graph (the runner whose heads read a rate per env); runner %r does not" % (args.runner,))
+        if not fused_heads:
+            raise ValueError("epsilon_ladder_alpha > 0 needs the fused rollout heads (fast_policy and fused_policy on a layout they take): "
+                             "the generic timestep and the per-layer heads explore at the scalar epsilon")
+    return alpha
+
+
 def per_beta(args, train_steps):
     """the importance-weight exponent of train step number train_steps (0-based): per_beta, annealed linearly to 1 over
     per_beta_anneal_steps train steps (0: constant)"""
@@ -223,6 +244,7 @@ def setup(config, logger=None):
     _check_prioritized(args, buffer, runner)
     mac = mac_REGISTRY[args.mac](buffer.scheme, groups, args)
     runner.setup(scheme=scheme, groups=groups, preprocess=preprocess, mac=mac)
+    _check_epsilon_ladder(args, fused_heads=runner.plans_fused_heads() if hasattr(runner, "plans_fused_heads") else False)
     learner = le_REGISTRY[args.learner](mac, buffer.scheme, logger, args)
     if args.use_cuda:
         learner.cuda()

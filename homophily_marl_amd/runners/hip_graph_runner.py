@@ -106,6 +106,23 @@ class HipGraphRunner(HipVecRunner):
         self._replay = buffer if ok else None
         return ok
 
+    def _runner_plan(self):
+        """(whether the fused heads are allowed, the RunnerPlan): pure, from the controller, the config and the env's palette"""
+        a = self.args
+        use_fused = bool(getattr(a, "fused_policy", True)) and self.env.native.cfg.obs_color == abi.COLOR_SIMPLIFIED
+        return use_fused, plan_runner(plan_rollout(self.mac, use_fused), a, self.episode_limit, self.obs_fmt)
+
+    def plans_fused_heads(self):
+        """whether the rollout will run on the fused heads (FastPolicy with .fused) -- known after setup(), before anything is allocated"""
+        use_fused, rp = self._runner_plan()
+        return bool(rp.fast and plan_rollout(self.mac, use_fused).fused)
+
+    def _ladder_total(self):
+        """all envs of the job: batch_size_run x ranks"""
+        import torch.distributed as dist
+        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        return self.batch_size * world
+
     # ---- static state ---------------------------------------------------------------------------------------------
     def _allocate(self):
         a, N, n, T = self.args, self.batch_size, self.args.n_agents, self.episode_limit
@@ -117,8 +134,7 @@ class HipGraphRunner(HipVecRunner):
                                and self.obs_fmt != abi.OBS_CODE and abi.encode_edge_supported(self.env.native.V))
         self._dense_cur = self.env.native.obs_buffers(self.obs_fmt, want_code=self._want_code)   # obs / pos / orient written by the env kernel
         self.cur = self._dense_cur
-        use_fused = bool(getattr(a, "fused_policy", True)) and simplified
-        rp = plan_runner(plan_rollout(self.mac, use_fused), a, self.episode_limit, self.obs_fmt)
+        use_fused, rp = self._runner_plan()
         self.direct_obs, self.fold_store, self.pipe, self._graph_steps_planned = rp.direct_obs, rp.fold_store, rp.pipe, rp.graph_steps
         self.t_dev = th.zeros(1, dtype=th.long, device=dev)
         self.rng_ctr = th.full((1,), rp.counter_start, dtype=th.long, device=dev)   # never reset: exploration draws differ between episodes
@@ -146,6 +162,17 @@ class HipGraphRunner(HipVecRunner):
             self.pos_t, self.orient_t = th.zeros(N, n, 2, device=dev), th.zeros(N, n, 2, device=dev)   # pose before the env step
             self.actions_i32 = th.zeros(N, n, dtype=th.int32, device=dev)
             self.t_store = th.zeros(1, dtype=th.long, device=dev)     # the encoder's copy of t_dev, read by the store-step launch
+        # epsilon_ladder_alpha > 0: a rate per env, eps ** expo[b], as a persistent table the captured graphs bake in like self.eps;
+        # refreshed from the scalar by one device op wherever the scalar is filled (_set_eps).  Off: no table, epsilon_rows stays NULL
+        self.ladder_alpha = float(getattr(a, "epsilon_ladder_alpha", 0.0) or 0.0)
+        self.expo = self.eps_rows = None
+        if self.ladder_alpha > 0.0:
+            if self.fast is None or not self.fast.fused:
+                raise ValueError("epsilon_ladder_alpha > 0 needs the fused rollout heads; this runner planned %s"
+                                 % ("the generic timestep" if self.fast is None else "the per-layer heads"))
+            from ..components.epsilon_schedules import ladder_exponents
+            self.expo = th.from_numpy(ladder_exponents(self.ladder_alpha, int(self.env.native.cfg.env_id_base), N, self._ladder_total())).to(dev)
+            self.eps_rows = th.zeros(N, device=dev)
         self.rng_copy = th.zeros(1, dtype=th.long, device=dev)          # pipelined: the env head's copy of rng_ctr for the inc head
         self.stored_state = bool(getattr(a, "train_stored_state", False))
         # per_initial_priority "rollout": the heads' Q-values of the current slot (FastPolicy's q_out is agent-major, the generic
@@ -259,7 +286,7 @@ class HipGraphRunner(HipVecRunner):
         def env_head():
             extra = dict(orient=orient, actions_i32=self.actions_i32, pos_copy=pos_t, orient_copy=orient_t) if fused else {}
             fast.head_env(self.prev_actions, self.prev_reward, self.prev_inc, pos, self.eps, self.rng_ctr, file=bundle.file_env,
-                          buf=buf, par=par, q_out=self.q_env, **extra)
+                          buf=buf, par=par, q_out=self.q_env, eps_rows=self.eps_rows, **extra)
 
         def env_step():
             if not fused:
@@ -277,9 +304,10 @@ class HipGraphRunner(HipVecRunner):
             file = bundle.file_inc if store_env_step else bundle.file_inc_last
             if inc_encode:
                 fast.act_inc_encode(actions, pos_t, orient_t, reward, clean, den, self.eps, inc_step, codes, slot_t=self.t_store, slot_add=1,
-                                    buf=buf, file=file, par=par, q_out=self.q_inc)
+                                    buf=buf, file=file, par=par, q_out=self.q_inc, eps_rows=self.eps_rows)
             else:
-                fast.act_inc(actions, pos_t, orient_t, reward, clean, den, self.eps, inc_step, file=file, buf=buf, par=par, q_out=self.q_inc)
+                fast.act_inc(actions, pos_t, orient_t, reward, clean, den, self.eps, inc_step, file=file, buf=buf, par=par, q_out=self.q_inc,
+                             eps_rows=self.eps_rows)
 
         def store_hidden():     # train_stored_state: the state after slot t, behind the inc head that produced it
             ops.store_hidden(bundle.hidden, self.env.device)
@@ -424,18 +452,18 @@ class HipGraphRunner(HipVecRunner):
             # a recorded test episode takes the eager launch sequence (no graph is replayed or captured): frame t is one ssd_render
             # launch after the env step of t
             self._begin_launches()
-            self.eps.fill_(sel.epsilon)
+            self._set_eps(sel.epsilon)
             self._recorder.frame()
             return
         # The episode's opening launches (env reset + first observation, the runner state's fills, the weight packs, the encoder of
         # slot 0) and its closing ones (slot-T pass, statistics) are ~25 small launches the host issues one by one while the GPU waits
         # for them (0.4 of a 7.5 ms iteration); from the third episode of a storage on they are two more hipGraph replays.
         if b.begin_graph is not None:
-            self.eps.fill_(sel.epsilon)
+            self._set_eps(sel.epsilon)
             b.begin_graph.replay()
             return
         self._begin_launches()
-        self.eps.fill_(sel.epsilon)
+        self._set_eps(sel.epsilon)
         if self._graph is None and self._episodes >= 2 and getattr(self.args, "rollout_graph", True) and self._graph_steps_planned:
             th.cuda.synchronize()
             g = th.cuda.CUDAGraph()
@@ -459,6 +487,34 @@ class HipGraphRunner(HipVecRunner):
             with th.no_grad(), th.cuda.graph(g, capture_error_mode="thread_local"):
                 self._begin_launches(in_capture=True)
             b.begin_graph = g
+
+    def _set_eps(self, epsilon):
+        """the episode's exploration rate: the device scalar and, under epsilon_ladder_alpha, the table of the envs' own rates
+        eps ** (1 + alpha g / (G - 1)) from it -- one device op, no upload (the host runs several rollouts ahead of the device)"""
+        self.eps.fill_(epsilon)
+        if self.eps_rows is not None:
+            th.pow(self.eps, self.expo, out=self.eps_rows)
+
+    def _stat_extra(self, test_mode):
+        return 4 if (not test_mode and float(getattr(self.args, "epsilon_ladder_alpha", 0.0) or 0.0) > 0.0) else 0
+
+    def _ladder_greedy_envs(self):
+        """the rank's ceil(N / 8) highest-id envs: the greediest rungs of the ladder"""
+        return -(-self.batch_size // 8)
+
+    def _stats_device(self, out, ep_return, test_mode):
+        super()._stats_device(out, ep_return, test_mode)
+        if self._stat_extra(test_mode):     # the same sums over the greediest eighth of the envs, behind the four of all envs
+            k = self._ladder_greedy_envs()
+            ops.runner_stats(out["collective_return"][-k:], out["equality"][-k:], ep_return[-k:], self._stat_buf(test_mode)[4:])
+
+    def _log_extra(self, sums, stats, prefix, test_mode):
+        if len(sums) == 4:
+            # return_mean now mixes rates from epsilon down to epsilon ** (1 + alpha); this stays comparable with near-greedy play
+            rollouts = max(1, stats["n_episodes"] // self.batch_size)
+            self.logger.log_stat("ladder_greedy_return_mean", sums[0] / (rollouts * self._ladder_greedy_envs()), self.t_env)
+            eps = float(self.mac.action_selector.epsilon)
+            self.logger.log_stat("epsilon_ladder_min", eps ** (1.0 + self.ladder_alpha) if eps > 0.0 else 0.0, self.t_env)
 
     def _begin_launches(self, in_capture=False):
         """the device work that opens an episode on the bound storage (everything but the epsilon scalar, which the host computes)"""

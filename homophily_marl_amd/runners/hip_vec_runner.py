@@ -187,12 +187,20 @@ class HipVecRunner:
         from .. import ops
         ops.runner_stats(out["collective_return"], out["equality"], ep_return, self._stat_acc(test_mode))
 
-    def _stat_acc(self, test_mode):
-        """device accumulator [sum collective_return, sum equality_metric, sum of returns, sum of squared returns]"""
+    def _stat_buf(self, test_mode):
+        """the device accumulator of a mode as the host reads it (_log): the four sums of _stat_acc and, behind them, whatever
+        _stat_extra says the runner accumulates as well -- one tensor, so a log event stays one device -> host read"""
         key = "_acc_test" if test_mode else "_acc_train"
         if getattr(self, key, None) is None:
-            setattr(self, key, th.zeros(4, dtype=th.float64, device=self.env.device))
+            setattr(self, key, th.zeros(4 + self._stat_extra(test_mode), dtype=th.float64, device=self.env.device))
         return getattr(self, key)
+
+    def _stat_extra(self, test_mode):
+        return 0
+
+    def _stat_acc(self, test_mode):
+        """device accumulator [sum collective_return, sum equality_metric, sum of returns, sum of squared returns]"""
+        return self._stat_buf(test_mode)[:4]
 
     # ---- behaviour statistics (config key behaviour_stats, default off) ---------------------------------------------------------------
     def _behaviour_acc(self, test_mode):
@@ -233,8 +241,9 @@ class HipVecRunner:
         return self.finish_episode()
 
     def _log(self, stats, prefix, test_mode):
-        acc = self._stat_acc(test_mode)
-        coll, eq, rs, rss = acc.cpu().tolist()          # the one device -> host read of the log interval
+        acc = self._stat_buf(test_mode)
+        sums = acc.cpu().tolist()                       # the one device -> host read of the log interval
+        coll, eq, rs, rss = sums[:4]
         acc.zero_()
         n_ep, n_ret = stats["n_episodes"], max(1, stats.get("n_returns", 0))
         mean = rs / n_ret
@@ -242,6 +251,7 @@ class HipVecRunner:
         self.logger.log_stat(prefix + "return_std", max(0.0, rss / n_ret - mean * mean) ** 0.5, self.t_env)    # np.std: population
         for k, v in (("collective_return", coll), ("equality_metric", eq), ("ep_length", stats.get("ep_length", 0))):
             self.logger.log_stat(prefix + k + "_mean", v / n_ep, self.t_env)
+        self._log_extra(sums[4:], stats, prefix, test_mode)
         if getattr(self.args, "behaviour_stats", False):
             bacc, _ = self._behaviour_acc(test_mode)
             vec = bacc.cpu().numpy()
@@ -249,6 +259,9 @@ class HipVecRunner:
             for k, v in abi.behaviour_summary(vec, self.args.n_agents, self.args.n_actions).items():
                 self.logger.log_stat(prefix + k, v, self.t_env)
         stats.clear()
+
+    def _log_extra(self, sums, stats, prefix, test_mode):
+        """what a runner logs from the sums behind the first four (_stat_extra)"""
 
 
 class EpisodeRunner(HipVecRunner):

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SSD_ABI_VERSION 10   /* (still 10 with ssd_policy_head.pipeline_gather appended: zero = as before) */
+#define SSD_ABI_VERSION 10   /* (still 10 with ssd_policy_head.pipeline_gather and .epsilon_rows appended: zero = as before) */
 
 #define SSD_MAX_AGENTS 10   /* maps hold at most 10 spawn points; agent ids >= 10 break the reference (map_env.py:370) */
 #define SSD_MAX_CELLS 1024  /* H*W upper bound (largest reference map is 48x18 = 864) */
@@ -880,7 +880,12 @@ int ssd_conv_wgrad_codes(const uint8_t* codes, const float* d_conv, float* parti
  *   x0 = mix32p(seed ^ mix32p(u32(step) * 0x9E3779B9 + key));   x1 = mix32p(x0 ^ 0x85EBCA6B)
  *   explore  <=>  f32(x0 >> 8) * 2^-24 < eps           (f32 compare; eps is the f32 device scalar: never for eps <= 0 or NaN,
  *                                                       always for eps >= 1)
- *   pick = (u64(x1) * popcount(live)) >> 32  ->  the pick-th lowest AVAILABLE action;  no action available: the greedy result
+ *   with ssd_policy_head.epsilon_rows (a rate per env, e.g. the Ape-X ladder eps^(1 + alpha g / (G - 1))): row b -- the LOCAL env
+ *   index of the launch -- of both heads
+ *   explore  <=>  f32(x0 >> 8) * 2^-24 < epsilon_rows[b]    (the same f32 compare; `epsilon` stays required and is not read for
+ *                                                       the rows; key, seed, step, pick, greedy rule and the inc head's zero
+ *                                                       diagonal are unchanged; ssd_dueling_pick has the scalar only)
+ *   pick =(u64(x1) * popcount(live)) >> 32  ->  the pick-th lowest AVAILABLE action;  no action available: the greedy result
  *   key  = (env_id_base + b) * n + i                    env head
  *   key  = ((env_id_base + b) * n + i) * n + j          inc head (diagonal forced to 0 afterwards, draw or not)
  *   seed = ssd_policy_head.seed (FastPolicy: its seed for the env head, seed ^ 0x5bd1e995 for the inc head);  step = *step mod 2^32
@@ -1005,6 +1010,11 @@ typedef struct ssd_policy_head {
     /* ---- appended for the pipelined launch of the gathered layouts (zero = as before) ---- */
     int32_t pipeline_gather;       /* read by ssd_policy_head_inc_encode only: nonzero = take the gathered fused launch (declared below
                                       the encoder's arguments) for a head that carries one of the two gather bits */
+    /* ---- appended for a rate per env (zero = as before: every row explores at *epsilon) ---- */
+    const float* epsilon_rows;     /* nullable: f32 [n_env], 4-byte aligned.  Row b (local env index) of ssd_policy_head_env,
+                                      ssd_policy_head_inc and every path of ssd_policy_head_inc_encode (dense, any-view, gathered)
+                                      explores at epsilon_rows[b] instead of *epsilon ("Exploration draws" above).  Misaligned:
+                                      SSD_ERR_INVALID. */
 } ssd_policy_head;
 #define SSD_INPUT_LAST_ACTION 1u   /* obs_last_action: one-hot of the previous env action, n_actions columns */
 #define SSD_INPUT_AGENT_ID    2u   /* obs_agent_id: one-hot of the agent, n columns */

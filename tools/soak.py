@@ -38,6 +38,8 @@ ap.add_argument("--prioritized", action="store_true", help="config key prioritiz
 ap.add_argument("--initial-priority", choices=("max", "rollout"), default="max", help="config key per_initial_priority (with --prioritized)")
 ap.add_argument("--per-unit", choices=("episode", "window"), default="episode", help="config key per_unit (with --prioritized and --train-window): a priority per episode or per training window")
 ap.add_argument("--per-window-stride", type=int, default=0, help="config key per_window_stride: the stride of the window grid (0: half overlap)")
+ap.add_argument("--epsilon-ladder", type=float, default=0.0, metavar="ALPHA",
+                help="config key epsilon_ladder_alpha: env g of G explores at epsilon ** (1 + ALPHA g / (G - 1)) (0: one epsilon for all)")
 ap.add_argument("--set", action="append", default=[], help="extra config override key=value (python literal)")
 a = ap.parse_args()
 c = CONFIGS[a.config]
@@ -57,6 +59,8 @@ if a.prioritized:
     over["per_initial_priority"] = a.initial_priority
 if a.per_unit == "window":             # (without --prioritized or --train-window, setup refuses it)
     over.update(per_unit="window", per_window_stride=a.per_window_stride)
+if a.epsilon_ladder:
+    over["epsilon_ladder_alpha"] = a.epsilon_ladder
 import ast
 for kv in a.set:
     k, v = kv.split("=", 1)
