@@ -9,6 +9,7 @@ reference env (Cleanup default5, 5 agents, short episodes), then records:
 pyclustering is absent: its two entry points are stubbed with the documented exact-value rule
 (cluster id = 2 * rewards_t + clean_num_t), so `loss_sim` is parity-pinned only relative to that rule.
 Output: tests/golden/learner_cleanup5.npz, learner_harvest5.npz, learner_cleanup5_w4.npz (the same at 4 x the initial weights)
+(construct / batch_arrays / checksums are shared with oracle/gen_target_sync_golden.py)
 """
 import contextlib
 import io
@@ -59,14 +60,18 @@ def merge(d, u):
     return d
 
 
-def main(env_name, env_over, out_name, seed, wscale=1.0):
-    OUT = os.path.join(GOLDEN, out_name)
+def construct(env_name, env_over, seed, wscale=1.0, extra=None):
+    """The reference's runner, controller and learner on its own env with batch_size episodes played and sampled.  Returns (args, cfg,
+    mac, learner, batch, the initial weights, fresh); fresh(sd) is a further (controller, learner) pair on the same scheme with the
+    weights sd, a target net equal to them and new optimiser state.  `extra`: further config keys (none that changes what the
+    construction draws)."""
     RH.import_reference()
     install_cluster_stub()
     cfg = {}
     for f in ("default.yaml", "envs/%s.yaml" % env_name, "algs/homophily.yaml"):
         merge(cfg, yaml.safe_load(open(os.path.join(RH.REF_SRC, "config", f))))
     merge(cfg, dict(env_args=env_over, batch_size=4, buffer_size=8, use_cuda=False, use_tensorboard=False, save_model=False))
+    merge(cfg, dict(extra or {}))
     np.random.seed(seed); random.seed(seed); th.manual_seed(seed)
     args = SimpleNamespace(**cfg)
     args.device = "cpu"
@@ -110,6 +115,16 @@ def main(env_name, env_over, out_name, seed, wscale=1.0):
         buffer.insert_episode_batch(runner.run(test_mode=False))
     batch = buffer.sample(args.batch_size)
     batch = batch[:, :batch.max_t_filled()]
+
+    def fresh(sd):
+        m = mac_REGISTRY[args.mac](buffer.scheme, groups, args)
+        m.agent.load_state_dict({k: th.as_tensor(v) for k, v in sd.items()})
+        return m, le_REGISTRY[args.learner](m, buffer.scheme, logger, args)
+    return args, cfg, mac, learner, batch, init_sd, fresh
+
+
+def batch_arrays(batch):
+    """the sampled batch as the fixtures store it (obs as u8 = obs * 256)"""
     out = {}
     for k in ("obs", "actions", "actions_inc", "reward", "terminated", "clean_num", "apple_den", "agent_pos", "agent_orientation",
               "avail_actions", "filled"):
@@ -119,6 +134,22 @@ def main(env_name, env_over, out_name, seed, wscale=1.0):
             assert (v8 / 256 == v).all()
             v = v8.astype(np.uint8)
         out["batch_" + k] = v
+    return out
+
+
+def checksums(mac):
+    """(names, sum, sum of squares, first five elements) of every entry of the agent's state_dict, in float64"""
+    names, sums, sqs, heads = [], [], [], []
+    for k, v in mac.agent.state_dict().items():
+        x = v.detach().double().reshape(-1)
+        names.append(k); sums.append(x.sum().item()); sqs.append((x * x).sum().item()); heads.append(np.resize(x[:5].numpy(), 5))
+    return np.array(names), np.array(sums), np.array(sqs), np.stack(heads)
+
+
+def main(env_name, env_over, out_name, seed, wscale=1.0):
+    OUT = os.path.join(GOLDEN, out_name)
+    args, cfg, mac, learner, batch, init_sd, _ = construct(env_name, env_over, seed, wscale)
+    out = batch_arrays(batch)
     for k, v in init_sd.items():
         out["w_" + k] = v
     with th.no_grad():
@@ -134,13 +165,10 @@ def main(env_name, env_over, out_name, seed, wscale=1.0):
         logs = learner.cal_loss_and_step(batch)
         for k, v in logs.items():
             out["step%d_%s" % (step, k)] = np.float64(v.item())
-        names, sums, sqs, heads = [], [], [], []
-        for k, v in mac.agent.state_dict().items():
-            x = v.detach().double().reshape(-1)
-            names.append(k); sums.append(x.sum().item()); sqs.append((x * x).sum().item()); heads.append(np.resize(x[:5].numpy(), 5))
-        out["step%d_param_sum" % step] = np.array(sums); out["step%d_param_sq" % step] = np.array(sqs)
-        out["step%d_param_head" % step] = np.stack(heads)
-        out["param_names"] = np.array(names)
+        names, sums, sqs, heads = checksums(mac)
+        out["step%d_param_sum" % step] = sums; out["step%d_param_sq" % step] = sqs
+        out["step%d_param_head" % step] = heads
+        out["param_names"] = names
     out["meta_seq_len"] = np.int64(batch.max_seq_length)
     import json
     out["meta"] = np.frombuffer(json.dumps(dict(env=env_name, env_args=cfg["env_args"], wscale=wscale)).encode(), np.uint8)

@@ -471,8 +471,10 @@ def test_the_benched_configuration_at_its_own_size(kind, n, view, N, slabs, iter
     A slab's episodes: 1st eager, 2nd captures the rollout graph, 3rd captures the episode-edge graphs (opening launches: reset, first
     observation, runner-state fills, weight re-pack, encoder of slot 0; closing launches: slot-T pass + statistics), 4th is PURE
     REPLAYS of all three -- eight iterations (four with one slab) put such an episode into every slab, with the weights stepped by
-    learner.train in between (a stale re-pack in the opening graph would change the actions the oracle replays).  EVERY rollout is
-    replayed on the CPU oracle with the stored actions (the waste permutation persists across episodes): rewards / clean_num /
+    learner.train in between.  EVERY rollout is
+    replayed on the CPU oracle with the STORED actions (the waste permutation persists across episodes), so this holds the env and the
+    storage to the oracle whatever weights chose the actions -- that the re-pack in the opening graph follows the stepped weights is held
+    by tests/test_weights_in_motion_gpu.py, not here: rewards / clean_num /
     apple_den / terminated of every step, pose and observation every 25 steps and at slot T.  Every captured train step is compared,
     gradient by gradient, with an eager evaluation on the same sampled batch (SSD_GRAPH_CHECK)."""
     from homophily_marl_amd import ops
@@ -547,7 +549,9 @@ def test_the_benched_configuration_at_its_own_size(kind, n, view, N, slabs, iter
 def test_episode_edge_graphs_equal_the_eager_episode_edges():
     """the episode's opening and closing launches as hipGraph replays (episode_edge_graphs, on by default) against the same
     launches issued one by one.  Two runs from the same seeds, seven episodes in ONE storage with learner.train between episodes (the
-    opening graph re-packs the weight images: a stale pack would show in the actions), edge graphs on / off: the stored batches
+    opening graph re-packs the weight images; both runs pack through the same FastPolicy.pack, so this comparison sees a pack that
+    differs between replay and eager launches, not one that stopped following the weights in both -- that is held by
+    tests/test_weights_in_motion_gpu.py), edge graphs on / off: the stored batches
     (slot T included), the runner state an episode leaves (previous actions / reward / incentive actions, returns, hidden states),
     the packed head images and the device-side statistics must be bit-equal; with the graphs on, episodes 4 .. 7 replay both."""
     from homophily_marl_amd.run import load_config, setup
