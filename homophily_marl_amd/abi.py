@@ -36,6 +36,7 @@ ERR_BAD_RENDER = 64
 COPY_BLOCKS_MAX = 32
 FILL_BLOCKS_MAX = 16
 ADAM_MAX_JOBS = 64
+POLYAK_MAX_JOBS, POLYAK_WORKGROUPS = 128, 256
 SAMPLE_IDS_MAX = 1024
 COLSUM_CHUNK = 64
 TD_LOSS_PARTIALS = 16
@@ -163,10 +164,31 @@ class SsdAdamJob(C.Structure):
                 ("exp_avg", C.c_void_p * 2), ("exp_avg_sq", C.c_void_p * 2), ("step", C.c_void_p * 2)]
 
 
+class SsdPolyakJob(C.Structure):
+    """one 2-D block of the Polyak target update of ssd_clip_adam_step (a target parameter, or a parameter's slice of a concatenated copy)"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("dst_row_stride", C.c_int64)]
+
+
 class SsdClipAdamArgs(C.Structure):
     _fields_ = [("flat_grad", C.c_void_p), ("total", C.c_int64), ("jobs", C.c_void_p),
                 ("n_jobs", C.c_int32), ("partials", C.c_void_p), ("lr_inc", C.c_float), ("lr_env", C.c_float), ("beta1", C.c_float),
-                ("beta2", C.c_float), ("eps", C.c_float), ("clip", C.c_float)]
+                ("beta2", C.c_float), ("eps", C.c_float), ("clip", C.c_float),
+                ("polyak_jobs", C.c_void_p), ("n_polyak", C.c_int32), ("target_tau", C.c_float), ("polyak_partials", C.c_void_p)]
+
+
+def polyak_job_table(blocks):
+    """(SsdPolyakJob * len(blocks)) of (src, dst, rows, cols, dst_row_stride) tuples (addresses, elements).  What the entry point cannot
+    check of a table in device memory is checked here: the count, non-null 4-byte aligned addresses, rows, cols >= 1, rows * cols < 2^31,
+    dst_row_stride >= cols."""
+    if not 1 <= len(blocks) <= POLYAK_MAX_JOBS:
+        raise ValueError("a Polyak job table holds 1 .. %d jobs, got %d" % (POLYAK_MAX_JOBS, len(blocks)))
+    jobs = (SsdPolyakJob * len(blocks))()
+    for j, (src, dst, rows, cols, stride) in zip(jobs, blocks):
+        if not src or not dst or src % 4 or dst % 4 or rows < 1 or cols < 1 or rows * cols >= 2 ** 31 or stride < cols:
+            raise ValueError("Polyak job (src 0x%x, dst 0x%x, rows %d, cols %d, dst_row_stride %d): addresses must be non-null and 4-byte aligned, "
+                             "rows, cols >= 1, rows * cols < 2^31, dst_row_stride >= cols" % (src or 0, dst or 0, rows, cols, stride))
+        j.src, j.dst, j.rows, j.cols, j.dst_row_stride = src, dst, rows, cols, stride
+    return jobs
 
 
 class SsdTdLossArgs(C.Structure):

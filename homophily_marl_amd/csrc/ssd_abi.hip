@@ -471,6 +471,11 @@ int ssd_clip_adam_step(const ssd_clip_adam_args* a, void* stream) {
     if (a->total > (int64_t)INT32_MAX) return fail(SSD_ERR_INVALID, "ssd_clip_adam_step: total");
     if (!(a->beta1 >= 0.f && a->beta1 < 1.f) || !(a->beta2 >= 0.f && a->beta2 < 1.f) || !(a->eps > 0.f) || !(a->clip > 0.f))
         return fail(SSD_ERR_INVALID, "ssd_clip_adam_step: betas / eps / clip");
+    // the Polyak target update behind the Adam launch (all zero / NULL: none)
+    if (a->n_polyak < 0 || a->n_polyak > SSD_POLYAK_MAX_JOBS) return fail(SSD_ERR_INVALID, "ssd_clip_adam_step: n_polyak outside 0 .. SSD_POLYAK_MAX_JOBS");
+    if (a->n_polyak > 0 && !a->polyak_jobs) return fail(SSD_ERR_INVALID, "ssd_clip_adam_step: n_polyak > 0 without polyak_jobs");
+    if (!(a->target_tau >= 0.f && a->target_tau <= 1.f)) return fail(SSD_ERR_INVALID, "ssd_clip_adam_step: target_tau outside [0, 1]");
+    if (a->n_polyak > 0 && a->target_tau == 0.f) return fail(SSD_ERR_INVALID, "ssd_clip_adam_step: n_polyak > 0 with target_tau 0 (an update that moves nothing)");
     launch_clip_adam(a, (hipStream_t)stream);
     return launched();
 }

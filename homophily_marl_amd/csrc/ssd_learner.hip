@@ -1458,6 +1458,19 @@ void launch_copy_blocks(const ssd_block_copy* blocks, int count, hipStream_t str
 // (include/ssd_hip.h: ssd_clip_adam_step; homophily_learner.py:223-226).  1024 elements per workgroup, 4 per thread.
 // ---------------------------------------------------------------------------------------------------------------------------
 constexpr int ADAM_CHUNK = 1024;
+// What the two Adam launches read of ssd_clip_adam_args: the members before polyak_jobs, at their offsets.  They take THIS by value, so
+// members appended to the public struct leave their kernel-argument segment (and `chunks` behind it) where it was.
+struct ClipAdamCore {
+    float* flat_grad;
+    int64_t total;
+    const ssd_adam_job* jobs;
+    int32_t n_jobs;
+    float* partials;
+    float lr_inc, lr_env, beta1, beta2, eps, clip;
+};
+static_assert(sizeof(ClipAdamCore) == offsetof(ssd_clip_adam_args, polyak_jobs) && offsetof(ClipAdamCore, partials) == offsetof(ssd_clip_adam_args, partials) &&
+              offsetof(ClipAdamCore, lr_inc) == offsetof(ssd_clip_adam_args, lr_inc) && offsetof(ClipAdamCore, clip) == offsetof(ssd_clip_adam_args, clip),
+              "ClipAdamCore is the head of ssd_clip_adam_args");
 __device__ __forceinline__ float block_sum_256(float v, float* red) {      // fixed-order tree over 256 threads
     const int t = threadIdx.x;
     red[t] = v;
@@ -1478,7 +1491,7 @@ __device__ __forceinline__ int adam_job_of(const long* j_off, int n_jobs, long b
     return lo;
 }
 
-__global__ __launch_bounds__(256) void k_gradsq_partials(ssd_clip_adam_args a) {
+__global__ __launch_bounds__(256) void k_gradsq_partials(ClipAdamCore a) {
     __shared__ float red[256];
     __shared__ long j_off[SSD_ADAM_MAX_JOBS + 1];
     __shared__ int j_seg[SSD_ADAM_MAX_JOBS];
@@ -1516,7 +1529,7 @@ __global__ __launch_bounds__(256) void k_gradsq_partials(ssd_clip_adam_args a) {
     }
 }
 
-__global__ __launch_bounds__(256) void k_clip_adam(ssd_clip_adam_args a, int chunks) {
+__global__ __launch_bounds__(256) void k_clip_adam(ClipAdamCore a, int chunks) {
     __shared__ float red[256];
     __shared__ long j_off[SSD_ADAM_MAX_JOBS + 1];
     __shared__ float j_size[SSD_ADAM_MAX_JOBS][2], j_rsq[SSD_ADAM_MAX_JOBS][2];   // lr / (1 - b1^t), 1 / sqrt(1 - b2^t) per optimiser
@@ -1575,10 +1588,74 @@ __global__ __launch_bounds__(256) void k_clip_adam(ssd_clip_adam_args a, int chu
     }
 }
 
+// k_polyak: the Polyak target update behind the Adam launch (include/ssd_hip.h: ssd_clip_adam_step, "Polyak target update").  All jobs
+// in one launch of SSD_POLYAK_WORKGROUPS workgroups: the jobs' element counts are scanned in LDS (the table is device memory: the host
+// cannot size a grid by it), a workgroup owns one contiguous range of the concatenated element space, a thread strides it by 256.
+__global__ __launch_bounds__(256) void k_polyak(const ssd_polyak_job* __restrict__ jobs, int n_jobs, float tau, float c, float* __restrict__ partials) {
+    __shared__ float red[256];
+    __shared__ long scan[2][SSD_POLYAK_MAX_JOBS];
+    __shared__ long j_off[SSD_POLYAK_MAX_JOBS + 1];
+    __shared__ ssd_polyak_job j_tab[SSD_POLYAK_MAX_JOBS];
+    const int t = threadIdx.x;
+    if (t < SSD_POLYAK_MAX_JOBS) {
+        long cnt = 0;
+        if (t < n_jobs) {
+            const ssd_polyak_job j = jobs[t];
+            j_tab[t] = j;
+            const long e = (long)j.rows * (long)j.cols;
+            if (j.rows >= 1 && j.cols >= 1 && j.dst_row_stride >= (int64_t)j.cols && e < (1l << 31)) cnt = e;     // else: skipped
+        }
+        scan[0][t] = cnt;
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int s = 1; s < SSD_POLYAK_MAX_JOBS; s <<= 1) {                      // inclusive scan of the counts (Hillis-Steele, 7 rounds)
+        if (t < SSD_POLYAK_MAX_JOBS) scan[cur ^ 1][t] = scan[cur][t] + (t >= s ? scan[cur][t - s] : 0);
+        cur ^= 1;
+        __syncthreads();
+    }
+    if (t < n_jobs) j_off[t + 1] = scan[cur][t];
+    if (t == 0) j_off[0] = 0;
+    __syncthreads();
+    const long total = j_off[n_jobs];
+    const long per = ((total + 256l * SSD_POLYAK_WORKGROUPS - 1) / (256l * SSD_POLYAK_WORKGROUPS)) * 256l;
+    const long begin = (long)blockIdx.x * per;
+    const long end = begin + per < total ? begin + per : total;
+    float s_gap = 0.f, s_live = 0.f;
+    long i = begin + t;
+    if (i < end) {
+        int job = 0, hi = n_jobs - 1;                                      // the last job whose first element is <= i
+        while (job < hi) { const int mid = (job + hi + 1) >> 1; if (j_off[mid] <= i) job = mid; else hi = mid - 1; }
+        for (; i < end; i += 256) {
+            while (i >= j_off[job + 1]) ++job;                             // (i < total = j_off[n_jobs]: stops at a job that holds i)
+            const uint32_t e = (uint32_t)(i - j_off[job]);
+            const uint32_t cols = (uint32_t)j_tab[job].cols;
+            const bool whole = j_tab[job].dst_row_stride == (int64_t)cols;
+            float* d = j_tab[job].dst + (whole ? (size_t)e : (size_t)(e / cols) * (size_t)j_tab[job].dst_row_stride + (e % cols));
+            const float l = j_tab[job].src[e];
+            const float a = *d * c, b = l * tau;                           // three roundings (the library is built without contraction)
+            const float v = a + b;
+            *d = v;
+            if (whole) { const float g = l - v; s_gap += g * g; s_live += l * l; }
+        }
+    }
+    if (partials) {
+        const float g = block_sum_256(s_gap, red), w = block_sum_256(s_live, red);
+        if (t == 0) { partials[(size_t)blockIdx.x * 2] = g; partials[(size_t)blockIdx.x * 2 + 1] = w; }
+    }
+}
+
 void launch_clip_adam(const ssd_clip_adam_args* a, hipStream_t stream) {
     const int chunks = (int)((a->total + ADAM_CHUNK - 1) / ADAM_CHUNK);
-    hipLaunchKernelGGL(k_gradsq_partials, dim3(chunks), dim3(256), 0, stream, *a);
-    hipLaunchKernelGGL(k_clip_adam, dim3(chunks), dim3(256), 0, stream, *a, chunks);
+    ClipAdamCore core;
+    core.flat_grad = a->flat_grad; core.total = a->total; core.jobs = a->jobs; core.n_jobs = a->n_jobs; core.partials = a->partials;
+    core.lr_inc = a->lr_inc; core.lr_env = a->lr_env; core.beta1 = a->beta1; core.beta2 = a->beta2; core.eps = a->eps; core.clip = a->clip;
+    hipLaunchKernelGGL(k_gradsq_partials, dim3(chunks), dim3(256), 0, stream, core);
+    hipLaunchKernelGGL(k_clip_adam, dim3(chunks), dim3(256), 0, stream, core, chunks);
+    if (a->n_polyak > 0) {
+        const float c = 1.f - a->target_tau;
+        hipLaunchKernelGGL(k_polyak, dim3(SSD_POLYAK_WORKGROUPS), dim3(256), 0, stream, a->polyak_jobs, (int)a->n_polyak, a->target_tau, c, a->polyak_partials);
+    }
 }
 
 static int grid_for(size_t total) {

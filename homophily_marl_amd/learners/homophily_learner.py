@@ -13,6 +13,7 @@ import os
 from collections.abc import Mapping
 from types import SimpleNamespace
 
+import numpy as np
 import torch as th
 import torch.distributed as dist
 from torch.optim import Adam
@@ -22,6 +23,30 @@ from ..components.episode_buffer import EpisodeBatch
 from ..controllers import REGISTRY as mac_REGISTRY
 
 NEG = -9999999
+
+
+def validate_target_tau(raw):
+    """target_tau (not a key of the reference's config) as a float in [0, 1]; absent / None / 0: the reference's hard syncs."""
+    try:
+        tau = 0.0 if raw is None else float(raw)
+    except (TypeError, ValueError):
+        tau = float("nan")
+    if isinstance(raw, bool) or not 0.0 <= tau <= 1.0:            # (NaN fails both comparisons)
+        raise ValueError("target_tau must be a finite number in [0, 1], got %r" % (raw,))
+    return tau
+
+
+def polyak_mix(target, live, tau):
+    """The Polyak rule as tensor ops: fl(fl(target * c) + fl(live * tau)), c = fl(1 - tau) in f32 -- a plain mul, mul, add (three
+    roundings, no alpha=, no lerp), the arithmetic of csrc/ssd_learner.hip: k_polyak bit for bit."""
+    tau32 = np.float32(tau)
+    return target.mul(float(np.float32(1.0) - tau32)).add(live.mul(float(tau32)))
+
+
+def gap_rel(partials):
+    """target_gap_rel = sqrt(sum (l - t)^2) / sqrt(sum l^2) from rows of {sum (l - t)^2, sum l^2}, added in float64 on the host"""
+    p = partials.detach().double().reshape(-1, 2).sum(dim=0).cpu()
+    return float(p[0].sqrt() / p[1].sqrt())
 
 
 def lambda_returns(r, terminated, mask, v, gamma, lam):
@@ -64,16 +89,20 @@ class _FusedLogs(Mapping):
     def __len__(self):
         return len(self.KEYS)
 
-    def host_items(self, extra=()):
+    def host_items(self, extra=(), gap=None):
         """(key, python float) of all nine scalars (+ extra (key, 0-d tensor) pairs) from ONE device -> host copy: the sums and the
         denominators travel once and the quotients are formed on the host in f32 as above -- twelve .item() calls were twelve
-        synchronisations (0.4 ms of an otherwise idle GPU per log interval)."""
+        synchronisations (0.4 ms of an otherwise idle GPU per log interval).  gap: the Polyak launch's partials, which ride in the same
+        copy and become target_gap_rel on the host (gap_rel)."""
         with th.no_grad():
-            flat = th.cat([self.sums.detach().float().reshape(-1), self.dens.detach().float().reshape(-1)] + [v.detach().float().reshape(1) for _, v in extra])
+            flat = th.cat([self.sums.detach().float().reshape(-1), self.dens.detach().float().reshape(-1)] + [v.detach().float().reshape(1) for _, v in extra]
+                          + ([] if gap is None else [gap.detach().float().reshape(-1)]))
         host = flat.cpu()
         ns = self.sums.numel()
         host_logs = _FusedLogs(host[:ns], host[ns:ns + self.dens.numel()], self.rows, self.n)
         out = [(k, float(host[ns + self.dens.numel() + i])) for i, (k, _) in enumerate(extra)]
+        if gap is not None:
+            out.append(("target_gap_rel", gap_rel(host[ns + self.dens.numel() + len(extra):])))
         return out + [(k, float(host_logs[k])) for k in self.KEYS]
 
     def synced(self):
@@ -107,6 +136,15 @@ class HomophilyLearner:
         self.params_env = mac.parameters_env()
         self.params_inc = mac.parameters_inc()
         self.last_target_update_episode = 0
+        # target_tau (not a key of the reference's config; absent or 0: its hard sync every target_update_interval train calls): after
+        # EVERY train call, behind both Adam steps, target <- (1 - tau) target + tau live (polyak_mix), and no hard sync is made
+        self.target_tau = validate_target_tau(getattr(args, "target_tau", 0.0))
+        self._polyak = None            # (the target net's caches the pairs were built for, the pairs): see _polyak_pairs
+        self._gap_partials = None      # the Polyak launch's partial sums {sum (live - target)^2, sum live^2} (device path)
+        self._gap_lazy = False         # the last update ran as tensor ops outside a capture: the sums are formed when they are read (_gap)
+        if self.target_tau > 0 and logger is not None and getattr(logger, "console_logger", None) is not None:
+            logger.console_logger.info("target_tau %g: the target network follows the live one after every train step; "
+                                       "target_update_interval (%s) is ignored" % (self.target_tau, getattr(args, "target_update_interval", None)))
         # train_graph: capture the step as hipGraphs (torch.cuda.CUDAGraph); needs capturable Adam (same arithmetic,
         # the step counter lives on the device)
         on_gpu = str(self.device).startswith("cuda")
@@ -413,6 +451,8 @@ class HomophilyLearner:
         """Arguments of ssd_clip_adam_step (both clips + both Adam steps as two launches over the flat gradient buffer), or None when
         the tensor-op tail below has to run: CPU, optimiser state not created yet (the first step creates it), options the kernel does
         not implement.  The plan holds pointers into the optimisers' own state tensors (checkpoints see the same state)."""
+        if self._opt_plan and self.target_tau > 0 and not self._polyak_current(self._opt_plan.polyak_for):
+            self._opt_plan = None      # the target net's caches were rebuilt (HomophilyAgent._apply): the job table points at the old ones
         if self._opt_plan is not None:
             return self._opt_plan or None
         self._opt_plan = False
@@ -459,20 +499,88 @@ class HomophilyLearner:
         gi, ge = opts[0].param_groups[0], opts[1].param_groups[0]
         args.lr_inc, args.lr_env, args.beta1, args.beta2, args.eps = float(gi["lr"]), float(ge["lr"]), float(gi["betas"][0]), float(gi["betas"][1]), float(gi["eps"])
         args.clip = float(a.grad_norm_clip)
-        self._opt_plan = SimpleNamespace(args=args, keep=(table, partials), lib=abi.load_library(), byref=C.byref)
+        keep, polyak_for, gap = (table, partials), None, None
+        if self.target_tau > 0:
+            # the Polyak job table: every target parameter and every slice of the target net's caches (built here, after the first
+            # forward, so the caches exist; the parameters and their slices are disjoint blocks)
+            blocks = []
+            for src, dst, whole in self._polyak_pairs():
+                cols = src.shape[-1] if not whole else src.numel()
+                # a slice's rows are one row stride apart through every leading axis
+                rows_ok = dst.is_contiguous() if whole else (dst.dim() >= 2 and dst.stride(-1) == 1 and all(
+                    dst.stride(k) == dst.stride(k + 1) * dst.shape[k + 1] for k in range(dst.dim() - 2)))
+                if not (src.is_cuda and dst.is_cuda and src.dtype == dst.dtype == th.float32 and src.is_contiguous() and rows_ok):
+                    raise ValueError("target_tau: a target tensor the Polyak launch cannot address (%s, %s)" % (tuple(dst.shape), dst.stride()))
+                blocks.append((src.data_ptr(), dst.data_ptr(), src.numel() // cols, cols, cols if whole else dst.stride(-2)))
+            ptable = th.frombuffer(bytearray(bytes(abi.polyak_job_table(blocks))), dtype=th.uint8).to(dev)
+            gap = th.zeros(abi.POLYAK_WORKGROUPS, 2, dtype=th.float32, device=dev)
+            args.polyak_jobs, args.n_polyak, args.target_tau, args.polyak_partials = ptable.data_ptr(), len(blocks), self.target_tau, gap.data_ptr()
+            keep, polyak_for = keep + (ptable, gap), self._polyak[0]
+        self._opt_plan = SimpleNamespace(args=args, keep=keep, lib=abi.load_library(), byref=C.byref, polyak_for=polyak_for, gap=gap)
         return self._opt_plan
+
+    def _polyak_current(self, made_for):
+        tgt = self.target_mac.agent
+        return made_for is not None and made_for[0] is tgt._gru_cache and made_for[1] is tgt._fc2_cache
+
+    def _polyak_pairs(self):
+        """[(live tensor, target tensor, whole)] of the Polyak update: every target parameter (whole) and every slice of the target
+        net's derived copies (_gru_cache, _fc2_cache: HomophilyAgent.cache_slices; a view [.., rows, cols] of the buffer against the
+        live parameter without its leading 1).  The encoder's weight fragments are packed afresh by every forward (ops.encode_codes):
+        there is no other persistent copy of target weights.  Rebuilt when the caches are (they appear with the first forward).
+        Staleness is told by the identity of the TARGET net's cache objects alone, while the pairs (and the job table built from
+        them) also hold views of the LIVE parameters: this relies on both nets moving together (learner.cuda() moves both; a
+        _apply on the live net alone would leave stale sources)."""
+        tgt, live = self.target_mac.agent, dict(self.mac.agent.named_parameters())
+        if self._polyak is None or not self._polyak_current(self._polyak[0]):
+            pairs = [(live[name].detach(), p.detach(), True) for name, p in tgt.named_parameters()]
+            for name, buf, col in tgt.cache_slices():
+                src = live[name].detach().squeeze(0)
+                pairs.append((src, buf[..., col:col + src.shape[-1]], False))
+            self._polyak = ((tgt._gru_cache, tgt._fc2_cache), pairs)
+        return self._polyak[1]
+
+    def _soft_update_ops(self):
+        """The Polyak update as tensor ops (CPU tensors; the device steps that take the tensor-op optimiser tail, such as the first one):
+        the parameters and the cache slices by the same rule -- a slice equals its parameter before, so it does after.  The gap's sums
+        are not formed here but when they are read (_gap).  A tensor-op tail taken INSIDE a capture logs no gap: the sums would be
+        ATen reductions, which never run inside a captured step, and a replay does not pass through this code."""
+        with th.no_grad():
+            for src, dst, whole in self._polyak_pairs():
+                dst.copy_(polyak_mix(dst, src, self.target_tau))
+        self._gap_partials = None
+        self._gap_lazy = not (self.params[0].is_cuda and th.cuda.is_current_stream_capturing())
+
+    def _gap(self):
+        """rows of {sum (live - target)^2, sum live^2} after the last Polyak update, or None (target_tau 0, no update yet, a captured
+        tensor-op tail): the launch's partial sums, or -- after a tensor-op update -- float64 sums over the parameters as they are now"""
+        if self.target_tau == 0 or self._gap_partials is not None or not self._gap_lazy:
+            return self._gap_partials if self.target_tau > 0 else None
+        with th.no_grad():
+            return th.stack([th.stack([((src.double() - dst.double()) ** 2).sum(), (src.double() ** 2).sum()])
+                             for src, dst, whole in self._polyak_pairs() if whole])
+
+    def target_gap_rel(self):
+        """sqrt(sum (live - target)^2) / sqrt(sum live^2) over all parameters after the last Polyak update, from its partial sums in
+        float64 (None before the first update and with target_tau 0).  Synchronises: the logger reads the same sums inside the log
+        event's one copy instead (train)."""
+        gap = self._gap()
+        return None if gap is None else gap_rel(gap)
 
     def clip_and_step(self):
         plan = self._optimiser_plan()
         if plan is not None:
             from .. import abi
             abi.check(plan.lib, plan.lib.ssd_clip_adam_step(plan.byref(plan.args), th.cuda.current_stream(self._flat_grad.device).cuda_stream))
+            self._gap_partials, self._gap_lazy = plan.gap, False    # (None with target_tau 0; else written by the Polyak launch of this call and every replay)
             return
         a = self.args
         th.nn.utils.clip_grad_norm_(self.params_inc, a.grad_norm_clip)
         th.nn.utils.clip_grad_norm_(self.params_env, a.grad_norm_clip)
         self.optimiser_inc.step()
         self.optimiser_env.step()
+        if self.target_tau > 0:
+            self._soft_update_ops()
 
     def cal_loss_and_step(self, batch):
         dens = self.denominators(batch)
@@ -569,7 +677,8 @@ class HomophilyLearner:
         # learner, the eager controller and the SSD_GRAPH_CHECK re-evaluation keep theirs); a captured step keeps what it was captured with
         with ops._precision(self.precision if batch["reward"].is_cuda else ops.LEARNER_PRECISION):
             logs = self._graph_step(batch) if self.use_graph else self.cal_loss_and_step(batch)
-        if (episode_num - self.last_target_update_episode) / self.args.target_update_interval >= 1.0:
+        # target_tau > 0: the target net moved inside the step (clip_and_step), the interval is not looked at
+        if self.target_tau == 0 and (episode_num - self.last_target_update_episode) / self.args.target_update_interval >= 1.0:
             self._update_targets()
             self.last_target_update_episode = episode_num
         clock = self.log_clock() if self.log_clock is not None else t_env
@@ -581,12 +690,15 @@ class HomophilyLearner:
                           ("per_unique_frac", plog[3] / batch.batch_size))
             if self.distributed and isinstance(logs, _FusedLogs):
                 logs = logs.synced()
+            gap = self._gap()                                            # every rank holds the same parameters: no collective
             if isinstance(logs, _FusedLogs):
-                for k, v in logs.host_items(means):                      # one device -> host copy for all eleven scalars
+                for k, v in logs.host_items(means, gap=gap):             # one device -> host copy for all eleven scalars (+ the gap's partials)
                     self.logger.log_stat(k, v, t_env)
             else:
                 for k, v in means + tuple(logs.items()):
                     self.logger.log_stat(k, v.item(), t_env)
+                if gap is not None:
+                    self.logger.log_stat("target_gap_rel", gap_rel(gap), t_env)
             self.log_stats_t = clock
             self.check_numeric_status(t_env)
 
@@ -621,7 +733,9 @@ class HomophilyLearner:
 
     def load_models(self, path):
         self.mac.load_models(path)
-        self.target_mac.load_models(path)       # reference: the target net is loaded from the same file (:281-288)
+        # reference: the target net is loaded from the same file (:281-288).  With target_tau > 0 this restarts the average at the
+        # loaded live weights (the target net is not part of a checkpoint); the job table goes with _opt_plan below
+        self.target_mac.load_models(path)
         load = lambda f: th.load("{}/{}".format(path, f), map_location=lambda storage, loc: storage, weights_only=True)
         self.optimiser_env.load_state_dict(load("opt_env.th"))
         self.optimiser_inc.load_state_dict(load("opt_inc.th"))

@@ -165,6 +165,28 @@ class HomophilyAgent(nn.Module):
         self._fc2_cache = None
         return super()._apply(fn, *args, **kwargs)
 
+    def cache_slices(self):
+        """[(parameter name, cache buffer, first column)] of every parameter slice the caches of a frozen copy hold at present (none
+        before they exist): the parameter, seen as [rows, cols], is columns first .. first + cols of the buffer's rows.  Whoever moves
+        a frozen copy's parameters without load_state_dict (the learner's Polyak target update) moves these with them."""
+        out = []
+
+        def slices(buf, names):
+            col = 0
+            for name in names:
+                out.append((name, buf, col))
+                col += getattr(self, name).shape[-1]
+            assert col == buf.shape[-1] and buf.is_contiguous(), names
+        if self._gru_cache is not None:
+            for head, (wi, wh, bi, bh) in self._gru_cache.items():
+                p = "rnn_%s_" % head
+                for buf, gates, kind in ((wi, ("ir", "iz", "in"), "_w"), (wh, ("hr", "hz", "hn"), "_w"), (bi, ("ir", "iz", "in"), "_b"), (bh, ("hr", "hz", "hn"), "_b")):
+                    slices(buf, [p + g + kind for g in gates])
+        if self._fc2_cache is not None:
+            for buf, names in zip(self._fc2_cache, (("fc2_env_w", "fc2_env_v_w"), ("fc2_env_b", "fc2_env_v_b"), ("fc2_inc_w", "fc2_inc_v_w"), ("fc2_inc_b", "fc2_inc_v_b"))):
+                slices(buf, names)
+        return out
+
     def unroll(self, inputs, act_onehot, agent_pos, agent_orientation, reward, clean_num, apple_den):
         """Evaluate both heads on whole episodes: inputs [B, T, n, in], act_onehot [B, T, n, A] (the env action taken at
         t), agent_pos / agent_orientation [B, T, n, 2], reward / clean_num / apple_den [B, T, n].

@@ -204,6 +204,15 @@ def _check_epsilon_ladder(args, fused_heads=True):
     return alpha
 
 
+def _check_target_tau(args):
+    """target_tau (absent = 0 = off: the reference's hard sync every target_update_interval), validated and written back.  A value in
+    (0, 1]: after every learner.train call the target net becomes (1 - tau) target + tau live on the device, inside the optimiser tail
+    (HomophilyLearner.clip_and_step), and target_update_interval is ignored.  Runs without a device; returns tau."""
+    from .learners.homophily_learner import validate_target_tau
+    args.target_tau = validate_target_tau(getattr(args, "target_tau", 0.0))
+    return args.target_tau
+
+
 def per_beta(args, train_steps):
     """the importance-weight exponent of train step number train_steps (0-based): per_beta, annealed linearly to 1 over
     per_beta_anneal_steps train steps (0: constant)"""
@@ -231,6 +240,7 @@ def setup(config, logger=None):
         ops.set_strict(True)
     logger = logger or Logger()
     _check_stored_state(args)
+    _check_target_tau(args)
     runner = r_REGISTRY[args.runner](args=args, logger=logger)
     env_info = runner.get_env_info()
     args.n_agents, args.n_actions = env_info["n_agents"], env_info["n_actions"]

@@ -572,8 +572,34 @@ int ssd_rollout_priority(const ssd_rollout_priority_args* args, void* stream);
  *      scaled gradients back and applies torch.optim.Adam's update (no weight decay / amsgrad; lerp form of the first moment,
  *      bias corrections from the per-parameter step counters) -- inc optimiser first, then env, as the reference steps them.
  * jobs: DEVICE array, one per parameter tensor in flat-buffer order; state index 0 = the inc optimiser's (exp_avg, exp_avg_sq, step),
- * 1 = the env optimiser's; a parameter outside an optimiser has NULLs there.  partials: f32 [ceil(total / 1024)][3] workspace. */
+ * 1 = the env optimiser's; a parameter outside an optimiser has NULLs there.  partials: f32 [ceil(total / 1024)][3] workspace.
+ *
+ * Polyak target update (config key target_tau; members from polyak_jobs on, all zero / NULL: exactly the two launches above).  With
+ * n_polyak > 0 ONE more launch behind the second moves every destination element of every job by
+ *     t_new = fl(fl(t * c) + fl(l * tau)),   c = fl(1 - tau),   all f32: three roundings, no fused multiply-add
+ * where l is the job's source element as the Adam launch left it (tau = 1: c = 0 and t_new = l).  A job is one 2-D block: src
+ * contiguous [rows, cols], dst rows of cols elements dst_row_stride elements apart -- a target parameter (dst_row_stride == cols) or a
+ * parameter's slice inside a concatenated copy of target weights (dst_row_stride > cols; the elements between the rows belong to
+ * other jobs and are neither read nor written).  Blocks of different jobs must not overlap.  src and dst need 4-byte alignment only.
+ * The launch is SSD_POLYAK_WORKGROUPS workgroups of 256 threads over the jobs' elements numbered job after job, row-major within a
+ * job (E in all): workgroup w owns elements [w P, (w + 1) P), P = 256 ceil(E / (256 SSD_POLYAK_WORKGROUPS)), and its thread t takes
+ * w P + t, w P + t + 256, ... in rising order.  Every element is written exactly once; no atomics, no cross-workgroup hand-off.
+ * polyak_partials (nullable): f32 [SSD_POLYAK_WORKGROUPS][2]; workgroup w writes {sum (l - t_new)^2, sum l^2} over ITS elements of the
+ * jobs with dst_row_stride == cols (the parameters; slices add nothing).  Order: every thread adds fl(d * d), d = fl(l - t_new)
+ * (resp. fl(l * l)) to an f32 accumulator starting at 0 in the order it takes its elements; the 256 accumulators a[0 .. 255] are then
+ * folded as  for s = 128, 64, .., 1: a[t] = fl(a[t] + a[t + s]) for t < s;  a[0] is written.
+ * DEVICE array polyak_jobs: a job with rows < 1, cols < 1, dst_row_stride < cols or rows * cols >= 2^31 is skipped (the table's
+ * builder checks them: abi.polyak_job_table).  Refused before any launch: n_polyak outside 0 .. SSD_POLYAK_MAX_JOBS; polyak_jobs NULL
+ * with n_polyak > 0; target_tau outside [0, 1] or NaN; target_tau == 0 with n_polyak > 0. */
 #define SSD_ADAM_MAX_JOBS 64
+#define SSD_POLYAK_MAX_JOBS 128
+#define SSD_POLYAK_WORKGROUPS 256
+typedef struct ssd_polyak_job {
+    const float* src;              /* [rows, cols] contiguous: the live parameter */
+    float* dst;
+    int32_t rows, cols;
+    int64_t dst_row_stride;        /* elements */
+} ssd_polyak_job;
 typedef struct ssd_adam_job {
     float* param;
     int64_t offset;                /* first element in the flat gradient buffer */
@@ -589,6 +615,10 @@ typedef struct ssd_clip_adam_args {
     int32_t n_jobs;
     float* partials;
     float lr_inc, lr_env, beta1, beta2, eps, clip;
+    const ssd_polyak_job* polyak_jobs;   /* DEVICE array (nullable with n_polyak == 0) */
+    int32_t n_polyak;
+    float target_tau;
+    float* polyak_partials;        /* nullable */
 } ssd_clip_adam_args;
 int ssd_clip_adam_step(const ssd_clip_adam_args* args, void* stream);
 

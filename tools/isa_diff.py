@@ -8,7 +8,9 @@ Every kernel of the FIRST listing whose name (the unqualified function name, tem
 matched with the symbol of the same mangled name in the second and their instruction streams compared.  Basic-block labels are
 normalised (their numbers follow the function's position in the file); assembler directives (.amdhsa_*, sections, symbol names) are
 left out.  Kernels of those names that only the second listing has are listed as new.  Exit status 1 if any stream differs or is
-missing.  (tools/kenv_isa_diff.py is the k_env-only predecessor, which also maps a changed template signature.)
+missing.  A kernel whose mangled name is gone from the second listing while exactly ONE kernel of the same unqualified name is new
+there (its parameter types changed, its body need not have) is compared with that one and reported as "identical (signature changed)".
+(tools/kenv_isa_diff.py is the k_env-only predecessor, which also maps a changed template signature.)
 """
 import re
 import subprocess
@@ -44,8 +46,14 @@ def main(before, after, names):
     pretty = demangle(old + new)
     bad = 0
     for sym in old:
-        same = sym in b and a[sym] == b[sym]
-        print("%-72s %6d instructions  %s" % (pretty[sym].replace("ssd::", ""), len(a[sym]), "identical" if same else ("DIFFERENT" if sym in b else "MISSING")))
+        other, note = sym, ""
+        if sym not in b:            # the same unqualified name under ONE new signature, none of the old ones left
+            cands = [k for k in new if base_name(k) == base_name(sym)]
+            if len(cands) == 1 and not any(base_name(k) == base_name(sym) for k in old if k in b):
+                other, note = cands[0], " (signature changed: %s)" % pretty[cands[0]].replace("ssd::", "")
+                new.remove(other)
+        same = other in b and a[sym] == b[other]
+        print("%-72s %6d instructions  %s%s" % (pretty[sym].replace("ssd::", ""), len(a[sym]), "identical" if same else ("DIFFERENT" if other in b else "MISSING"), note))
         bad += not same
     for sym in new:
         print("%-72s %6d instructions  new" % (pretty[sym].replace("ssd::", ""), len(b[sym])))

@@ -40,6 +40,8 @@ ap.add_argument("--per-unit", choices=("episode", "window"), default="episode", 
 ap.add_argument("--per-window-stride", type=int, default=0, help="config key per_window_stride: the stride of the window grid (0: half overlap)")
 ap.add_argument("--epsilon-ladder", type=float, default=0.0, metavar="ALPHA",
                 help="config key epsilon_ladder_alpha: env g of G explores at epsilon ** (1 + ALPHA g / (G - 1)) (0: one epsilon for all)")
+ap.add_argument("--target-tau", type=float, default=0.0, metavar="TAU",
+                help="config key target_tau: Polyak target update after every train step (0: hard syncs every target_update_interval)")
 ap.add_argument("--set", action="append", default=[], help="extra config override key=value (python literal)")
 a = ap.parse_args()
 c = CONFIGS[a.config]
@@ -61,6 +63,8 @@ if a.per_unit == "window":             # (without --prioritized or --train-windo
     over.update(per_unit="window", per_window_stride=a.per_window_stride)
 if a.epsilon_ladder:
     over["epsilon_ladder_alpha"] = a.epsilon_ladder
+if a.target_tau:
+    over["target_tau"] = a.target_tau
 import ast
 for kv in a.set:
     k, v = kv.split("=", 1)
@@ -76,7 +80,8 @@ if a.anomaly:
 ctx = setup(cfg)
 print("config %s, %d envs, %d learner.train per rollout, schedule_unit %s, epsilon %g -> %g over %d clock steps, target sync every %d" % (
     a.config, N, a.train_steps_per_rollout, ctx.args.schedule_unit, ctx.args.epsilon_start, ctx.args.epsilon_finish,
-    ctx.args.epsilon_anneal_time, ctx.args.target_update_interval), flush=True)
+    ctx.args.epsilon_anneal_time, ctx.args.target_update_interval) + (
+        " -- ignored: target_tau %g, a Polyak update after every train step" % ctx.args.target_tau if ctx.args.target_tau else ""), flush=True)
 ep, t0 = 0, time.time()
 acc, cnt = 0.0, 0
 if a.nan_check:      # check after EVERY learner.train: the first step whose gradient is not finite, and where its forward breaks
@@ -183,6 +188,8 @@ for it in range(a.iters):
             pl = ctx.buffer._draws.log.tolist()
             print("   per_priority_mean %.4f  per_priority_max %.4f  per_weight_min %.4f  per_unique_frac %.4f" % (
                 pl[0], pl[1], pl[2], pl[3] / ctx.args.batch_size), flush=True)
+        if a.target_tau:                                               # the Polyak update's own partial sums (learner.target_gap_rel)
+            print("   target_gap_rel %.5f" % ctx.learner.target_gap_rel(), flush=True)
         acc, cnt = 0.0, 0
         assert bool(th.isfinite(p).all())
 assert ctx.runner.env.native.poll_error() == 0
