@@ -30,7 +30,7 @@ from dataclasses import dataclass
 import torch as th
 import torch.nn.functional as F
 
-from . import abi
+from . import abi, ops
 
 
 @dataclass(frozen=True)
@@ -150,7 +150,7 @@ class FastPolicy:
         if self._pack_calls == 3 and self.dev.type == "cuda" and not th.cuda.is_current_stream_capturing():
             th.cuda.synchronize()
             g = th.cuda.CUDAGraph()
-            with th.cuda.graph(g, capture_error_mode="thread_local"):
+            with ops.capture(g, capture_error_mode="thread_local"):
                 self._pack_eager()
             self._pack_graph = g
             g.replay()

@@ -609,10 +609,10 @@ class HomophilyLearner:
         ops.reserve_bmm_scratch(self._capture_stream)
         # thread_local: with an initialised process group the RCCL watchdog thread keeps polling events while we capture
         g1, g2 = th.cuda.CUDAGraph(), th.cuda.CUDAGraph()
-        with th.cuda.graph(g1, stream=self._capture_stream, capture_error_mode="thread_local"):
+        with ops.capture(g1, stream=self._capture_stream, capture_error_mode="thread_local"):
             # data parallel: the denominators are all-reduced OUTSIDE the graph and handed in; else they are part of the graph
             self._static_logs = self.forward_backward(self._static_batch, self._static_dens if self.distributed else None)
-        with th.cuda.graph(g2, pool=g1.pool(), stream=self._capture_stream, capture_error_mode="thread_local"):
+        with ops.capture(g2, pool=g1.pool(), stream=self._capture_stream, capture_error_mode="thread_local"):
             self.clip_and_step()
         self._graph = (g1, g2)
 

@@ -118,6 +118,38 @@ def set_strict(on=True):
     STRICT = bool(on)
 
 
+class capture:
+    """th.cuda.graph(graph, **kw) with Python's cyclic collector kept out of the capture.  torch.cuda.graph no longer collects before
+    it begins to capture (torch >= 2.9: only under torch.compiler.config.force_cudagraph_gc), so a dead reference cycle that owns
+    device resources -- an earlier learner with its captured graphs and their memory pool, an env handle -- could be finalised by a
+    collection that happens to start between two captured launches; what its finalisers call (hipFree, hipGraphExecDestroy, a
+    synchronisation) is illegal on a capturing thread, invalidates the capture and ends the process in abort().  Here the cycles
+    are collected before the capture begins, where their finalisers are legal, and none is collected until it has ended."""
+
+    def __init__(self, graph, **kw):
+        self.ctx = th.cuda.graph(graph, **kw)
+
+    def __enter__(self):
+        import gc
+        gc.collect()
+        self.gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            return self.ctx.__enter__()
+        except BaseException:
+            if self.gc_was_on:
+                gc.enable()
+            raise
+
+    def __exit__(self, *exc):
+        import gc
+        try:
+            return self.ctx.__exit__(*exc)
+        finally:
+            if self.gc_was_on:
+                gc.enable()
+
+
 def _leaving_kernels(op, t, why):
     """called on every branch that evaluates an operator with tensor ops: fine for host tensors, an error for device tensors under
     strict_device_ops."""

@@ -471,7 +471,7 @@ class HipGraphRunner(HipVecRunner):
             # slot); K divides the episode length, so an episode is episode_limit / K replays
             K = self._graph_steps_planned
             self._graph_steps = K
-            with th.no_grad(), th.cuda.graph(g, capture_error_mode="thread_local"):
+            with th.no_grad(), ops.capture(g, capture_error_mode="thread_local"):
                 for k in range(K):
                     self._par = k & 1        # a replay starts at a multiple of K (even when pipelined)
                     self._select(True)
@@ -484,7 +484,7 @@ class HipGraphRunner(HipVecRunner):
             # just run eagerly for THIS episode, the capture itself runs nothing
             th.cuda.synchronize()
             g = th.cuda.CUDAGraph()
-            with th.no_grad(), th.cuda.graph(g, capture_error_mode="thread_local"):
+            with th.no_grad(), ops.capture(g, capture_error_mode="thread_local"):
                 self._begin_launches(in_capture=True)
             b.begin_graph = g
 
@@ -571,7 +571,7 @@ class HipGraphRunner(HipVecRunner):
                 self._stat_acc(False)                                   # the accumulator exists before the capture
             th.cuda.synchronize()
             g = th.cuda.CUDAGraph()
-            with th.cuda.graph(g, capture_error_mode="thread_local"):
+            with ops.capture(g, capture_error_mode="thread_local"):
                 self._select(False)
                 if stats_on:
                     self._stats_device(self._out, self._ep_return, False)
