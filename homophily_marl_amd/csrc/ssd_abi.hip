@@ -654,14 +654,18 @@ int ssd_td_sim_loss(const ssd_td_loss_args* a, int32_t mode, void* stream) {
     return launched();
 }
 
+// the edges the two refusal messages below name
+static_assert(encoder_lds_bytes(36) <= kDefaultLdsLimit && encoder_lds_bytes(37) > kDefaultLdsLimit, "ssd_encoder's message names 3 .. 36");
+static_assert(conv_leaky_lds_bytes(73) <= kDefaultLdsLimit && conv_leaky_lds_bytes(74) > kDefaultLdsLimit, "ssd_conv_leaky's message names 3 .. 73");
 int ssd_encoder(const float* obs, int32_t rows, int32_t view_edge, int32_t conv_out, int32_t feat_out, const float* conv_w,
                 const float* conv_b, const float* lin_w, const float* lin_b, float* out, int32_t out_stride, int32_t n_agents,
                 int32_t agent_major, float* store_obs, int64_t store_env_stride, const int64_t* store_t, void* stream) {
     if (!obs || !conv_w || !conv_b || !lin_w || !lin_b || !out || rows < 1 || view_edge < 3) return fail(SSD_ERR_INVALID, "bad argument");
     if (conv_out != 6 || feat_out != 32) return fail(SSD_ERR_UNSUPPORTED, "ssd_encoder is instantiated for conv_out 6, obs_dim_net 32 (config/default.yaml:59-63)");
+    if (encoder_lds_bytes(view_edge) > kDefaultLdsLimit)       // (before the storage checks: an accepted edge with a storage fault names the storage)
+        return fail(SSD_ERR_INVALID, "ssd_encoder: the LDS staging of four windows of this view_edge exceeds the 64 KiB a launch may ask for (view_edge 3 .. 36)");
     if ((agent_major || store_obs) && (n_agents < 1 || rows % n_agents)) return fail(SSD_ERR_INVALID, "rows must be a multiple of n_agents");
     if (store_obs && !store_t) return fail(SSD_ERR_INVALID, "store_obs needs store_t");
-    if (4 * 4 * (3 * view_edge * view_edge + 4) * 4 > 160 * 1024) return fail(SSD_ERR_INVALID, "view too large for the encoder's LDS staging");
     launch_encoder(obs, rows, view_edge, conv_w, conv_b, lin_w, lin_b, out, out_stride, n_agents, agent_major, store_obs,
                    (long)store_env_stride, store_t, (hipStream_t)stream);
     return launched();
@@ -672,6 +676,8 @@ int ssd_conv_leaky(const float* obs, int32_t rows, int32_t view_edge, int32_t co
                    const int64_t* store_t, void* stream) {
     if (!obs || !conv_w || !conv_b || !out || rows < 1 || view_edge < 3 || n_agents < 1 || rows % n_agents) return fail(SSD_ERR_INVALID, "bad argument");
     if (conv_out != 6) return fail(SSD_ERR_UNSUPPORTED, "ssd_conv_leaky is instantiated for conv_out 6 (config/default.yaml:59)");
+    if (conv_leaky_lds_bytes(view_edge) > kDefaultLdsLimit)
+        return fail(SSD_ERR_INVALID, "ssd_conv_leaky: the LDS staging of a window of this view_edge exceeds the 64 KiB a launch may ask for (view_edge 3 .. 73)");
     if (store_obs && !store_t) return fail(SSD_ERR_INVALID, "store_obs needs store_t");
     launch_conv_leaky(obs, rows, view_edge, conv_w, conv_b, out, n_agents, agent_major, store_obs, (long)store_env_stride, store_t,
                       (hipStream_t)stream);

@@ -163,6 +163,14 @@ void launch_dueling_q(const float* a, const float* v, float* q, const float* dq,
                       int ld = 0, int merged = 0, float* gs = nullptr);
 void launch_gather_rows(const ssd_row_gather* fields, int count, const int64_t* ids, int n_ids, hipStream_t stream);
 void launch_td_sim_loss(const ssd_td_loss_args* a, int mode, hipStream_t stream);
+// Dynamic LDS of the two per-layer encoder launches (csrc/ssd_policy.hip), in bytes: the launch asks for it and the entry point's
+// refusal (csrc/ssd_abi.hip) tests the same expression.  Neither kernel raises its LDS attribute, so a launch may ask for at most
+// kDefaultLdsLimit.  k_encoder: kEncoderRowsPerBlock windows of 3 V^2 floats + 4 of padding; k_conv_leaky: one window, 6 x 27 weights
+// and 6 biases.
+constexpr long long kDefaultLdsLimit = 64 * 1024;
+constexpr int kEncoderRowsPerWave = 1, kEncoderRowsPerBlock = 4 * kEncoderRowsPerWave;
+constexpr long long encoder_lds_bytes(long long V) { return kEncoderRowsPerBlock * (3 * V * V + 4) * (long long)sizeof(float); }
+constexpr long long conv_leaky_lds_bytes(long long V) { return (3 * V * V + 6 * 27 + 6) * (long long)sizeof(float); }
 void launch_encoder(const float* obs, int rows, int V, const float* cw, const float* cb, const float* lw, const float* lb, float* out,
                     int out_stride, int n_agents, int agent_major, float* store, long store_env_stride, const int64_t* store_t,
                     hipStream_t s);

@@ -290,15 +290,15 @@ __global__ void k_dueling_pick(const float* __restrict__ av, int R, int A, const
 void launch_encoder(const float* obs, int rows, int V, const float* cw, const float* cb, const float* lw, const float* lb, float* out,
                     int out_stride, int n_agents, int agent_major, float* store, long store_env_stride, const int64_t* store_t,
                     hipStream_t s) {
-    constexpr int RPW = 1;
-    const size_t lds = 4 * RPW * (size_t)(3 * V * V + 4) * sizeof(float);
-    const int rows_per_block = 4 * RPW;
+    constexpr int RPW = kEncoderRowsPerWave;
+    const size_t lds = (size_t)encoder_lds_bytes(V);
+    const int rows_per_block = kEncoderRowsPerBlock;
     hipLaunchKernelGGL((k_encoder<6, 32, RPW>), dim3((rows + rows_per_block - 1) / rows_per_block), dim3(256), lds, s, obs, rows, V, cw, cb,
                        lw, lb, out, out_stride, n_agents, agent_major, store, store_env_stride, store_t);
 }
 void launch_conv_leaky(const float* obs, int rows, int V, const float* cw, const float* cb, float* out, int n_agents, int agent_major,
                        float* store, long store_env_stride, const int64_t* store_t, hipStream_t s) {
-    const size_t lds = (size_t)(3 * V * V + 6 * 27 + 6) * sizeof(float);
+    const size_t lds = (size_t)conv_leaky_lds_bytes(V);
     if (V == 15) hipLaunchKernelGGL((k_conv_leaky<6, 15>), dim3(rows), dim3(256), lds, s, obs, rows, V, cw, cb, out, n_agents, agent_major, store, store_env_stride, store_t);
     else if (V == 31) hipLaunchKernelGGL((k_conv_leaky<6, 31>), dim3(rows), dim3(256), lds, s, obs, rows, V, cw, cb, out, n_agents, agent_major, store, store_env_stride, store_t);
     else hipLaunchKernelGGL((k_conv_leaky<6, 0>), dim3(rows), dim3(256), lds, s, obs, rows, V, cw, cb, out, n_agents, agent_major, store, store_env_stride, store_t);

@@ -678,6 +678,8 @@ int ssd_td_sim_loss(const ssd_td_loss_args* args, int32_t mode, void* stream);
  * ssd_encoder: HomophilyAgent.rgb_preprocess (homophily_agent.py:20-27,213-214) = Conv2d(3, conv_out, 3, 1) + LeakyReLU +
  *   Flatten + Linear(conv_out * (V-2)^2, feat_out) + LeakyReLU on obs f32 [rows, 3, V, V] -> out[row * out_stride + 0..feat_out).
  *   agent_major: rows are (env b, agent i); write row (i * (rows / n_agents) + b) instead (per-agent batched GEMM layout).
+ *   view_edge 3 .. 36: a workgroup stages four windows (4 * (3 V^2 + 4) floats) in the 64 KiB of LDS a launch gets without raising
+ *   its attribute; a larger edge is SSD_ERR_INVALID (ssd_conv_leaky, one window + 168 floats of weights: 3 .. 73).
  * ssd_gru_gates: the gate arithmetic of the hand-written GRU cell (homophily_agent.py:162-165,188-191) on gi = x W_i + b_i,
  *   gh = h W_h + b_h, both [rows, 3 * hidden] in (r, z, n) order; h [rows, hidden] is updated in place.
  * ssd_dueling_pick: q = v + a - mean(a) (homophily_agent.py:168-170,204-206) on av [rows, n_actions + 1] (advantages, then the

@@ -84,6 +84,55 @@ def replay(make_env, make_tape, path, n_env=1):
     return len(z["kind"])
 
 
+# the recordings replayed with every step issued as one step_observe request: the TAPE instantiations of that request, without
+# (tests/test_hip_parity.py) and with the beam record of render mode (tests/test_render_gpu.py)
+FUSED_TAPE_TRAJ = ("traj_cleanup5_cluster.npz", "traj_harvest5_allact.npz")
+FUSED_TAPE_RENDER = ("render_cleanup5_simplified.npz", "render_harvest5_fire.npz")
+
+
+def replay_fused(make_env, make_tape, make_ref, make_ref_tape, path, formats, n_env=5, render=False):
+    """The recording `path` with every step as ONE step_observe request (HipEnv), the observation format rotating over `formats`.
+    After every call: the step outputs and the state against the recording (the reference's numbers) and against the backend `make_ref`
+    (the CPU oracle) replaying the same tapes in lockstep; the observation the request wrote against the oracle's get_obs of the same
+    state; with `render`, render mode is on and every env's frame equals the recording's.  Returns the number of steps."""
+    z, meta = load(path)
+    n = meta["num_agents"]
+    env, ref = make_env(meta["env"], **env_kwargs(meta, n_env)), make_ref(meta["env"], **env_kwargs(meta, n_env))
+    if render:
+        env.e.set_render(True)
+    U, Wn = z["uniforms"].shape[1], z["waste_order"].shape[1]
+    rep = lambda a: np.repeat(np.asarray(a)[None], n_env, 0)
+    name, steps = os.path.basename(path), 0
+    for c in range(len(z["kind"])):
+        arrs = [rep(z[k][c]) for k in ("move_order", "uniforms", "waste_order", "spawn_rot")] + ([rep(z["spawn_order"][c])] if "spawn_order" in z else [])
+        tape, ref_tape = make_tape(n_env, n, U, Wn, *arrs), make_ref_tape(n_env, n, U, Wn, *arrs)
+        if z["kind"][c] == 0:
+            env.reset(tape); ref.reset(ref_tape)
+        else:
+            pre = dict(pos=rep(z["pre_pos"][c]), orient=rep(z["pre_orient"][c]), **(dict(grid=rep(z["pre_grid"][c].reshape(-1))) if "pre_grid" in z else {}))
+            env.import_state(**pre); ref.import_state(**pre)
+            fmt = formats[steps % len(formats)]
+            steps += 1
+            o, r = env.step_observe(rep(z["actions"][c]), tape, fmt), ref.step(rep(z["actions"][c]), ref_tape)
+            ob = ref.observe(fmt)
+            for k in ("reward", "clean_num", "apple_den", "terminated", "n_draws"):
+                assert (o[k] == r[k]).all(), (name, c, k)
+            for k in ("obs", "pos", "orient"):
+                assert o[k].shape == ob[k].shape and (o[k] == ob[k]).all(), (name, c, fmt, k, np.argwhere(o[k] != ob[k])[:4].tolist())
+            assert (o["reward"] == z["reward"][c].astype(np.float32)[None]).all(), (name, c, "reward")
+            assert (o["clean_num"] == z["clean_num"][c].astype(np.float32)[None]).all(), (name, c, "clean_num")
+            assert (o["n_draws"] == z["n_uniforms"][c]).all(), (name, c, "n_draws")
+        st, rs = env.export_state(), ref.export_state()
+        for k in ("grid", "pos", "orient", "ep_reward", "ep_step"):
+            assert (st[k] == rs[k]).all(), (name, c, k)
+        assert (st["grid"] == z["grid"][c].reshape(1, -1)).all() and (st["pos"] == z["pos"][c][None]).all() and (st["orient"] == z["orient"][c][None]).all(), (name, c)
+        if render:
+            fr = env.e.get_frames().cpu().numpy()
+            assert (fr == z["frames"][c][None]).all(), (name, c, "frames", int((fr != z["frames"][c][None]).any(-1).sum()))
+    env.close(); ref.close()
+    return steps
+
+
 def replay_kats(make_env, make_tape, chunk=512):
     """kat_moves.npz: every shuffle result of every scenario, batched `chunk` envs at a time."""
     z = np.load(os.path.join(GOLDEN, "kat_moves.npz"))

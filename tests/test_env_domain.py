@@ -206,7 +206,10 @@ def test_layouts_past_the_limits_are_refused():
 
 
 # ---- render mode at a large window -------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n,view", [(1, 20), (2, 16)])
+RENDER_VIEWS = [(1, 20), (2, 16)]
+
+
+@pytest.mark.parametrize("n,view", RENDER_VIEWS)
 def test_render_mode_at_large_views(n, view):
     """Render mode runs the run-time team size for every team but 5, and every observation format: its observations still match
     the oracle above 32 x 32 windows."""

@@ -35,6 +35,18 @@ def test_golden_trajectory_batched():
         GU.replay(HipEnv, hip_tape, path, n_env=7)      # 7: a partially filled workgroup (4 envs per workgroup)
 
 
+@pytest.mark.parametrize("name", GU.FUSED_TAPE_TRAJ)
+def test_golden_trajectory_through_step_observe(name):
+    """The TAPE instantiation of the step-and-observe request (k_env<2, 0, true, 0, false>), which the replays above never launch (they
+    step, then observe): the reference's recording with every step as one step_observe, 5 envs (a second, partly filled workgroup),
+    the four formats in turn; outputs and state against the recording and the oracle, the observation against the oracle's."""
+    from oracle.oracle_py import OracleEnv, make_tape
+    HipEnv, hip_tape = _hip()
+    path = [p for p in GU.traj_files() if p.endswith(name)][0]
+    fmts = (abi.OBS_CODE, abi.OBS_F32, abi.OBS_U8, abi.OBS_BF16)
+    assert GU.replay_fused(HipEnv, hip_tape, OracleEnv, lambda *a: make_tape(*a)[0], path, fmts) >= 40
+
+
 def test_move_kats():
     HipEnv, hip_tape = _hip()
     assert GU.replay_kats(HipEnv, hip_tape) > 2000
@@ -65,8 +77,11 @@ def _compare_state(tag, dev, orc):
         assert (sa[k] == sb[k]).all(), (tag, k, np.argwhere(sa[k] != sb[k])[:4].tolist())
 
 
-@pytest.mark.parametrize("env_name,n,mapname,view", [("cleanup", 4, "default5", 7), ("cleanup", 7, "default10", 7), ("cleanup", 5, "default5", 7),
-                                                     ("cleanup", 10, "default10", 7), ("harvest", 6, "default10", 7)])
+OTHER_TEAMS = [("cleanup", 4, "default5", 7), ("cleanup", 7, "default10", 7), ("cleanup", 5, "default5", 7), ("cleanup", 10, "default10", 7),
+               ("harvest", 6, "default10", 7)]
+
+
+@pytest.mark.parametrize("env_name,n,mapname,view", OTHER_TEAMS)
 def test_counter_mode_other_team_sizes_and_the_class_code_request(env_name, n, mapname, view):
     """The step kernel has instantiations per team size (3 / 5 / 10 at compile time, anything else at run time) and per observation
     request (class-code windows and f32 planes have their own, everything else takes the all-formats kernel): team sizes that take

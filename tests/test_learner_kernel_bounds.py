@@ -438,8 +438,11 @@ def test_gather_rows_in_the_arena(count, n_ids):
 
 # ---- ssd_sample_ids / ssd_runner_stats -----------------------------------------------------------------------------------------------
 # (with the register-slot edges of the wave kernel: 64 / 128 / 256 picks and one past each)
-@pytest.mark.parametrize("count,population", [(1, 1), (1, 7), (2, 2), (2, 4096), (16, 8192), (64, 64), (65, 70), (128, 128), (129, 4096), (256, 256), (257, 300),
-                                              (abi.SAMPLE_IDS_MAX, abi.SAMPLE_IDS_MAX), (abi.SAMPLE_IDS_MAX, 5000)])
+SAMPLE_IDS_CASES = [(1, 1), (1, 7), (2, 2), (2, 4096), (16, 8192), (64, 64), (65, 70), (128, 128), (129, 4096), (256, 256), (257, 300),
+                    (abi.SAMPLE_IDS_MAX, abi.SAMPLE_IDS_MAX), (abi.SAMPLE_IDS_MAX, 5000)]      # (count, population)
+
+
+@pytest.mark.parametrize("count,population", SAMPLE_IDS_CASES)
 def test_sample_ids_in_the_arena(count, population):
     """the expected ids come from ops.sample_ids on a HOST tensor: that branch is a pure-Python restatement of the generator and of
     Floyd's sampling (no library call), i.e. a second implementation, not the kernel; distinctness and range are asserted on their own."""
@@ -517,7 +520,10 @@ def test_incentive_transfer_in_the_arena(B, T, n):
 
 
 # ---- ssd_conv_wgrad_codes (+ ssd_conv_wgrad_partial_rows) -----------------------------------------------------------------------------
-@pytest.mark.parametrize("R,V", [(1, 3), (3, 5), (4, 15), (5, 17), (203, 31), (5, 63), (203, 3), (1, 63), (3, 31), (4, 5), (5, 15), (203, 17)])
+CONV_WGRAD_CASES = [(1, 3), (3, 5), (4, 15), (5, 17), (203, 31), (5, 63), (203, 3), (1, 63), (3, 31), (4, 5), (5, 15), (203, 17)]      # (R, V)
+
+
+@pytest.mark.parametrize("R,V", CONV_WGRAD_CASES)
 def test_conv_wgrad_codes_in_the_arena(R, V):
     """rows around CW_ROWS = 4 windows per wave and 203; V = 3 .. 63; `partial` has exactly ssd_conv_wgrad_partial_rows(R) rows -- the
     row behind it is a band; the class codes' bands hold 0xFF (no class)."""
@@ -643,8 +649,11 @@ def _status_clear():
     assert ops.numeric_status() == 0
 
 
+GRU_SEQ_CASES = [(1, 1, 16, 1), (2, 3, 48, 1), (101, 3, 16, 1), (2, 10, 16, 0), (1, 20, 48, 1), (101, 1, 48, 0), (2, 20, 16, 1)]      # (T, G, B, train)
+
+
 @pytest.mark.parametrize("bf", [False, True], ids=["f32", "bf16"])
-@pytest.mark.parametrize("T,G,B,train", [(1, 1, 16, 1), (2, 3, 48, 1), (101, 3, 16, 1), (2, 10, 16, 0), (1, 20, 48, 1), (101, 1, 48, 0), (2, 20, 16, 1)])
+@pytest.mark.parametrize("T,G,B,train", GRU_SEQ_CASES)
 def test_gru_sequence_in_the_arena(T, G, B, train, bf):
     """ssd_gru_seq_fwd (with and without rzn / ghn) and ssd_gru_seq_bwd, every tensor 16-byte aligned as the header requires (the
     refusal of anything else: tests/test_learner_abi_refusals.py).  f32: states < 1e-5, gradients < 2e-5 of their scale

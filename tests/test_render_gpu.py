@@ -9,6 +9,7 @@ import pytest
 import torch as th
 
 from homophily_marl_amd import abi
+from tests import golden_util as GU
 
 pytestmark = pytest.mark.gpu
 
@@ -66,6 +67,19 @@ def test_frames_match_the_reference(path, n_env):
     st = env.export_state()
     assert (st["grid"][0] == z["grid"][-1].reshape(-1)).all()
     env.close()
+
+
+@pytest.mark.parametrize("name", GU.FUSED_TAPE_RENDER)
+def test_frames_match_the_reference_through_step_observe(name):
+    """The beam-recording TAPE instantiation of the step-and-observe request (k_env<2, 0, true, 0, true>; the replay above steps
+    without observing): every step of the recording as one step_observe in render mode, 5 envs -- frames, rewards and state against the
+    reference's recording, the observation of every call (the four formats in turn) against the CPU oracle replaying the same tapes."""
+    from oracle.oracle_py import OracleEnv, make_tape
+    from tests.hip_adapter import HipEnv, hip_tape
+    assert set(GU.FUSED_TAPE_RENDER) <= {os.path.basename(p) for p in render_files()}
+    fmts = (abi.OBS_CODE, abi.OBS_F32, abi.OBS_U8, abi.OBS_BF16)
+    steps = GU.replay_fused(HipEnv, hip_tape, OracleEnv, lambda *a: make_tape(*a)[0], os.path.join(GOLDEN, name), fmts, render=True)
+    assert steps >= 40
 
 
 @pytest.mark.parametrize("n", [1, 2, 5, 10])

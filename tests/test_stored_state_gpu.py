@@ -88,8 +88,13 @@ def test_bf16_instantiations_at_the_bf16_bar():
     try:
         hs = ops.gru_sequence(d[0], d[1], d[2], h0=h0.cuda())
         (hs * wout.cuda()).sum().backward()
+        with th.no_grad():                                                    # the bf16 form without saved gates (the target net's unroll)
+            hs2 = ops.gru_sequence(d[0], d[1], d[2], h0=h0.cuda())
     finally:
         ops.set_learner_precision(2)
+    err2 = float((hs2.double().cpu() - ref).abs().max())
+    print("bf16 states without saved gates: max error %.3e" % err2)
+    assert err2 < BF16_Q_TOL and th.equal(hs2[:, 0].cpu(), h0) and not th.equal(hs2, f32)
     err = float((hs.detach().double().cpu() - ref).abs().max())
     print("bf16 states: max error %.3e" % err)
     assert err < BF16_Q_TOL and th.equal(hs[:, 0].cpu(), h0)
