@@ -359,6 +359,14 @@ HIP_SIGNATURES = {name: (C.c_int, args) for name, args in {
 }.items()}
 # library, lifecycle, step / observe, state, inputs and incentives: shared with the CPU checker
 HIP_SIGNATURES.update(_sigs("ssd_", True))
+# the exports of include/ssd_hip_train.h (the train step's shared launches of the live and the target net, fc1's row assembly); every
+# one returns int.  tests/test_train_pairs_host.py holds this table to that header and every entry to a refusal table.
+TRAIN_SIGNATURES = {name: (C.c_int, args) for name, args in {
+    "ssd_bias_bmm_pair_fwd": [vp] * 5 + [i32] + [vp] * 5 + [i32] * 8 + [vp],
+    "ssd_dueling_head_pair_fwd": [vp, vp, i32, vp, vp, i32] + [i32] * 4 + [vp],
+    "ssd_fc1_rows_fwd": [vp] * 8 + [i32] * 6 + [vp],
+    "ssd_fc1_rows_bwd": [vp] * 3 + [i32] * 7 + [vp],
+}.items()}
 
 
 # ---- size / layout helpers ---------------------------------------------------------------------------------------------------
@@ -526,6 +534,7 @@ def load_library():
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback." % HIP_LIB_PATH)
         lib = C.CDLL(HIP_LIB_PATH)
         bind(lib, HIP_SIGNATURES)
+        bind(lib, TRAIN_SIGNATURES)
         ver = lib.ssd_abi_version()
         if ver != ABI_VERSION:
             raise ImportError("libssd_hip.so ABI version %d != %d" % (ver, ABI_VERSION))

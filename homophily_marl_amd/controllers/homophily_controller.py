@@ -238,20 +238,45 @@ class HomophilyMAC(nn.Module):
 
     def unroll_pre(self, batch, shared):
         """Encoder, input assembly, fc1 and the input-side GRU projections of this net: [gi_env, gi_inc] (each [n, T * B, 3H]), wh, bh."""
+        return self.agent.unroll_pre(self.unroll_inputs(batch, shared), shared["onehot"], act_tm=shared.get("act_tm"))
+
+    def unroll_feat(self, batch, shared):
+        """The encoder of this net on the whole batch: features [B * T * n, F0] (the observation itself without rgb_input)."""
         a = self.args
         B, T, n = batch.batch_size, batch.max_seq_length, self.n_agents
         obs = shared["obs"]
         if shared.get("codes") is not None:
-            feat = self.agent.rgb_preprocess_codes(shared["codes"].reshape(B * T * n, a.obs_dims[0], a.obs_dims[1]))
-        elif a.rgb_input:
-            feat = self.agent.rgb_preprocess(obs.reshape(B * T * n, 3, a.obs_dims[0], a.obs_dims[1]))
-        else:
-            feat = obs.reshape(B * T * n, -1)
+            return self.agent.rgb_preprocess_codes(shared["codes"].reshape(B * T * n, a.obs_dims[0], a.obs_dims[1]))
+        if a.rgb_input:
+            return self.agent.rgb_preprocess(obs.reshape(B * T * n, 3, a.obs_dims[0], a.obs_dims[1]))
+        return obs.reshape(B * T * n, -1)
+
+    def unroll_inputs(self, batch, shared):
+        """Encoder and input assembly of this net: the agent's inputs [B, T, n, input_shape]."""
+        B, T, n = batch.batch_size, batch.max_seq_length, self.n_agents
+        feat = self.unroll_feat(batch, shared)
         if shared["tail"] is not None:
-            inputs = th.cat([feat, shared["tail"]], dim=1).reshape(B, T, n, -1)
-        else:
-            inputs = self.assemble_inputs(feat, *shared["hist"], False).reshape(B, T, n, -1)
-        return self.agent.unroll_pre(inputs, shared["onehot"], act_tm=shared.get("act_tm"))
+            return th.cat([feat, shared["tail"]], dim=1).reshape(B, T, n, -1)
+        return self.assemble_inputs(feat, *shared["hist"], False).reshape(B, T, n, -1)
+
+    def unroll_rows_pair(self, tgt, batch, shared):
+        """The input rows of the two fc1 layers, set-major and time-major, of this (live) net and of `tgt`, a frozen copy (the learner's
+        target network): (x_env, x_inc, x_env_t, x_inc_t), x_env [n, T * B, input_shape], x_inc [n, T * B, input_shape + n_actions].
+        With the input tail and the one-hot actions from the device kernels (unroll_shared) ONE launch assembles all four where fc1
+        reads them (ops.fc1_rows); else the tensor operations of unroll_inputs / HomophilyAgent.unroll_pre per net."""
+        B, T, n = batch.batch_size, batch.max_seq_length, self.n_agents
+        if shared["tail"] is not None and shared.get("act_tm") is not None:
+            feat = self.unroll_feat(batch, shared)
+            with th.no_grad():
+                feat_t = tgt.unroll_feat(batch, shared)
+            return ops.fc1_rows(feat, shared["tail"], shared["act_tm"], B, T, n, feat_t)
+        tm = lambda x: x.permute(2, 1, 0, 3).reshape(n, T * B, x.shape[-1])          # time-major rows [n, T*B, f]
+        x = tm(self.unroll_inputs(batch, shared))
+        act = shared["act_tm"] if shared.get("act_tm") is not None else tm(shared["onehot"].to(x.dtype))
+        with th.no_grad():
+            x_t = tm(tgt.unroll_inputs(batch, shared))
+            xa_t = th.cat([x_t, act], dim=-1)
+        return x, th.cat([x, act], dim=-1), x_t, xa_t
 
     def _build_inputs(self, batch, t):
         if self.args.rgb_input:

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "ssd_device.h"
+#include "../../include/ssd_hip_train.h"
 
 using namespace ssd;
 
@@ -878,6 +879,50 @@ int ssd_bias_bmm_bwd_x(const float* g, const float* w, float* dx, int32_t n, int
     if (!g || !w || !dx || n < 1 || rows < 1 || in < 1 || out < 1 || w_set < (int64_t)in * out) return fail(SSD_ERR_INVALID, "bad argument");
     if (launch_bias_bmm_bwd(g, nullptr, w, dx, nullptr, nullptr, nullptr, n, rows, in, out, (hipStream_t)stream, 0, 0, nullptr, nullptr, 0, 1, 0, (long)w_set))
         return fail(SSD_ERR_UNSUPPORTED, "ssd_bias_bmm_bwd_x: an operand set of 2^30 elements or more");
+    return launched();
+}
+int ssd_bias_bmm_pair_fwd(const float* x_a, const float* x2_a, const float* w_a, const float* b_a, float* y_a, int32_t n_a, const float* x_b,
+                          const float* x2_b, const float* w_b, const float* b_b, float* y_b, int32_t n_b, int32_t rows, int32_t in1, int32_t in2,
+                          int32_t out, int32_t x1_div, int32_t x2_shared, int32_t leaky, void* stream) {
+    if (!x_a || !w_a || !b_a || !y_a || !x_b || !w_b || !b_b || !y_b) return fail(SSD_ERR_INVALID, "ssd_bias_bmm_pair_fwd: a null operand of either group");
+    if (n_a < 1 || n_b < 1) return fail(SSD_ERR_INVALID, "ssd_bias_bmm_pair_fwd: both groups need a set count >= 1");
+    if (rows < 1 || in1 < 1 || in2 < 0 || out < 1) return fail(SSD_ERR_INVALID, "ssd_bias_bmm_pair_fwd: bad argument");
+    if ((in2 > 0) != (x2_a != nullptr) || (in2 > 0) != (x2_b != nullptr))
+        return fail(SSD_ERR_INVALID, "ssd_bias_bmm_pair_fwd: in2 > 0 needs the second source of both groups, in2 == 0 neither");
+    if ((long)n_a + n_b > 65535) return fail(SSD_ERR_UNSUPPORTED, "ssd_bias_bmm_pair_fwd: more than 65535 weight sets in one grid");
+    const int rc = launch_bias_bmm_pair_fwd(x_a, x2_a, w_a, b_a, y_a, n_a, x_b, x2_b, w_b, b_b, y_b, n_b, rows, in1, in2, out, x1_div, x2_shared, leaky != 0,
+                                            (hipStream_t)stream);
+    if (rc == -3)
+        return fail(SSD_ERR_INVALID, "ssd_bias_bmm_pair_fwd: rows a multiple of x1_div >= 1; in1 a multiple of 16 unless in2 is no multiple of 4");
+    if (rc) return fail(SSD_ERR_UNSUPPORTED, "ssd_bias_bmm_pair_fwd: a weight / operand set of 2^30 elements or more");
+    return launched();
+}
+int ssd_dueling_head_pair_fwd(const float* y_a, float* q_a, int32_t n_a, const float* y_b, float* q_b, int32_t n_b, int32_t T, int32_t B, int32_t inner,
+                              int32_t K, void* stream) {
+    if (!y_a || !q_a || !y_b || !q_b) return fail(SSD_ERR_INVALID, "ssd_dueling_head_pair_fwd: a null operand of either group");
+    if (n_a < 1 || n_b < 1) return fail(SSD_ERR_INVALID, "ssd_dueling_head_pair_fwd: both groups need a set count >= 1");
+    if (T < 1 || B < 1 || inner < 1 || K < 1 || K > 15) return fail(SSD_ERR_INVALID, "ssd_dueling_head_pair_fwd: bad argument");
+    launch_dueling_q(y_a, y_a + K, q_a, nullptr, nullptr, nullptr, n_a, T, B, inner, K, (hipStream_t)stream, K + 1, 1, nullptr, y_b, y_b + K, q_b, n_b);
+    return launched();
+}
+int ssd_fc1_rows_fwd(const float* feat_a, const float* feat_b, const float* tail, const float* act, float* x_env_a, float* x_inc_a, float* x_env_b,
+                     float* x_inc_b, int32_t B, int32_t T, int32_t n, int32_t feat_w, int32_t tail_w, int32_t act_w, void* stream) {
+    if (!feat_a || !act || !x_env_a || !x_inc_a) return fail(SSD_ERR_INVALID, "ssd_fc1_rows_fwd: a null operand of the first net");
+    if ((feat_b != nullptr) != (x_env_b != nullptr) || (feat_b != nullptr) != (x_inc_b != nullptr))
+        return fail(SSD_ERR_INVALID, "ssd_fc1_rows_fwd: the second net's features and both its outputs come together or not at all");
+    if (B < 1 || T < 1 || n < 1 || feat_w < 1 || tail_w < 0 || act_w < 1) return fail(SSD_ERR_INVALID, "ssd_fc1_rows_fwd: bad argument");
+    if ((tail_w > 0) != (tail != nullptr)) return fail(SSD_ERR_INVALID, "ssd_fc1_rows_fwd: tail_w > 0 needs tail, tail_w == 0 none");
+    if ((int64_t)B * T * n * ((int64_t)feat_w + tail_w + act_w) >= ((int64_t)1 << 40)) return fail(SSD_ERR_UNSUPPORTED, "ssd_fc1_rows_fwd: 2^40 elements or more");
+    launch_fc1_rows(feat_a, feat_b, tail, act, x_env_a, x_inc_a, x_env_b, x_inc_b, B, T, n, feat_w, tail_w, act_w, (hipStream_t)stream);
+    return launched();
+}
+int ssd_fc1_rows_bwd(const float* d_x_env, const float* d_x_inc, float* d_feat, int32_t B, int32_t T, int32_t n, int32_t feat_w, int32_t tail_w, int32_t act_w,
+                     int32_t d_feat_stride, void* stream) {
+    if (!d_x_env || !d_x_inc || !d_feat) return fail(SSD_ERR_INVALID, "ssd_fc1_rows_bwd: a null operand");
+    if (B < 1 || T < 1 || n < 1 || feat_w < 1 || tail_w < 0 || act_w < 1) return fail(SSD_ERR_INVALID, "ssd_fc1_rows_bwd: bad argument");
+    if (d_feat_stride < feat_w) return fail(SSD_ERR_INVALID, "ssd_fc1_rows_bwd: d_feat_stride below feat_w");
+    if ((int64_t)B * T * n * ((int64_t)feat_w + tail_w + act_w) >= ((int64_t)1 << 40)) return fail(SSD_ERR_UNSUPPORTED, "ssd_fc1_rows_bwd: 2^40 elements or more");
+    launch_fc1_rows_bwd(d_x_env, d_x_inc, d_feat, B, T, n, feat_w, tail_w, act_w, d_feat_stride, (hipStream_t)stream);
     return launched();
 }
 int ssd_bmm_reserve_scratch(void* stream) {

@@ -37,6 +37,9 @@ struct BmmK {
     long w_set;                // elements between two weight sets of w (default I * O; larger when w is the leading rows of a wider layer)
     float* part;               // backward with row_chunks > 1: per (set, tile, chunk) partial dw tile [64 lanes x 4] + db [16] (BMM_PART floats)
     int row_chunks;            // the rows (K of dw) are cut into this many chunks, one workgroup each; k_bmm_dw_reduce adds them in order
+    // forward, second operand group (the learner's live and target net in ONE grid): weight sets blockIdx.y >= n_a are the sets
+    // 0 .. n - n_a - 1 of x_b / x2_b / w_b / b_b / y_b, same shapes and flags as the first group; n_a == 0: one group
+    const float *x_b, *x2_b, *w_b, *b_b; float* y_b; int n_a;
 };
 constexpr int BMM_PART = 272;                    // floats per partial record: 256 (dw tile) + 16 (db)
 
@@ -84,20 +87,24 @@ __global__ __launch_bounds__(256) void k_bias_bmm_fwd(BmmK a) {
     const int otiles = (O + 15) >> 4, groups = (otiles + BMM_TPW - 1) / BMM_TPW, rtiles = (R + 15) >> 4;
     const int unit = blockIdx.x * 4 + wave;
     if (unit >= rtiles * groups) return;
-    const int g = blockIdx.y, row0 = (unit / groups) * 16, t0 = (unit % groups) * BMM_TPW;
+    const int row0 = (unit / groups) * 16, t0 = (unit % groups) * BMM_TPW;
     const int rowc = row0 + m < R ? row0 + m : R - 1;
+    const bool grp_b = a.n_a && (int)blockIdx.y >= a.n_a;              // (uniform) a weight set of the second operand group, see BmmK
+    const int g = grp_b ? blockIdx.y - a.n_a : blockIdx.y;
+    const float *ax = grp_b ? a.x_b : a.x, *ax2 = grp_b ? a.x2_b : a.x2, *aw = grp_b ? a.w_b : a.w, *ab = grp_b ? a.b_b : a.b;
+    float* ay = grp_b ? a.y_b : a.y;
     const bool two = a.x2 != nullptr;                                  // (uniform) two-source rows, see BmmK
     const int I1 = two ? a.I1 : I;
-    const float* xs = a.x + (two ? (size_t)g * (size_t)(R / a.x1_div) * I1 : (size_t)g * R * I);      // the weight set's rows (uniform)
+    const float* xs = ax + (two ? (size_t)g * (size_t)(R / a.x1_div) * I1 : (size_t)g * R * I);      // the weight set's rows (uniform)
     const uint32_t xrow = two ? (uint32_t)(rowc / a.x1_div) * (uint32_t)I1 : (uint32_t)rowc * (uint32_t)I;   // this lane's row starts at xrow
-    const float* x2s = two ? a.x2 + (size_t)g * a.x2_set : a.x;
+    const float* x2s = two ? ax2 + (size_t)g * a.x2_set : ax;
     const uint32_t x2row = (uint32_t)rowc * (uint32_t)(I - I1);
-    const float* wg = a.w + (size_t)g * (a.w_set ? a.w_set : (long)I * O);
+    const float* wg = aw + (size_t)g * (a.w_set ? a.w_set : (long)I * O);
     f32x4 acc[BMM_TPW];
 #pragma unroll
     for (int t = 0; t < BMM_TPW; ++t) {
         const int o = 16 * (t0 + t) + m;
-        const float bv = (t0 + t < otiles && o < O) ? a.b[(size_t)g * O + o] : 0.f;
+        const float bv = (t0 + t < otiles && o < O) ? ab[(size_t)g * O + o] : 0.f;
         acc[t] = f32x4{bv, bv, bv, bv};
     }
     // Loads never branch (a predicated load makes hipcc wait for everything in flight where the branch joins): addresses are clamped
@@ -182,7 +189,7 @@ __global__ __launch_bounds__(256) void k_bias_bmm_fwd(BmmK a) {
         for (int r = 0; r < 4; ++r) {
             const int row = row0 + 4 * q + r;
             const float v = acc[t][r];
-            if (row < R) a.y[((size_t)g * R + row) * O + o] = (a.leaky && !(v > 0.f)) ? 0.01f * v : v;
+            if (row < R) ay[((size_t)g * R + row) * O + o] = (a.leaky && !(v > 0.f)) ? 0.01f * v : v;
         }
     }
 }
@@ -451,6 +458,36 @@ int launch_bias_bmm2_fwd(const float* x1, const float* x2, const float* w, const
     const int otiles = (O + 15) / 16, units = ((R + 15) / 16) * ((otiles + BMM_TPW - 1) / BMM_TPW);
     const dim3 grid((units + 3) / 4, n);
     const bool xv = (I2 & 3) == 0;      // 16-byte row loads need rows of whole quads in both sources (Harvest: 15 extra features -> scalar loads)
+    if (g_learner_precision == 1) {
+        if (xv) hipLaunchKernelGGL((k_bias_bmm_fwd<true, true>), grid, dim3(256), 0, s, k);
+        else hipLaunchKernelGGL((k_bias_bmm_fwd<false, true>), grid, dim3(256), 0, s, k);
+    } else {
+        if (xv) hipLaunchKernelGGL((k_bias_bmm_fwd<true, false>), grid, dim3(256), 0, s, k);
+        else hipLaunchKernelGGL((k_bias_bmm_fwd<false, false>), grid, dim3(256), 0, s, k);
+    }
+    return 0;
+}
+
+// The forward of two operand groups of one layer shape in ONE grid (BmmK::n_a): n_a sets of group a, n_b of group b, each set computed
+// as launch_bias_bmm_fwd (I2 == 0: x2 unused) / launch_bias_bmm2_fwd would compute it -- the same instantiation, the same arithmetic
+// per set.  Two-source rows whose first source is no multiple of 16 columns wide take the per-lane source select (XV false), so
+// they need a second source that the single launch sends there too (I2 not a multiple of 4).
+int launch_bias_bmm_pair_fwd(const float* x_a, const float* x2_a, const float* w_a, const float* b_a, float* y_a, int n_a, const float* x_b,
+                             const float* x2_b, const float* w_b, const float* b_b, float* y_b, int n_b, int R, int I1, int I2, int O, int x1_div,
+                             int x2_shared, int leaky, hipStream_t s) {
+    BmmK k = {};
+    const int I = I1 + I2;
+    bool xv = (I & 3) == 0;
+    if (I2) {
+        xv = (I2 & 3) == 0;
+        if (x1_div < 1 || R % x1_div || (xv && (I1 & 15))) return -3;
+        k.x2 = x2_a; k.x2_b = x2_b; k.I1 = I1; k.x1_div = x1_div; k.x2_set = x2_shared ? 0 : (long)R * I2;
+    }
+    if ((long)I * O >= (1L << 30) || (long)R * I >= (1L << 30)) return -2;        // 32-bit byte offsets inside a weight set
+    k.x = x_a; k.w = w_a; k.b = b_a; k.y = y_a; k.x_b = x_b; k.w_b = w_b; k.b_b = b_b; k.y_b = y_b; k.n_a = n_a;
+    k.n = n_a + n_b; k.R = R; k.I = I; k.O = O; k.leaky = leaky;
+    const int otiles = (O + 15) / 16, units = ((R + 15) / 16) * ((otiles + BMM_TPW - 1) / BMM_TPW);
+    const dim3 grid((units + 3) / 4, n_a + n_b);
     if (g_learner_precision == 1) {
         if (xv) hipLaunchKernelGGL((k_bias_bmm_fwd<true, true>), grid, dim3(256), 0, s, k);
         else hipLaunchKernelGGL((k_bias_bmm_fwd<false, true>), grid, dim3(256), 0, s, k);

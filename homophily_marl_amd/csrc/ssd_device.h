@@ -160,7 +160,8 @@ void launch_column_sums(const float* x, float* out, int G, int R, int C, float* 
 void launch_copy_blocks(const ssd_block_copy* blocks, int count, hipStream_t stream);
 void launch_clip_adam(const ssd_clip_adam_args* a, hipStream_t stream);
 void launch_dueling_q(const float* a, const float* v, float* q, const float* dq, float* da, float* dv, int n, int T, int B, int inner, int K, hipStream_t stream,
-                      int ld = 0, int merged = 0, float* gs = nullptr);
+                      int ld = 0, int merged = 0, float* gs = nullptr, const float* a_b = nullptr, const float* v_b = nullptr, float* q_b = nullptr,
+                      int n_b = 0);
 void launch_gather_rows(const ssd_row_gather* fields, int count, const int64_t* ids, int n_ids, hipStream_t stream);
 void launch_td_sim_loss(const ssd_td_loss_args* a, int mode, hipStream_t stream);
 // Dynamic LDS of the two per-layer encoder launches (csrc/ssd_policy.hip), in bytes: the launch asks for it and the entry point's
@@ -218,6 +219,12 @@ int launch_bias_bmm_bwd(const float* g, const float* x, const float* w, float* d
                         int x1_div = 1, int x2_shared = 0, long w_set = 0);
 int launch_bias_bmm2_fwd(const float* x1, const float* x2, const float* w, const float* b, float* y, int n, int R, int I1, int I2, int O, int x1_div,
                          int x2_shared, hipStream_t s);
+int launch_bias_bmm_pair_fwd(const float* x_a, const float* x2_a, const float* w_a, const float* b_a, float* y_a, int n_a, const float* x_b,
+                             const float* x2_b, const float* w_b, const float* b_b, float* y_b, int n_b, int R, int I1, int I2, int O, int x1_div,
+                             int x2_shared, int leaky, hipStream_t s);
+void launch_fc1_rows(const float* feat_a, const float* feat_b, const float* tail, const float* act, float* xe_a, float* xi_a, float* xe_b, float* xi_b, int B,
+                     int T, int n, int F0, int F1, int A, hipStream_t s);
+void launch_fc1_rows_bwd(const float* dxe, const float* dxi, float* d_feat, int B, int T, int n, int F0, int F1, int A, int ld, hipStream_t s);
 #ifdef SSD_STAMPS
 void set_policy_stamps(unsigned long long* buf);
 #endif

@@ -705,17 +705,23 @@ static int grid_for(size_t total);
 template <bool BWD>
 __global__ __launch_bounds__(256) void k_dueling_q(const float* __restrict__ a, const float* __restrict__ v, float* __restrict__ q,
                                                    const float* __restrict__ dq, float* __restrict__ da, float* __restrict__ dv, int n, int T, int B,
-                                                   int inner, int K, int ld, int merged, float* __restrict__ gs) {
+                                                   int inner, int K, int ld, int merged, float* __restrict__ gs, const float* __restrict__ a_b,
+                                                   const float* __restrict__ v_b, float* __restrict__ q_b, int n_a) {
     const long rows = (long)T * B * inner, total = rows * n;
     const int vld = merged ? ld : 1;
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-        const int i = (int)(idx / rows);
+        int i = (int)(idx / rows);
         const long r = idx - (long)i * rows;
         const long tb = r / inner;
         const int j = (int)(r - tb * inner), t = (int)(tb / B), b = (int)(tb - (long)t * B);
-        const size_t qo = ((((size_t)b * T + t) * n + i) * inner + j) * K, ao = ((size_t)i * rows + r) * ld;
+        // !BWD, n_a > 0: a second group of sets (the target net's next to the live net's): sets i >= n_a are the sets 0 .. n - n_a - 1
+        // of a_b / v_b / q_b
+        const bool grp_b = !BWD && n_a && i >= n_a;
+        const int ng = !BWD && n_a ? (grp_b ? n - n_a : n_a) : n;
+        if (grp_b) i -= n_a;
+        const size_t qo = ((((size_t)b * T + t) * ng + i) * inner + j) * K, ao = ((size_t)i * rows + r) * ld;
         float x[16], sum = 0.f;
-        for (int k = 0; k < K; ++k) { x[k] = BWD ? dq[qo + k] : a[ao + k]; sum += x[k]; }
+        for (int k = 0; k < K; ++k) { x[k] = BWD ? dq[qo + k] : (grp_b ? a_b : a)[ao + k]; sum += x[k]; }
         if (BWD) {
             const float mean = sum / (float)K;
             for (int k = 0; k < K; ++k) da[ao + k] = x[k] - mean;
@@ -735,18 +741,22 @@ __global__ __launch_bounds__(256) void k_dueling_q(const float* __restrict__ a, 
                 for (int k = 0; k <= K; ++k) go[k] = g[k];
             }
         } else {
-            const float vv = v[((size_t)i * rows + r) * vld], mean = sum / (float)K;
-            for (int k = 0; k < K; ++k) q[qo + k] = (vv + x[k]) - mean;               // v + a - mean(a), in the reference's order
+            const float vv = (grp_b ? v_b : v)[((size_t)i * rows + r) * vld], mean = sum / (float)K;
+            float* qg = grp_b ? q_b : q;
+            for (int k = 0; k < K; ++k) qg[qo + k] = (vv + x[k]) - mean;              // v + a - mean(a), in the reference's order
         }
     }
 }
 
 void launch_dueling_q(const float* a, const float* v, float* q, const float* dq, float* da, float* dv, int n, int T, int B, int inner, int K,
-                      hipStream_t stream, int ld, int merged, float* gs) {
+                      hipStream_t stream, int ld, int merged, float* gs, const float* a_b, const float* v_b, float* q_b, int n_b) {
+    // forward with a second group (a_b, v_b, q_b: n_b sets): the kernel sees n + n_b sets, the first n of them the first group's
+    const int n_a = (!dq && n_b > 0) ? n : 0;
+    if (n_a) n += n_b;
     const size_t total = (size_t)n * T * B * inner;
     if (ld <= 0) ld = K;
-    if (dq) hipLaunchKernelGGL(k_dueling_q<true>, dim3(grid_for(total)), dim3(256), 0, stream, a, v, q, dq, da, dv, n, T, B, inner, K, ld, merged, gs);
-    else hipLaunchKernelGGL(k_dueling_q<false>, dim3(grid_for(total)), dim3(256), 0, stream, a, v, q, dq, da, dv, n, T, B, inner, K, ld, merged, gs);
+    if (dq) hipLaunchKernelGGL(k_dueling_q<true>, dim3(grid_for(total)), dim3(256), 0, stream, a, v, q, dq, da, dv, n, T, B, inner, K, ld, merged, gs, a_b, v_b, q_b, n_a);
+    else hipLaunchKernelGGL(k_dueling_q<false>, dim3(grid_for(total)), dim3(256), 0, stream, a, v, q, dq, da, dv, n, T, B, inner, K, ld, merged, gs, a_b, v_b, q_b, n_a);
 }
 
 // k_gather_rows: rows ids[e] of up to SSD_COPY_BLOCKS_MAX fields into consecutive rows of their destinations (blockIdx.y = field,

@@ -192,12 +192,12 @@ class HomophilyLearner:
 
     def unroll_pair(self, batch):
         """(q_env, q_inc) of the live net and (tq_env, tq_inc) of the target net (no grad) on the same batch: the weight-independent
-        preparation is shared and both recurrences (4n weight sets) run in ONE sequence launch per direction."""
+        preparation is shared, both recurrences (4n weight sets) run in ONE sequence launch per direction, and every affine layer and
+        dueling combination around them goes out once for both nets (unroll_pre_pair / unroll_post_pair), on fc1 rows that one launch
+        assembles for both (unroll_rows_pair)."""
         mac, tgt = self.mac, self.target_mac
         shared = mac.unroll_shared(batch)
-        gi, wh, bh = mac.unroll_pre(batch, shared)
-        with th.no_grad():
-            gi_t, wh_t, bh_t = tgt.unroll_pre(batch, shared)
+        (gi, wh, bh), (gi_t, wh_t, bh_t) = mac.agent.unroll_pre_pair(tgt.agent, *mac.unroll_rows_pair(tgt, batch, shared))
         # live env / inc, target env / inc: the four projection outputs AND the four recurrence weight images go to the sequence kernel
         # as they are (no concatenation), and the states come back as four tensors (no slicing: a slice's backward is a zero-fill + copy)
         # train_stored_state: the live and the target net both start from the state the rollout stored for the batch's first slot
@@ -206,9 +206,7 @@ class HomophilyLearner:
                                                     h0=None if h0 is None else h0 + h0)
         if h0 is not None:
             self.last_first_states = (he.detach()[:, 0], hi.detach()[:, 0])            # [n, B, H] each: what row 0 was evaluated on (the tests read it)
-        q_env, q_inc = mac.agent.unroll_post(he, hi, shared["other"])
-        with th.no_grad():
-            tq_env, tq_inc = tgt.agent.unroll_post(he_t.detach(), hi_t.detach(), shared["other"])
+        (q_env, q_inc), (tq_env, tq_inc) = mac.agent.unroll_post_pair(tgt.agent, he, hi, he_t.detach(), hi_t.detach(), shared["other"])
         return q_env, q_inc, tq_env, tq_inc
 
     def _all_reduce_grad(self):

@@ -213,6 +213,33 @@ class HomophilyAgent(nn.Module):
         (wie, whe, bie, bhe), (wii, whi, bii, bhi) = self._gru_weights_both()
         return [ops.bias_bmm(xe, wie, bie), ops.bias_bmm(xi, wii, bii)], [whe, whi], [bhe, bhi]      # (weight parts: no concatenation)
 
+    def unroll_pre_pair(self, tgt, x, xa, x_t, xa_t):
+        """unroll_pre of this (live) net and of `tgt`, a frozen copy (the learner's target network), from the rows the two fc1 layers read
+        (set-major, time-major: x [n, T * B, input_shape] and xa = [x | one-hot action] of this net, x_t and xa_t of tgt): (parts, wh, bh)
+        of each.  The four affine layers of the two nets go out as four launches, not eight (ops.bias_bmm_pair: the weight sets of both
+        nets in one grid); every value is the one unroll_pre of its net returns."""
+        with th.no_grad():
+            (wie_t, whe_t, bie_t, bhe_t), (wii_t, whi_t, bii_t, bhi_t) = tgt._gru_weights_both()
+        xe, xe_t = ops.bias_bmm_pair(x, self._w("fc1_env_w"), self._b("fc1_env_b"), x_t, tgt._w("fc1_env_w"), tgt._b("fc1_env_b"), leaky=True)
+        xi, xi_t = ops.bias_bmm_pair(xa, self._w("fc1_inc_w"), self._b("fc1_inc_b"), xa_t, tgt._w("fc1_inc_w"), tgt._b("fc1_inc_b"), leaky=True)
+        (wie, whe, bie, bhe), (wii, whi, bii, bhi) = self._gru_weights_both()
+        gie, gie_t = ops.bias_bmm_pair(xe, wie, bie, xe_t, wie_t, bie_t)
+        gii, gii_t = ops.bias_bmm_pair(xi, wii, bii, xi_t, wii_t, bii_t)
+        return ([gie, gii], [whe, whi], [bhe, bhi]), ([gie_t, gii_t], [whe_t, whi_t], [bhe_t, bhi_t])
+
+    def unroll_post_pair(self, tgt, he, hi, he_t, hi_t, other):
+        """unroll_post of this (live) net on (he, hi) and of `tgt`, a frozen copy, on (he_t, hi_t): (q_env, q_inc), (tq_env, tq_inc).  Per
+        head the layer of both nets is one launch and the dueling combination of both is one (ops.dueling_head_pair)."""
+        n, H = self.n_agents, self.hidden
+        T, B = he.shape[1], he.shape[2]
+        he, hi, he_t, hi_t = (h.reshape(n, T * B, H) for h in (he, hi, he_t, hi_t))
+        w_env, b_env, w_inc, b_inc = self._fc2_merged()
+        with th.no_grad():
+            w_env_t, b_env_t, w_inc_t, b_inc_t = tgt._fc2_merged()
+        q_env, tq_env = ops.dueling_head_pair(he, None, w_env, b_env, he_t, w_env_t, b_env_t, B, T, 1)
+        q_inc, tq_inc = ops.dueling_head_pair(hi, other, w_inc, b_inc, hi_t, w_inc_t, b_inc_t, B, T, n)
+        return (q_env, q_inc), (tq_env, tq_inc)
+
     @staticmethod
     def unroll_other(act_onehot, agent_pos, agent_orientation, reward, clean_num, apple_den, dtype):
         """other_j = [onehot(a_j), pos_j, orient_j, r_j, clean_j, apple_den_j] (homophily_agent.py:194-201) as [T*B, n(j), E];

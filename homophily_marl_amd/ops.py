@@ -540,9 +540,8 @@ class _DuelingHead(th.autograd.Function):
         return dh, None, dw, db, None, None, None
 
 
-def dueling_head(h, other, w, b, B, T, inner):
-    """q [B, T, n, K] (inner = 1, other None) or [B, T, n, inner, K] of one dueling head: h [n, T * B, H] the recurrence states (rows
-    t * B + b), other [T * B, inner, E] or None, w [n, H (+ E), K + 1] = [advantage layer | value layer], b [n, 1, K + 1]."""
+def _dueling_head_fit(h, other, w, b, B, T, inner):
+    """dueling_head's argument checks (ValueError naming the argument); True when the kernels take the call"""
     if h.dim() != 3 or h.shape[1] != T * B:
         raise _unfit("dueling_head", "h", h, "[n, T * B = %d, H] expected" % (T * B))
     n, TB, H = h.shape
@@ -555,8 +554,16 @@ def dueling_head(h, other, w, b, B, T, inner):
     if b.device != h.device:
         raise _unfit("dueling_head", "b", b, "the device of h expected")
     # the kernels: f32 throughout, b one row per weight set, the gradient of `other` not among those they emit
-    if (h.is_cuda and _f32_on(h, w, b) and K <= 15 and H % 16 == 0 and b.shape == (n, 1, K + 1) and (other is not None or inner == 1)
-            and (other is None or (other.dtype == th.float32 and E >= 1 and not (other.requires_grad and th.is_grad_enabled())))):
+    return (h.is_cuda and _f32_on(h, w, b) and K <= 15 and H % 16 == 0 and b.shape == (n, 1, K + 1) and (other is not None or inner == 1)
+            and (other is None or (other.dtype == th.float32 and E >= 1 and not (other.requires_grad and th.is_grad_enabled()))))
+
+
+def dueling_head(h, other, w, b, B, T, inner):
+    """q [B, T, n, K] (inner = 1, other None) or [B, T, n, inner, K] of one dueling head: h [n, T * B, H] the recurrence states (rows
+    t * B + b), other [T * B, inner, E] or None, w [n, H (+ E), K + 1] = [advantage layer | value layer], b [n, 1, K + 1]."""
+    fit = _dueling_head_fit(h, other, w, b, B, T, inner)
+    n, TB, K = h.shape[0], h.shape[1], w.shape[2] - 1
+    if fit:
         q = _DuelingHead.apply(h, other, w, b, B, T, inner)
     else:
         _leaving_kernels("dueling_head", h, "layout / dtypes / a bias that is not [n, 1, K + 1] / other requires a gradient")
@@ -566,6 +573,66 @@ def dueling_head(h, other, w, b, B, T, inner):
         a, v = y[..., :K], y[..., K:]
         q = (v + a - a.mean(dim=-1, keepdim=True)).reshape(n, T, B, inner, K).permute(2, 1, 0, 3, 4)
     return q.reshape(B, T, n, K) if inner == 1 else q
+
+
+class _DuelingHeadPair(th.autograd.Function):
+    """_DuelingHead of a live net (h, w, b: gradients as _DuelingHead) and of a second, frozen net (h_t, w_t, b_t: no gradient) on the same
+    `other`, the layer of both as ONE launch and the dueling combination of both as one (ssd_bias_bmm_pair_fwd, ssd_dueling_head_pair_fwd):
+    (q, q_t), each what _DuelingHead returns for its net alone, bit for bit.  Backward: _DuelingHead's, on the live operands."""
+
+    @staticmethod
+    def forward(ctx, h, other, w, b, B, T, inner, h_t, w_t, b_t):
+        lib = abi.load_library()
+        h, w, b, h_t, w_t, b_t = (t.contiguous() for t in (h, w, b, h_t, w_t, b_t))
+        n, TB, H = h.shape
+        n_t = h_t.shape[0]
+        K = w.shape[2] - 1
+        st = _stream(h)
+        y = th.empty(n, TB * inner, K + 1, dtype=th.float32, device=h.device)
+        y_t = th.empty(n_t, TB * inner, K + 1, dtype=th.float32, device=h.device)
+        if other is None:
+            assert inner == 1 and w.shape[1] == H
+            abi.check(lib, lib.ssd_bias_bmm_pair_fwd(h.data_ptr(), None, w.data_ptr(), b.data_ptr(), y.data_ptr(), n, h_t.data_ptr(), None, w_t.data_ptr(),
+                                                     b_t.data_ptr(), y_t.data_ptr(), n_t, TB, H, 0, K + 1, 1, 0, 0, st))
+        else:
+            other = other.contiguous()
+            E = other.shape[-1]
+            assert other.shape[0] == TB and other.shape[1] == inner and w.shape[1] == H + E
+            abi.check(lib, lib.ssd_bias_bmm_pair_fwd(h.data_ptr(), other.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), n, h_t.data_ptr(), other.data_ptr(),
+                                                     w_t.data_ptr(), b_t.data_ptr(), y_t.data_ptr(), n_t, TB * inner, H, E, K + 1, inner, 1, 0, st))
+        q = th.empty((B, T, n, inner, K), dtype=th.float32, device=h.device)
+        q_t = th.empty((B, T, n_t, inner, K), dtype=th.float32, device=h.device)
+        abi.check(lib, lib.ssd_dueling_head_pair_fwd(y.data_ptr(), q.data_ptr(), n, y_t.data_ptr(), q_t.data_ptr(), n_t, T, B, inner, K, st))
+        ctx.save_for_backward(h, w, *(() if other is None else (other,)))
+        ctx.dims = (B, T, inner, K)
+        ctx.precision = LEARNER_PRECISION
+        ctx.mark_non_differentiable(q_t)
+        ctx.set_materialize_grads(False)         # (no zero-filled gradient for q_t: a launch per backward otherwise)
+        return q, q_t
+
+    @staticmethod
+    def backward(ctx, dq, dq_t):
+        if dq is None:
+            return (None,) * 10
+        with _precision(ctx.precision):
+            return _DuelingHead._backward(ctx, dq) + (None, None, None)
+
+
+def dueling_head_pair(h, other, w, b, h_t, w_t, b_t, B, T, inner):
+    """(dueling_head(h, other, w, b, ...), dueling_head(h_t, other, w_t, b_t, ...) without a gradient): a live net and a frozen copy
+    (the learner's target network) on the same batch.  On the device both go out together: one launch for the layer of both, one for
+    the dueling combination of both; anywhere else, or when the second net asks for a gradient, the two calls one after the other."""
+    fit = _dueling_head_fit(h, other, w, b, B, T, inner)
+    frozen = not (th.is_grad_enabled() and (h_t.requires_grad or w_t.requires_grad or b_t.requires_grad))
+    if (fit and frozen and _dueling_head_fit(h_t, other, w_t, b_t, B, T, inner) and h_t.device == h.device
+            and tuple(h_t.shape[1:]) == tuple(h.shape[1:]) and tuple(w_t.shape[1:]) == tuple(w.shape[1:])):
+        q, q_t = _DuelingHeadPair.apply(h, other, w, b, B, T, inner, h_t, w_t, b_t)
+        K = w.shape[2] - 1
+        return (q.reshape(B, T, h.shape[0], K), q_t.reshape(B, T, h_t.shape[0], K)) if inner == 1 else (q, q_t)
+    q = dueling_head(h, other, w, b, B, T, inner)
+    with th.no_grad() if frozen else th.enable_grad():
+        q_t = dueling_head(h_t, other, w_t, b_t, B, T, inner)
+    return q, q_t
 
 
 def _mix32p(x):
@@ -1025,6 +1092,123 @@ class _BiasBmm(th.autograd.Function):
         return dx, dw, db, None
 
 
+def _bias_bmm_pair_fwd(x, w, b, x_t, w_t, b_t, leaky):
+    lib = abi.load_library()
+    x, w, b, x_t, w_t, b_t = (t.contiguous() for t in (x, w, b, x_t, w_t, b_t))
+    n, R, I = x.shape
+    n_t, O = x_t.shape[0], w.shape[2]
+    y = th.empty(n, R, O, dtype=th.float32, device=x.device)
+    y_t = th.empty(n_t, R, O, dtype=th.float32, device=x.device)
+    abi.check(lib, lib.ssd_bias_bmm_pair_fwd(x.data_ptr(), None, w.data_ptr(), b.data_ptr(), y.data_ptr(), n, x_t.data_ptr(), None, w_t.data_ptr(), b_t.data_ptr(),
+                                             y_t.data_ptr(), n_t, R, I, 0, O, 1, 0, int(bool(leaky)), _stream(x)))
+    return y, y_t
+
+
+class _BiasBmmPair(th.autograd.Function):
+    """_BiasBmm of a live net (x, w, b) and the same layer of a second, frozen net (x_t, w_t, b_t: no gradient) as ONE forward launch
+    (ssd_bias_bmm_pair_fwd: the sets of both nets in one grid, each computed as the single launch computes it); backward: _BiasBmm's
+    single launch (ssd_bias_bmm_bwd / _leaky_bwd) on the live operands."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, leaky, x_t, w_t, b_t):
+        x, w = x.contiguous(), w.contiguous()
+        y, y_t = _bias_bmm_pair_fwd(x, w, b, x_t, w_t, b_t, leaky)
+        ctx.leaky = leaky
+        ctx.precision = LEARNER_PRECISION
+        ctx.save_for_backward(x, w, *((y,) if leaky else ()))
+        ctx.mark_non_differentiable(y_t)
+        ctx.set_materialize_grads(False)         # (no zero-filled gradient for y_t: a launch per backward otherwise)
+        return y, y_t
+
+    @staticmethod
+    def backward(ctx, g, g_t):
+        if g is None:
+            return (None,) * 7
+        with _precision(ctx.precision):
+            return _BiasBmm._backward(ctx, g) + (None, None, None)
+
+
+def bias_bmm_pair(x, w, b, x_t, w_t, b_t, leaky=False):
+    """(bias_bmm(x, w, b, leaky), bias_bmm(x_t, w_t, b_t, leaky) without a gradient): one layer of a live net and of a frozen copy (the
+    learner's target network) with the same shapes.  On the device ONE forward launch computes both; anywhere else, or when the second
+    net asks for a gradient, the two calls one after the other."""
+    frozen = not (th.is_grad_enabled() and (x_t.requires_grad or w_t.requires_grad or b_t.requires_grad))
+    if (frozen and _bmm_kernel_ok(x, w, b) and _bmm_kernel_ok(x_t, w_t, b_t) and x_t.device == x.device and tuple(x_t.shape[1:]) == tuple(x.shape[1:])
+            and tuple(w_t.shape[1:]) == tuple(w.shape[1:])):
+        if th.is_grad_enabled() and (w.requires_grad or b.requires_grad or x.requires_grad):
+            return _BiasBmmPair.apply(x, w, b, leaky, x_t, w_t, b_t)
+        return _bias_bmm_pair_fwd(x, w, b, x_t, w_t, b_t, leaky)
+    y = bias_bmm(x, w, b, leaky)
+    with th.no_grad() if frozen else th.enable_grad():
+        y_t = bias_bmm(x_t, w_t, b_t, leaky)
+    return y, y_t
+
+
+class _Fc1Rows(th.autograd.Function):
+    """fc1_rows on the device: ONE launch writes the rows of both fc1 layers, of both nets when feat_t is given (ssd_fc1_rows_fwd), and
+    one returns the live features' gradient (ssd_fc1_rows_bwd: the two layers' input gradients added and transposed back)."""
+
+    @staticmethod
+    def forward(ctx, feat, tail, act, B, T, n, feat_t):
+        lib = abi.load_library()
+        feat, tail, act = feat.contiguous(), tail.contiguous(), act.contiguous()
+        F0, F1, A = feat.shape[1], tail.shape[1], act.shape[2]
+        new = lambda w: th.empty(n, T * B, w, dtype=th.float32, device=feat.device)
+        xe, xi = new(F0 + F1), new(F0 + F1 + A)
+        xe_t = xi_t = None
+        if feat_t is not None:
+            feat_t, xe_t, xi_t = feat_t.contiguous(), new(F0 + F1), new(F0 + F1 + A)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        abi.check(lib, lib.ssd_fc1_rows_fwd(feat.data_ptr(), ptr(feat_t), tail.data_ptr(), act.data_ptr(), xe.data_ptr(), xi.data_ptr(), ptr(xe_t), ptr(xi_t),
+                                            B, T, n, F0, F1, A, _stream(feat)))
+        ctx.dims = (B, T, n, F0, F1, A)
+        ctx.set_materialize_grads(False)         # (no zero-filled gradients for the second net's rows: a launch each per backward otherwise)
+        if feat_t is None:
+            return xe, xi
+        ctx.mark_non_differentiable(xe_t, xi_t)
+        return xe, xi, xe_t, xi_t
+
+    @staticmethod
+    def backward(ctx, dxe, dxi, *unused):
+        lib = abi.load_library()
+        B, T, n, F0, F1, A = ctx.dims
+        if dxe is None and dxi is None:
+            return (None,) * 7
+        like = dxe if dxe is not None else dxi
+        dxe = like.new_zeros(n, T * B, F0 + F1) if dxe is None else dxe.contiguous()
+        dxi = like.new_zeros(n, T * B, F0 + F1 + A) if dxi is None else dxi.contiguous()
+        # the leading F0 columns of rows F0 + F1 wide: the layout the slice of th.cat([feat, tail])'s gradient has, so whatever reads
+        # it (a library GEMM of the tensor-op encoder chooses its kernel by the strides too) is handed what it was handed before
+        d_in = th.empty(B * T * n, F0 + F1, dtype=th.float32, device=dxe.device)
+        abi.check(lib, lib.ssd_fc1_rows_bwd(dxe.data_ptr(), dxi.data_ptr(), d_in.data_ptr(), B, T, n, F0, F1, A, F0 + F1, _stream(dxe)))
+        return d_in[:, :F0], None, None, None, None, None, None
+
+
+def fc1_rows(feat, tail, act, B, T, n, feat_t=None):
+    """The input rows of the two fc1 layers in the learner's set-major, time-major layout, from the pieces where they lie: feat
+    [B * T * n, F0] (the encoder's output, rows (b * T + t) * n + i), tail [B * T * n, F1] (the non-visual input columns, same rows), act
+    [n, T * B, A] (the one-hot actions, rows t * B + b) -> (x_env [n, T * B, F0 + F1] = [feat | tail], x_inc [n, T * B, F0 + F1 + A] =
+    [feat | tail | act]); with feat_t (the features of a frozen second net: no gradient) also (x_env_t, x_inc_t).  The values of
+    th.cat([feat, tail], 1) transposed to time-major rows, and of its concatenation with act."""
+    for name, t, shape in (("tail", tail, (B * T * n, tail.shape[-1])), ("act", act, (n, T * B, act.shape[-1]))) + (
+            () if feat_t is None else (("feat_t", feat_t, tuple(feat.shape)),)):
+        if tuple(t.shape) != shape or t.device != feat.device:
+            raise _unfit("fc1_rows", name, t, "%s on the device of feat expected" % (shape,))
+    if feat.dim() != 2 or feat.shape[0] != B * T * n:
+        raise _unfit("fc1_rows", "feat", feat, "[B * T * n = %d, F0] expected" % (B * T * n))
+    frozen = feat_t is None or not (th.is_grad_enabled() and feat_t.requires_grad)
+    if feat.is_cuda and frozen and _f32_on(feat, tail, act, *(() if feat_t is None else (feat_t,))) and tail.shape[1] >= 1 and not (
+            th.is_grad_enabled() and (tail.requires_grad or act.requires_grad)):
+        return _Fc1Rows.apply(feat, tail, act, B, T, n, feat_t)
+    _leaving_kernels("fc1_rows", feat, "dtypes / a tail or actions that ask for a gradient")
+    tm = lambda x: x.reshape(B, T, n, -1).permute(2, 1, 0, 3).reshape(n, T * B, -1)
+    out = ()
+    for f in (feat,) + (() if feat_t is None else (feat_t,)):
+        x = tm(th.cat([f, tail.to(f.dtype)], dim=1))
+        out += (x, th.cat([x, act.to(f.dtype)], dim=-1))
+    return out
+
+
 def bias_bmm(x, w, b, leaky=False):
     """x @ w + b for per-agent weights: x [n, R, I], w [n, I, O], b [n, 1, O]; leaky: followed by LeakyReLU (slope 0.01)."""
     if _bmm_kernel_ok(x, w, b):
@@ -1160,7 +1344,8 @@ class _EncodeCodes(th.autograd.Function):
         R = codes.shape[0]
         K = act[0].numel()
         st = _stream(codes)
-        g2 = th.ops.aten.leaky_relu_backward(d_feat.contiguous(), feat, 0.01, True)   # dL/d(Linear output): LeakyReLU'(x) from the sign of LeakyReLU(x), one launch
+        # dL/d(Linear output): LeakyReLU'(x) from the sign of LeakyReLU(x), one launch (it reads a row-strided d_feat where it lies)
+        g2 = th.ops.aten.leaky_relu_backward(d_feat, feat, 0.01, True).contiguous()
         d_lin_b = column_sums(g2)
         # the two products of the Linear's backward on the per-agent-layer kernels (csrc/ssd_bmm.hip, one weight set):
         #   d_lin_w [32, K] = g2^T act   (its "dw" role: rows = K of the product, split over 16 waves per tile)
