@@ -367,6 +367,12 @@ TRAIN_SIGNATURES = {name: (C.c_int, args) for name, args in {
     "ssd_fc1_rows_fwd": [vp] * 8 + [i32] * 6 + [vp],
     "ssd_fc1_rows_bwd": [vp] * 3 + [i32] * 7 + [vp],
 }.items()}
+# the export of include/ssd_hip_reward.h (the reward model over a finished rollout); returns int.  tests/test_social_reward_host.py
+# holds this table to that header and the entry to a refusal table.
+REWARD_IA, REWARD_PROSOCIAL = 1, 2
+REWARD_SIGNATURES = {name: (C.c_int, args) for name, args in {
+    "ssd_social_reward": [i32] + [vp] * 3 + [i32] * 7 + [f32] * 3 + [vp],
+}.items()}
 
 
 # ---- size / layout helpers ---------------------------------------------------------------------------------------------------
@@ -535,6 +541,7 @@ def load_library():
         lib = C.CDLL(HIP_LIB_PATH)
         bind(lib, HIP_SIGNATURES)
         bind(lib, TRAIN_SIGNATURES)
+        bind(lib, REWARD_SIGNATURES)
         ver = lib.ssd_abi_version()
         if ver != ABI_VERSION:
             raise ImportError("libssd_hip.so ABI version %d != %d" % (ver, ABI_VERSION))

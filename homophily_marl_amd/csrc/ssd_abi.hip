@@ -9,6 +9,7 @@
 
 #include "ssd_device.h"
 #include "../../include/ssd_hip_train.h"
+#include "../../include/ssd_hip_reward.h"
 
 using namespace ssd;
 
@@ -923,6 +924,32 @@ int ssd_fc1_rows_bwd(const float* d_x_env, const float* d_x_inc, float* d_feat, 
     if (d_feat_stride < feat_w) return fail(SSD_ERR_INVALID, "ssd_fc1_rows_bwd: d_feat_stride below feat_w");
     if ((int64_t)B * T * n * ((int64_t)feat_w + tail_w + act_w) >= ((int64_t)1 << 40)) return fail(SSD_ERR_UNSUPPORTED, "ssd_fc1_rows_bwd: 2^40 elements or more");
     launch_fc1_rows_bwd(d_x_env, d_x_inc, d_feat, B, T, n, feat_w, tail_w, act_w, d_feat_stride, (hipStream_t)stream);
+    return launched();
+}
+// include/ssd_hip_reward.h: the reward model over a finished rollout (csrc/ssd_social_reward.hip)
+int ssd_social_reward(int32_t model, const float* reward, float* shaped, double* acc, int32_t n_env, int32_t t_slots, int32_t n_agents,
+                      int32_t src_env_stride, int32_t src_slot_stride, int32_t dst_env_stride, int32_t dst_slot_stride, float p0, float p1, float p2,
+                      void* stream) {
+    if (!reward || !shaped) return fail(SSD_ERR_INVALID, "ssd_social_reward: a null reward or shaped");
+    if (model != SSD_REWARD_IA && model != SSD_REWARD_PROSOCIAL) return fail(SSD_ERR_INVALID, "ssd_social_reward: model must be SSD_REWARD_IA (1) or SSD_REWARD_PROSOCIAL (2)");
+    if (n_env < 1) return fail(SSD_ERR_INVALID, "ssd_social_reward: n_env must be >= 1");
+    if (t_slots < 2) return fail(SSD_ERR_INVALID, "ssd_social_reward: t_slots must be >= 2 (one slot and the bootstrap slot)");
+    if (n_agents < 2 || n_agents > SSD_MAX_AGENTS) return fail(SSD_ERR_INVALID, "ssd_social_reward: n_agents out of range (2..10)");
+    if (src_slot_stride < n_agents || dst_slot_stride < n_agents) return fail(SSD_ERR_INVALID, "ssd_social_reward: a slot stride below n_agents");
+    if (src_env_stride < (int64_t)t_slots * src_slot_stride || dst_env_stride < (int64_t)t_slots * dst_slot_stride)
+        return fail(SSD_ERR_INVALID, "ssd_social_reward: an env stride below t_slots * slot_stride");
+    if (!(p0 >= 0.0f) || !(p1 >= 0.0f) || !std::isfinite(p0) || !std::isfinite(p1))
+        return fail(SSD_ERR_INVALID, "ssd_social_reward: p0 and p1 must be finite and >= 0");
+    if (model == SSD_REWARD_IA && !(p2 >= 0.0f && p2 < 1.0f)) return fail(SSD_ERR_INVALID, "ssd_social_reward: the decay p2 must lie in [0, 1)");
+    const int64_t src_ext = (int64_t)(n_env - 1) * src_env_stride + (int64_t)(t_slots - 1) * src_slot_stride + n_agents;
+    const int64_t dst_ext = (int64_t)(n_env - 1) * dst_env_stride + (int64_t)(t_slots - 1) * dst_slot_stride + n_agents;
+    if (src_ext > INT32_MAX || dst_ext > INT32_MAX) return fail(SSD_ERR_INVALID, "ssd_social_reward: an extent past 2^31 - 1 elements");
+    if (((uintptr_t)reward | (uintptr_t)shaped) & 3) return fail(SSD_ERR_INVALID, "ssd_social_reward: reward or shaped is not 4-byte aligned");
+    if ((uintptr_t)acc & 7) return fail(SSD_ERR_INVALID, "ssd_social_reward: acc (f64) is not 8-byte aligned");
+    if ((uintptr_t)shaped < (uintptr_t)reward + 4 * (uintptr_t)src_ext && (uintptr_t)reward < (uintptr_t)shaped + 4 * (uintptr_t)dst_ext)
+        return fail(SSD_ERR_INVALID, "ssd_social_reward: shaped and reward must be distinct buffers that do not overlap");
+    launch_social_reward(model, reward, shaped, acc, n_env, t_slots, n_agents, src_env_stride, src_slot_stride, dst_env_stride, dst_slot_stride, p0, p1, p2,
+                         (hipStream_t)stream);
     return launched();
 }
 int ssd_bmm_reserve_scratch(void* stream) {

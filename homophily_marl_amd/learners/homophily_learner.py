@@ -256,7 +256,7 @@ class HomophilyLearner:
     def _sim_inputs(self, batch):
         """windowed activity flags -> similarity mask (homophily_learner.py:184-206,214); depends on batch data only."""
         a, n, h = self.args, self.n_agents, self.sim_horizon
-        rewards = batch["reward"][:, :-1] / a.reward_scale
+        rewards = batch[ops.reward_field(a)][:, :-1] / a.reward_scale
         clean_num = (batch["clean_num"][:, :-1] > 0).float()
         cn_cum, rw_cum = th.cumsum(clean_num, dim=1), th.cumsum(rewards, dim=1)
         cn_h, rw_h = cn_cum.clone(), rw_cum.clone()
@@ -342,7 +342,7 @@ class HomophilyLearner:
         a = self.args
         n = self.n_agents
         logs = {}
-        rewards = batch["reward"][:, :-1] / a.reward_scale                     # [bs, t-1, n]
+        rewards = batch[ops.reward_field(a)][:, :-1] / a.reward_scale                     # [bs, t-1, n]
         actions = batch["actions"][:, :-1]                                     # [bs, t-1, n, 1]
         actions_inc = batch["actions_inc"][:, :-1]                             # [bs, t-1, n, n, 1]
         actions_inc_all = batch["actions_inc"]                                 # [bs, t, n, n, 1]

@@ -262,7 +262,7 @@ def _td_loss_args(batch, a, n_actions, partials):
     c = lambda x: x.contiguous()
     B, T1, n = batch.batch_size, batch.max_seq_length, batch["reward"].shape[-1]
     keep = dict(actions=c(batch["actions"].squeeze(-1)), actions_inc=c(batch["actions_inc"].squeeze(-1)), avail=c(batch["avail_actions"]),
-                reward=c(batch["reward"].float()), clean_num=c(batch["clean_num"].float()),
+                reward=c(batch[reward_field(a)].float()), clean_num=c(batch["clean_num"].float()),
                 terminated=c(batch["terminated"].squeeze(-1)), filled=c(batch["filled"].squeeze(-1)))
     assert keep["avail"].dtype == th.int32 and keep["terminated"].dtype == th.uint8 and keep["filled"].dtype == th.int64
     t = abi.SsdTdLossArgs()
@@ -399,6 +399,92 @@ def behaviour_stats(actions, actions_inc, reward, clean_num, n_actions, acc, wor
              th.tensor([N, N * T], dtype=th.int64, device=dev)]
     acc += th.cat([i64(p).reshape(-1) for p in parts]).to(th.float64)
     return acc
+
+
+REWARD_MODELS = {"inequity_aversion": abi.REWARD_IA, "prosocial": abi.REWARD_PROSOCIAL}
+
+
+def reward_field(a):
+    """The storage field the loss reads its reward from under the config `a`: "reward", or "reward_model" (the rollout's rewards shaped
+    by social_reward) when the key reward_model names a model.  Observations, statistics and returns always read "reward"."""
+    model = getattr(a, "reward_model", "individual")
+    return "reward" if model is None or model == "individual" else "reward_model"
+
+
+def social_reward_scalars(model, n_agents, ia_alpha=5.0, ia_beta=0.05, ia_decay=0.96525, prosocial_weight=0.5):
+    """(p0, p1, p2) of ssd_social_reward as Python floats that hold f32 values: the keys rounded to f32, then one f32 operation each --
+    inequity_aversion (alpha / (n - 1), beta / (n - 1), decay), prosocial (1 - rho, rho / (n - 1), 0).  Raises ValueError for a model,
+    a team size or a key outside the ranges of include/ssd_hip_reward.h."""
+    import numpy as np
+    if not isinstance(model, str) or model not in REWARD_MODELS:
+        raise ValueError('reward_model must be "individual", "inequity_aversion" or "prosocial", got %r' % (model,))
+    if not 2 <= int(n_agents) <= abi.MAX_AGENTS:
+        raise ValueError("reward_model %r needs n_agents 2 .. %d (a model compares an agent with the others), got %r" % (model, abi.MAX_AGENTS, n_agents))
+    f, others = np.float32, np.float32(int(n_agents) - 1)
+    num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
+    if model == "inequity_aversion":
+        for name, v in (("ia_alpha", ia_alpha), ("ia_beta", ia_beta)):
+            if not num(v) or not 0.0 <= v < float("inf"):
+                raise ValueError("%s must be a finite number >= 0, got %r" % (name, v))
+        if not num(ia_decay) or not 0.0 <= ia_decay < 1.0 or not float(f(ia_decay)) < 1.0:
+            raise ValueError("ia_decay must lie in [0, 1), got %r" % (ia_decay,))
+        return float(f(ia_alpha) / others), float(f(ia_beta) / others), float(f(ia_decay))
+    if not num(prosocial_weight) or not 0.0 <= prosocial_weight <= 1.0:
+        raise ValueError("prosocial_weight must lie in [0, 1], got %r" % (prosocial_weight,))
+    return float(f(1.0) - f(prosocial_weight)), float(f(prosocial_weight) / others), 0.0
+
+
+def social_reward(reward, out, model, params, acc=None):
+    """out = the rewards of a finished rollout shaped by a reward model (include/ssd_hip_reward.h, ssd_social_reward: the contract of
+    the arithmetic and its order).  reward, out f32 [N, t_slots, n] with unit stride over the agents (views of a larger storage are
+    fine: the env and slot strides are passed on), distinct memory; slot t_slots - 1 of out becomes 0.  model "inequity_aversion" or
+    "prosocial"; params the three scalars of social_reward_scalars.  acc (optional) f64 [N, n, 3] contiguous: += the column sums over
+    the slots.  Device tensors: one launch.  Host tensors: the same rule in f32 tensor operations in the stated order, equal to the bit."""
+    if not isinstance(model, str) or model not in REWARD_MODELS:
+        raise ValueError('ops.social_reward: model must be "inequity_aversion" or "prosocial", got %r' % (model,))
+    if reward.dim() != 3 or reward.dtype != th.float32 or reward.stride(2) != 1:
+        raise _unfit("social_reward", "reward", reward, "f32 [N, t_slots, n] with unit stride over the agents expected")
+    N, T1, n = reward.shape
+    if out.shape != reward.shape or out.dtype != th.float32 or out.device != reward.device or out.stride(2) != 1:
+        raise _unfit("social_reward", "out", out, "f32 %s with unit stride over the agents on the device of reward expected" % ((N, T1, n),))
+    if acc is not None and (acc.shape != (N, n, 3) or acc.dtype != th.float64 or acc.device != reward.device or not acc.is_contiguous()):
+        raise _unfit("social_reward", "acc", acc, "contiguous f64 %s on the device of reward expected" % ((N, n, 3),))
+    if N < 1 or T1 < 2 or not 2 <= n <= abi.MAX_AGENTS:
+        raise _unfit("social_reward", "reward", reward, "n_env >= 1, t_slots >= 2, n_agents 2 .. %d" % abi.MAX_AGENTS)
+    p0, p1, p2 = (float(p) for p in params)
+    if reward.is_cuda:
+        lib = abi.load_library()
+        abi.check(lib, lib.ssd_social_reward(REWARD_MODELS[model], reward.data_ptr(), out.data_ptr(), acc.data_ptr() if acc is not None else None, N, T1, n,
+                                             reward.stride(0), reward.stride(1), out.stride(0), out.stride(1), p0, p1, p2, _stream(reward)))
+        return out
+    if reward.untyped_storage().data_ptr() == out.untyped_storage().data_ptr():
+        raise _unfit("social_reward", "out", out, "must not share memory with reward")
+    s = lambda v: th.tensor(v, dtype=th.float32)
+    p0, p1, p2 = s(p0), s(p1), s(p2)
+    agents = th.arange(n).view(1, n)
+    e = th.zeros(N, n)
+    zero = th.zeros(())
+    for t in range(T1 - 1):
+        r = reward[:, t]
+        first, third = th.zeros(N, n), th.zeros(N, n)
+        if model == "inequity_aversion":
+            e = p2 * e + r
+            for j in range(n):
+                ej = e[:, j:j + 1]
+                first = th.where(agents == j, first, first + th.maximum(ej - e, zero))
+                third = th.where(agents == j, third, third + th.maximum(e - ej, zero))
+            second, third = p0 * first, p1 * third
+            u = (r - second) - third
+        else:
+            for j in range(n):
+                first = th.where(agents == j, first, first + r[:, j:j + 1])
+            second = p1 * first
+            u = p0 * r + second
+        out[:, t] = u
+        if acc is not None:
+            acc += th.stack([u, second, third], dim=-1).to(th.float64)
+    out[:, T1 - 1] = 0.0
+    return out
 
 
 def column_sums(x):

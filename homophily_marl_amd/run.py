@@ -57,6 +57,10 @@ def build_scheme(args, env_info):
     if getattr(args, "train_stored_state", False):
         # the rollout's recurrent state AFTER the controller consumed the slot, [h_env | h_inc] per agent (ssd_store_hidden)
         scheme["hidden"] = {"vshape": (2 * args.rnn_hidden_dim,), "group": "agents", "dtype": th.float32}
+    from . import ops
+    if ops.reward_field(args) != "reward":
+        # the rollout's rewards shaped by the reward model (ssd_social_reward, one launch per training rollout): what the loss reads
+        scheme["reward_model"] = {"vshape": (args.n_agents,), "dtype": th.float32}
     groups = {"agents": args.n_agents}
     preprocess = {"actions": ("actions_onehot", [OneHot(out_dim=args.n_actions)])}
     return scheme, groups, preprocess
@@ -204,6 +208,36 @@ def _check_epsilon_ladder(args, fused_heads=True):
     return alpha
 
 
+def _check_reward_model(args):
+    """reward_model (absent = "individual" = off: the env's own rewards, no field, no launch), validated and written back.
+    "inequity_aversion" (ia_alpha, ia_beta, ia_decay; Hughes et al. 2018) or "prosocial" (prosocial_weight): after every TRAINING
+    rollout the runner shapes the stored rewards into the storage field "reward_model" (ops.social_reward, one eager launch over the
+    finished rollout: inequity aversion carries a recurrence from slot 0, which a sampled window cannot form), and the loss reads that
+    field.  Observations, statistics, returns and replays keep the env's rewards.  Needs args.n_agents; runs without a device; returns
+    the three scalars of the launch, or None when off."""
+    from . import ops
+    model = getattr(args, "reward_model", "individual")
+    args.reward_model = model = "individual" if model is None else model
+    if model == "individual":
+        return None
+    if not isinstance(model, str) or model not in ops.REWARD_MODELS:
+        raise ValueError('reward_model must be "individual", "inequity_aversion" or "prosocial", got %r' % (model,))
+    if not getattr(args, "ind_reward", True):
+        raise ValueError("reward_model %r needs ind_reward: True (a model compares the agents' own rewards; a team reward has nothing to compare)" % (model,))
+    if args.runner not in ("hip_vec", "hip_graph"):
+        raise ValueError("reward_model %r needs a vectorised runner (hip_vec or hip_graph: the runners that shape a finished rollout on the "
+                         "device); runner %r does not" % (model, args.runner))
+    if getattr(args, "per_initial_priority", "max") == "rollout":
+        raise ValueError('reward_model %r with per_initial_priority "rollout": those priorities are formed during the rollout from the '
+                         "env's rewards and would not be the errors the train step measures" % (model,))
+    keys = {k: getattr(args, k) for k in ("ia_alpha", "ia_beta", "ia_decay", "prosocial_weight") if hasattr(args, k)}
+    try:
+        args.reward_model_scalars = ops.social_reward_scalars(model, args.n_agents, **keys)
+    except ValueError as e:
+        raise ValueError("reward_model %r: %s" % (model, e)) from None
+    return args.reward_model_scalars
+
+
 def _check_target_tau(args):
     """target_tau (absent = 0 = off: the reference's hard sync every target_update_interval), validated and written back.  A value in
     (0, 1]: after every learner.train call the target net becomes (1 - tau) target + tau live on the device, inside the optimiser tail
@@ -247,6 +281,7 @@ def setup(config, logger=None):
     args.state_shape, args.obs_shape = env_info["state_shape"], env_info["obs_shape"]
     if args.rgb_input:
         args.state_dims, args.obs_dims = env_info["state_dims"], env_info["obs_dims"]
+    _check_reward_model(args)
     scheme, groups, preprocess = build_scheme(args, env_info)
     buffer = ReplayBuffer(scheme, groups, args.buffer_size, env_info["episode_limit"] + 1, preprocess=preprocess,
                           device="cpu" if args.buffer_cpu_only else args.device)

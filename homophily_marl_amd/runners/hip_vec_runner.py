@@ -165,6 +165,8 @@ class HipVecRunner:
             stats["n_returns"] = ep_return.numel() + stats.get("n_returns", 0)
         if getattr(self.args, "behaviour_stats", False):
             self._behaviour_device(test_mode)
+        if not test_mode and self._reward_model_on():
+            self._reward_model_device()
         if not test_mode:
             self.t_env += self.t * self.batch_size
             self.rollouts += 1
@@ -223,6 +225,48 @@ class HipVecRunner:
         acc, ws = self._behaviour_acc(test_mode)
         ops.behaviour_stats(st["actions"], st["actions_inc"], st["reward"], st["clean_num"], self.args.n_actions, acc, ws)
 
+    # ---- reward model (config key reward_model, default "individual" = off) -------------------------------------------------------------
+    def _reward_model_on(self):
+        """the predicate of the learner and the scheme (ops.reward_field): a model is named (absent, None and "individual" are off)"""
+        from .. import ops
+        return ops.reward_field(self.args) != "reward"
+
+    def _reward_model_device(self):
+        """this training rollout's rewards shaped by the reward model, storage field "reward" -> "reward_model" (what the loss reads):
+        one eager launch over the episode's storage (self.batch: the runner's own, or the replay buffer's reserved slots) before the
+        batch is returned for insertion, on the current stream, never inside a stream capture.  The launch adds the per-(env, agent)
+        sums of the shaped reward and of its two model terms to an f64 accumulator that _log reads and zeroes."""
+        from .. import ops
+        if th.cuda.is_available() and th.cuda.is_current_stream_capturing():
+            raise RuntimeError("reward_model is launched eagerly: _finish_stats was reached inside a stream capture")
+        st = self.batch.data.transition_data
+        if getattr(self, "_reward_acc", None) is None:
+            self._reward_acc = th.zeros(self.batch_size, self.args.n_agents, 3, dtype=th.float64, device=st["reward"].device)
+            self._reward_rollouts = 0
+        a = self.args
+        if getattr(a, "reward_model_scalars", None) is None:        # a runner built without run.setup
+            a.reward_model_scalars = ops.social_reward_scalars(a.reward_model, a.n_agents, **{k: getattr(a, k) for k in (
+                "ia_alpha", "ia_beta", "ia_decay", "prosocial_weight") if hasattr(a, k)})
+        ops.social_reward(st["reward"], st["reward_model"], a.reward_model, a.reward_model_scalars, self._reward_acc)
+        self._reward_rollouts += 1
+
+    def reward_model_means(self, reset=True):
+        """{name: mean} of the shaped reward and of its two model terms per (env, slot < T, agent) over the training rollouts since the
+        accumulator was last zeroed ({} before the first).  The accumulator [N, n, 3] is copied to the host once and each column summed
+        there in a stated order -- ascending (env, agent), left to right from 0 (a running sum, not a tree) -- then divided once by the
+        count, so a logged mean equals its restatement in plain loops to the bit.  Synchronises; eager, outside any capture."""
+        if getattr(self, "_reward_acc", None) is None or not self._reward_rollouts:
+            return {}
+        import numpy as np
+        cells = self._reward_acc.cpu().numpy().reshape(-1, 3)
+        sums = np.add.accumulate(cells, axis=0)[-1].tolist()         # accumulate is sequential: ((c0 + c1) + c2) + ...
+        count = float(self._reward_rollouts * self.batch_size * self.episode_limit * self.args.n_agents)
+        if reset:
+            self._reward_acc.zero_()
+            self._reward_rollouts = 0
+        names = ("reward_model_mean", "ia_envy_mean", "ia_guilt_mean") if self.args.reward_model == "inequity_aversion" else ("reward_model_mean", "prosocial_others_mean")
+        return {k: v / count for k, v in zip(names, sums)}
+
     def behaviour(self, test_mode=False, reset=False):
         """The behaviour accumulator of the training (or test) episodes since it was last zeroed, by block name (abi.behaviour_layout):
         dict[str, np.ndarray] of f64 integers.  Synchronises.  Rank-local under data parallelism, like the other runner statistics."""
@@ -258,6 +302,9 @@ class HipVecRunner:
             bacc.zero_()
             for k, v in abi.behaviour_summary(vec, self.args.n_agents, self.args.n_actions).items():
                 self.logger.log_stat(prefix + k, v, self.t_env)
+        if not test_mode and self._reward_model_on():
+            for k, v in self.reward_model_means().items():
+                self.logger.log_stat(k, v, self.t_env)
         stats.clear()
 
     def _log_extra(self, sums, stats, prefix, test_mode):

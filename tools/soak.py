@@ -42,6 +42,11 @@ ap.add_argument("--epsilon-ladder", type=float, default=0.0, metavar="ALPHA",
                 help="config key epsilon_ladder_alpha: env g of G explores at epsilon ** (1 + ALPHA g / (G - 1)) (0: one epsilon for all)")
 ap.add_argument("--target-tau", type=float, default=0.0, metavar="TAU",
                 help="config key target_tau: Polyak target update after every train step (0: hard syncs every target_update_interval)")
+ap.add_argument("--reward-model", choices=("ia", "prosocial"), default=None,
+                help="config key reward_model: train on inequity-aversion (ia) or prosocial rewards shaped on the device (default: the env's own)")
+ap.add_argument("--ia-alpha", type=float, default=None, help="config key ia_alpha (with --reward-model ia)")
+ap.add_argument("--ia-beta", type=float, default=None, help="config key ia_beta (with --reward-model ia)")
+ap.add_argument("--prosocial-weight", type=float, default=None, help="config key prosocial_weight (with --reward-model prosocial)")
 ap.add_argument("--set", action="append", default=[], help="extra config override key=value (python literal)")
 a = ap.parse_args()
 c = CONFIGS[a.config]
@@ -65,6 +70,9 @@ if a.epsilon_ladder:
     over["epsilon_ladder_alpha"] = a.epsilon_ladder
 if a.target_tau:
     over["target_tau"] = a.target_tau
+if a.reward_model:
+    over["reward_model"] = {"ia": "inequity_aversion", "prosocial": "prosocial"}[a.reward_model]
+    over.update({k: v for k, v in (("ia_alpha", a.ia_alpha), ("ia_beta", a.ia_beta), ("prosocial_weight", a.prosocial_weight)) if v is not None})
 import ast
 for kv in a.set:
     k, v = kv.split("=", 1)
@@ -184,6 +192,8 @@ for it in range(a.iters):
                 vec = [x for k in abi.behaviour_layout(n, ctx.args.n_actions) for x in b[k].reshape(-1)]
                 s = abi.behaviour_summary(vec, n, ctx.args.n_actions)
                 print("   behaviour %s (%d episodes): " % (label, int(b["n_episodes"][0])) + "  ".join("%s %.4f" % kv for kv in s.items()), flush=True)
+        if a.reward_model:         # the training rollouts since the last report (runner_stats is off in this tool: read and zeroed here)
+            print("   " + "  ".join("%s %.5f" % kv for kv in ctx.runner.reward_model_means().items()), flush=True)
         if a.prioritized and ctx.buffer._draws.log is not None:      # the last sample launch's four log values
             pl = ctx.buffer._draws.log.tolist()
             print("   per_priority_mean %.4f  per_priority_max %.4f  per_weight_min %.4f  per_unique_frac %.4f" % (
