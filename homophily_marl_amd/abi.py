@@ -191,6 +191,16 @@ def polyak_job_table(blocks):
     return jobs
 
 
+def tie_job_table(triples):
+    """(c_int64 * (3 n)) of n (first, copies, inner) triples: the job table of include/ssd_hip_tie.h as the entry points read it on
+    the host (first: an element offset into the flat gradient buffer for ssd_tie_agent_grads, an address for ssd_agent_spread).  The
+    device copy is the caller's: th.tensor(list(table), dtype=th.int64, device=...)."""
+    flat = [int(v) for t in triples for v in t]
+    if len(flat) != 3 * len(triples):
+        raise ValueError("a tie job is a (first, copies, inner) triple")
+    return (C.c_int64 * len(flat))(*flat)
+
+
 class SsdTdLossArgs(C.Structure):
     _fields_ = [("batch", C.c_int32), ("t_slots", C.c_int32), ("n_agents", C.c_int32), ("n_actions", C.c_int32), ("sim_horizon", C.c_int32),
                 ("double_q", C.c_int32),
@@ -373,6 +383,13 @@ REWARD_IA, REWARD_PROSOCIAL = 1, 2
 REWARD_SIGNATURES = {name: (C.c_int, args) for name, args in {
     "ssd_social_reward": [i32] + [vp] * 3 + [i32] * 7 + [f32] * 3 + [vp],
 }.items()}
+# the exports of include/ssd_hip_tie.h (heads shared across agents: config key share_heads); return int.  Job tables are plain int64
+# triples (tie_job_table), given as a host and a device copy.  tests/test_share_heads_host.py holds this table to that header and both
+# entries to a refusal table.
+TIE_SIGNATURES = {name: (C.c_int, args) for name, args in {
+    "ssd_tie_agent_grads": [vp, i64, vp, vp, i32, vp],
+    "ssd_agent_spread": [vp, vp, i32, vp, vp],
+}.items()}
 
 
 # ---- size / layout helpers ---------------------------------------------------------------------------------------------------
@@ -542,6 +559,7 @@ def load_library():
         bind(lib, HIP_SIGNATURES)
         bind(lib, TRAIN_SIGNATURES)
         bind(lib, REWARD_SIGNATURES)
+        bind(lib, TIE_SIGNATURES)
         ver = lib.ssd_abi_version()
         if ver != ABI_VERSION:
             raise ImportError("libssd_hip.so ABI version %d != %d" % (ver, ABI_VERSION))

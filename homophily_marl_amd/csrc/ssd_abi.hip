@@ -10,6 +10,7 @@
 #include "ssd_device.h"
 #include "../../include/ssd_hip_train.h"
 #include "../../include/ssd_hip_reward.h"
+#include "../../include/ssd_hip_tie.h"
 
 using namespace ssd;
 
@@ -950,6 +951,40 @@ int ssd_social_reward(int32_t model, const float* reward, float* shaped, double*
         return fail(SSD_ERR_INVALID, "ssd_social_reward: shaped and reward must be distinct buffers that do not overlap");
     launch_social_reward(model, reward, shaped, acc, n_env, t_slots, n_agents, src_env_stride, src_slot_stride, dst_env_stride, dst_slot_stride, p0, p1, p2,
                          (hipStream_t)stream);
+    return launched();
+}
+// include/ssd_hip_tie.h: heads shared across agents (csrc/ssd_agent_tie.hip).  Everything is checked on the host table.
+int ssd_tie_agent_grads(float* flat, int64_t total, const int64_t* jobs_host, const int64_t* jobs_dev, int32_t n_jobs, void* stream) {
+    if (n_jobs < 0 || n_jobs > SSD_ADAM_MAX_JOBS) return fail(SSD_ERR_INVALID, "ssd_tie_agent_grads: n_jobs outside 0 .. SSD_ADAM_MAX_JOBS");
+    if (n_jobs == 0) return SSD_OK;
+    if (!flat || !jobs_host || !jobs_dev) return fail(SSD_ERR_INVALID, "ssd_tie_agent_grads: a null flat, jobs_host or jobs_dev");
+    if ((uintptr_t)flat & 3) return fail(SSD_ERR_INVALID, "ssd_tie_agent_grads: flat is not 4-byte aligned");
+    if (total < 1 || total > (int64_t)INT32_MAX) return fail(SSD_ERR_INVALID, "ssd_tie_agent_grads: total outside 1 .. 2^31 - 1");
+    int64_t end = 0, max_inner = 0;
+    for (int32_t k = 0; k < n_jobs; ++k) {
+        const int64_t offset = jobs_host[3 * k], copies = jobs_host[3 * k + 1], inner = jobs_host[3 * k + 2];
+        if (copies < 2 || copies > SSD_MAX_AGENTS) return fail(SSD_ERR_INVALID, "ssd_tie_agent_grads: copies outside 2 .. SSD_MAX_AGENTS");
+        if (inner < 1) return fail(SSD_ERR_INVALID, "ssd_tie_agent_grads: inner must be >= 1");
+        if (offset < 0 || offset > total || inner > (total - offset) / copies) return fail(SSD_ERR_INVALID, "ssd_tie_agent_grads: an extent past total");
+        if (offset < end) return fail(SSD_ERR_INVALID, "ssd_tie_agent_grads: jobs overlap or do not ascend");
+        end = offset + copies * inner;
+        if (inner > max_inner) max_inner = inner;
+    }
+    launch_tie_agent_grads(flat, jobs_dev, n_jobs, (long)max_inner, (hipStream_t)stream);
+    return launched();
+}
+int ssd_agent_spread(const int64_t* jobs_host, const int64_t* jobs_dev, int32_t n_jobs, double* out, void* stream) {
+    if (n_jobs < 0 || n_jobs > SSD_ADAM_MAX_JOBS) return fail(SSD_ERR_INVALID, "ssd_agent_spread: n_jobs outside 0 .. SSD_ADAM_MAX_JOBS");
+    if (n_jobs == 0) return SSD_OK;
+    if (!jobs_host || !jobs_dev || !out) return fail(SSD_ERR_INVALID, "ssd_agent_spread: a null jobs_host, jobs_dev or out");
+    if ((uintptr_t)out & 7) return fail(SSD_ERR_INVALID, "ssd_agent_spread: out (f64) is not 8-byte aligned");
+    for (int32_t k = 0; k < n_jobs; ++k) {
+        const int64_t address = jobs_host[3 * k], copies = jobs_host[3 * k + 1], inner = jobs_host[3 * k + 2];
+        if (address == 0 || (address & 3)) return fail(SSD_ERR_INVALID, "ssd_agent_spread: an address that is null or not 4-byte aligned");
+        if (copies < 2 || copies > SSD_MAX_AGENTS) return fail(SSD_ERR_INVALID, "ssd_agent_spread: copies outside 2 .. SSD_MAX_AGENTS");
+        if (inner < 1 || inner > (int64_t)INT32_MAX / copies) return fail(SSD_ERR_INVALID, "ssd_agent_spread: inner outside 1 .. (2^31 - 1) / copies");
+    }
+    launch_agent_spread(jobs_dev, n_jobs, out, (hipStream_t)stream);
     return launched();
 }
 int ssd_bmm_reserve_scratch(void* stream) {

@@ -227,6 +227,8 @@ void launch_fc1_rows(const float* feat_a, const float* feat_b, const float* tail
 void launch_fc1_rows_bwd(const float* dxe, const float* dxi, float* d_feat, int B, int T, int n, int F0, int F1, int A, int ld, hipStream_t s);
 void launch_social_reward(int model, const float* src, float* dst, double* acc, int n_env, int t_slots, int n, int src_env_stride, int src_slot_stride,
                           int dst_env_stride, int dst_slot_stride, float p0, float p1, float p2, hipStream_t s);
+void launch_tie_agent_grads(float* flat, const int64_t* jobs_dev, int n_jobs, long max_inner, hipStream_t s);
+void launch_agent_spread(const int64_t* jobs_dev, int n_jobs, double* out, hipStream_t s);
 #ifdef SSD_STAMPS
 void set_policy_stamps(unsigned long long* buf);
 #endif

@@ -49,6 +49,40 @@ def gap_rel(partials):
     return float(p[0].sqrt() / p[1].sqrt())
 
 
+def tie_agent_grads(g):
+    """The rule of config key share_heads on one gradient tensor [1, n, ...], in place: the n per-agent slices summed in f32 in
+    ascending agent order, one rounding per add -- fl(...fl(fl(g_0 + g_1) + g_2)... + g_n-1), an explicit loop of plain adds (not
+    sum(dim), whose order is not ours to state) -- and the sum written to all n slices: csrc/ssd_agent_tie.hip: k_tie_agent_grads bit
+    for bit.  The sum, not the mean: the gradient of the same loss with respect to one shared parameter."""
+    acc = g[:, 0].clone()
+    for i in range(1, g.shape[1]):
+        acc = acc + g[:, i]
+    g.copy_(acc.unsqueeze(1).expand_as(g))
+    return g
+
+
+def spread_rows(params):
+    """rows {sum_i sum_e (t_i[e] - m[e])^2, sum_i sum_e t_i[e]^2} (float64, m the mean over the agents) of per-agent tensors [1, n, ...]:
+    what ssd_agent_spread returns, as tensor ops (CPU tensors)"""
+    rows = []
+    for p in params:
+        x = p.detach().double().squeeze(0)
+        s = x[0].clone()
+        for i in range(1, x.shape[0]):
+            s = s + x[i]
+        m = s / x.shape[0]
+        rows.append(th.stack([((x - m) ** 2).sum(), (x ** 2).sum()]))
+    return th.stack(rows)
+
+
+def spread_rel(rows):
+    """head_spread = sqrt(sum (t_i - m)^2) / sqrt(sum t_i^2) from a group's rows, added in ascending order in float64 on the host"""
+    num = den = 0.0
+    for a, b in rows.tolist():
+        num, den = num + a, den + b
+    return float(np.sqrt(num) / np.sqrt(den)) if den > 0 else 0.0
+
+
 def lambda_returns(r, terminated, mask, v, gamma, lam):
     """TD(lambda) targets G [B, T, n] of one head, f32 on the tensors' device.  r, mask [B, T, n]: the head's rewards and the TD mask;
     terminated [B, T] (or [B, T, 1]); v [B, T + 1, n]: slot t + 1 is the bootstrap value of row t (slot 0 is never read).
@@ -89,20 +123,27 @@ class _FusedLogs(Mapping):
     def __len__(self):
         return len(self.KEYS)
 
-    def host_items(self, extra=(), gap=None):
+    def host_items(self, extra=(), gap=None, spread=None):
         """(key, python float) of all nine scalars (+ extra (key, 0-d tensor) pairs) from ONE device -> host copy: the sums and the
         denominators travel once and the quotients are formed on the host in f32 as above -- twelve .item() calls were twelve
         synchronisations (0.4 ms of an otherwise idle GPU per log interval).  gap: the Polyak launch's partials, which ride in the same
-        copy and become target_gap_rel on the host (gap_rel)."""
+        copy and become target_gap_rel on the host (gap_rel).  spread: (float64 rows of ssd_agent_spread, {key: row indices}); the
+        rows ride in the same copy as the bit patterns of their two f32 halves and become head_spread_* on the host (spread_rel)."""
+        ng = 0 if gap is None else gap.numel()
         with th.no_grad():
             flat = th.cat([self.sums.detach().float().reshape(-1), self.dens.detach().float().reshape(-1)] + [v.detach().float().reshape(1) for _, v in extra]
-                          + ([] if gap is None else [gap.detach().float().reshape(-1)]))
+                          + ([] if gap is None else [gap.detach().float().reshape(-1)])
+                          + ([] if spread is None else [spread[0].detach().contiguous().view(th.float32).reshape(-1)]))
         host = flat.cpu()
         ns = self.sums.numel()
         host_logs = _FusedLogs(host[:ns], host[ns:ns + self.dens.numel()], self.rows, self.n)
         out = [(k, float(host[ns + self.dens.numel() + i])) for i, (k, _) in enumerate(extra)]
+        first = ns + self.dens.numel() + len(extra)
         if gap is not None:
-            out.append(("target_gap_rel", gap_rel(host[ns + self.dens.numel() + len(extra):])))
+            out.append(("target_gap_rel", gap_rel(host[first:first + ng])))
+        if spread is not None:
+            rows = host[first + ng:].clone().view(th.float64).reshape(-1, 2)
+            out += [(k, spread_rel(rows[idx])) for k, idx in spread[1].items()]
         return out + [(k, float(host_logs[k])) for k in self.KEYS]
 
     def synced(self):
@@ -145,6 +186,14 @@ class HomophilyLearner:
         if self.target_tau > 0 and logger is not None and getattr(logger, "console_logger", None) is not None:
             logger.console_logger.info("target_tau %g: the target network follows the live one after every train step; "
                                        "target_update_interval (%s) is ignored" % (self.target_tau, getattr(args, "target_update_interval", None)))
+        # share_heads (not a key of the reference's config; absent or "none": every agent keeps its own heads): the gradients of the
+        # per-agent copies of every tied tensor are summed and written back to all copies in front of the first clip (tie_agent_grads;
+        # on the device ssd_tie_agent_grads, the first launch of the captured optimiser graph).  The copies start equal
+        # (HomophilyAgent.__init__), so the clip's one factor, Adam and the Polyak update -- all elementwise -- keep them equal to the bit
+        self.share_tags = mac.agent.share_tags if hasattr(mac.agent, "share_tags") else ()
+        self._tied = [p for _, p in mac.agent.tied_parameters()] if self.share_tags else []
+        self._spread_groups = None     # (the 36 per-agent tensors of the live net, {logged key: their rows}): see _head_spread
+        self._spread_plan = None       # the job table of ssd_agent_spread over the live parameters (device path)
         # train_graph: capture the step as hipGraphs (torch.cuda.CUDAGraph); needs capturable Adam (same arithmetic,
         # the step counter lives on the device)
         on_gpu = str(self.device).startswith("cuda")
@@ -514,7 +563,19 @@ class HomophilyLearner:
             gap = th.zeros(abi.POLYAK_WORKGROUPS, 2, dtype=th.float32, device=dev)
             args.polyak_jobs, args.n_polyak, args.target_tau, args.polyak_partials = ptable.data_ptr(), len(blocks), self.target_tau, gap.data_ptr()
             keep, polyak_for = keep + (ptable, gap), self._polyak[0]
-        self._opt_plan = SimpleNamespace(args=args, keep=keep, lib=abi.load_library(), byref=C.byref, polyak_for=polyak_for, gap=gap)
+        tie = None
+        if self._tied:
+            # the tie's job table: (offset, copies, inner) of every tied tensor, at the offsets of the Adam jobs above
+            tied_ids, triples, o = {id(p) for p in self._tied}, [], 0
+            for p in self.params:
+                if id(p) in tied_ids:
+                    triples.append((o, p.shape[1], p.numel() // p.shape[1]))
+                o += p.numel()
+            host = abi.tie_job_table(triples)
+            tdev = th.tensor(list(host), dtype=th.int64, device=dev)
+            tie = (self._flat_grad.data_ptr(), off, host, tdev.data_ptr(), len(triples))
+            keep = keep + (host, tdev)
+        self._opt_plan = SimpleNamespace(args=args, keep=keep, lib=abi.load_library(), byref=C.byref, polyak_for=polyak_for, gap=gap, tie=tie)
         return self._opt_plan
 
     def _polyak_current(self, made_for):
@@ -565,14 +626,57 @@ class HomophilyLearner:
         gap = self._gap()
         return None if gap is None else gap_rel(gap)
 
+    def _head_spread(self):
+        """(float64 rows [36, 2] of {sum_i sum_e (t_i - m)^2, sum_i sum_e t_i^2}, one per per-agent tensor of the live net, on the
+        parameters' device; {"head_spread_env": row indices, "head_spread_inc": ...}) or None with one agent.  On the device one
+        ssd_agent_spread launch on the current stream (the log interval only, never inside a captured graph); CPU tensors: spread_rows."""
+        if self.n_agents < 2:
+            return None
+        if self._spread_groups is None:
+            groups = [("head_spread_" + tag, [p for _, p in self.mac.agent.head_parameters(tag)]) for tag in ("env", "inc")]
+            idx, o = {}, 0
+            for key, ps in groups:
+                idx[key], o = list(range(o, o + len(ps))), o + len(ps)
+            self._spread_groups = ([p for _, ps in groups for p in ps], idx)
+        params, idx = self._spread_groups
+        if not params[0].is_cuda:
+            return spread_rows(params), idx
+        from .. import abi
+        ptrs = (params[0].data_ptr(), params[-1].data_ptr(), len(params))      # (the net moves as a whole: .cuda() / .to())
+        plan = self._spread_plan
+        if plan is None or plan.ptrs != ptrs:
+            host = abi.tie_job_table([(p.data_ptr(), p.shape[1], p.numel() // p.shape[1]) for p in params])
+            dev = params[0].device
+            plan = self._spread_plan = SimpleNamespace(ptrs=ptrs, host=host, dev=th.tensor(list(host), dtype=th.int64, device=dev),
+                                                       out=th.zeros(len(params), 2, dtype=th.float64, device=dev), lib=abi.load_library())
+        abi.check(plan.lib, plan.lib.ssd_agent_spread(plan.host, plan.dev.data_ptr(), len(params), plan.out.data_ptr(),
+                                                      th.cuda.current_stream(params[0].device).cuda_stream))
+        return plan.out, idx
+
+    def head_spreads(self):
+        """{"head_spread_env": .., "head_spread_inc": ..} of the live parameters as they are now: sqrt(sum (t_i - m)^2) / sqrt(sum t_i^2)
+        over the group's 18 tensors, float64; exactly 0.0 for a tied group.  Synchronises (the logger reads the same rows inside the log
+        event's one copy instead: train)."""
+        spread = self._head_spread()
+        if spread is None:
+            return {}
+        rows = spread[0].cpu()
+        return {k: spread_rel(rows[idx]) for k, idx in spread[1].items()}
+
     def clip_and_step(self):
         plan = self._optimiser_plan()
         if plan is not None:
             from .. import abi
+            stream = th.cuda.current_stream(self._flat_grad.device).cuda_stream
+            if plan.tie is not None:
+                abi.check(plan.lib, plan.lib.ssd_tie_agent_grads(*plan.tie, stream))
             abi.check(plan.lib, plan.lib.ssd_clip_adam_step(plan.byref(plan.args), th.cuda.current_stream(self._flat_grad.device).cuda_stream))
             self._gap_partials, self._gap_lazy = plan.gap, False    # (None with target_tau 0; else written by the Polyak launch of this call and every replay)
             return
         a = self.args
+        with th.no_grad():
+            for p in self._tied:
+                tie_agent_grads(p.grad)
         th.nn.utils.clip_grad_norm_(self.params_inc, a.grad_norm_clip)
         th.nn.utils.clip_grad_norm_(self.params_env, a.grad_norm_clip)
         self.optimiser_inc.step()
@@ -689,14 +793,20 @@ class HomophilyLearner:
             if self.distributed and isinstance(logs, _FusedLogs):
                 logs = logs.synced()
             gap = self._gap()                                            # every rank holds the same parameters: no collective
+            spread = self._head_spread()                                 # (share_heads on or off: how far the agents' heads lie apart)
             if isinstance(logs, _FusedLogs):
-                for k, v in logs.host_items(means, gap=gap):             # one device -> host copy for all eleven scalars (+ the gap's partials)
+                # one device -> host copy for all eleven scalars (+ the gap's partials, + the spread's rows)
+                for k, v in logs.host_items(means, gap=gap, spread=spread):
                     self.logger.log_stat(k, v, t_env)
             else:
                 for k, v in means + tuple(logs.items()):
                     self.logger.log_stat(k, v.item(), t_env)
                 if gap is not None:
                     self.logger.log_stat("target_gap_rel", gap_rel(gap), t_env)
+                if spread is not None:
+                    rows = spread[0].cpu()
+                    for k, idx in spread[1].items():
+                        self.logger.log_stat(k, spread_rel(rows[idx]), t_env)
             self.log_stats_t = clock
             self.check_numeric_status(t_env)
 
@@ -729,7 +839,29 @@ class HomophilyLearner:
         th.save(self.optimiser_env.state_dict(), "{}/opt_env.th".format(path))
         th.save(self.optimiser_inc.state_dict(), "{}/opt_inc.th".format(path))
 
+    def _refuse_untied_checkpoint(self, path):
+        """share_heads: a checkpoint whose tied tensors, or whose Adam moments of them, differ across agents in any bit is refused
+        before anything is loaded -- a shared run cannot continue an unshared one (the copies would never meet again)."""
+        load = lambda f: th.load("{}/{}".format(path, f), map_location="cpu", weights_only=True)
+        bits_equal = lambda t: bool((t[:, 1:].contiguous().view(th.int32) == t[:, :1].contiguous().view(th.int32)).all())
+        tied = dict(self.mac.agent.tied_parameters())
+        sd = load("agent.th")
+        for name in tied:
+            if name in sd and not bits_equal(sd[name].float()):
+                raise ValueError("share_heads %r: the checkpoint's %s differs across agents; a shared run cannot continue an unshared one"
+                                 % (self.args.share_heads, name))
+        names = {id(p): name for name, p in tied.items()}
+        for f, params in (("opt_env.th", self.params_env), ("opt_inc.th", self.params_inc)):
+            state = load(f)["state"]
+            for k, p in enumerate(params):
+                for key in ("exp_avg", "exp_avg_sq"):
+                    if id(p) in names and k in state and th.is_tensor(state[k].get(key)) and not bits_equal(state[k][key].float()):
+                        raise ValueError("share_heads %r: the checkpoint's Adam %s of %s (%s) differs across agents; a shared run cannot "
+                                         "continue an unshared one" % (self.args.share_heads, key, names[id(p)], f))
+
     def load_models(self, path):
+        if self._tied:
+            self._refuse_untied_checkpoint(path)
         self.mac.load_models(path)
         # reference: the target net is loaded from the same file (:281-288).  With target_tau > 0 this restarts the average at the
         # loaded live weights (the target net is not part of a checkpoint); the job table goes with _opt_plan below

@@ -12,6 +12,17 @@ import torch.nn.functional as F
 
 from ... import ops
 
+# share_heads (not a key of the reference's config): the head groups whose per-agent copies are held equal (tags of parameter names)
+SHARE_HEADS = {"none": (), "env": ("env",), "inc": ("inc",), "both": ("env", "inc")}
+
+
+def share_heads_tags(raw):
+    """share_heads as the tuple of tied groups; absent / None: "none".  Anything else than the four values is refused."""
+    raw = "none" if raw is None else raw
+    if not isinstance(raw, str) or raw not in SHARE_HEADS:
+        raise ValueError('share_heads must be "none", "env", "inc" or "both", got %r' % (raw,))
+    return SHARE_HEADS[raw]
+
 
 class HomophilyAgent(nn.Module):
     def __init__(self, input_shape, args):
@@ -56,11 +67,28 @@ class HomophilyAgent(nn.Module):
             setattr(self, "fc2_%s_b" % head, bias(fc2_in, fc2_out))
             setattr(self, "fc2_%s_v_w" % head, weight(fc2_in, 1, kaiming=True))
             setattr(self, "fc2_%s_v_b" % head, bias(fc2_in, 1))
+        # share_heads: agent 0's slice of every tied tensor over the others, AFTER the usual initialisation (the generator is consumed
+        # as without the key); the learner's tied gradients keep the copies equal from here on
+        self.share_tags = share_heads_tags(getattr(args, "share_heads", "none"))
+        if self.share_tags and n < 2:
+            raise ValueError("share_heads %r needs n_agents >= 2" % (getattr(args, "share_heads", None),))
+        with th.no_grad():
+            for _, p in self.tied_parameters():
+                p[:, 1:] = p[:, :1]
 
     # ---- parameter groups (homophily_agent.py:127-146): the encoder belongs to BOTH groups -----------------------
     def _group(self, tag):
         params = list(self.conv_to_fc.parameters()) if self.args.rgb_input else []
         return params + [p for name, p in self.named_parameters() if tag in name]
+
+    def head_parameters(self, tag):
+        """[(name, parameter)] of the per-agent tensors [1, n, in, out] of a head group ("env" / "inc"): fc1, the six GRU matrices and
+        the dueling layers with their biases, 18 tensors, in registration order.  The shared encoder is in no group."""
+        return [(name, p) for name, p in self.named_parameters() if not name.startswith("conv_to_fc") and ("_%s_" % tag) in name]
+
+    def tied_parameters(self):
+        """[(name, parameter)] of every tensor share_heads ties, in registration order"""
+        return [(name, p) for name, p in self.named_parameters() if any(("_%s_" % t) in name and not name.startswith("conv_to_fc") for t in self.share_tags)]
 
     def parameters_env(self):
         return self._group("env")

@@ -238,6 +238,20 @@ def _check_reward_model(args):
     return args.reward_model_scalars
 
 
+def _check_share_heads(args):
+    """share_heads (absent = "none" = off: every agent keeps its own heads, no launch, the same bits), validated and written back.
+    "env", "inc" or "both": the per-agent copies of that head group start equal (agent 0's initialisation) and the learner ties their
+    gradients in front of the first clip (homophily_learner.tie_agent_grads; on the device ssd_tie_agent_grads inside the captured
+    optimiser graph), which keeps them equal to the bit.  setup calls it twice: before the runner exists (the value) and once
+    args.n_agents is known (one agent has nothing to share).  Runs without a device; returns the tied groups."""
+    from .modules.agents.homophily_agent import share_heads_tags
+    tags = share_heads_tags(getattr(args, "share_heads", "none"))
+    args.share_heads = "none" if getattr(args, "share_heads", None) is None else args.share_heads
+    if tags and getattr(args, "n_agents", None) is not None and args.n_agents < 2:
+        raise ValueError("share_heads %r needs n_agents >= 2 (one agent has nothing to share with)" % (args.share_heads,))
+    return tags
+
+
 def _check_target_tau(args):
     """target_tau (absent = 0 = off: the reference's hard sync every target_update_interval), validated and written back.  A value in
     (0, 1]: after every learner.train call the target net becomes (1 - tau) target + tau live on the device, inside the optimiser tail
@@ -275,6 +289,7 @@ def setup(config, logger=None):
     logger = logger or Logger()
     _check_stored_state(args)
     _check_target_tau(args)
+    _check_share_heads(args)
     runner = r_REGISTRY[args.runner](args=args, logger=logger)
     env_info = runner.get_env_info()
     args.n_agents, args.n_actions = env_info["n_agents"], env_info["n_actions"]
@@ -282,6 +297,7 @@ def setup(config, logger=None):
     if args.rgb_input:
         args.state_dims, args.obs_dims = env_info["state_dims"], env_info["obs_dims"]
     _check_reward_model(args)
+    _check_share_heads(args)
     scheme, groups, preprocess = build_scheme(args, env_info)
     buffer = ReplayBuffer(scheme, groups, args.buffer_size, env_info["episode_limit"] + 1, preprocess=preprocess,
                           device="cpu" if args.buffer_cpu_only else args.device)

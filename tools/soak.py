@@ -47,6 +47,9 @@ ap.add_argument("--reward-model", choices=("ia", "prosocial"), default=None,
 ap.add_argument("--ia-alpha", type=float, default=None, help="config key ia_alpha (with --reward-model ia)")
 ap.add_argument("--ia-beta", type=float, default=None, help="config key ia_beta (with --reward-model ia)")
 ap.add_argument("--prosocial-weight", type=float, default=None, help="config key prosocial_weight (with --reward-model prosocial)")
+ap.add_argument("--share-heads", choices=("env", "inc", "both"), default=None,
+                help="config key share_heads: that head group's per-agent copies tied (default: every agent its own heads); "
+                     "prints head_spread_env / head_spread_inc with each report")
 ap.add_argument("--set", action="append", default=[], help="extra config override key=value (python literal)")
 a = ap.parse_args()
 c = CONFIGS[a.config]
@@ -73,6 +76,8 @@ if a.target_tau:
 if a.reward_model:
     over["reward_model"] = {"ia": "inequity_aversion", "prosocial": "prosocial"}[a.reward_model]
     over.update({k: v for k, v in (("ia_alpha", a.ia_alpha), ("ia_beta", a.ia_beta), ("prosocial_weight", a.prosocial_weight)) if v is not None})
+if a.share_heads:
+    over["share_heads"] = a.share_heads
 import ast
 for kv in a.set:
     k, v = kv.split("=", 1)
@@ -198,6 +203,8 @@ for it in range(a.iters):
             pl = ctx.buffer._draws.log.tolist()
             print("   per_priority_mean %.4f  per_priority_max %.4f  per_weight_min %.4f  per_unique_frac %.4f" % (
                 pl[0], pl[1], pl[2], pl[3] / ctx.args.batch_size), flush=True)
+        if a.share_heads:                                              # how far the agents' heads lie apart (0 for a tied group)
+            print("   " + "  ".join("%s %.6f" % kv for kv in ctx.learner.head_spreads().items()), flush=True)
         if a.target_tau:                                               # the Polyak update's own partial sums (learner.target_gap_rel)
             print("   target_gap_rel %.5f" % ctx.learner.target_gap_rel(), flush=True)
         acc, cnt = 0.0, 0
