@@ -390,6 +390,11 @@ TIE_SIGNATURES = {name: (C.c_int, args) for name, args in {
     "ssd_tie_agent_grads": [vp, i64, vp, vp, i32, vp],
     "ssd_agent_spread": [vp, vp, i32, vp, vp],
 }.items()}
+# the export of include/ssd_hip_mix.h (the VDN mixer of the env head: config key mixer); returns int.  It takes the SsdTdLossArgs that
+# ssd_td_sim_loss has just been handed.  tests/test_team_mixer_host.py holds this table to that header and the entry to a refusal table.
+MIX_SIGNATURES = {name: (C.c_int, args) for name, args in {
+    "ssd_team_td": [vp, vp],
+}.items()}
 
 
 # ---- size / layout helpers ---------------------------------------------------------------------------------------------------
@@ -560,6 +565,7 @@ def load_library():
         bind(lib, TRAIN_SIGNATURES)
         bind(lib, REWARD_SIGNATURES)
         bind(lib, TIE_SIGNATURES)
+        bind(lib, MIX_SIGNATURES)
         ver = lib.ssd_abi_version()
         if ver != ABI_VERSION:
             raise ImportError("libssd_hip.so ABI version %d != %d" % (ver, ABI_VERSION))

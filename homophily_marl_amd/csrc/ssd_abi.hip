@@ -11,6 +11,7 @@
 #include "../../include/ssd_hip_train.h"
 #include "../../include/ssd_hip_reward.h"
 #include "../../include/ssd_hip_tie.h"
+#include "../../include/ssd_hip_mix.h"
 
 using namespace ssd;
 
@@ -985,6 +986,24 @@ int ssd_agent_spread(const int64_t* jobs_host, const int64_t* jobs_dev, int32_t 
         if (inner < 1 || inner > (int64_t)INT32_MAX / copies) return fail(SSD_ERR_INVALID, "ssd_agent_spread: inner outside 1 .. (2^31 - 1) / copies");
     }
     launch_agent_spread(jobs_dev, n_jobs, out, (hipStream_t)stream);
+    return launched();
+}
+// include/ssd_hip_mix.h: the VDN mixer of the env head (csrc/ssd_team_mix.hip), behind ssd_td_sim_loss(args, 1) on the same struct
+int ssd_team_td(const ssd_td_loss_args* a, void* stream) {
+    if (!a) return fail(SSD_ERR_INVALID, "ssd_team_td: null args");
+    if (a->batch < 1 || a->t_slots < 2 || a->n_actions < 1) return fail(SSD_ERR_INVALID, "ssd_team_td: batch >= 1, t_slots >= 2, n_actions >= 1");
+    if (a->n_agents < 2 || a->n_agents > SSD_MAX_AGENTS) return fail(SSD_ERR_INVALID, "ssd_team_td: n_agents outside 2 .. SSD_MAX_AGENTS");
+    if ((int64_t)a->batch * a->t_slots * a->n_agents > SSD_ROWS32_MAX) return fail(SSD_ERR_INVALID, "ssd_team_td: batch * t_slots * n_agents over SSD_ROWS32_MAX");
+    if (!a->q_env || !a->tq_env || !a->actions || !a->actions_inc || !a->avail || !a->reward || !a->terminated || !a->filled || !a->dens || !a->dq_env
+        || !a->partials)
+        return fail(SSD_ERR_INVALID, "ssd_team_td: null member pointer (q_env, tq_env, actions, actions_inc, avail, reward, terminated, filled, dens, dq_env, partials)");
+    if ((reinterpret_cast<uintptr_t>(a->q_env) | reinterpret_cast<uintptr_t>(a->tq_env) | reinterpret_cast<uintptr_t>(a->actions) | reinterpret_cast<uintptr_t>(a->actions_inc)
+         | reinterpret_cast<uintptr_t>(a->avail) | reinterpret_cast<uintptr_t>(a->reward) | reinterpret_cast<uintptr_t>(a->filled) | reinterpret_cast<uintptr_t>(a->dens)
+         | reinterpret_cast<uintptr_t>(a->dq_env) | reinterpret_cast<uintptr_t>(a->partials)) & 3)
+        return fail(SSD_ERR_INVALID, "ssd_team_td: an operand is not 4-byte aligned (q_env, tq_env, actions, actions_inc, avail, reward, filled, dens, dq_env, partials)");
+    if (!(a->seq_len > 0.f) || !(a->reward_scale != 0.f)) return fail(SSD_ERR_INVALID, "ssd_team_td: seq_len <= 0 or reward_scale == 0");
+    if (!unit_interval(a->td_lambda)) return fail(SSD_ERR_INVALID, "ssd_team_td: td_lambda outside [0, 1]");
+    launch_team_td(a, (hipStream_t)stream);
     return launched();
 }
 int ssd_bmm_reserve_scratch(void* stream) {

@@ -229,6 +229,7 @@ void launch_social_reward(int model, const float* src, float* dst, double* acc, 
                           int dst_env_stride, int dst_slot_stride, float p0, float p1, float p2, hipStream_t s);
 void launch_tie_agent_grads(float* flat, const int64_t* jobs_dev, int n_jobs, long max_inner, hipStream_t s);
 void launch_agent_spread(const int64_t* jobs_dev, int n_jobs, double* out, hipStream_t s);
+void launch_team_td(const ssd_td_loss_args* a, hipStream_t s);
 #ifdef SSD_STAMPS
 void set_policy_stamps(unsigned long long* buf);
 #endif

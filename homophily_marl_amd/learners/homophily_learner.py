@@ -83,6 +83,17 @@ def spread_rel(rows):
     return float(np.sqrt(num) / np.sqrt(den)) if den > 0 else 0.0
 
 
+def team_td(td):
+    """The rule of config key mixer: "vdn" on the agents' TD errors td [B, T, n]: the team's error ((td_0 + td_1) + td_2) + ... -- f32
+    adds in ascending agent order, one rounding each, as ssd_team_td forms it -- broadcast back over the n agents.  VDN's team value is
+    the sum of the agents' values, so this is the TD error of the summed chosen values against the summed targets; the squared-error sum
+    over the n equal rows is n times the team's, and autograd hands every agent's chosen value the factor n with it."""
+    team = td[..., 0]
+    for i in range(1, td.shape[-1]):
+        team = team + td[..., i]
+    return team.unsqueeze(-1).expand_as(td)
+
+
 def lambda_returns(r, terminated, mask, v, gamma, lam):
     """TD(lambda) targets G [B, T, n] of one head, f32 on the tensors' device.  r, mask [B, T, n]: the head's rewards and the TD mask;
     terminated [B, T] (or [B, T, 1]); v [B, T + 1, n]: slot t + 1 is the bootstrap value of row t (slot 0 is never read).
@@ -171,6 +182,12 @@ class HomophilyLearner:
         lam = float(getattr(args, "td_lambda", 0.0) or 0.0)
         if not 0.0 <= lam <= 1.0:                      # (NaN fails both comparisons)
             raise ValueError("td_lambda must lie in [0, 1], got %r" % (getattr(args, "td_lambda", None),))
+        # mixer (PyMARL's key; absent, None, "" or "none": independent learners, nothing added): "vdn" trains the env head on the TEAM's
+        # TD error, the ascending f32 sum of the agents' errors of a (b, t) (team_td; on the device ssd_team_td behind the loss launch).
+        # Acting stays per agent; the inc head has no mixer.  loss_value_env is then the team loss (PyMARL's QLearner under VDNMixer)
+        self.mixer = ops.team_mixer(args)
+        if self.mixer is not None and n < 2:
+            raise ValueError("mixer %r needs n_agents >= 2 (one agent is its own team)" % (self.mixer,))
         # prioritised replay (ours; run.setup validates the keys): how a trained sample's new priority is formed (ops.priority_update)
         self.per = (float(getattr(args, "per_alpha", 0.6)), float(getattr(args, "per_eta", 0.9)), float(getattr(args, "per_eps", 1e-3)))
         self.params = list(mac.parameters())
@@ -376,12 +393,13 @@ class HomophilyLearner:
         q_env, q_inc, tq_env, tq_inc = self.unroll_pair(batch)
         priority = batch.priority
         if priority is None:
-            dq_env, dq_inc, sums = ops.td_sim_loss_grads(q_env, q_inc, tq_env, tq_inc, dens, batch, a)
+            dq_env, dq_inc, sums = ops.td_sim_loss_grads(q_env, q_inc, tq_env, tq_inc, dens, batch, a, mixer=self.mixer)
         else:
             # prioritised replay: the samples' new priorities from the rows the loss kernel just wrote, the importance weights on
-            # the gradient seeds, the table written -- in this step, before the next rollout reuses a slot (two launches)
+            # the gradient seeds, the table written -- in this step, before the next rollout reuses a slot (two launches).  Under a
+            # mixer the rows and the seeds are already the team's when priority_update reads them
             table, ids, weights = priority
-            dq_env, dq_inc, sums, partials = ops.td_sim_loss_grads(q_env, q_inc, tq_env, tq_inc, dens, batch, a, with_partials=True)
+            dq_env, dq_inc, sums, partials = ops.td_sim_loss_grads(q_env, q_inc, tq_env, tq_inc, dens, batch, a, with_partials=True, mixer=self.mixer)
             self.last_q_new = ops.priority_update(partials, ids, weights, dq_env, dq_inc, th.empty(batch.batch_size, dtype=th.int32, device=dq_env.device),
                                                   table, *self.per)
         self._backward([q_env, q_inc], seeds=[dq_env, dq_inc])
@@ -446,6 +464,8 @@ class HomophilyLearner:
                 targets_inc = lambda_returns(rewards_for_inc, terminated, mask, pad((tmax_inc * self.inc_mask).sum(dim=-1)), a.gamma_inc, lam)
             self.last_lambda_returns = (targets_env, targets_inc)                  # [B, T, n] each (the tests pin them to the reference)
         td_env = chosen_env.sum(dim=-1) - targets_env.detach()
+        if self.mixer is not None:                     # VDN: every agent's row carries the team's error (under td_lambda: of the per-agent returns)
+            td_env = team_td(td_env)
         td_inc = (chosen_inc * self.inc_mask).sum(dim=-1) - targets_inc.detach()
         value_loss_env = ((td_env * mask) ** 2).sum() / dens[0]
         value_loss_inc = ((td_inc * mask) ** 2).sum() / dens[0]

@@ -289,14 +289,30 @@ def loss_denominators(batch, a, n_actions):
     return column_sums(partials)[:2]
 
 
-def td_sim_loss_grads(q_env, q_inc, tq_env, tq_inc, dens, batch, a, with_partials=False):
+MIXERS = ("vdn",)
+
+
+def team_mixer(a):
+    """The mixer of the env head under the config `a`: None (key absent, None, "" or "none": independent learners, no launch), or
+    "vdn".  Anything else raises ValueError.  One predicate for run.setup, the learner and the loss launch."""
+    raw = getattr(a, "mixer", None)
+    if raw is None or (isinstance(raw, str) and raw in ("", "none")):
+        return None
+    if not isinstance(raw, str) or raw not in MIXERS:
+        raise ValueError('mixer must be null (or "none") or "vdn", got %r' % (raw,))
+    return raw
+
+
+def td_sim_loss_grads(q_env, q_inc, tq_env, tq_inc, dens, batch, a, with_partials=False, mixer=None):
     """(dL/dq_env, dL/dq_inc, column sums of the per-row partials) of the loss
         (sum (td_env mask)^2 + sum (td_inc mask)^2) / dens[0] + sim_loss_weight * sum_sim / (1 + dens[1])
     from one launch (csrc/ssd_learner.hip: k_td_sim_loss / k_td_lambda_loss), WITHOUT an autograd node: the learner seeds the backward pass of the two Q tensors with the gradients directly (th.autograd.grad(..., grad_outputs=...)) --
     the loss scalar is a logged quantity only (_FusedLogs forms it when it is read), so the six scalar launches that assembled it and
     the two multiplications by d loss / d loss = 1 of the autograd form are gone.  Columns 13..15 of the partials are never read
     (13 / 14 are written only with td_lambda > 0: the rows' lambda-returns).  with_partials: the per-row partials as a fourth result
-    (prioritised replay forms the samples' new priorities from columns 0, 2, 3: priority_update)."""
+    (prioritised replay forms the samples' new priorities from columns 0, 2, 3: priority_update).  mixer (team_mixer(a); None: no
+    second launch, nothing changes): "vdn" issues ssd_team_td directly behind the loss launch -- dq_env's seeds and column 2 become the
+    team's (the sum over the agents of a (b, t)), every other output stays the loss launch's."""
     lib = abi.load_library()
     B, T, n = batch.batch_size, batch.max_seq_length - 1, q_env.shape[2]
     q_env, q_inc, tq_env, tq_inc = q_env.detach().contiguous(), q_inc.detach().contiguous(), tq_env.contiguous(), tq_inc.contiguous()
@@ -307,6 +323,12 @@ def td_sim_loss_grads(q_env, q_inc, tq_env, tq_inc, dens, batch, a, with_partial
     dens = dens.contiguous().float()
     t.dens, t.dq_env, t.dq_inc = dens.data_ptr(), dq_env.data_ptr(), dq_inc.data_ptr()
     abi.check(lib, lib.ssd_td_sim_loss(C.byref(t), 1, _stream(q_env)))
+    if mixer is not None:
+        if mixer not in MIXERS:
+            raise ValueError("td_sim_loss_grads: mixer must be None or one of %r, got %r" % (MIXERS, mixer))
+        # VDN: the team's TD error from the rows the loss launch just wrote, over the env head's seeds and column 2 (include/ssd_hip_mix.h),
+        # in front of the column sums and of priority_update, which then read the team's numbers
+        abi.check(lib, lib.ssd_team_td(C.byref(t), _stream(q_env)))
     if with_partials:
         return dq_env, dq_inc, column_sums(partials), partials
     return dq_env, dq_inc, column_sums(partials)

@@ -252,6 +252,25 @@ def _check_share_heads(args):
     return tags
 
 
+def _check_mixer(args):
+    """mixer (PyMARL's key; absent, None, "" or "none" = off: independent learners, no launch, no tensor, the same bits), validated and
+    written back as None or the name.  "vdn": the env head trains on the team's TD error, the sum over the agents of a (b, t)
+    (homophily_learner.team_td; on the device ssd_team_td directly behind the loss launch); acting, the inc head and every other key
+    are as without it -- reward_model, td_lambda, train_window, share_heads, target_tau and prioritized_replay compose, and under
+    per_initial_priority "rollout" the starting priorities stay the per-agent one-step form the first train step overwrites.  setup
+    calls it twice: before the runner exists (the value, ind_reward) and once args.n_agents is known.  Runs without a device."""
+    from . import ops
+    args.mixer = mixer = ops.team_mixer(args)
+    if mixer is None:
+        return None
+    if not getattr(args, "ind_reward", True):
+        raise ValueError("mixer %r needs ind_reward: True (the mixer sums the agents' own rewards into the team's; under ind_reward: False "
+                         "every agent is already paid the team reward and the sum would pay it n times)" % (mixer,))
+    if getattr(args, "n_agents", None) is not None and args.n_agents < 2:
+        raise ValueError("mixer %r needs n_agents >= 2 (one agent is its own team)" % (mixer,))
+    return mixer
+
+
 def _check_target_tau(args):
     """target_tau (absent = 0 = off: the reference's hard sync every target_update_interval), validated and written back.  A value in
     (0, 1]: after every learner.train call the target net becomes (1 - tau) target + tau live on the device, inside the optimiser tail
@@ -290,7 +309,8 @@ def setup(config, logger=None):
     _check_stored_state(args)
     _check_target_tau(args)
     _check_share_heads(args)
-    runner = r_REGISTRY[args.runner](args=args, logger=logger)
+    _check_mixer(args)
+    runner =r_REGISTRY[args.runner](args=args, logger=logger)
     env_info = runner.get_env_info()
     args.n_agents, args.n_actions = env_info["n_agents"], env_info["n_actions"]
     args.state_shape, args.obs_shape = env_info["state_shape"], env_info["obs_shape"]
@@ -298,6 +318,7 @@ def setup(config, logger=None):
         args.state_dims, args.obs_dims = env_info["state_dims"], env_info["obs_dims"]
     _check_reward_model(args)
     _check_share_heads(args)
+    _check_mixer(args)
     scheme, groups, preprocess = build_scheme(args, env_info)
     buffer = ReplayBuffer(scheme, groups, args.buffer_size, env_info["episode_limit"] + 1, preprocess=preprocess,
                           device="cpu" if args.buffer_cpu_only else args.device)

@@ -50,6 +50,9 @@ ap.add_argument("--prosocial-weight", type=float, default=None, help="config key
 ap.add_argument("--share-heads", choices=("env", "inc", "both"), default=None,
                 help="config key share_heads: that head group's per-agent copies tied (default: every agent its own heads); "
                      "prints head_spread_env / head_spread_inc with each report")
+ap.add_argument("--mixer", choices=("vdn",), default=None,
+                help="config key mixer: the env head trains on the team's TD error (default: independent learners); loss_value_env is "
+                     "then the team loss")
 ap.add_argument("--set", action="append", default=[], help="extra config override key=value (python literal)")
 a = ap.parse_args()
 c = CONFIGS[a.config]
@@ -78,6 +81,8 @@ if a.reward_model:
     over.update({k: v for k, v in (("ia_alpha", a.ia_alpha), ("ia_beta", a.ia_beta), ("prosocial_weight", a.prosocial_weight)) if v is not None})
 if a.share_heads:
     over["share_heads"] = a.share_heads
+if a.mixer:
+    over["mixer"] = a.mixer
 import ast
 for kv in a.set:
     k, v = kv.split("=", 1)
